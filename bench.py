@@ -8,7 +8,7 @@ ETH3D full resolution 6048x4032, 10 source views, 8 iterations, --blocksize 11, 
 region.  N GPUs = N reference views, one per rank (weak scaling), results gathered to rank 0 over RCCL
 inside the timed region (the "gather before fusion" of the north star).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 6048 --height 4032 --views 10 --iters 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 6048 --height 4032 --views 10 --iters 8] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -162,6 +162,29 @@ def host_boundary(args, sc):
             "note": "host buffers in (H2D + quad build), host buffers out (D2H); one view; value = page-locked float32 caller buffers (tsar_host_alloc); u8_pinned = the 8-bit decode handed over as bytes (tsar_set_views_u8)"}
 
 
+DUMP_MAX_PIXELS = 1 << 21      # over all ranks: 2 Mi pixels x (depth + normal + cost) x 4 B = 40 MiB, inside the 64 MB bound
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, maps, h, w):
+    """--dump-outputs DIR: the maps the timed path handed back in its last step, as DIR/<name>.npy (float32), so that two builds run
+    with the same arguments (hence the same inputs) can be compared output for output.  maps = {name: [one (h, w) or (h, w, C) tensor
+    per rank]}.  While every rank's pixels fit in DUMP_MAX_PIXELS the maps are written whole: (h, w[, C]) for one rank, (ranks, h,
+    w[, C]) for several.  Larger maps are cut to one fixed sample of pixels, the same for every map, rank and run: DUMP_MAX_PIXELS //
+    ranks row-major pixel indices drawn without replacement by numpy's default_rng(DUMP_SEED), sorted; (n[, C]) or (ranks, n[, C])."""
+    os.makedirs(out_dir, exist_ok=True)
+    ranks = len(next(iter(maps.values())))
+    n = DUMP_MAX_PIXELS // ranks
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=n, replace=False)) if h * w > n else None
+    for name, per_rank in maps.items():
+        arrs = []
+        for t in per_rank:
+            if idx is not None:
+                t = t.reshape(h * w, *t.shape[2:]).index_select(0, torch.from_numpy(idx).to(t.device))
+            arrs.append(t.float().cpu().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), arrs[0] if ranks == 1 else np.stack(arrs))
+
+
 def tolerance_fast_vs_strict(fast, strict):
     """The float tolerance of the headline (fast-arithmetic) result, measured in THIS run against the strict result of the same
     scene, seed and step (strict = the reference's arithmetic, bit-identical to the CPU oracle): fractions over the pixels valid
@@ -294,7 +317,13 @@ def main():
     ap.add_argument("--no-strict-record", action="store_true", dest="no_strict_record")
     ap.add_argument("--verify-gather", action="store_true", dest="verify_gather",
                     help="after the timed steps, check that rank 0's gathered buffers hold every rank's own results (bit for bit)")
+    ap.add_argument("--dump-outputs", metavar="DIR", dest="dump_outputs",
+                    help="after the timed steps, write the depth / normal / cost maps of the last timed step (rank 0: the gathered maps of all "
+                         "ranks) as DIR/<name>.npy in float32; maps beyond %d pixels in all are written at a fixed, seeded sample of pixels "
+                         "(bench.dump_outputs), e.g. bench_outputs/" % DUMP_MAX_PIXELS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -413,6 +442,14 @@ def main():
     gt = sc.gt_depth
     out_depth = sets[state["last"]][0]
     frac_ok = float(((out_depth - gt).abs() / gt < 0.01).float().mean().item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: this rank's maps, or with a process group the gathered maps of all
+        names = ("depth", "normal", "cost")
+        if dist is not None:
+            maps = {n: gathered[state["last"]][i] for i, n in enumerate(names)}
+        else:
+            maps = {n: [t] for n, t in zip(names, sets[state["last"]])}
+        dump_outputs(args.dump_outputs, maps, h, w)
 
     gather_check = None
     if dist is not None and args.verify_gather:
