@@ -218,6 +218,38 @@ int tsar_load_planes(tsar_ctx* ctx, const float* depth, const float* normal_worl
 int tsar_compute_disp(tsar_ctx* ctx);
 int tsar_compute_disp_final(tsar_ctx* ctx, const float* resize_planes, const float* text, int mem);
 int tsar_depth_to_plane(tsar_ctx* ctx);
+
+/* ---- coarse-to-fine PatchMatch (the remedy of the ACMM / APD line for textureless regions) ------------------------------ */
+/* Installs on `coarse` the 1 + N views of `fine`, each downsampled by 2 on the device (no host round trip; `fine` keeps its views,
+ * so the call chains for further levels).  The filter is OpenCV's pyrDown, which the reference uses (main.cpp:377-379, 621-622):
+ *   - kernel [1 4 6 4 1]^T [1 4 6 4 1] / 256, its centre on source pixel (2x, 2y);
+ *   - border BORDER_REFLECT_101;
+ *   - output size ((w + 1) / 2, (h + 1) / 2);
+ *   - views from tsar_set_views_u8: integer sum s of the weighted texels, (s + 128) >> 8 (pyrDown on CV_8U), so the coarse level is an
+ *     8-bit decode again (its tap loops, box limits and TSAR_FLAG_TEX_FILTER_8BIT apply as at the fine level);
+ *   - views from tsar_set_views: float32 without rounding, per source row r_j = (((t0 + 4 t1) + 6 t2) + 4 t3) + t4, then
+ *     (((r0 + 4 r1) + 6 r2) + 4 r3) + r4, times 1/256, each operation rounded in that order (no fused multiply-add).
+ * Cameras: the coarse K is the fine K with fx, fy, cx, cy halved (exact for a filter centred on (2x, 2y); --cam_scale's convention,
+ * cameraGeometryUtils.h:143-154); R, t and the depth range stay; everything else is derived as tsar_set_views derives it.  `coarse`
+ * takes `fine`'s params (box, n_best, cost_comb, flags, seed, cam_scale) and view subset.  TSAR_ERR_INVALID, with the reason in
+ * tsar_last_error(coarse): contexts on different devices, `fine` without views, a coarse side smaller than the window (or than 8).
+ * The contexts' streams are ordered by an event. */
+int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine);
+/* Starts `fine`'s plane state from `coarse`'s (planes (n, d) are metric and independent of K, getD_cu gipuma.cu:71-90).  Fine pixel
+ * (x, y) scores the coarse planes at (x / 2 + i, y / 2 + j), i, j in {0, 1}, clamped to the coarse image, in the order (0,0), (1,0),
+ * (0,1), (1,1), with its own multi-view cost (tsar_pm_cost_planes's, in the context's arithmetic, window, best-N and subset); the
+ * lowest cost wins, the first on a tie.  The winner's plane, cost, best view and ratio become the state the next tsar_pm_iterate
+ * starts from (like tsar_pm_init's: the sweep counter restarts at 0), and the winning planes are kept as the context's upsampled
+ * planes (the reference's lines->resize4, linestate.h:64, which its snapshot allocates and never fills).  TSAR_ERR_INVALID unless
+ * coarse holds a plane state of ((w + 1) / 2, (h + 1) / 2) on the same device.  Timed as "pm_upsample". */
+int tsar_upsample_planes(tsar_ctx* fine, const tsar_ctx* coarse);
+/* tsar_compute_disp_final with resize4 = the planes the last tsar_upsample_planes kept (TSAR_ERR_INVALID if there are none).
+ * text [h][w] is lines->text, which the reference never fills; here it is the region text of the pixel's weak-texture label,
+ * text[p] = region_text[labels[p]] from tsar_detect_weak_texture (main.cpp:575-589): -1 textureless, 1 otherwise. */
+int tsar_compute_disp_final_upsampled(tsar_ctx* ctx, const float* text, int mem);
+/* Diagnostics: the image of view `view` as the context holds it, [h][w] float32 (a pyramid level's views included). */
+int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem);
+
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */
 int tsar_get_result(tsar_ctx* ctx, float* depth, float* normal_world, float* cost, float* confid,

@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "tsar_default_params", "tsar_set_params", "tsar_set_views", "tsar_set_views_u8", "tsar_set_view_subset",
     "tsar_pm_init", "tsar_pm_iterate", "tsar_pm_iterate_final", "tsar_pm_sweep", "tsar_set_sweep_counter", "tsar_pm_cost_planes", "tsar_set_plane", "tsar_get_plane",
     "tsar_load_planes", "tsar_compute_disp", "tsar_compute_disp_final", "tsar_depth_to_plane", "tsar_get_result",
+    "tsar_pyramid_views", "tsar_upsample_planes", "tsar_compute_disp_final_upsampled", "tsar_get_view_image",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -110,6 +111,10 @@ def load_library(path: str = LIB_PATH):
     L.tsar_compute_disp.argtypes = [C.c_void_p]
     L.tsar_compute_disp_final.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_depth_to_plane.argtypes = [C.c_void_p]
+    L.tsar_pyramid_views.argtypes = [C.c_void_p, C.c_void_p]
+    L.tsar_upsample_planes.argtypes = [C.c_void_p, C.c_void_p]
+    L.tsar_compute_disp_final_upsampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.tsar_get_view_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -191,6 +196,7 @@ class Matcher:
         if rc != TSAR_OK:
             raise TsarError(rc, "tsar_create failed (is a HIP device visible?)")
         self.w = self.h = self.n_views = 0
+        self.device = device
         self._keep = []
 
     def close(self):
@@ -309,6 +315,31 @@ class Matcher:
 
     def depth_to_plane(self):
         self._chk(self.L.tsar_depth_to_plane(self._ctx))
+
+    # ---- coarse-to-fine ----
+    def pyramid_from(self, fine: "Matcher"):
+        """install fine's views downsampled by 2 (pyrDown) with K / 2, fine's params and view subset (tsar_pyramid_views)"""
+        self._chk(self.L.tsar_pyramid_views(self._ctx, fine._ctx))
+        self.w, self.h, self.n_views = (fine.w + 1) // 2, (fine.h + 1) // 2, fine.n_views
+        self.params = fine.params
+
+    def upsample_planes(self, coarse: "Matcher"):
+        """start this context's plane state from coarse's (each pixel keeps the cheapest of its four nearest coarse planes) and keep
+        the chosen planes for compute_disp_final_upsampled (tsar_upsample_planes)"""
+        self._chk(self.L.tsar_upsample_planes(self._ctx, coarse._ctx))
+
+    def get_view_image(self, view: int):
+        """the image of `view` as the context holds it: [h, w] float32"""
+        out = np.empty((self.h, self.w), np.float32)
+        self._chk(self.L.tsar_get_view_image(self._ctx, view, _ptr(out)[0], MEM_HOST))
+        return out
+
+    def compute_disp_final_upsampled(self, text):
+        """compute_disp_final with the planes the last upsample_planes kept; text [h, w] = lines->text (-1 textureless, 1 otherwise),
+        a numpy array or a torch device tensor"""
+        t = text if _is_torch(text) else np.ascontiguousarray(text, np.float32)
+        p, kind = _ptr(t)
+        self._chk(self.L.tsar_compute_disp_final_upsampled(self._ctx, p, kind))
 
     def get_result(self, want=("depth", "normal", "cost", "confid"), pinned=False, out=None):
         """pinned=True: the result arrays are page-locked (tsar_host_alloc), so the D2H copies run at PCIe rate.
@@ -497,6 +528,26 @@ def matcher_from_scene(scene, box=11, n_best=1, cost_comb=COMB_BEST_N, flags=0, 
     if subset is not None:
         m.set_view_subset(subset)
     return m
+
+
+def run_multiscale(matcher: Matcher, levels: int, coarse_iters: int, fine_iters: int, coarse=None):
+    """Coarse-to-fine PatchMatch on `matcher`'s views: init + `coarse_iters` iterations at the coarsest of `levels` pyramid levels,
+    then at every finer level (matcher's own included) upsample + `fine_iters` iterations.  levels = 0 is plain init + coarse_iters.
+    coarse: the coarse contexts of an earlier call (finest first), reused; returns the list used, for the next call."""
+    if levels < 0 or coarse_iters < 0 or fine_iters < 0:
+        raise ValueError("levels and iteration counts must be >= 0")
+    coarse = list(coarse or [])
+    while len(coarse) < levels:
+        coarse.append(Matcher(matcher.device))
+    chain = [matcher] + coarse[:levels]
+    for finer, coarser in zip(chain[:-1], chain[1:]):
+        coarser.pyramid_from(finer)
+    chain[-1].pm_init()
+    chain[-1].pm_iterate(coarse_iters)
+    for k in range(levels - 1, -1, -1):
+        chain[k].upsample_planes(chain[k + 1])
+        chain[k].pm_iterate(fine_iters)
+    return coarse
 
 
 def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = None, cap: int | None = None, device: int = 0, matcher=None):

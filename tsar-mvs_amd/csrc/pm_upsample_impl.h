@@ -1,0 +1,87 @@
+// pm_upsample_impl.h — plane upsampling of the coarse-to-fine mode (tsar_upsample_planes): every fine pixel scores the planes of
+// its four nearest coarse pixels with the context's own multi-view cost and keeps the cheapest.  The every-pixel kernel of
+// pm_init_impl.h with four hypotheses instead of one: the reference window is staged and hoisted once per pixel and the four
+// candidates run the same tap loop (box-11 loop / general-window loop / one-tap loop) as tsar_pm_cost_planes, so each candidate's
+// cost, best view and ratio are bit for bit what that call returns for it.
+#pragma once
+#include "pm_core.h"
+
+#define UP_RH 8
+
+// coarse: [ch][cw] plane map of the coarse level.  Candidates of fine pixel (x, y): coarse (x / 2 + i, y / 2 + j), i, j in {0, 1},
+// clamped to the coarse image, in the order (0,0), (1,0), (0,1), (1,1); the lowest cost wins, the first on a tie.  Writes the
+// winner's plane to n_out and keep_out (the context's resize4), its cost / best view / ratio to c_out / beview_out / ratio_out.
+template <int NB, int HR, bool STRICT, bool QUAD, int V = 0>
+__global__ __launch_bounds__(PM_BLOCK) void pm_upsample_kernel(const DevScene* __restrict__ sc, const float4* __restrict__ coarse, int cw, int ch,
+                                                               float* __restrict__ c_out, float4* __restrict__ n_out, float4* __restrict__ keep_out,
+                                                               int32_t* __restrict__ beview_out, float* __restrict__ ratio_out, int tiles_x,
+                                                               int n_tiles, int strip_w) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    typedef typename TileOf<QUAD>::type TileT;
+    const int hr = HR > 0 ? HR : sc->hrad, vr = HR > 0 ? HR : sc->vrad;
+    const int tw = PM_RW + 2 * hr, th = UP_RH + 2 * vr;
+    constexpr bool LUTW = (V & 1024) != 0;
+    const size_t lut_bytes = LUTW ? (size_t)(sc->lut_classes + 1) * 1024 : 0;
+    TileT* tile = (TileT*)(lds_raw + lut_bytes);
+    float* wts = LUTW ? (float*)lds_raw : (float*)(lds_raw + tile_bytes<QUAD>(tw, th)) + threadIdx.x;
+    if constexpr (LUTW) build_weight_lut<PM_BLOCK>(sc, wts);
+    const int t = xcd_tile(blockIdx.x, n_tiles);
+    int tix, tiy;
+    strip_tile(t, tiles_x, n_tiles / tiles_x, strip_w, tix, tiy);
+    const int ty0 = tiy * UP_RH, tx0 = tix * PM_RW;
+    stage_ref_tile<UP_RH, TileT>(sc, tile, tx0, ty0, hr, vr, LUTW ? LUT_TILE_PAD_ROWS : 0);
+    __syncthreads();
+    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31;
+    const int x = tx0 + lx, y = ty0 + ly;
+    const int w = sc->w, h = sc->h;
+    if (x >= w || y >= h) return;
+    const int p = y * w + x;
+    const int own = (ly + vr) * tw + lx + hr;
+
+    const int cx0 = min(x >> 1, cw - 1), cy0 = min(y >> 1, ch - 1);
+    const int cx1 = min(cx0 + 1, cw - 1), cy1 = min(cy0 + 1, ch - 1);
+
+    PixelRef pr;
+    if constexpr (LUTW) pr = hoist_reference_lut(sc, tile, tw, own, wts);
+    else pr = hoist_reference<HR, TileT>(tile, tw, own, wts, hr, vr);
+    // candidates are loaded where they are scored and the winner is kept as its coarse index (an array of the four planes, indexed in
+    // the rolled loop, would live in scratch)
+    int best_q = cy0 * cw + cx0;
+    float best_c = TSAR_MAXCOST, best_rt = 0.f;
+    int best_bv = -1;
+    if (pr.textured) {      // an untextured reference window scores MAXCOST / -1 / 0 for every plane: the first candidate wins
+        best_c = __builtin_inff();
+#pragma unroll 1
+        for (int k = 0; k < 4; k++) {
+            const int q = ((k & 2) ? cy1 : cy0) * cw + ((k & 1) ? cx1 : cx0);
+            int bv = -1;
+            float rt = 0.f;
+            const float c = multiview_cost<NB, HR, STRICT, QUAD, V>(sc, tile, tw, own, wts, pr, x, y, coarse[q], bv, rt);
+            if (c < best_c) { best_c = c; best_q = q; best_bv = bv; best_rt = rt; }
+        }
+    }
+    const float4 best_n = coarse[best_q];
+    n_out[p] = best_n;
+    keep_out[p] = best_n;
+    c_out[p] = best_c;
+    beview_out[p] = best_bv;
+    ratio_out[p] = best_rt;
+}
+
+template <int NB, int HR, bool STRICT, bool QUAD, int V = 0>
+static int launch_up_t(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
+    const DevScene& hs = ctx->hscene;
+    const int tiles_x = (hs.w + PM_RW - 1) / PM_RW, tiles_y = (hs.h + UP_RH - 1) / UP_RH;
+    const int n_tiles = tiles_x * tiles_y;
+    const size_t lds = tile_bytes<QUAD>(PM_RW + 2 * hs.hrad, UP_RH + 2 * hs.vrad + ((V & 1024) ? LUT_TILE_PAD_ROWS : 0)) +
+                       ((V & 1024) ? (size_t)(hs.lut_classes + 1) * 1024 : sizeof(float) * (size_t)(hs.hrad + 1) * (hs.vrad + 1) * PM_BLOCK);
+    auto kern = pm_upsample_kernel<NB, HR, STRICT, QUAD, V>;
+    if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    {
+        ScopedKernelTimer tm(ctx, "pm_upsample");
+        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(PM_BLOCK), lds, ctx->stream, ctx->dscene, coarse, cw, ch, ctx->buf[0].c, ctx->buf[0].n4,
+                           ctx->resize4, ctx->beview, ctx->ratio, tiles_x, n_tiles, strip_width(ctx->strip_w, tiles_x));
+    }
+    TSAR_HIP_TRY(ctx, hipGetLastError());
+    return TSAR_OK;
+}

@@ -295,6 +295,8 @@ static void free_planes(tsar_ctx* ctx) {
     dev_free(ctx->ratio); dev_free(ctx->depth); dev_free(ctx->scale); dev_free(ctx->lrdiff); dev_free(ctx->confid);
     dev_free(ctx->fakedepth); dev_free(ctx->beview); dev_free(ctx->canny); dev_free(ctx->out4);
     dev_free(ctx->memo_cand); dev_free(ctx->memo_seq); dev_free(ctx->changed_seq);
+    dev_free(ctx->resize4);
+    ctx->have_resize = false;
 }
 
 extern "C" int tsar_destroy(tsar_ctx* ctx) {
@@ -406,6 +408,7 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     ctx->have_views = false;
     ctx->have_state = false;
     ctx->have_out = false;
+    ctx->have_resize = false;
     // The image and quad-texture buffers of the previous views are kept when the size is the same (a worker matching view after
     // view of a scene): 2 x n_views hipMalloc + hipFree of ~100 MB each cost 55 ms per call at ETH3D size, more than the copies.
     // Buffers beyond n_views stay in the pool; a change of size releases everything.
@@ -464,6 +467,8 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     }
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     derive_cameras(ctx, cams);
+    ctx->cams.assign(cams, cams + n_views);
+    ctx->views_u8 = elem == 1;
     // Can the matching kernels run this window?  8-bit imagery shares one weight table per workgroup (pm_core_lut.h): any box whose
     // taps have <= TSAR_LUT_MAX_CLASSES distinct distances (every square box; rectangular ones unless their radii have mixed
     // parity, e.g. 63 x 61 -> 202).  Everything else keeps the hoisted bilateral weights per thread in LDS, (hrad+1)(vrad+1) taps
@@ -751,6 +756,98 @@ extern "C" int tsar_compute_disp_final(tsar_ctx* ctx, const float* resize_planes
     ctx->have_out = true;
     return TSAR_OK;
 }
+// ---- coarse-to-fine ------------------------------------------------------------------------------
+// Orders `waiter`'s stream after the work issued so far on `producer`'s (the two contexts' streams are not ordered otherwise).
+static int stream_after(tsar_ctx* waiter, tsar_ctx* producer) {
+    hipEvent_t ev = nullptr;
+    TSAR_HIP_TRY(waiter, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, producer->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(waiter->stream, ev, 0);
+    hipEventDestroy(ev);
+    if (e != hipSuccess) { waiter->err = std::string("stream ordering: ") + hipGetErrorString(e); return TSAR_ERR_HIP; }
+    return TSAR_OK;
+}
+
+extern "C" int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine_in) {
+    CHECK_CTX(coarse);
+    tsar_ctx* fine = const_cast<tsar_ctx*>(fine_in);   // its views are only read; its stream is recorded on
+    if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: fine must be another context");
+    if (fine->device != coarse->device) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the two contexts are on different devices");
+    if (!fine->have_views) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the fine context has no views");
+    const tsar_params& fp = fine->params;
+    const int cw = (fine->w + 1) / 2, ch = (fine->h + 1) / 2;
+    if (cw < fp.box_hsize || ch < fp.box_vsize || cw < 8 || ch < 8)
+        return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the coarse level would be smaller than the matching window (or than 8 x 8)");
+    const int n = fine->n_views;
+    TRY(tsar_set_params(coarse, &fp));
+    std::vector<tsar_camera> cams(fine->cams);
+    for (tsar_camera& c : cams) { c.K[0] *= 0.5f; c.K[2] *= 0.5f; c.K[4] *= 0.5f; c.K[5] *= 0.5f; }   // exact: a power of two
+    const bool u8 = fine->views_u8;
+    int rc = stream_after(coarse, fine);
+    {
+        ScratchScope scratch(coarse);
+        std::vector<const void*> lv(n, nullptr);
+        for (int v = 0; v < n && rc == TSAR_OK; v++) {
+            void* dst = scratch.alloc((size_t)cw * ch * (u8 ? 1 : sizeof(float)));
+            if (!dst) { rc = fail(coarse, TSAR_ERR_NOMEM, "hipMalloc failed"); break; }
+            rc = launch_pyr_down(coarse, fine->img[v], fine->w, fine->h, dst, u8);
+            lv[v] = dst;
+        }
+        if (rc == TSAR_OK) rc = set_views_impl(coarse, n, cw, ch, lv.data(), u8 ? 1 : 4, TSAR_MEM_DEVICE, cams.data());
+        hipStreamSynchronize(coarse->stream);     // the staging buffers go back to the arena
+    }
+    TRY(rc);
+    if (fine->hscene.n_sel >= 1) TRY(tsar_set_view_subset(coarse, fine->hscene.n_sel, fine->hscene.sel));
+    return TSAR_OK;
+}
+
+extern "C" int tsar_upsample_planes(tsar_ctx* fine, const tsar_ctx* coarse_in) {
+    CHECK_CTX(fine);
+    tsar_ctx* coarse = const_cast<tsar_ctx*>(coarse_in);
+    if (!coarse || coarse == fine) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: coarse must be another context");
+    NEED_VIEWS(fine);
+    NEED_SOURCES(fine);
+    if (coarse->device != fine->device) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the two contexts are on different devices");
+    if (!coarse->have_views || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
+        return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one (tsar_pyramid_views)");
+    if (!coarse->have_state) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context has no plane state");
+    if (!fine->resize4) TRY(dev_alloc(fine, &fine->resize4, (size_t)fine->w * fine->h));
+    fine->have_resize = false;
+    TRY(stream_after(fine, coarse));
+    TRY(launch_pm_upsample(fine, coarse->buf[0].n4, coarse->w, coarse->h));
+    TSAR_HIP_TRY(fine, hipStreamSynchronize(fine->stream));
+    fine->have_state = true;
+    fine->have_out = false;
+    fine->have_resize = true;
+    fine->sweeps_done = 0;              // the sweeps that follow draw like the ones after tsar_pm_init
+    fine->cost_consistent = true;       // every cost is its plane's score on the sweep window
+    return TSAR_OK;
+}
+
+extern "C" int tsar_compute_disp_final_upsampled(tsar_ctx* ctx, const float* text, int mem) {
+    CHECK_CTX(ctx);
+    NEED_STATE(ctx);
+    if (!text) return fail(ctx, TSAR_ERR_INVALID, "text is NULL");
+    if (!ctx->have_resize) return fail(ctx, TSAR_ERR_INVALID, "tsar_compute_disp_final_upsampled: no upsampled planes kept (call tsar_upsample_planes first)");
+    const size_t np = (size_t)ctx->w * ctx->h;
+    TmpIn<float> t(ctx, text, np, mem);
+    TRY(t.rc);
+    ctx->cost_consistent = false;
+    TRY(launch_compute_disp_final(ctx, ctx->resize4, t.d));
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->have_out = true;
+    return TSAR_OK;
+}
+
+extern "C" int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (!out || view < 0 || view >= ctx->n_views) return fail(ctx, TSAR_ERR_INVALID, "tsar_get_view_image: view out of range or out is NULL");
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->img[view], (size_t)ctx->w * ctx->h * sizeof(float), out_kind(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSAR_OK;
+}
+
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);

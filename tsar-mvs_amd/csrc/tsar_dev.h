@@ -133,6 +133,11 @@ struct tsar_ctx {
     int call_launch = 0;              // launches since the current tsar_pm_iterate call began
     int memo_mode = 1;                // TSAR_MEMO=0: off
     int compact_from = 6;             // TSAR_COMPACT_FROM=n (-1: never): from launch n of a call on, a wave packs its surviving hypotheses (pm_sweep_impl.h)
+    // coarse-to-fine mode (tsar_pyramid_views / tsar_upsample_planes)
+    std::vector<tsar_camera> cams;    // the cameras tsar_set_views was given (before cam_scale), from which a coarser level derives its own
+    bool views_u8 = false;            // the views came through tsar_set_views_u8 (a coarser level is then an 8-bit decode too)
+    float4* resize4 = nullptr;        // [h][w] the planes the last tsar_upsample_planes chose (the reference's lines->resize4, linestate.h:64)
+    bool have_resize = false;
     const float* final_text = nullptr;   // device lines->text while tsar_pm_iterate_final runs (the kernels' `final` mode), else null
     // timing
     int variant = 2;             // TSAR_VARIANT=n: code-generation variant of the fast-mode tap loop (pm_core.h view_cost); tsar_create picks 250 (med3/fract + D16 window loads + clamp-free loop for in-image windows + wave priority + SGPR-pinned texture base and line-top weight loads + row-wise window walk in fast mode; strict mode runs it as 122, the oracle's column order) when the D16 probe passes, else 114
@@ -241,6 +246,9 @@ static inline bool lut_path_applies(const tsar_ctx* ctx) {
 int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out, uint32_t stream_id,
                                int do_prop, int do_refine, int* launched);   // pm_sweep_experiments.hip (TSAR_EXPERIMENTS builds)
 int launch_pm_cost_planes(tsar_ctx* ctx, const float4* planes, float* cost, int32_t* beview, float* ratio);
+int launch_pm_upsample(tsar_ctx* ctx, const float4* coarse, int cw, int ch);                     // pm_upsample.hip
+int launch_pm_upsample_lut(tsar_ctx* ctx, int need, const float4* coarse, int cw, int ch);       // pm_upsample_lut.hip
+int launch_pyr_down(tsar_ctx* ctx, const float* src, int w, int h, void* dst, bool u8);        // tsar_pyramid.hip
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world);
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);

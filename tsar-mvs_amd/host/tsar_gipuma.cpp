@@ -22,6 +22,12 @@
 //                      GPU's worker with a fresh context; the exit status is non-zero if any view's outputs are still missing.
 //   --num_consistent= --reproj_error= --depth_diff= --angle= --used_list=   the fuser's options (x/1.sh:20-30), for --fuse
 //   --seed=S, --strict, --fix-quirks, --texture-filter-8bit (TSAR_FLAG_TEX_FILTER_8BIT)
+//   --multi_scale=L [--coarse_iterations=N] [--textureless_merge]   (--mode=patchmatch) coarse-to-fine: L pyramid levels
+//                      (tsar_pyramid_views), init + N iterations (default --iterations) at the coarsest, then per finer level
+//                      tsar_upsample_planes + --iterations iterations; --textureless_merge ends with the reference view's weak-texture
+//                      regions and tsar_compute_disp_final_upsampled instead of tsar_compute_disp.  L = 0 (default): single scale.
+//                      --all keeps each worker's coarse contexts across views; APD/<id>/TSAR_multiscale.txt records the settings of a
+//                      multi-scale view's maps, and the resume skips a view only when that record matches the run's settings
 // Images: the scene's JPEGs as they are (host/tsar_jpeg.h: libjpeg's grayscale output = what the reference's imread returns,
 // main.cpp:1302; bit-identical to libjpeg-turbo, tests/test_jpeg_decode.py), or binary PGM / PPM.  A name is looked up as the same
 // stem + .pgm (.ppm with -color_processing) first — a user's own conversion wins — then as the JPEG of that stem.
@@ -60,6 +66,8 @@ struct Options {
     int gpus = 1, workers = 1;      // --all: worker threads per GPU; each overlaps its file output with the next view's kernels
     uint64_t seed = 0;
     std::string mode = "patchmatch";
+    int multi_scale = 0, coarse_iterations = -1;     // -1: --iterations
+    bool coarse_iterations_set = false, textureless_merge = false;
 };
 
 #include "tsar_io.h"
@@ -154,6 +162,7 @@ static void usage() {
     printf("usage: tsar_gipuma <ref image> <source images...> -images_folder DIR/ -mslp_folder DIR/ [-krt_file F] [-output_folder DIR]\n"
            "                   [--iterations=N] [--blocksize=N] [--cost_comb=all|best_n|angle|good] [--n_best=N] [--cam_scale=S]\n"
            "                   [--depth_min=D --depth_max=D] [--mode=patchmatch|load|tsar] [--all --gpus=N --workers=W] [--seed=S] [--strict] [--fix-quirks] [--texture-filter-8bit] [-color_processing] [--display_outputs] [--timing]\n"
+           "                   [--multi_scale=L [--coarse_iterations=N] [--textureless_merge]]\n"
            "       tsar_gipuma --all [--gpus=N] [--force] [--fuse [--num_consistent=N --reproj_error=PX --depth_diff=REL --angle=DEG --used_list=0|1]]\n"
            "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n");
 }
@@ -183,6 +192,19 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
         else if (starts("--workers=")) o.workers = atoi(a + 10);
         else if (starts("--seed=")) o.seed = strtoull(a + 7, nullptr, 10);
         else if (starts("--mode=")) o.mode = a + 7;
+        else if (starts("--multi_scale=") || starts("--coarse_iterations=")) {
+            const bool ms = starts("--multi_scale=");
+            const char* v = strchr(a, '=') + 1;
+            char* end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 0 || k > (ms ? 8 : 1000000)) {
+                printf("Command-line parameter error: %s must be %s\n", a, ms ? "an integer in 0..8" : "a non-negative integer");
+                return -1;
+            }
+            if (ms) o.multi_scale = (int)k;
+            else { o.coarse_iterations = (int)k; o.coarse_iterations_set = true; }
+        }
+        else if (!strcmp(a, "--textureless_merge")) o.textureless_merge = true;
         else if (starts("--check-mask=")) {          // diagnostics, no GPU: decode a weak.png the way --mode=tsar does
             std::vector<float> scale;
             int mw = 0, mh = 0;
@@ -331,12 +353,23 @@ struct HostResult {
     std::string out_dir;        // where the view's .dmb files go
     int w = 0, h = 0;
     tsar_ctx** shared_ctx = nullptr;   // the worker's context, kept across its views (device planes are allocated once)
+    std::vector<tsar_ctx*>* shared_coarse = nullptr;   // --multi_scale: the worker's coarse contexts, finest first, kept likewise
+    std::string ms_record;             // --multi_scale: the settings written beside the maps (empty: single scale, no record)
     bool device_image_cache = false;   // --all: images stay resident on the device across views (a one-view process would only hold every image twice)
 };
+static const char* const MS_RECORD = "TSAR_multiscale.txt";
 static bool write_view_files(const HostResult& r) {   // the two files side by side: a write is a copy into the page cache
+    // the settings record goes first and comes back last: maps that are being replaced never carry the record of other settings
+    unlink((r.out_dir + MS_RECORD).c_str());
     auto normals = std::async(std::launch::async, [&r]() { return write_dmb(r.out_dir + "TSAR_normals.dmb", r.normal.data(), r.h, r.w, 3); });
     const bool depth_ok = write_dmb(r.out_dir + "TSAR_disp.dmb", r.depth.data(), r.h, r.w, 1);
-    return normals.get() && depth_ok;
+    bool ok = normals.get() && depth_ok;
+    if (ok && !r.ms_record.empty()) {
+        FILE* f = fopen((r.out_dir + MS_RECORD).c_str(), "w");
+        ok = f && fputs(r.ms_record.c_str(), f) >= 0;
+        if (f && fclose(f) != 0) ok = false;
+    }
+    return ok;
 }
 
 // Fault injection for the re-queue path (tests): TSAR_GIPUMA_INJECT_FAILURE=<view id>[:<times>] makes the first <times> (default 1)
@@ -353,12 +386,28 @@ static void read_injection() {
 }
 static std::string view_dir_of(const Options& o, int ref) { char b[32]; snprintf(b, sizeof b, "%08d", ref); return o.mslp_folder + "APD/" + b + "/"; }
 static std::string view_image_of(const Options& o, int ref) { char b[32]; snprintf(b, sizeof b, "%08d.pgm", ref); return o.images_folder + pnm_name(b, o.color ? ".ppm" : ".pgm"); }
-// the done marker of a view: both output maps complete for the size of its reference image
+// what a multi-scale view records beside its maps (empty for a single-scale run, which leaves no record)
+static std::string ms_record_of(const Options& o) {
+    if (o.multi_scale == 0) return "";
+    char b[128];
+    snprintf(b, sizeof b, "multi_scale=%d coarse_iterations=%d textureless_merge=%d\n", o.multi_scale,
+             o.coarse_iterations_set ? o.coarse_iterations : o.iterations, o.textureless_merge ? 1 : 0);
+    return b;
+}
+// the done marker of a view: both output maps complete for the size of its reference image, made with this run's multi-scale settings
 static bool outputs_complete(const Options& o, int ref) {
     int w = 0, h = 0;
     if (!view_image_size(view_image_of(o, ref), w, h)) return false;
     const std::string d = view_dir_of(o, ref);
-    return dmb_complete(d + "TSAR_disp.dmb", h, w, 1) && dmb_complete(d + "TSAR_normals.dmb", h, w, 3);
+    if (!dmb_complete(d + "TSAR_disp.dmb", h, w, 1) || !dmb_complete(d + "TSAR_normals.dmb", h, w, 3)) return false;
+    std::string rec;
+    if (FILE* f = fopen((d + MS_RECORD).c_str(), "r")) {
+        char b[256];
+        size_t k;
+        while ((k = fread(b, 1, sizeof b, f)) > 0) rec.append(b, k);
+        fclose(f);
+    }
+    return rec == ms_record_of(o);
 }
 
 static int run_view(const Options& o, int device, const std::vector<std::string>& names, const std::vector<int>& subset_slots, int ref_id, double* seconds,
@@ -482,6 +531,31 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
         if (!ext.normal_ok || ext.nh != h || ext.nw != w || ext.nnb != 3) { fprintf(stderr, "cannot read %snormals.dmb\n", out_dir.c_str()); drop_ctx(); return -1; }
         if (tsar_load_planes(ctx, ext.depth(), ext.normal(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
         stamp("load_planes");
+    } else if (o.multi_scale > 0) {
+        // coarse to fine: the pyramid below ctx, init + coarse iterations at the coarsest level, upsample + iterations at each finer one
+        std::vector<tsar_ctx*> own_coarse;
+        std::vector<tsar_ctx*>& coarse = (reuse && reuse->shared_coarse) ? *reuse->shared_coarse : own_coarse;
+        auto drop_coarse = [&]() { for (tsar_ctx* c : coarse) tsar_destroy(c); coarse.clear(); };
+        auto ms_fail = [&](const char* what, tsar_ctx* c) { fprintf(stderr, "%s: %s\n", what, tsar_last_error(c)); drop_coarse(); drop_ctx(); return -1; };
+        while ((int)coarse.size() < o.multi_scale) {
+            tsar_ctx* c = nullptr;
+            const int rc = tsar_create(device, &c);
+            if (rc != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed: %d\n", device, rc); drop_coarse(); drop_ctx(); return rc; }
+            coarse.push_back(c);
+        }
+        const int L = o.multi_scale;
+        for (int k = 0; k < L; k++)
+            if (tsar_pyramid_views(coarse[k], k ? coarse[k - 1] : ctx) != TSAR_OK) return ms_fail("tsar_pyramid_views", coarse[k]);
+        stamp("pyramid_views");
+        if (tsar_pm_init(coarse[L - 1]) != TSAR_OK) return ms_fail("tsar_pm_init (coarsest level)", coarse[L - 1]);
+        if (tsar_pm_iterate(coarse[L - 1], o.coarse_iterations_set ? o.coarse_iterations : o.iterations) != TSAR_OK) return ms_fail("tsar_pm_iterate (coarsest level)", coarse[L - 1]);
+        for (int k = L - 1; k >= 0; k--) {
+            tsar_ctx* finer = k ? coarse[k - 1] : ctx;
+            if (tsar_upsample_planes(finer, coarse[k]) != TSAR_OK) return ms_fail("tsar_upsample_planes", finer);
+            if (tsar_pm_iterate(finer, o.iterations) != TSAR_OK) return ms_fail("tsar_pm_iterate", finer);
+        }
+        if (&coarse == &own_coarse) drop_coarse();
+        stamp("coarse-to-fine pm_init + pm_iterate");
     } else {
         if (tsar_pm_init(ctx) != TSAR_OK) return fail("tsar_pm_init");
         if (o.timing) { tsar_synchronize(ctx); stamp("pm_init (first launch of its code object)"); }
@@ -508,6 +582,15 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
         if (tsar_fill_textureless(ctx) != TSAR_OK) return fail("tsar_fill_textureless");
         stamp("fake_depth + fill_textureless");
         printf("view %08d: %d regions labelled, textureless ones refitted and filled\n", ref_id, n_regions);
+    } else if (o.textureless_merge) {
+        // TSAR's multi-scale merge (gipuma_compute_disp_final): lines->text = the region text of each pixel's weak-texture label
+        std::vector<int32_t> labels(np);
+        std::vector<float> region_text(np), text(np);
+        int n_regions = 0;
+        if (tsar_detect_weak_texture(ctx, labels.data(), TSAR_MEM_HOST, &n_regions, region_text.data(), nullptr, (int)np) != TSAR_OK) return fail("tsar_detect_weak_texture");
+        for (size_t p = 0; p < np; p++) text[p] = region_text[labels[p]];
+        if (tsar_compute_disp_final_upsampled(ctx, text.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_compute_disp_final_upsampled");
+        stamp("detect_weak_texture + compute_disp_final_upsampled");
     } else if (tsar_compute_disp(ctx) != TSAR_OK) return fail("tsar_compute_disp");
     if (sizing.valid()) sizing.get();
     PinnedFloats &depth = hr.depth, &normal = hr.normal;
@@ -521,6 +604,7 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
         if (tsar_get_result(ctx, keep->depth, keep->normal, nullptr, nullptr, TSAR_MEM_DEVICE) != TSAR_OK) return fail("tsar_get_result (device)");
     }
     hr.out_dir = out_dir; hr.w = w; hr.h = h;
+    hr.ms_record = ms_record_of(o);
     if (!defer_write && !write_view_files(hr)) return -1;      // deferred: the caller writes while the next view is being matched
     if (!defer_write) stamp("write .dmb");
     if (o.timing) {
@@ -579,6 +663,10 @@ int main(int argc, char** argv) {
     const int pr = parse_args(argc, argv, o);
     if (pr != 0) return pr < 0 ? 1 : 0;
     if (o.mslp_folder.empty() || o.images_folder.empty()) { usage(); return 1; }
+    if (o.multi_scale > 0 || o.coarse_iterations_set || o.textureless_merge) {
+        if (o.mode != "patchmatch") { fprintf(stderr, "--multi_scale / --coarse_iterations / --textureless_merge work with --mode=patchmatch only\n"); return 1; }
+        if (o.multi_scale == 0) { fprintf(stderr, "--coarse_iterations / --textureless_merge need --multi_scale=L with L >= 1\n"); return 1; }
+    }
     if (o.mslp_folder.back() != '/') o.mslp_folder += '/';
     if (o.images_folder.back() != '/') o.images_folder += '/';
     std::map<int, std::vector<int>> pairs;
@@ -620,7 +708,9 @@ int main(int argc, char** argv) {
                 // kernels of view k+1 run (file output is ~0.1 s of a 0.5 s view at ETH3D size)
                 HostResult host_result[2];
                 tsar_ctx* worker_ctx = nullptr;
+                std::vector<tsar_ctx*> worker_coarse;
                 host_result[0].shared_ctx = host_result[1].shared_ctx = &worker_ctx;
+                host_result[0].shared_coarse = host_result[1].shared_coarse = &worker_coarse;
                 host_result[0].device_image_cache = host_result[1].device_image_cache = true;
                 std::future<bool> writing[2];
                 // refinement modes: a ring of (page-locked) input buffers; the maps, weak.png and reference image of the next seven
@@ -665,6 +755,7 @@ int main(int argc, char** argv) {
                 }
                 for (auto& f : writing)
                     if (f.valid() && !f.get()) status[t] = -1;
+                for (tsar_ctx* c : worker_coarse) tsar_destroy(c);
                 tsar_destroy(worker_ctx);
             });
         for (auto& t : th) t.join();
