@@ -250,6 +250,47 @@ int tsar_compute_disp_final_upsampled(tsar_ctx* ctx, const float* text, int mem)
 /* Diagnostics: the image of view `view` as the context holds it, [h][w] float32 (a pyramid level's views included). */
 int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem);
 
+/* ---- geometric consistency ----------------------------------------------------------------- */
+/* A second PatchMatch pass whose cost also asks whether the source views' depth maps agree (the ACMM / APD family's geometric
+ * consistency).  With maps installed, view v's cost of hypothesis plane n4 at reference pixel (x, y) becomes c_v + lambda e_v.  Validity
+ * (c_v < MAXCOST, gipuma.cu:506-510) is decided on the photometric c_v before the term is added; best-N, best view and ratio then
+ * proceed as without the term, on the summed costs.  A view without a map (NULL entry) adds nothing.
+ * e_v, in float32, every operation one IEEE-754 operation rounded to nearest (no fused multiply-add), in exactly this order:
+ *   D  = the hypothesis's depth at (x, y) (getDepthFromPlane3_cu, gipuma.cu:436-453; once per hypothesis);  X = float(x), Y = float(y)
+ *   F  = [A | b] of view v: A = K_v R K_ref^-1, b = K_v t, the float32 matrices the context holds for the fast homography (rounded
+ *        once from float64: tsar_set_views), so that F (x D, y D, D, 1) is K_v (R (D K_ref^-1 (x, y, 1)) + t);
+ *        xd = X * D, yd = Y * D;  a_r = ((F[r][0] * xd + F[r][1] * yd) + F[r][2] * D) + F[r][3]  for r = 0, 1, 2 -> (a, b, s)
+ *   u = a / s, v = b / s (correctly rounded quotients);  c = floor(u + 0.5), r = floor(v + 0.5) (the sum rounded first)
+ *   inside = s > 0 and 0 <= c <= w - 1 and 0 <= r <= h - 1;  D_v = depth_v[r][c] if inside, else 0
+ *   B  = the 3 x 4 matrix [K_ref R^T K_v^-1 | -K_ref R^T t] of view v, formed in float64 from the float64 K_ref, K_v, R, t from which
+ *        tsar_set_views rounds its float32 cameras (K_v^-1 by the adjugate, then the products (K_ref R^T) K_v^-1 and -(K_ref R^T) t,
+ *        each entry a sum over k in increasing order), each entry rounded once to float32.  It takes (c D_v, r D_v, D_v, 1) to the
+ *        reference image: cd = c * D_v, rd = r * D_v;  p_r = ((B[r][0] * cd + B[r][1] * rd) + B[r][2] * D_v) + B[r][3]
+ *   x' = p_0 / p_2, y' = p_1 / p_2 (correctly rounded);  dx = x' - X, dy = y' - Y;  e2 = dx * dx + dy * dy
+ *   e  = tau if not (inside and D_v > 0 and p_2 > 0 and e2 < tau * tau) (this covers every non-finite intermediate: NaN fails each
+ *        comparison); else 0 if e2 < 2^-100; else min(sqrt(e2), tau), the square root correctly rounded
+ *   the view's cost: c_v + (lambda * e)
+ * tsar_get_geom_matrices returns F and B as the kernels read them (row-major 3 x 4).  Defaults lambda = 0.2, tau = 3 px are ACMM's
+ * (not the reference's, whose live path reads such a pass's output from a closed binary, main.cpp:1462-1474).
+ *
+ * tsar_set_geom_depths: depth[v], v >= 1, is view v's depth map [h][w] in its own camera (what tsar_get_result / TSAR_disp.dmb hold;
+ * <= 0 = no estimate); depth[0] is ignored; NULL = no term for that view.  The maps are copied into memory the context owns.  Voids the
+ * stored costs and the propagation memo (like tsar_set_view_subset).  TSAR_ERR_INVALID: n_views other than the context's, depth NULL,
+ * weight < 0 or not finite, clip not in (0, 2^20]; TSAR_ERR_STATE: a context without source views.  tsar_set_views removes the term.
+ * With a term installed every plane-scoring entry includes it (tsar_pm_init, tsar_pm_iterate[_final], tsar_pm_sweep,
+ * tsar_pm_cost_planes, tsar_pm_rescore; the sweeps are timed as "pm_sweep_geom"); tsar_pyramid_views and tsar_upsample_planes return
+ * TSAR_ERR_STATE (coarse-to-fine with the term is not supported).
+ * tsar_clear_geom: removes the term and frees the maps.
+ * tsar_pm_rescore: scores the current planes with the context's cost (the term included when installed) and writes cost, best view and
+ * ratio.  A pixel whose plane is not a valid hypothesis — its depth not finite or outside [depth_min, depth_max], as the depth-0
+ * pixels of a loaded map are — instead gets the hypothesis tsar_pm_init draws there, with its score.  Afterwards every stored cost is
+ * its plane's score (the sweeps' memo holds), and the sweep counter restarts at 0 as after tsar_pm_init, so a pass does not depend on
+ * what the context ran before.  Timed as "pm_rescore". */
+int tsar_set_geom_depths(tsar_ctx* ctx, int n_views, const float* const* depth, int mem, float weight, float clip);
+int tsar_clear_geom(tsar_ctx* ctx);
+int tsar_pm_rescore(tsar_ctx* ctx);
+int tsar_get_geom_matrices(tsar_ctx* ctx, int view, float* forward, float* back);   /* forward[12], back[12], row-major 3 x 4 */
+
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */
 int tsar_get_result(tsar_ctx* ctx, float* depth, float* normal_world, float* cost, float* confid,

@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "tsar_pm_init", "tsar_pm_iterate", "tsar_pm_iterate_final", "tsar_pm_sweep", "tsar_set_sweep_counter", "tsar_pm_cost_planes", "tsar_set_plane", "tsar_get_plane",
     "tsar_load_planes", "tsar_compute_disp", "tsar_compute_disp_final", "tsar_depth_to_plane", "tsar_get_result",
     "tsar_pyramid_views", "tsar_upsample_planes", "tsar_compute_disp_final_upsampled", "tsar_get_view_image",
+    "tsar_set_geom_depths", "tsar_clear_geom", "tsar_pm_rescore", "tsar_get_geom_matrices",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -115,6 +116,10 @@ def load_library(path: str = LIB_PATH):
     L.tsar_upsample_planes.argtypes = [C.c_void_p, C.c_void_p]
     L.tsar_compute_disp_final_upsampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_view_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.tsar_set_geom_depths.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_float, C.c_float]
+    L.tsar_clear_geom.argtypes = [C.c_void_p]
+    L.tsar_pm_rescore.argtypes = [C.c_void_p]
+    L.tsar_get_geom_matrices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -341,6 +346,43 @@ class Matcher:
         p, kind = _ptr(t)
         self._chk(self.L.tsar_compute_disp_final_upsampled(self._ctx, p, kind))
 
+    # ---- geometric consistency ----
+    def set_geom_depths(self, depths, weight: float = 0.2, clip: float = 3.0):
+        """install the source views' depth maps for the geometric-consistency term (tsar_set_geom_depths): depths[v] is view v's
+        [h, w] depth in its own camera (numpy or torch; <= 0 = no estimate) or None (no term for v); depths[0] is ignored.
+        weight = lambda, clip = tau in pixels (ACMM's defaults)."""
+        n = len(depths)
+        ptrs = (C.c_void_p * n)()
+        keep, kinds = [], set()
+        for v, d in enumerate(depths):
+            if v == 0 or d is None:
+                continue
+            if not _is_torch(d):
+                d = np.ascontiguousarray(d, np.float32)
+            assert tuple(d.shape) == (self.h, self.w), "depth map %d has shape %s, the views are %dx%d" % (v, tuple(d.shape), self.w, self.h)
+            keep.append(d)
+            p, kind = _ptr(d)
+            ptrs[v] = p
+            kinds.add(kind)
+        assert len(kinds) <= 1, "all depth maps must live in the same memory space"
+        self._chk(self.L.tsar_set_geom_depths(self._ctx, n, ptrs, kinds.pop() if kinds else MEM_HOST, float(weight), float(clip)))
+
+    def clear_geom(self):
+        """remove the geometric-consistency term (tsar_clear_geom)"""
+        self._chk(self.L.tsar_clear_geom(self._ctx))
+
+    def rescore(self):
+        """score the current planes with the context's cost, the geometric term included; pixels whose plane is not a valid hypothesis
+        get tsar_pm_init's draw (tsar_pm_rescore)"""
+        self._chk(self.L.tsar_pm_rescore(self._ctx))
+
+    def get_geom_matrices(self, view: int):
+        """(forward, back): the two float32 3 x 4 matrices of view's geometric term as the kernels read them (include/tsar.h)"""
+        f = np.empty((3, 4), np.float32)
+        b = np.empty((3, 4), np.float32)
+        self._chk(self.L.tsar_get_geom_matrices(self._ctx, view, _ptr(f)[0], _ptr(b)[0]))
+        return f, b
+
     def get_result(self, want=("depth", "normal", "cost", "confid"), pinned=False, out=None):
         """pinned=True: the result arrays are page-locked (tsar_host_alloc), so the D2H copies run at PCIe rate.
         out: dict of caller-owned arrays to fill instead (e.g. page-locked ones allocated once and reused per view)."""
@@ -548,6 +590,19 @@ def run_multiscale(matcher: Matcher, levels: int, coarse_iters: int, fine_iters:
         chain[k].upsample_planes(chain[k + 1])
         chain[k].pm_iterate(fine_iters)
     return coarse
+
+
+def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, iters: int, weight: float = 0.2, clip: float = 3.0):
+    """The geometric-consistency pass of one reference view: start from its own photometric result (depth [h, w], world normals
+    [h, w, 3]), install the source views' depth maps (src_depths[v] for view v of the matcher, [0] ignored, None = no term), rescore,
+    run `iters` iterations with the term, compute_disp.  The term stays installed (clear_geom removes it)."""
+    if iters < 0:
+        raise ValueError("iters must be >= 0")
+    matcher.load_planes(own_depth, own_normal_world)
+    matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
+    matcher.rescore()
+    matcher.pm_iterate(iters)
+    matcher.compute_disp()
 
 
 def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = None, cap: int | None = None, device: int = 0, matcher=None):

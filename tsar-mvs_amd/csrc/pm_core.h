@@ -192,17 +192,62 @@ DEVFN float view_cost_generic(const DevScene* __restrict__ sc, const DevView& vw
 #include "pm_tap_r5.h"     // view_cost_r5: the production loop for box 11 on 8-bit imagery (variants 114 / 122 / 250, + 131072 = buffer loads)
 #include "pm_core_lut.h"   // view_cost_lut: any window, weights from a shared table (variant bit 10; chunk length in bits 11-13)
 
+// The geometric-consistency term lambda e of view vi for the hypothesis whose depth at (x, y) is D (include/tsar.h states the
+// sequence; tests/test_geom_cpu.py restates it in numpy float32).  Every operation is one IEEE fp32 operation (no contraction: the
+// library is built with -ffp-contract=off and no fma_ is written here); the two quotient pairs are persp_divide_exact's correctly rounded
+// ones and the root is sqrt_rsq_exact's, so the value is the same in both arithmetic modes.  The projection into the view uses
+// DevView A = K_v R K_ref^-1 and b = K_v t (the point D K_ref^-1 (x, y, 1) moved and projected in one 3 x 4 product), the way back
+// the host's geom_back matrix.  A view without a depth map adds 0 (scalar branch: the pointer is wave-uniform).
+DEVFN float geom_term(const DevScene* __restrict__ sc, const DevView& vw, int vi, int x, int y, float D) {
+    const float* dm = sc->geom_depth[vi];
+    if (dm == nullptr) return 0.0f;
+    const int w = sc->w, h = sc->h;
+    const float xf = (float)x, yf = (float)y;
+    const float xd = xf * D, yd = yf * D;
+    const float a = ((vw.A[0] * xd + vw.A[1] * yd) + vw.A[2] * D) + vw.b[0];
+    const float b = ((vw.A[3] * xd + vw.A[4] * yd) + vw.A[5] * D) + vw.b[1];
+    const float s = ((vw.A[6] * xd + vw.A[7] * yd) + vw.A[8] * D) + vw.b[2];
+    float u, v;
+    persp_divide_exact<true>(a, b, s, u, v);
+    const float cf = floorf(u + 0.5f), rf = floorf(v + 0.5f);
+    // (NaN fails every comparison: a non-finite projection is "outside")
+    const bool inside = s > 0.0f && cf >= 0.0f && cf <= (float)(w - 1) && rf >= 0.0f && rf <= (float)(h - 1);
+    float Dv = 0.0f;
+    if (inside) Dv = ((global_f32_ptr)dm)[(int)rf * w + (int)cf];
+    const float* M = sc->geom_back[vi];
+    const float cd = cf * Dv, rd = rf * Dv;
+    const float p0 = ((M[0] * cd + M[1] * rd) + M[2] * Dv) + M[3];
+    const float p1 = ((M[4] * cd + M[5] * rd) + M[6] * Dv) + M[7];
+    const float p2 = ((M[8] * cd + M[9] * rd) + M[10] * Dv) + M[11];
+    float xq, yq;
+    persp_divide_exact<true>(p0, p1, p2, xq, yq);
+    const float dx = xq - xf, dy = yq - yf;
+    const float e2 = dx * dx + dy * dy;
+    const float tau = sc->geom_clip;
+    // e2 in [2^-100, tau^2): the correctly rounded root (sqrt_rsq_exact's range holds: tau <= 2^20); below: 0; else (also NaN): tau
+    const float r = sqrt_rsq_exact(fminf(fmaxf(e2, 0x1p-100f), 0x1p100f));
+    float e = e2 < 0x1p-100f ? 0.0f : r;
+    e = (inside && Dv > 0.0f && p2 > 0.0f && e2 < sc->geom_clip_sq) ? fminf(e, tau) : tau;
+    return sc->geom_weight * e;
+}
+
 // pmCostMultiview_cu gipuma.cu:455-518: best-N combination over the selected views.  The NB
 // smallest costs are kept sorted in registers (sort_small :425-434 sorts all of them).
+// V & TSAR_V_GEOM: each view's cost becomes c_v + lambda e_v (geom_term) after the validity test, which stays on c_v; the depth of the
+// hypothesis at (x, y) is computed once, before the view loop.  The other bits of V name the tap loop.
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileOf<QUAD>::type* tile, int tw, int own, const float* wts, const PixelRef& pr,
                            int x, int y, const float4& n4, int& beview, float& ratio) {
+    constexpr bool GEOM = (V & TSAR_V_GEOM) != 0;
+    constexpr int VT = V & ~(TSAR_V_GEOM | TSAR_V_REDRAW);
     float best[NB];
 #pragma unroll
     for (int k = 0; k < NB; k++) best[k] = __builtin_inff();
     const int num = sc->n_sel;
     int valid = 0, bv = -1;
     float cmin = __builtin_inff();
+    float depth_h = 0.0f;
+    if constexpr (GEOM) depth_h = plane_depth(sc->ref, n4, x, y);
     int vi_next = sc->sel[0];
     for (int i = 0; i < num; i++) {
         // the NEXT view's index is loaded now (scalar load, wave-uniform), a whole view of tap loops ahead of its use: otherwise
@@ -212,15 +257,15 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
         float c;
         // V names the tap loop: bit 10 = the general-window loop (chunk length in bits 11-13), a production variant of the box-11
         // loop (pm_tap_r5.h), 0 = the generic one-tap loop; anything else exists in the experiments build only
-        if constexpr ((V & 1024) != 0) c = view_cost_lut<STRICT, (V >> 11) & 7, (V & 131072) != 0 && !STRICT, (V & 2097152) != 0 && !STRICT>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
-        else if constexpr (QUAD && HR == 5 && r5_production_variant(V))
-            c = view_cost_r5<STRICT, (V & 128) != 0 && !STRICT, (V & 8) != 0, (V & 131072) != 0, (V & 2097152) != 0, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
+        if constexpr ((VT & 1024) != 0) c = view_cost_lut<STRICT, (VT >> 11) & 7, (VT & 131072) != 0 && !STRICT, (VT & 2097152) != 0 && !STRICT>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
+        else if constexpr (QUAD && HR == 5 && r5_production_variant(VT))
+            c = view_cost_r5<STRICT, (VT & 128) != 0 && !STRICT, (VT & 8) != 0, (VT & 131072) != 0, (VT & 2097152) != 0, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
 #ifdef TSAR_EXPERIMENTS
-        else if constexpr (QUAD && HR == 5 && r5_diag_variant(V))
-            c = view_cost_r5<false, true, true, true, true, BLK, (V & 4194304) ? 1 : 2>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
+        else if constexpr (QUAD && HR == 5 && r5_diag_variant(VT))
+            c = view_cost_r5<false, true, true, true, true, BLK, (VT & 4194304) ? 1 : 2>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
 #endif
         else {
-            static_assert(V == 0, "unknown tap-loop variant");
+            static_assert(VT == 0, "unknown tap-loop variant");
             c = view_cost_generic<HR, STRICT, QUAD, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
         }
         // if (c < MAXCOST) valid++; else c = MAXCOST;  if (c <= cmin) { cmin = c; bv = vi; } (last view attaining the minimum,
@@ -232,6 +277,7 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
         auto vmax = [](float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; };
         c = vmin(c, TSAR_MAXCOST);
         valid -= (int32_t)__float_as_uint(c - TSAR_MAXCOST) >> 31;
+        if constexpr (GEOM) c = c + geom_term(sc, sc->view[vi], vi, x, y, depth_h);     // (validity was decided on the photometric cost)
         {
             const uint32_t worse = (uint32_t)((int32_t)__float_as_uint(cmin - c) >> 31);      // all ones where c > cmin (cmin = +inf at first: inf - c > 0)
             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(bv) : "v"(worse), "v"(bv), "s"(vi));       // (worse & bv) | (~worse & vi): the compiler turns the C form back into v_cmp + v_cndmask

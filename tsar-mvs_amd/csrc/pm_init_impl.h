@@ -34,7 +34,16 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_full_kernel(const DevScene* __res
     const DevRef& rf = sc->ref;
 
     float4 n4;
-    if (INIT) {
+    // V & TSAR_V_REDRAW (tsar_pm_rescore): the given plane stays where its depth at (x, y) is a valid hypothesis (finite, inside
+    // [depthMin, depthMax]); elsewhere the pixel draws what tsar_pm_init draws there.  Either way the plane is scored and written.
+    constexpr bool REDRAW = INIT && (V & TSAR_V_REDRAW) != 0;
+    bool draw = true;
+    if constexpr (REDRAW) {
+        n4 = planes_in[p];
+        const float d = plane_depth(rf, n4, x, y);
+        draw = !(d >= rf.depthMin && d <= rf.depthMax);
+    }
+    if (INIT && draw) {
         float vv[3];
         view_vector(rf, x, y, vv);
         Rand4 rn = philox_uniform4((uint32_t)p, 0u, 0u, sc->seed_lo, sc->seed_hi);
@@ -58,10 +67,11 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_full_kernel(const DevScene* __res
         const float depth = rf.f * rf.baseline / disp;
         n4.x = n[0]; n4.y = n[1]; n4.z = n[2];
         n4.w = plane_offset(rf, n, x, y, depth);
-        n_out[p] = n4;
-    } else {
+        if constexpr (!REDRAW) n_out[p] = n4;
+    } else if (!INIT) {
         n4 = planes_in[p];
     }
+    if constexpr (REDRAW) n_out[p] = n4;
     PixelRef pr;
     if constexpr (LUTW) pr = hoist_reference_lut(sc, tile, tw, own, wts);
     else pr = hoist_reference<HR, TileT>(tile, tw, own, wts, hr, vr);
@@ -69,7 +79,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_full_kernel(const DevScene* __res
     int bv = -1;
     if (pr.textured) cost = multiview_cost<NB, HR, STRICT, QUAD, V>(sc, tile, tw, own, wts, pr, x, y, n4, bv, rt);
     c_out[p] = cost;
-    if (!INIT) {
+    if (!INIT || REDRAW) {
         if (beview_out) beview_out[p] = bv;
         if (ratio_out) ratio_out[p] = rt;
     }
@@ -85,10 +95,20 @@ static int launch_full_t(tsar_ctx* ctx, const float4* planes, float* c, float4* 
     auto kern = pm_full_kernel<NB, HR, STRICT, QUAD, INIT, V>;
     if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
-        ScopedKernelTimer tm(ctx, INIT ? "pm_init" : "pm_cost_planes");
+        ScopedKernelTimer tm(ctx, (INIT && (V & TSAR_V_REDRAW)) ? "pm_rescore" : INIT ? "pm_init" : "pm_cost_planes");
         hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(PM_BLOCK), lds, ctx->stream, ctx->dscene, planes, c, n, bv, rt, tiles_x, n_tiles, strip_width(ctx->strip_w, tiles_x));
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;
 }
 
+// The production launchers' entry: with a geometric-consistency term installed the same kernel with variant bit 24; tsar_pm_rescore
+// (ctx->rescoring) runs the initialising form with bit 25 as well (which always carries the term's code: without maps every view's
+// term is 0 and the scores are the photometric ones bit for bit).
+template <int NB, int HR, bool STRICT, bool QUAD, bool INIT, int V = 0>
+static int launch_full_g(tsar_ctx* ctx, const float4* planes, float* c, float4* n, int32_t* bv, float* rt) {
+    if constexpr (INIT)
+        if (ctx->rescoring) return launch_full_t<NB, HR, STRICT, QUAD, true, V | TSAR_V_GEOM | TSAR_V_REDRAW>(ctx, planes, c, n, bv, rt);
+    if (ctx->hscene.geom_on) return launch_full_t<NB, HR, STRICT, QUAD, INIT, V | TSAR_V_GEOM>(ctx, planes, c, n, bv, rt);
+    return launch_full_t<NB, HR, STRICT, QUAD, INIT, V>(ctx, planes, c, n, bv, rt);
+}

@@ -7,9 +7,9 @@
 template <int NB, bool STRICT, bool INIT>
 static int launch_full_lut_nsi(tsar_ctx* ctx, int ch, const float4* planes, float* c, float4* n, int32_t* bv, float* rt) {
     switch (ch) {
-        case 4: return launch_full_t<NB, 0, STRICT, true, INIT, LUT_V(4)>(ctx, planes, c, n, bv, rt);
-        case 5: return launch_full_t<NB, 0, STRICT, true, INIT, LUT_V(5)>(ctx, planes, c, n, bv, rt);
-        default: return launch_full_t<NB, 0, STRICT, true, INIT, LUT_V(6)>(ctx, planes, c, n, bv, rt);
+        case 4: return launch_full_g<NB, 0, STRICT, true, INIT, LUT_V(4)>(ctx, planes, c, n, bv, rt);
+        case 5: return launch_full_g<NB, 0, STRICT, true, INIT, LUT_V(5)>(ctx, planes, c, n, bv, rt);
+        default: return launch_full_g<NB, 0, STRICT, true, INIT, LUT_V(6)>(ctx, planes, c, n, bv, rt);
     }
 }
 template <int NB, bool STRICT>

@@ -457,7 +457,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
 
 // the tap loops of 8-bit imagery — box 11's own and the general-window one — have a packed form (CMP) beside the rolled one
 template <int HR, bool QUAD, int V>
-constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V)) || (V & 1024) != 0); }
+constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~TSAR_V_GEOM)) || (V & 1024) != 0); }
 
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
@@ -492,7 +492,7 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
     }
     if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
-        ScopedKernelTimer tm(ctx, "pm_sweep");
+        ScopedKernelTimer tm(ctx, (V & TSAR_V_GEOM) ? "pm_sweep_geom" : "pm_sweep");
         ScopedKernelTimer tm_packed(ctx, packed ? "pm_sweep_packed" : nullptr);      // (the packed launches a second time under their own name)
         hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(BLK), lds, ctx->stream, ctx->dscene, colour, same_in.c, same_in.n4, other.c,
                            other.n4, same_out.c, same_out.n4, ctx->ratio, ctx->beview, stream_id, do_prop, do_refine, tiles_x, n_tiles,
@@ -500,4 +500,14 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;
+}
+
+// The production launchers' entry: the same kernel with the geometric-consistency term (variant bit 24) while one is installed
+// (tsar_set_geom_depths).  The maps are fixed for the whole call, so a plane's score is still a function of the plane and the pixel:
+// the memo and the packed form hold as they are.
+template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
+static int launch_sweep_g(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
+                          uint32_t stream_id, int do_prop, int do_refine) {
+    if (ctx->hscene.geom_on) return launch_sweep_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, BLK>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
+    return launch_sweep_t<NB, HR, STRICT, QUAD, V, BLK>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
 }

@@ -148,6 +148,19 @@ static void derive_cameras(tsar_ctx* ctx, const tsar_camera* cams) {
             for (int i = 0; i < 9; i++) dv.A[i] = (float)A[i];
             for (int r = 0; r < 3; r++) dv.b[r] = (float)(Kv[3 * r] * trel[0] + Kv[3 * r + 1] * trel[1] + Kv[3 * r + 2] * trel[2]);
         }
+        {                                                        // geometric consistency, the way back: [K0 R^T Kv^-1 | -K0 R^T t]
+            double Kvinv[9], RT[9], K0RT[9], B[9];
+            inv3(Kv, Kvinv);
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) RT[3 * r + c] = Rrel[3 * c + r];
+            mul3(K0, RT, K0RT);
+            mul3(K0RT, Kvinv, B);
+            float* G = sc.geom_back[v];
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) G[4 * r + c] = (float)B[3 * r + c];
+                G[4 * r + 3] = (float)(-(K0RT[3 * r] * trel[0] + K0RT[3 * r + 1] * trel[1] + K0RT[3 * r + 2] * trel[2]));
+            }
+        }
         if (v == 0) {
             DevRef& rf = sc.ref;
             double Kinv[9], M[9], Minv[9];
@@ -290,6 +303,12 @@ static void free_views(tsar_ctx* ctx) {
     ctx->quad.clear();
     ctx->dquad.clear();
 }
+static void free_geom(tsar_ctx* ctx) {
+    for (auto& p : ctx->geom_maps) dev_free(p);
+    ctx->geom_maps.clear();
+    for (auto& p : ctx->hscene.geom_depth) p = nullptr;
+    ctx->hscene.geom_on = 0;
+}
 static void free_planes(tsar_ctx* ctx) {
     for (int b = 0; b < 2; b++) { dev_free(ctx->buf[b].c); dev_free(ctx->buf[b].n4); }
     dev_free(ctx->ratio); dev_free(ctx->depth); dev_free(ctx->scale); dev_free(ctx->lrdiff); dev_free(ctx->confid);
@@ -306,6 +325,7 @@ extern "C" int tsar_destroy(tsar_ctx* ctx) {
     drain_timers(ctx);
     free_views(ctx);
     free_planes(ctx);
+    free_geom(ctx);
     dev_free(ctx->dscene); dev_free(ctx->region_text); dev_free(ctx->region_size); dev_free(ctx->region_n4);
     if (ctx->scratch.base) hipFree(ctx->scratch.base);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
@@ -409,6 +429,7 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     ctx->have_state = false;
     ctx->have_out = false;
     ctx->have_resize = false;
+    free_geom(ctx);                        // depth maps of the previous views' sources: not this scene's
     // The image and quad-texture buffers of the previous views are kept when the size is the same (a worker matching view after
     // view of a scene): 2 x n_views hipMalloc + hipFree of ~100 MB each cost 55 ms per call at ETH3D size, more than the copies.
     // Buffers beyond n_views stay in the pool; a change of size releases everything.
@@ -774,6 +795,8 @@ extern "C" int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine_in) {
     if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: fine must be another context");
     if (fine->device != coarse->device) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the two contexts are on different devices");
     if (!fine->have_views) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the fine context has no views");
+    if (fine->hscene.geom_on || coarse->hscene.geom_on)
+        return fail(coarse, TSAR_ERR_STATE, "tsar_pyramid_views: coarse-to-fine with a geometric-consistency term is not supported (tsar_clear_geom first)");
     const tsar_params& fp = fine->params;
     const int cw = (fine->w + 1) / 2, ch = (fine->h + 1) / 2;
     if (cw < fp.box_hsize || ch < fp.box_vsize || cw < 8 || ch < 8)
@@ -808,6 +831,8 @@ extern "C" int tsar_upsample_planes(tsar_ctx* fine, const tsar_ctx* coarse_in) {
     NEED_VIEWS(fine);
     NEED_SOURCES(fine);
     if (coarse->device != fine->device) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the two contexts are on different devices");
+    if (fine->hscene.geom_on || coarse->hscene.geom_on)
+        return fail(fine, TSAR_ERR_STATE, "tsar_upsample_planes: coarse-to-fine with a geometric-consistency term is not supported (tsar_clear_geom first)");
     if (!coarse->have_views || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
         return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one (tsar_pyramid_views)");
     if (!coarse->have_state) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context has no plane state");
@@ -845,6 +870,82 @@ extern "C" int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem)
     if (!out || view < 0 || view >= ctx->n_views) return fail(ctx, TSAR_ERR_INVALID, "tsar_get_view_image: view out of range or out is NULL");
     TSAR_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->img[view], (size_t)ctx->w * ctx->h * sizeof(float), out_kind(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSAR_OK;
+}
+
+// ---- geometric consistency -----------------------------------------------------------------------
+extern "C" int tsar_set_geom_depths(tsar_ctx* ctx, int n_views, const float* const* depth, int mem, float weight, float clip) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (ctx->n_views < 2 || ctx->hscene.n_sel < 1) return fail(ctx, TSAR_ERR_STATE, "tsar_set_geom_depths: the context has no source views");
+    if (n_views != ctx->n_views) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: n_views must be the context's number of views (one map per view, [h][w] each)");
+    if (!depth) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: depth is NULL");
+    if (!(weight >= 0.0f) || !(weight < 1e30f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: weight must be finite and >= 0");
+    if (!(clip > 0.0f) || !(clip <= 1048576.0f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: clip must be in (0, 2^20] pixels");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // no kernel may still read the maps about to be freed
+    free_geom(ctx);
+    const size_t np = (size_t)ctx->w * ctx->h;
+    ctx->geom_maps.assign(n_views, nullptr);
+    DevScene& sc = ctx->hscene;
+    for (int v = 1; v < n_views; v++) {
+        if (!depth[v]) continue;
+        // (failure: the device block must not keep pointers to the freed maps, so it is uploaded without any term)
+        if (dev_alloc(ctx, &ctx->geom_maps[v], np) != TSAR_OK) { free_geom(ctx); upload_scene(ctx); return TSAR_ERR_NOMEM; }
+        if (hipMemcpyAsync(ctx->geom_maps[v], depth[v], np * sizeof(float), in_kind(mem), ctx->stream) != hipSuccess) {
+            hipStreamSynchronize(ctx->stream);
+            free_geom(ctx);
+            upload_scene(ctx);
+            return fail(ctx, TSAR_ERR_HIP, "tsar_set_geom_depths: copy of a depth map failed");
+        }
+        sc.geom_depth[v] = ctx->geom_maps[v];
+    }
+    sc.geom_weight = weight;
+    sc.geom_clip = clip;
+    sc.geom_clip_sq = clip * clip;
+    sc.geom_on = 1;
+    // stored costs were scored without this term (or with other maps): void them and the memo, as tsar_set_view_subset does
+    if (ctx->have_state) ctx->cost_consistent = false;
+    ctx->memo_valid_from = ctx->launch_seq + 1;
+    return upload_scene(ctx);              // (synchronises the stream: the copies above are complete on return)
+}
+
+extern "C" int tsar_clear_geom(tsar_ctx* ctx) {
+    CHECK_CTX(ctx);
+    if (!ctx->hscene.geom_on && ctx->geom_maps.empty()) return TSAR_OK;
+    if (ctx->stream) TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    free_geom(ctx);
+    if (ctx->have_state) ctx->cost_consistent = false;
+    ctx->memo_valid_from = ctx->launch_seq + 1;
+    return ctx->dscene ? upload_scene(ctx) : TSAR_OK;
+}
+
+extern "C" int tsar_pm_rescore(tsar_ctx* ctx) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    NEED_SOURCES(ctx);
+    NEED_STATE(ctx);
+    // read buf[0], write buf[1] (the kernel's plane pointers are restrict-qualified), then buf[1] is the state
+    TRY(launch_pm_rescore(ctx, ctx->buf[0].n4, ctx->buf[1].c, ctx->buf[1].n4, ctx->beview, ctx->ratio));
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::swap(ctx->buf[0], ctx->buf[1]);
+    ctx->sweeps_done = 0;                  // the sweeps that follow draw like the ones after tsar_pm_init (whatever the context ran before)
+    ctx->cost_consistent = true;           // every c[p] is n4[p]'s score under the context's cost, on the sweep window
+    ctx->memo_valid_from = ctx->launch_seq + 1;
+    ctx->have_out = false;
+    return TSAR_OK;
+}
+
+extern "C" int tsar_get_geom_matrices(tsar_ctx* ctx, int view, float* forward, float* back) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (view < 0 || view >= ctx->n_views || !forward || !back) return fail(ctx, TSAR_ERR_INVALID, "tsar_get_geom_matrices: view out of range or NULL output");
+    const DevView& dv = ctx->hscene.view[view];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) forward[4 * r + c] = dv.A[3 * r + c];
+        forward[4 * r + 3] = dv.b[r];
+    }
+    for (int i = 0; i < 12; i++) back[i] = ctx->hscene.geom_back[view][i];
     return TSAR_OK;
 }
 

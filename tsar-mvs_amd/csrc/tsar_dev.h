@@ -70,7 +70,17 @@ struct DevScene {
     int lut_d2[TSAR_LUT_MAX_CLASSES];              // i^2 + j^2 per class
     uint32_t tap_row[TSAR_LUT_LINES * TSAR_LUT_TAPS + 8];   // [line * lut_pad_taps + tap of the line] -> byte offset of the tap's row in the
                                                    // table (padding slots -> the zero row); chunks are consecutive: a walk reads it linearly
+    // Geometric-consistency term (include/tsar.h tsar_set_geom_depths; pm_core.h geom_term).  Appended last so that no field above
+    // moves: the kernels without the term (variant bit 24 clear) compile to the same code as before it existed.
+    const float* geom_depth[TSAR_MAX_VIEWS];       // view v's depth map [h][w] in its own camera (device, owned by the context); null = no term
+    float geom_back[TSAR_MAX_VIEWS][12];           // [K_ref R^T K_v^-1 | -K_ref R^T t]: (c D_v, r D_v, D_v, 1) -> reference image (derive_cameras)
+    float geom_weight, geom_clip, geom_clip_sq;    // lambda, tau, tau * tau
+    int geom_on;                                   // a term is installed: the launchers pick the variant-bit-24 kernels
 };
+
+// Variant bits of the geometric-consistency kernels (the remaining bits name the tap loop as before)
+#define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term)
+#define TSAR_V_REDRAW 33554432    // bit 25, with INIT: pm_full_kernel keeps the given plane where it is a valid hypothesis (tsar_pm_rescore)
 
 // State planes of one ping-pong buffer (linestate.h:12-13).
 struct PlaneBuf {
@@ -139,6 +149,9 @@ struct tsar_ctx {
     float4* resize4 = nullptr;        // [h][w] the planes the last tsar_upsample_planes chose (the reference's lines->resize4, linestate.h:64)
     bool have_resize = false;
     const float* final_text = nullptr;   // device lines->text while tsar_pm_iterate_final runs (the kernels' `final` mode), else null
+    // geometric consistency (tsar_set_geom_depths): the source views' depth maps, owned; hscene.geom_depth points into them
+    std::vector<float*> geom_maps;
+    bool rescoring = false;           // tsar_pm_rescore's launch of the every-pixel kernel (variant bit 25) is under way
     // timing
     int variant = 2;             // TSAR_VARIANT=n: code-generation variant of the fast-mode tap loop (pm_core.h view_cost); tsar_create picks 250 (med3/fract + D16 window loads + clamp-free loop for in-image windows + wave priority + SGPR-pinned texture base and line-top weight loads + row-wise window walk in fast mode; strict mode runs it as 122, the oracle's column order) when the D16 probe passes, else 114
     bool mix_gather = true;      // TSAR_MIX_GATHER=0: keep the byte texture for the buffer-load launches too (pm_tap_r5.h MIX off)
@@ -246,6 +259,7 @@ static inline bool lut_path_applies(const tsar_ctx* ctx) {
 int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out, uint32_t stream_id,
                                int do_prop, int do_refine, int* launched);   // pm_sweep_experiments.hip (TSAR_EXPERIMENTS builds)
 int launch_pm_cost_planes(tsar_ctx* ctx, const float4* planes, float* cost, int32_t* beview, float* ratio);
+int launch_pm_rescore(tsar_ctx* ctx, const float4* planes, float* cost, float4* n, int32_t* beview, float* ratio);   // pm_init.hip
 int launch_pm_upsample(tsar_ctx* ctx, const float4* coarse, int cw, int ch);                     // pm_upsample.hip
 int launch_pm_upsample_lut(tsar_ctx* ctx, int need, const float4* coarse, int cw, int ch);       // pm_upsample_lut.hip
 int launch_pyr_down(tsar_ctx* ctx, const float* src, int w, int h, void* dst, bool u8);        // tsar_pyramid.hip

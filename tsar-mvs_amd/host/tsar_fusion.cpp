@@ -14,7 +14,8 @@
 
 int main(int argc, char** argv) {
     if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
-        printf("usage: tsar_fusion <mslp_dir> [--num_consistent= N] [--reproj_error= PX] [--depth_diff= REL] [--angle= DEG] [--used_list= 0|1] [--gpu=K]\n");
+        printf("usage: tsar_fusion <mslp_dir> [--num_consistent= N] [--reproj_error= PX] [--depth_diff= REL] [--angle= DEG] [--used_list= 0|1] [--gpu=K] [--geom]\n"
+               "       --geom: fuse APD/%%08d/TSAR_geom_disp.dmb + TSAR_geom_normals.dmb instead of TSAR_disp.dmb + TSAR_normals.dmb\n");
         return argc < 2 ? 1 : 0;
     }
     std::string dir = argv[1];
@@ -22,6 +23,7 @@ int main(int argc, char** argv) {
     tsar_fusion_params prm;
     tsar_default_fusion_params(&prm);
     int gpu = 0;
+    bool geom = false;          // --geom: the geometric-consistency pass's maps (tsar_gipuma --all --geom_consistency)
     for (int i = 2; i < argc; i++) {
         const char* a = argv[i];
         auto value = [&](const char* opt) -> const char* {      // "--opt=VALUE" or "--opt= VALUE"
@@ -37,9 +39,11 @@ int main(int argc, char** argv) {
         else if ((v = value("--angle="))) prm.angle_deg = (float)atof(v);
         else if ((v = value("--used_list="))) prm.used_list = atoi(v);
         else if ((v = value("--gpu="))) gpu = atoi(v);
+        else if (!strcmp(a, "--geom")) geom = true;
         else printf("Command-line parameter warning: unknown option %s\n", a);
     }
     printf("num_consistent: %d\nreproj_error: %g\ndepth_diff: %g\nangle: %g\nused_list: %d\n", prm.num_consistent, prm.reproj_error, prm.depth_diff, prm.angle_deg, prm.used_list);
+    const std::string depth_file = geom ? "TSAR_geom_disp.dmb" : "TSAR_disp.dmb", normal_file = geom ? "TSAR_geom_normals.dmb" : "TSAR_normals.dmb";
     std::map<int, std::vector<int>> pairs;
     if (!read_pairs(dir + "pair.txt", pairs)) { fprintf(stderr, "cannot read %spair.txt\n", dir.c_str()); return 1; }
     std::vector<int> ids;
@@ -61,10 +65,10 @@ int main(int argc, char** argv) {
         if (!read_cam(dir + "cams/" + name + "_cam.txt", cf)) { problem[k] = std::string("cannot read camera of view ") + name; return; }
         cams[k] = cf.cam;
         int hh, ww, nb;
-        if (!read_dmb(dir + "APD/" + name + "/TSAR_disp.dmb", depth[k], hh, ww, nb) || nb != 1) { problem[k] = std::string("cannot read APD/") + name + "/TSAR_disp.dmb"; return; }
+        if (!read_dmb(dir + "APD/" + name + "/" + depth_file, depth[k], hh, ww, nb) || nb != 1) { problem[k] = std::string("cannot read APD/") + name + "/" + depth_file; return; }
         vw[k] = ww; vh[k] = hh;
         int h2, w2;
-        if (!read_dmb(dir + "APD/" + name + "/TSAR_normals.dmb", normal[k], h2, w2, nb) || nb != 3 || w2 != ww || h2 != hh) { problem[k] = std::string("cannot read APD/") + name + "/TSAR_normals.dmb"; return; }
+        if (!read_dmb(dir + "APD/" + name + "/" + normal_file, normal[k], h2, w2, nb) || nb != 3 || w2 != ww || h2 != hh) { problem[k] = std::string("cannot read APD/") + name + "/" + normal_file; return; }
         int iw, ih;
         bool have = read_pgm(dir + "images/" + name + ".pgm", gray[k], iw, ih);
         for (const char* ext : {".jpg", ".JPG", ".jpeg", ".JPEG"}) {          // the scene's own JPEG (host/tsar_jpeg.h), like tsar_gipuma

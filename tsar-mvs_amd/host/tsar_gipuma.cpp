@@ -16,6 +16,11 @@
 //   --all --fuse       after matching, every view's depth / normal map is gathered from the GPU that produced it to GPU 0
 //                      over xGMI (tsar_peer_copy) and fused there (tsar_fuse) into D/APD/APD_TSAR.ply — the fuser of
 //                      x/1.sh:30 without the round trip through .dmb files (which are still written)
+//   --all --geom_consistency [--geom_iterations=N (2)] [--geom_weight=W (0.2)] [--geom_clip=PX (3)]   phase 2 after every view's phase 1:
+//                      each view starts from its own TSAR_disp.dmb + TSAR_normals.dmb, installs its pair.txt sources' TSAR_disp.dmb as
+//                      the geometric-consistency term (include/tsar.h tsar_set_geom_depths), rescores, runs N iterations at full
+//                      resolution and writes TSAR_geom_disp.dmb + TSAR_geom_normals.dmb + TSAR_geom.txt (its settings); resumed only
+//                      when that record matches and no input is newer than the outputs; with --fuse the geom maps are fused
 //   --all resumes: a view whose APD/<id>/TSAR_disp.dmb and TSAR_normals.dmb are complete (the reference's header, main.cpp:1817-1860 /
 //                      fileIoUtils.h:333-381, and exactly h*w*nb floats behind it) is skipped — the output files are the per-view
 //                      checkpoints; --force recomputes.  A view that fails on one GPU is retried once on the next
@@ -68,6 +73,9 @@ struct Options {
     std::string mode = "patchmatch";
     int multi_scale = 0, coarse_iterations = -1;     // -1: --iterations
     bool coarse_iterations_set = false, textureless_merge = false;
+    bool geom = false;                               // --geom_consistency: phase 2 of --all (run_geom_view)
+    int geom_iterations = 2;
+    float geom_weight = 0.2f, geom_clip = 3.0f;      // ACMM's lambda and tau (include/tsar.h tsar_set_geom_depths)
 };
 
 #include "tsar_io.h"
@@ -164,6 +172,7 @@ static void usage() {
            "                   [--depth_min=D --depth_max=D] [--mode=patchmatch|load|tsar] [--all --gpus=N --workers=W] [--seed=S] [--strict] [--fix-quirks] [--texture-filter-8bit] [-color_processing] [--display_outputs] [--timing]\n"
            "                   [--multi_scale=L [--coarse_iterations=N] [--textureless_merge]]\n"
            "       tsar_gipuma --all [--gpus=N] [--force] [--fuse [--num_consistent=N --reproj_error=PX --depth_diff=REL --angle=DEG --used_list=0|1]]\n"
+           "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX]]\n"
            "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n");
 }
 
@@ -234,6 +243,10 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
             return 1;
         }
         else if (!strcmp(a, "--all")) o.all = true;
+        else if (!strcmp(a, "--geom_consistency")) o.geom = true;
+        else if (starts("--geom_iterations=")) o.geom_iterations = atoi(a + 18);
+        else if (starts("--geom_weight=")) o.geom_weight = (float)atof(a + 14);
+        else if (starts("--geom_clip=")) o.geom_clip = (float)atof(a + 12);
         else if (!strcmp(a, "--fuse")) o.fuse = true;
         else if (!strcmp(a, "--force")) o.force = true;                        // --all: recompute views whose outputs are already there
         else if (starts("--num_consistent=")) o.fusion.num_consistent = atoi(a + 17);
@@ -656,6 +669,165 @@ static double ms_since_exec() {
     return (up - (double)start_ticks / (double)sysconf(_SC_CLK_TCK)) * 1e3;
 }
 
+// ---- --all --geom_consistency: phase 2 ----------------------------------------------------------------------------------------
+// Every view starts from its own phase-1 maps (TSAR_disp.dmb + TSAR_normals.dmb), installs its pair.txt sources' TSAR_disp.dmb as the
+// geometric-consistency term, rescores, runs --geom_iterations iterations (single scale, full resolution) and writes
+// TSAR_geom_disp.dmb + TSAR_geom_normals.dmb (the layout of the phase-1 maps) and TSAR_geom.txt, the settings they were made with.
+static const char* const GEOM_RECORD = "TSAR_geom.txt";
+static std::string geom_record_of(const Options& o) {
+    char b[320];
+    snprintf(b, sizeof b, "geom_iterations=%d geom_weight=%.9g geom_clip=%.9g blocksize=%d n_best=%d cost_comb=%d seed=%llu strict=%d fix_quirks=%d texture_filter_8bit=%d cam_scale=%.9g depth_min=%.9g depth_max=%.9g\n",
+             o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
+             o.fix_quirks ? 1 : 0, o.tex8 ? 1 : 0, (double)o.cam_scale, (double)o.depth_min, (double)o.depth_max);
+    return b;
+}
+static bool mtime_of(const std::string& path, struct timespec& t) {
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0) return false;
+    t = st.st_mtim;
+    return true;
+}
+static bool newer(const struct timespec& a, const struct timespec& b) { return a.tv_sec != b.tv_sec ? a.tv_sec > b.tv_sec : a.tv_nsec > b.tv_nsec; }
+// resume of phase 2: both geom maps complete, the record of this run's settings, and no input (the view's own phase-1 maps, its
+// sources' depth maps) newer than the older of the two outputs
+static bool geom_outputs_current(const Options& o, int ref, const std::vector<int>& srcs) {
+    int w = 0, h = 0;
+    if (!view_image_size(view_image_of(o, ref), w, h)) return false;
+    const std::string d = view_dir_of(o, ref);
+    if (!dmb_complete(d + "TSAR_geom_disp.dmb", h, w, 1) || !dmb_complete(d + "TSAR_geom_normals.dmb", h, w, 3)) return false;
+    std::string rec;
+    if (FILE* f = fopen((d + GEOM_RECORD).c_str(), "r")) {
+        char b[512];
+        size_t k;
+        while ((k = fread(b, 1, sizeof b, f)) > 0) rec.append(b, k);
+        fclose(f);
+    }
+    if (rec != geom_record_of(o)) return false;
+    struct timespec t1, t2, ti;
+    if (!mtime_of(d + "TSAR_geom_disp.dmb", t1) || !mtime_of(d + "TSAR_geom_normals.dmb", t2)) return false;
+    const struct timespec out = newer(t1, t2) ? t2 : t1;
+    std::vector<std::string> inputs = {d + "TSAR_disp.dmb", d + "TSAR_normals.dmb"};
+    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + "TSAR_disp.dmb");
+    for (const std::string& in : inputs)
+        if (!mtime_of(in, ti) || newer(ti, out)) return false;
+    return true;
+}
+
+// One view's phase 2 on `device`; ctx is the worker's context (created on first use, kept across its views, dropped after a failure).
+static int run_geom_view(const Options& o, int device, tsar_ctx*& ctx, int ref, const std::vector<int>& srcs, double* seconds) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ctx && tsar_create(device, &ctx) != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed\n", device); ctx = nullptr; return -1; }
+    auto fail = [&](const char* what) { fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, ctx ? tsar_last_error(ctx) : ""); tsar_destroy(ctx); ctx = nullptr; return -1; };
+    std::vector<int> ids = {ref};
+    ids.insert(ids.end(), srcs.begin(), srcs.end());
+    const int n = (int)ids.size();
+    std::vector<std::shared_ptr<ImageCache::Entry>> gray(n);
+    std::vector<const uint8_t*> ptrs(n);
+    std::vector<tsar_camera> cams(n);
+    int w = 0, h = 0;
+    float dmin = o.depth_min, dmax = o.depth_max;
+    for (int i = 0; i < n; i++) {
+        const std::string ip = view_image_of(o, ids[i]);
+        gray[i] = g_images.get(ip);
+        if (!gray[i]->ok) { fprintf(stderr, "cannot read image %s: %s\n", ip.c_str(), gray[i]->why.c_str()); return -1; }
+        if (i == 0) { w = gray[i]->w; h = gray[i]->h; }
+        if (gray[i]->w != w || gray[i]->h != h) { fprintf(stderr, "image %s has a different size\n", ip.c_str()); return -1; }
+        ptrs[i] = gray[i]->gray.data();
+        char cn[32];
+        snprintf(cn, sizeof cn, "%08d", ids[i]);
+        CamFile cf;
+        const std::string cp = o.mslp_folder + "cams/" + cn + "_cam.txt";
+        if (!read_cam(cp, cf)) { fprintf(stderr, "cannot read camera %s\n", cp.c_str()); return -1; }
+        cams[i] = cf.cam;
+        if (i == 0) {   // depth range of the reference view unless given on the command line (as in phase 1)
+            if (dmin <= 0) dmin = cf.depth_min;
+            if (dmax <= 0) dmax = cf.depth_max;
+        }
+    }
+    // the maps: the view's own phase-1 result and its sources' depths, each of the image size
+    const std::string d = view_dir_of(o, ref);
+    std::vector<float> own_d, own_n;
+    std::vector<std::vector<float>> src_d(n);
+    int hh = 0, ww = 0, nb = 0;
+    if (!read_dmb(d + "TSAR_disp.dmb", own_d, hh, ww, nb) || hh != h || ww != w || nb != 1) { fprintf(stderr, "cannot read %sTSAR_disp.dmb\n", d.c_str()); return -1; }
+    if (!read_dmb(d + "TSAR_normals.dmb", own_n, hh, ww, nb) || hh != h || ww != w || nb != 3) { fprintf(stderr, "cannot read %sTSAR_normals.dmb\n", d.c_str()); return -1; }
+    std::vector<const float*> maps(n, nullptr);
+    for (int i = 1; i < n; i++) {
+        const std::string sp = view_dir_of(o, ids[i]) + "TSAR_disp.dmb";
+        if (!read_dmb(sp, src_d[i], hh, ww, nb) || hh != h || ww != w || nb != 1) { fprintf(stderr, "cannot read %s\n", sp.c_str()); return -1; }
+        maps[i] = src_d[i].data();
+    }
+    tsar_params p;
+    tsar_default_params(&p);
+    p.box_hsize = p.box_vsize = o.blocksize;
+    p.n_best = o.n_best; p.cost_comb = o.cost_comb; p.cam_scale = o.cam_scale;
+    p.depth_min = dmin; p.depth_max = dmax;
+    p.seed = o.seed + (uint64_t)ref;
+    p.flags = (o.strict ? TSAR_FLAG_STRICT_DIV : 0) | (o.fix_quirks ? (TSAR_FLAG_FIX_DOWN_FAR_SEED | TSAR_FLAG_FIX_RIGHT_FAR_CMP) : 0) |
+              (o.tex8 ? TSAR_FLAG_TEX_FILTER_8BIT : 0);
+    if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
+    if (tsar_set_views_u8(ctx, n, w, h, ptrs.data(), TSAR_MEM_HOST, cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
+    if (tsar_load_planes(ctx, own_d.data(), own_n.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
+    if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
+    if (tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
+    if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
+    if (tsar_compute_disp(ctx) != TSAR_OK) return fail("tsar_compute_disp");
+    const size_t np = (size_t)w * h;
+    std::vector<float> depth(np), normal(3 * np);
+    if (tsar_get_result(ctx, depth.data(), normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
+    if (tsar_clear_geom(ctx) != TSAR_OK) return fail("tsar_clear_geom");
+    // the record goes last: maps being replaced never carry the record of other settings
+    unlink((d + GEOM_RECORD).c_str());
+    bool ok = write_dmb(d + "TSAR_geom_disp.dmb", depth.data(), h, w, 1) && write_dmb(d + "TSAR_geom_normals.dmb", normal.data(), h, w, 3);
+    if (ok) {
+        FILE* f = fopen((d + GEOM_RECORD).c_str(), "w");
+        ok = f && fputs(geom_record_of(o).c_str(), f) >= 0;
+        if (f && fclose(f) != 0) ok = false;
+    }
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return ok ? 0 : -1;
+}
+
+// Phase 2 over every view, dealt round-robin to the GPUs (one worker per GPU); a failed view is retried once on the next GPU with a
+// fresh context.  Returns the number of views without current geom outputs.
+static int run_geom_phase(const Options& o, const std::vector<int>& refs, std::map<int, std::vector<int>>& pairs) {
+    const int ngpu = o.gpus < 1 ? 1 : o.gpus;
+    std::vector<int> rc(refs.size(), 0), gpu_of(refs.size(), 0);
+    std::vector<char> skip(refs.size(), 0);
+    size_t n_skip = 0;
+    if (!o.force)
+        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = geom_outputs_current(o, refs[k], pairs[refs[k]]) ? 1 : 0);
+    if (n_skip) printf("geom: resuming: %zu of %zu views have current TSAR_geom_disp.dmb / TSAR_geom_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
+    std::vector<std::thread> th;
+    for (int g = 0; g < ngpu; g++)
+        th.emplace_back([&, g]() {
+            tsar_ctx* ctx = nullptr;
+            for (size_t k = g; k < refs.size(); k += ngpu) {
+                gpu_of[k] = g;
+                if (skip[k]) { printf("view %08d: geom outputs present, skipped\n", refs[k]); continue; }
+                double sec = 0;
+                rc[k] = run_geom_view(o, g, ctx, refs[k], pairs[refs[k]], &sec);
+                printf("view %08d on gpu %d (geom): %s (%.2f s)\n", refs[k], g, rc[k] == 0 ? "ok" : "FAILED", sec);
+            }
+            tsar_destroy(ctx);
+        });
+    for (auto& t : th) t.join();
+    int missing = 0;
+    for (size_t k = 0; k < refs.size(); k++) {
+        if (skip[k]) continue;
+        if (rc[k] != 0) {
+            const int g2 = (gpu_of[k] + 1) % ngpu;
+            tsar_ctx* ctx = nullptr;
+            double sec = 0;
+            rc[k] = run_geom_view(o, g2, ctx, refs[k], pairs[refs[k]], &sec);
+            tsar_destroy(ctx);
+            printf("view %08d on gpu %d (geom, retry): %s (%.2f s)\n", refs[k], g2, rc[k] == 0 ? "ok" : "FAILED", sec);
+        }
+        if (rc[k] != 0) { fprintf(stderr, "view %08d: geom outputs missing\n", refs[k]); missing++; }
+    }
+    return missing;
+}
+
 int main(int argc, char** argv) {
     const double ms_exec_to_main = ms_since_exec();
     Options o;
@@ -666,6 +838,11 @@ int main(int argc, char** argv) {
     if (o.multi_scale > 0 || o.coarse_iterations_set || o.textureless_merge) {
         if (o.mode != "patchmatch") { fprintf(stderr, "--multi_scale / --coarse_iterations / --textureless_merge work with --mode=patchmatch only\n"); return 1; }
         if (o.multi_scale == 0) { fprintf(stderr, "--coarse_iterations / --textureless_merge need --multi_scale=L with L >= 1\n"); return 1; }
+    }
+    if (o.geom) {
+        if (!o.all) { fprintf(stderr, "--geom_consistency needs --all (phase 2 reads every view's phase-1 maps)\n"); return 1; }
+        if (o.mode == "tsar") { fprintf(stderr, "--geom_consistency does not work with --mode=tsar\n"); return 1; }
+        if (o.geom_iterations < 0 || !(o.geom_weight >= 0.f) || !(o.geom_clip > 0.f)) { fprintf(stderr, "--geom_iterations must be >= 0, --geom_weight >= 0, --geom_clip > 0\n"); return 1; }
     }
     if (o.mslp_folder.back() != '/') o.mslp_folder += '/';
     if (o.images_folder.back() != '/') o.images_folder += '/';
@@ -689,11 +866,13 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = outputs_complete(o, refs[k]) ? 1 : 0);
         if (n_skip) printf("resuming: %zu of %zu views already have complete TSAR_disp.dmb / TSAR_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
         // --fuse needs a skipped view's maps on a device all the same: read back from its files
-        auto load_kept = [&](size_t k, int g) {
+        auto load_kept = [&](size_t k, int g, bool geom_maps = false) {
             std::vector<float> d, nr;
             int h = 0, w = 0, nb = 0, h2 = 0, w2 = 0, nb2 = 0;
             const std::string dir = view_dir_of(o, refs[k]);
-            if (!read_dmb(dir + "TSAR_disp.dmb", d, h, w, nb) || !read_dmb(dir + "TSAR_normals.dmb", nr, h2, w2, nb2) || h != h2 || w != w2 || nb != 1 || nb2 != 3) return false;
+            const char* dn = geom_maps ? "TSAR_geom_disp.dmb" : "TSAR_disp.dmb";
+            const char* nn = geom_maps ? "TSAR_geom_normals.dmb" : "TSAR_normals.dmb";
+            if (!read_dmb(dir + dn, d, h, w, nb) || !read_dmb(dir + nn, nr, h2, w2, nb2) || h != h2 || w != w2 || nb != 1 || nb2 != 3) return false;
             DeviceResult& r = kept[k];
             r.device = g; r.w = w; r.h = h;
             r.depth = (float*)tsar_device_alloc(g, d.size() * 4);
@@ -786,6 +965,20 @@ int main(int argc, char** argv) {
         for (int s : status)
             if (s != 0) missing++;      // a file of an otherwise matched view could not be written
         if (missing) return 1;
+        if (o.geom) {
+            // phase 2 starts once every view has its phase-1 maps; it reads them from the files
+            if (run_geom_phase(o, refs, pairs) != 0) return 1;
+            if (o.fuse)        // --fuse fuses the geom maps: they replace the phase-1 maps kept on each view's device
+                for (size_t k = 0; k < refs.size(); k++) {
+                    const int g = kept[k].device >= 0 ? kept[k].device : (int)(k % (size_t)ngpu);
+                    if (kept[k].depth) tsar_device_free(kept[k].device, kept[k].depth);
+                    if (kept[k].normal) tsar_device_free(kept[k].device, kept[k].normal);
+                    const tsar_camera cam = kept[k].cam;
+                    kept[k] = DeviceResult{};
+                    kept[k].cam = cam;
+                    if (!load_kept(k, g, true)) { fprintf(stderr, "view %08d: cannot read its geom maps for --fuse\n", refs[k]); return 1; }
+                }
+        }
         if (o.fuse) {
             // gather: every view's maps to GPU 0 (peer copies over xGMI; views matched on GPU 0 are already there), then fuse
             const auto t0 = std::chrono::steady_clock::now();
