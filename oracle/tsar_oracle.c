@@ -39,6 +39,9 @@
  *   S6 ratio = c0/c1 needs two selected views; with one it is defined as 0 (reference reads an
  *      uninitialised slot, gipuma.cu:505).
  *
+ * The geometric-consistency term (geom_term, orc_set_geom, orc_pm_rescore) is not in the reference: it is restated from its
+ * statement in include/tsar.h (tsar_set_geom_depths, tsar_pm_rescore), not from the kernels.
+ *
  * Build: see oracle/Makefile (gcc -O2 -ffp-contract=off -mfma -fopenmp -shared).
  */
 #include <math.h>
@@ -112,6 +115,11 @@ typedef struct {
     int launch; /* number of red/black launches so far (RNG stream) */
     const float *rcp_table; /* S7 (1): v_rcp_f32 of 1 + m 2^-23 for m = 0 .. 2^23 - 1, borrowed */
     int rcp_out_of_range;   /* S7 (1): operands the table could not serve (zero, denormal, inf, nan, result not normal): must stay 0 */
+    /* geometric-consistency term (include/tsar.h, tsar_set_geom_depths): off unless geom_on */
+    int geom_on;
+    float geom_weight, geom_clip;
+    const float *geom_depth[ORC_MAX_VIEWS];          /* view v's depth map [h][w], borrowed; NULL = no term for v */
+    float geom_F[ORC_MAX_VIEWS][12], geom_B[ORC_MAX_VIEWS][12];   /* row-major 3 x 4, as given (tsar_get_geom_matrices) */
 } orc_state;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -459,13 +467,47 @@ static void sort_small(float *d, int n) {
         d[j] = tmp;
     }
 }
-/* pmCostMultiview_cu gipuma.cu:455-518 */
+/* The geometric-consistency term lambda e of view v for a hypothesis of depth D at (x, y), restated from the statement in
+ * include/tsar.h (tsar_set_geom_depths): plain float operations, each one IEEE operation (-ffp-contract=off, no fmaf: the same in
+ * every build of this file), the quotients '/', the root sqrtf, and the header's comparisons (NaN fails each one). */
+static float geom_term(const orc_state *s, int view, int x, int y, float D) {
+    const float *dm = s->geom_depth[view];
+    if (!dm) return 0.0f;
+    const float *F = s->geom_F[view], *B = s->geom_B[view];
+    const float X = (float)x, Y = (float)y, tau = s->geom_clip;
+    const float xd = X * D, yd = Y * D;
+    const float a = ((F[0] * xd + F[1] * yd) + F[2] * D) + F[3];
+    const float b = ((F[4] * xd + F[5] * yd) + F[6] * D) + F[7];
+    const float sz = ((F[8] * xd + F[9] * yd) + F[10] * D) + F[11];
+    const float u = a / sz, v = b / sz;
+    const float c = floorf(u + 0.5f), r = floorf(v + 0.5f);
+    const int inside = sz > 0.0f && c >= 0.0f && c <= (float)(s->w - 1) && r >= 0.0f && r <= (float)(s->h - 1);
+    const float Dv = inside ? dm[(size_t)(int)r * s->w + (int)c] : 0.0f;
+    const float cd = c * Dv, rd = r * Dv;
+    const float p0 = ((B[0] * cd + B[1] * rd) + B[2] * Dv) + B[3];
+    const float p1 = ((B[4] * cd + B[5] * rd) + B[6] * Dv) + B[7];
+    const float p2 = ((B[8] * cd + B[9] * rd) + B[10] * Dv) + B[11];
+    const float xq = p0 / p2, yq = p1 / p2;
+    const float dx = xq - X, dy = yq - Y;
+    const float e2 = dx * dx + dy * dy;
+    float e;
+    if (!(inside && Dv > 0.0f && p2 > 0.0f && e2 < tau * tau)) e = tau;
+    else if (e2 < 0x1p-100f) e = 0.0f;
+    else e = fminf(sqrtf(e2), tau);
+    return s->geom_weight * e;
+}
+float orc_geom_term(const orc_state *s, int view, int x, int y, float D) { return geom_term(s, view, x, y, D); }
+
+/* pmCostMultiview_cu gipuma.cu:455-518.  With a geometric term installed, view v's cost becomes c_v + lambda e_v after the validity
+ * test (include/tsar.h); D is the hypothesis's depth at (x, y), once per hypothesis. */
 static float pm_cost_multiview(const orc_state *s, int x, int y, const float *n4, int *beview, float *ratio) {
     float cv[ORC_MAX_VIEWS], ov[ORC_MAX_VIEWS];
     int num = s->n_sel, valid = 0;
+    const float D = s->geom_on ? depth_from_plane(&s->cam[0], n4, x, y) : 0.0f;
     for (int i = 0; i < num; i++) {
         float c = pm_cost(s, s->sel[i], x, y, n4);
         if (c < ORC_MAXCOST) valid++; else c = ORC_MAXCOST;
+        if (s->geom_on) c = c + geom_term(s, s->sel[i], x, y, D);
         cv[i] = c; ov[i] = c;
     }
     sort_small(cv, num);
@@ -501,11 +543,11 @@ void orc_pm_cost_planes(const orc_state *s, const float *planes, float *cost, in
 }
 
 /* ------------------------------------------------------------------------------------------ */
-/* gipuma_init_cu2 gipuma.cu:678-729 */
-static void init_pixel(orc_state *s, int x, int y) {
+/* gipuma_init_cu2 gipuma.cu:678-729: the random hypothesis of pixel (x, y) */
+static void draw_plane(const orc_state *s, int x, int y, float *n4) {
     const orc_camera *cm = &s->cam[0];
     size_t p = (size_t)y * s->w + x;
-    float vv[3], u[4], n4[4];
+    float vv[3], u[4];
     view_vector(cm, x, y, vv);
     rng4(s, (uint32_t)p, 0u, 0u, u);
     float disp = between(u[0], s->min_disp, s->max_disp);
@@ -527,6 +569,11 @@ static void init_pixel(orc_state *s, int x, int y) {
     if (dot3f(n4, vv) > 0.0f) { n4[0] = -n4[0]; n4[1] = -n4[1]; n4[2] = -n4[2]; } /* vecOnHemisphere_cu :106-112 */
     float depth = cm->f * cm->baseline / disp;
     n4[3] = getD(n4, x, y, depth, cm);
+}
+static void init_pixel(orc_state *s, int x, int y) {
+    size_t p = (size_t)y * s->w + x;
+    float n4[4];
+    draw_plane(s, x, y, n4);
     memcpy(s->norm4 + 4 * p, n4, sizeof n4);
     int bv; float rt;
     s->c[p] = pm_cost_multiview(s, x, y, n4, &bv, &rt);
@@ -540,6 +587,25 @@ void orc_pm_init(orc_state *s) {
     for (int y = 0; y < s->h; y++)
         for (int x = 0; x < s->w; x++) init_pixel(s, x, y);
     s->hrad = hr; s->vrad = vr;
+    s->launch = 0;
+}
+/* tsar_pm_rescore (include/tsar.h): a plane whose depth at (x, y) is finite and inside [depthMin, depthMax] stays, any other pixel
+ * gets the hypothesis init draws there; every pixel is scored on the sweeps' window (not init's box / 2) with cost, best view and
+ * ratio written, and the launch counter restarts as after orc_pm_init. */
+void orc_pm_rescore(orc_state *s) {
+    const orc_camera *cm = &s->cam[0];
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int y = 0; y < s->h; y++)
+        for (int x = 0; x < s->w; x++) {
+            size_t p = (size_t)y * s->w + x;
+            float *n4 = s->norm4 + 4 * p;
+            const float d = depth_from_plane(cm, n4, x, y);
+            if (!(d >= cm->depthMin && d <= cm->depthMax)) draw_plane(s, x, y, n4);
+            int bv; float rt;
+            s->c[p] = pm_cost_multiview(s, x, y, n4, &bv, &rt);
+            s->beview[p] = bv;
+            s->ratio[p] = rt;
+        }
     s->launch = 0;
 }
 
@@ -960,6 +1026,22 @@ void orc_set_params(orc_state *s, int box_hsize, int box_vsize, int n_best, int 
 }
 void orc_set_rcp_table(orc_state *s, const float *table) { s->rcp_table = table; s->rcp_out_of_range = 0; } /* S7 (1); borrowed */
 int orc_rcp_out_of_range(const orc_state *s) { return s->rcp_out_of_range; }
+/* the geometric-consistency term: view's depth map (borrowed; NULL = no term for that view) and its F, B (12 floats each, row-major
+ * 3 x 4, passed in as the library reports them); weight lambda and clip tau; orc_clear_geom removes the term */
+void orc_set_geom(orc_state *s, int view, const float *depth, const float *F, const float *B) {
+    s->geom_depth[view] = depth;
+    memcpy(s->geom_F[view], F, sizeof s->geom_F[view]);
+    memcpy(s->geom_B[view], B, sizeof s->geom_B[view]);
+    s->geom_on = 1;
+}
+void orc_set_geom_params(orc_state *s, float weight, float clip) { s->geom_weight = weight; s->geom_clip = clip; }
+void orc_clear_geom(orc_state *s) {
+    s->geom_on = 0;
+    s->geom_weight = 0.0f; s->geom_clip = 0.0f;
+    memset(s->geom_depth, 0, sizeof s->geom_depth);
+    memset(s->geom_F, 0, sizeof s->geom_F);
+    memset(s->geom_B, 0, sizeof s->geom_B);
+}
 float orc_rcp_gpu(const orc_state *s, float x) { return rcp_gpu(s, x); }
 void orc_set_subset(orc_state *s, int n, const int32_t *idx) {
     s->n_sel = n;

@@ -133,6 +133,16 @@ def _bind(L):
     L.orc_rcp_out_of_range.argtypes = [C.c_void_p]
     L.orc_rcp_gpu.restype = C.c_float
     L.orc_rcp_gpu.argtypes = [C.c_void_p, C.c_float]
+    L.orc_set_geom.restype = None
+    L.orc_set_geom.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_set_geom_params.restype = None
+    L.orc_set_geom_params.argtypes = [C.c_void_p, C.c_float, C.c_float]
+    L.orc_clear_geom.restype = None
+    L.orc_clear_geom.argtypes = [C.c_void_p]
+    L.orc_pm_rescore.restype = None
+    L.orc_pm_rescore.argtypes = [C.c_void_p]
+    L.orc_geom_term.restype = C.c_float
+    L.orc_geom_term.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]
     return real
 
 
@@ -319,6 +329,38 @@ class Oracle:
 
     def pm_init(self):
         self.L.orc_pm_init(self.s)
+
+    def set_geom(self, maps, matrices, weight=0.2, clip=3.0):
+        """install the geometric-consistency term (include/tsar.h): maps[v] = view v's depth map [h, w] or None (no term for v;
+        maps[0] is ignored), matrices[v] = (F, B), the 3 x 4 float32 matrices the library reports (Matcher.get_geom_matrices)"""
+        self.clear_geom()
+        keep = []
+        for v in range(1, self.n_views):
+            F, B = (np.ascontiguousarray(m, np.float32).reshape(12) for m in matrices[v])
+            d = None
+            if maps[v] is not None:
+                d = np.ascontiguousarray(maps[v], np.float32)
+                assert d.shape == (self.h, self.w)
+                keep.append(d)
+            self.L.orc_set_geom(self.s, C.c_int(v), _p(d) if d is not None else None, _p(F), _p(B))
+        self._geom_maps = keep               # borrowed by the C side
+        self.L.orc_set_geom_params(self.s, C.c_float(weight), C.c_float(clip))
+
+    def clear_geom(self):
+        self.L.orc_clear_geom(self.s)
+        self._geom_maps = []
+
+    def rescore(self):
+        """tsar_pm_rescore: keep the valid planes, redraw the others as pm_init does, score every pixel (sweep window)"""
+        self.L.orc_pm_rescore(self.s)
+
+    def geom_term(self, view, x, y, D):
+        """lambda e of `view` for hypotheses of depth D at pixels (x, y) (arrays of one shape, or scalars)"""
+        x, y, D = np.broadcast_arrays(np.asarray(x), np.asarray(y), np.asarray(D, np.float32))
+        out = np.empty(D.shape, np.float32)
+        for i in np.ndindex(D.shape):
+            out[i] = self.L.orc_geom_term(self.s, C.c_int(view), C.c_int(int(x[i])), C.c_int(int(y[i])), C.c_float(D[i]))
+        return out
 
     def pm_sweep(self, colour, do_prop=1, do_refine=1):
         self.L.orc_pm_sweep(self.s, C.c_int(colour), C.c_int(do_prop), C.c_int(do_refine))

@@ -1,6 +1,7 @@
 """The geometric-consistency term (include/tsar.h, pm_core.h geom_term) restated in numpy float32, operation for operation, and that
-restatement held to the float64 closed form of the same reprojection; the register budget of the kernels that carry the term.  No GPU:
-tests/test_gpu_geom.py holds the kernels to `geom_term` below bit for bit."""
+restatement held to the float64 closed form of the same reprojection; the CPU oracle's own statement of the term (oracle/tsar_oracle.c
+orc_geom_term, its multi-view cost and orc_pm_rescore) held to the numpy restatement bit for bit; the register budget of the kernels that
+carry the term.  No GPU: tests/test_gpu_geom.py and tests/test_gpu_call_parity.py hold the kernels to these."""
 import os
 import re
 import shutil
@@ -13,6 +14,7 @@ from tsar_mvs_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
+MAXCOST = F32(2.0)
 
 
 def geom_term(F, B, depth_v, x, y, D, weight, clip):
@@ -45,6 +47,48 @@ def geom_term(F, B, depth_v, x, y, D, weight, clip):
         ok = inside & (Dv > 0) & (p2 > 0) & (e2 < tau * tau)
         e = np.where(ok, np.minimum(e, tau), tau).astype(F32)
         return (F32(weight) * e).astype(F32)
+
+
+def expected_cost_planes(orc, matrices, maps, planes, n_best, weight, clip):
+    """what pm_cost_planes must return with `maps` installed: `orc`'s photometric cost per view (the oracle's pm_cost, which carries no
+    term), the numpy restatement of the term, the best-N of multiview_cost (pm_core.h) in numpy.  matrices[v] = (F, B) of view v."""
+    h, w = planes.shape[:2]
+    n_views = len(maps)
+    ys, xs = np.mgrid[0:h, 0:w]
+    D = np.empty((h, w), F32)
+    per_view = []
+    for y in range(h):
+        for x in range(w):
+            D[y, x] = orc.depth_from_plane(planes[y, x], x, y)
+    for v in range(1, n_views):
+        c = np.empty((h, w), F32)
+        for y in range(h):
+            for x in range(w):
+                c[y, x] = orc.pm_cost(v, x, y, planes[y, x])
+        c = np.minimum(c, MAXCOST)
+        valid = c < MAXCOST
+        F, B = matrices[v]
+        g = geom_term(F, B, maps[v], xs, ys, D, weight, clip) if maps[v] is not None else np.zeros((h, w), F32)
+        per_view.append((v, (c + g).astype(F32), valid))
+    # multiview_cost: last view attaining the minimum, the NB smallest sorted, nb = min(valid, n_best)
+    cmin = np.full((h, w), np.inf, F32)
+    bv = np.full((h, w), -1, np.int32)
+    nvalid = np.zeros((h, w), np.int32)
+    for v, c, valid in per_view:
+        take = c <= cmin
+        bv = np.where(take, v, bv)
+        cmin = np.minimum(cmin, c)
+        nvalid += valid
+    srt = np.sort(np.stack([c for _, c, _ in per_view]), axis=0)
+    nb = np.minimum(nvalid, n_best)
+    cost = np.zeros((h, w), F32)
+    for k in range(min(n_best, srt.shape[0])):
+        cost = np.where(k < nb, (cost + srt[k]).astype(F32), cost)
+    cost = np.where(nb > 0, (cost / nb.astype(F32)).astype(F32), MAXCOST)
+    ratio = (srt[0] / srt[1]).astype(F32) if srt.shape[0] >= 2 else np.zeros((h, w), F32)
+    ratio = np.where(nb > 0, ratio, F32(0))
+    bv = np.where(nb > 0, bv, -1)
+    return cost, bv, ratio
 
 
 def relative_pose(K, R, t, v):

@@ -8,12 +8,11 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from test_geom_cpu import geom_term
+from test_geom_cpu import expected_cost_planes, geom_term
 from tsar_mvs_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-MAXCOST = F32(2.0)
 
 
 def _u8(sc):
@@ -54,48 +53,6 @@ def _gt_maps(sc, hole=True):
         for v in range(1, len(maps)):
             maps[v][h // 3:h // 3 + 12, w // 4:w // 4 + 16] = 0
     return maps
-
-
-def _expected(orc, m, maps, planes, n_best, weight, clip):
-    """what tsar_pm_cost_planes must return with `maps` installed: the oracle's photometric cost per view, the numpy restatement of the
-    term, the best-N of multiview_cost (pm_core.h) in numpy"""
-    h, w = planes.shape[:2]
-    n_views = len(maps)
-    ys, xs = np.mgrid[0:h, 0:w]
-    D = np.empty((h, w), F32)
-    per_view = []
-    for y in range(h):
-        for x in range(w):
-            D[y, x] = orc.depth_from_plane(planes[y, x], x, y)
-    for v in range(1, n_views):
-        c = np.empty((h, w), F32)
-        for y in range(h):
-            for x in range(w):
-                c[y, x] = orc.pm_cost(v, x, y, planes[y, x])
-        c = np.minimum(c, MAXCOST)
-        valid = c < MAXCOST
-        F, B = m.get_geom_matrices(v)
-        g = geom_term(F, B, maps[v], xs, ys, D, weight, clip) if maps[v] is not None else np.zeros((h, w), F32)
-        per_view.append((v, (c + g).astype(F32), valid))
-    # multiview_cost: last view attaining the minimum, the NB smallest sorted, nb = min(valid, n_best)
-    cmin = np.full((h, w), np.inf, F32)
-    bv = np.full((h, w), -1, np.int32)
-    nvalid = np.zeros((h, w), np.int32)
-    for v, c, valid in per_view:
-        take = c <= cmin
-        bv = np.where(take, v, bv)
-        cmin = np.minimum(cmin, c)
-        nvalid += valid
-    srt = np.sort(np.stack([c for _, c, _ in per_view]), axis=0)
-    nb = np.minimum(nvalid, n_best)
-    cost = np.zeros((h, w), F32)
-    for k in range(min(n_best, srt.shape[0])):
-        cost = np.where(k < nb, (cost + srt[k]).astype(F32), cost)
-    cost = np.where(nb > 0, (cost / nb.astype(F32)).astype(F32), MAXCOST)
-    ratio = (srt[0] / srt[1]).astype(F32) if srt.shape[0] >= 2 else np.zeros((h, w), F32)
-    ratio = np.where(nb > 0, ratio, F32(0))
-    bv = np.where(nb > 0, bv, -1)
-    return cost, bv, ratio
 
 
 def _test_planes(sc, m, maps, kind):
@@ -140,7 +97,7 @@ def test_term_is_the_restatement_bit_for_bit(strict, box, n_best, kind):
     m.set_geom_depths(maps, weight=0.2, clip=3.0)
     cost, bv, rt = m.pm_cost_planes(planes)
     orc = _oracle(sc, imgs, box, n_best, strict, m)
-    ec, ebv, ert = _expected(orc, m, maps, planes, n_best, 0.2, 3.0)
+    ec, ebv, ert = expected_cost_planes(orc, [None] + [m.get_geom_matrices(v) for v in range(1, len(maps))], maps, planes, n_best, 0.2, 3.0)
     assert _bits_equal(cost, ec), (kind, int((cost.view(np.uint32) != ec.view(np.uint32)).sum()))
     assert np.array_equal(bv, ebv)
     assert _bits_equal(rt, ert)

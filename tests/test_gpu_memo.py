@@ -4,10 +4,11 @@ Within one tsar_pm_iterate call a pixel remembers the eight candidates of its pr
 same neighbour with a plane unchanged since was scored at this pixel then and rejected (or taken and since improved on), the
 pixel's cost never rises, so it would be rejected again (gipuma.cu:555) and is not scored.  From the launch TSAR_COMPACT_FROM on, a
 wave packs the surviving (pixel, arm) pairs 64 per trip, whichever lanes' pixels they belong to.  Neither may change a bit of the
-state: the reference evaluates every hypothesis, every time.  The oracle-based whole-run tests (test_gpu_fast_exact.py,
-test_gpu_baseline_configs.py) run through tsar_pm_iterate and so through both; this file compares the library with itself —
-memo on / memo off / the packed form from the first launch it can serve / one call per iteration (no memo across calls) — at sizes
-and settings the oracle cannot reach in test time, and checks that the packed launches did run."""
+state: the reference evaluates every hypothesis, every time.  tests/test_gpu_call_parity.py holds both to the oracle: whole calls
+long enough for the packed form, at both workgroup shapes, both arithmetic modes, the box-11 and general-window loops and the
+geometric-consistency term.  This file compares the library with itself — memo on / memo off / the packed form from the first
+launch it can serve / one call per iteration (no memo across calls) — at sizes and settings the oracle cannot reach in test time,
+and checks that the packed launches did run."""
 import os
 
 import numpy as np
@@ -18,11 +19,11 @@ from tsar_mvs_amd import api, synth
 pytestmark = pytest.mark.gpu
 
 
-def _run(scene, env, iters, flags, n_best=1, one_call=True, timing=False, box=11):
+def _run(scene, env, iters, flags, n_best=1, one_call=True, timing=False, box=11, subset=None):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        m = api.matcher_from_scene(scene, box=box, n_best=n_best, seed=77, flags=flags)      # the knobs are read once, by tsar_create
+        m = api.matcher_from_scene(scene, box=box, n_best=n_best, seed=77, flags=flags, subset=subset)   # the knobs are read once, by tsar_create
     finally:
         for k, v in old.items():
             if v is None:
@@ -77,10 +78,11 @@ def test_memo_and_packed_form_change_no_bit(mode, shape):
 def test_packed_form_with_two_best_views_and_a_view_subset():
     """n_best 2 (the reference binary's default) takes the best-two kernel; a subset changes which views a pixel's cost is over"""
     sc = synth.make_scene(640, 480, 6, seed=9)
-    a, _ = _run(sc, {"TSAR_MEMO": "0"}, 5, 0, n_best=2)
-    b, t = _run(sc, {"TSAR_COMPACT_FROM": "2"}, 5, 0, n_best=2, timing=True)
+    a, _ = _run(sc, {"TSAR_MEMO": "0"}, 5, 0, n_best=2, subset=[2, 5, 3])
+    b, t = _run(sc, {"TSAR_COMPACT_FROM": "2"}, 5, 0, n_best=2, timing=True, subset=[2, 5, 3])
     _same(a, b)
     assert t["pm_sweep_packed"][0] == 8
+    assert set(np.unique(a[2])) <= {-1, 0, 2, 3, 5} and (a[2] == 5).any()   # (the best views come from the subset; 0 = never written)
 
 
 @pytest.mark.parametrize("mode", ["fast", "strict"])
