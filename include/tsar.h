@@ -278,8 +278,8 @@ int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem);
  * stored costs and the propagation memo (like tsar_set_view_subset).  TSAR_ERR_INVALID: n_views other than the context's, depth NULL,
  * weight < 0 or not finite, clip not in (0, 2^20]; TSAR_ERR_STATE: a context without source views.  tsar_set_views removes the term.
  * With a term installed every plane-scoring entry includes it (tsar_pm_init, tsar_pm_iterate[_final], tsar_pm_sweep,
- * tsar_pm_cost_planes, tsar_pm_rescore; the sweeps are timed as "pm_sweep_geom"); tsar_pyramid_views and tsar_upsample_planes return
- * TSAR_ERR_STATE (coarse-to-fine with the term is not supported).
+ * tsar_pm_cost_planes, tsar_pm_rescore, tsar_pyramid_planes, tsar_upsample_merge; the sweeps are timed as "pm_sweep_geom");
+ * tsar_pyramid_views and tsar_upsample_planes return TSAR_ERR_STATE (the pass runs coarse to fine through the three entries below).
  * tsar_clear_geom: removes the term and frees the maps.
  * tsar_pm_rescore: scores the current planes with the context's cost (the term included when installed) and writes cost, best view and
  * ratio.  A pixel whose plane is not a valid hypothesis — its depth not finite or outside [depth_min, depth_max], as the depth-0
@@ -290,6 +290,37 @@ int tsar_set_geom_depths(tsar_ctx* ctx, int n_views, const float* const* depth, 
 int tsar_clear_geom(tsar_ctx* ctx);
 int tsar_pm_rescore(tsar_ctx* ctx);
 int tsar_get_geom_matrices(tsar_ctx* ctx, int view, float* forward, float* back);   /* forward[12], back[12], row-major 3 x 4 */
+
+/* The geometric-consistency pass coarse to fine (ACMM's multi-scale geometric consistency).  Build every level first with
+ * tsar_pyramid_views while no term is installed anywhere, then install the term level by level with these entries:
+ *   fine: tsar_load_planes, tsar_set_geom_depths;  each coarser level: tsar_geom_pyramid, tsar_pyramid_planes;
+ *   coarsest: tsar_pm_iterate;  each finer level, down to the full resolution: tsar_upsample_merge, tsar_pm_iterate.
+ * Coarse pixel (x, y) lies on fine pixel (2x, 2y) (tsar_pyramid_views halves fx, fy, cx, cy exactly).
+ *
+ * tsar_geom_pyramid: installs on `coarse` a term with fine's weight and clip.  The clip keeps its value, now in pixels of the coarser
+ * level (ACMM keeps tau per scale).  Each source map of `fine` is carried one level down, without arithmetic:
+ *   Dc[y][x] = Df[2y][2x] if that is > 0; otherwise the first value > 0 among Df[2y][2x+1], Df[2y+1][2x], Df[2y+1][2x+1], counting only
+ *   pixels inside the image; otherwise 0 (no estimate).
+ * A NULL map stays NULL.  The coarse context owns its maps (tsar_clear_geom frees them), and it may be the `fine` of the next level.
+ * Voids coarse's stored costs and memo like tsar_set_geom_depths.  TSAR_ERR_STATE if `fine` has no term; TSAR_ERR_INVALID unless
+ * `coarse` holds ((w + 1) / 2, (h + 1) / 2) views of as many views, on the same device, with fine's cameras and their fx, fy, cx, cy
+ * halved (what tsar_pyramid_views installs).  The contexts' streams are ordered by an event.  Timed as "geom_pyramid".
+ * tsar_pyramid_planes: coarse plane (x, y) = fine plane (2x, 2y), bit for bit (planes are metric, getD_cu); then the coarse planes
+ * are scored as tsar_pm_rescore scores them, with the coarse context's own cost, its term included: a plane that is not a valid
+ * hypothesis there gets tsar_pm_init's draw, every stored cost is its plane's score, and the sweep counter restarts at 0.
+ * TSAR_ERR_INVALID if `fine` has no plane state or `coarse` holds no views of ((w + 1) / 2, (h + 1) / 2) on the same device.  Timed as
+ * "pm_pyramid_planes" (the copy) and "pm_rescore".
+ * tsar_upsample_merge: like tsar_upsample_planes, with the pixel's own plane kept as a candidate (in place of ACMM's detail restorer).
+ * Fine pixel (x, y) scores five planes with its full multi-view cost (tsar_pm_cost_planes's: arithmetic, window, best-N, subset, and
+ * the term when one is installed): 1. its own current plane; 2.-5. the coarse planes at (x / 2 + i, y / 2 + j), clamped, in the order
+ * (0,0), (1,0), (0,1), (1,1).  The lowest cost wins, the earlier candidate on a tie (so the own plane wins ties).  Plane, cost, best view
+ * and ratio are written as tsar_upsample_planes writes them; afterwards every stored cost is its plane's score and the sweep counter
+ * is 0.  Allowed with or without a term on either context.  The planes kept for tsar_compute_disp_final_upsampled are not touched.
+ * TSAR_ERR_INVALID if `fine` has no plane state, or `coarse` has no plane state of ((w + 1) / 2, (h + 1) / 2) on the same device.
+ * Timed as "pm_upsample_merge". */
+int tsar_geom_pyramid(tsar_ctx* coarse, const tsar_ctx* fine);
+int tsar_pyramid_planes(tsar_ctx* coarse, const tsar_ctx* fine);
+int tsar_upsample_merge(tsar_ctx* fine, const tsar_ctx* coarse);
 
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */

@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "tsar_load_planes", "tsar_compute_disp", "tsar_compute_disp_final", "tsar_depth_to_plane", "tsar_get_result",
     "tsar_pyramid_views", "tsar_upsample_planes", "tsar_compute_disp_final_upsampled", "tsar_get_view_image",
     "tsar_set_geom_depths", "tsar_clear_geom", "tsar_pm_rescore", "tsar_get_geom_matrices",
+    "tsar_geom_pyramid", "tsar_pyramid_planes", "tsar_upsample_merge",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -120,6 +121,9 @@ def load_library(path: str = LIB_PATH):
     L.tsar_clear_geom.argtypes = [C.c_void_p]
     L.tsar_pm_rescore.argtypes = [C.c_void_p]
     L.tsar_get_geom_matrices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.tsar_geom_pyramid.argtypes = [C.c_void_p, C.c_void_p]
+    L.tsar_pyramid_planes.argtypes = [C.c_void_p, C.c_void_p]
+    L.tsar_upsample_merge.argtypes = [C.c_void_p, C.c_void_p]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -383,6 +387,20 @@ class Matcher:
         self._chk(self.L.tsar_get_geom_matrices(self._ctx, view, _ptr(f)[0], _ptr(b)[0]))
         return f, b
 
+    # ---- the geometric-consistency pass coarse to fine ----
+    def geom_pyramid_from(self, fine: "Matcher"):
+        """install fine's term one level down (tsar_geom_pyramid): this context must hold fine's views from pyramid_from"""
+        self._chk(self.L.tsar_geom_pyramid(self._ctx, fine._ctx))
+
+    def pyramid_planes_from(self, fine: "Matcher"):
+        """start this context's plane state from fine's planes at (2x, 2y), rescored with this context's cost (tsar_pyramid_planes)"""
+        self._chk(self.L.tsar_pyramid_planes(self._ctx, fine._ctx))
+
+    def upsample_merge(self, coarse: "Matcher"):
+        """each pixel keeps the cheapest of its own plane and its four nearest coarse planes, the own plane winning ties
+        (tsar_upsample_merge)"""
+        self._chk(self.L.tsar_upsample_merge(self._ctx, coarse._ctx))
+
     def get_result(self, want=("depth", "normal", "cost", "confid"), pinned=False, out=None):
         """pinned=True: the result arrays are page-locked (tsar_host_alloc), so the D2H copies run at PCIe rate.
         out: dict of caller-owned arrays to fill instead (e.g. page-locked ones allocated once and reused per view)."""
@@ -603,6 +621,39 @@ def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, ite
     matcher.rescore()
     matcher.pm_iterate(iters)
     matcher.compute_disp()
+
+
+def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_depths, levels: int, coarse_iters: int, fine_iters: int,
+                             weight: float = 0.2, clip: float = 3.0, coarse=None):
+    """The geometric-consistency pass coarse to fine (include/tsar.h tsar_geom_pyramid): `levels` pyramid levels below `matcher`; the
+    view's own result and the term are carried down the chain, `coarse_iters` iterations run at the coarsest level, then every finer
+    level (matcher's own included) merges the coarser planes into its own and runs `fine_iters` iterations; compute_disp.  levels = 0
+    is run_geom_pass(matcher, ..., fine_iters).  coarse: the coarse contexts of an earlier call (finest first), reused; returns the
+    list used.  The terms stay installed (clear_geom removes them)."""
+    if levels < 0 or coarse_iters < 0 or fine_iters < 0:
+        raise ValueError("levels and iteration counts must be >= 0")
+    if levels == 0:
+        run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip)
+        return list(coarse or [])
+    coarse = list(coarse or [])
+    while len(coarse) < levels:
+        coarse.append(Matcher(matcher.device))
+    chain = [matcher] + coarse[:levels]
+    for m in chain:                    # tsar_pyramid_views refuses contexts with a term
+        m.clear_geom()
+    for finer, coarser in zip(chain[:-1], chain[1:]):
+        coarser.pyramid_from(finer)
+    matcher.load_planes(own_depth, own_normal_world)
+    matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
+    for finer, coarser in zip(chain[:-1], chain[1:]):
+        coarser.geom_pyramid_from(finer)
+        coarser.pyramid_planes_from(finer)
+    chain[-1].pm_iterate(coarse_iters)
+    for k in range(levels - 1, -1, -1):
+        chain[k].upsample_merge(chain[k + 1])
+        chain[k].pm_iterate(fine_iters)
+    matcher.compute_disp()
+    return coarse
 
 
 def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = None, cap: int | None = None, device: int = 0, matcher=None):

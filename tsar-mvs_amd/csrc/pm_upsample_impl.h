@@ -3,6 +3,8 @@
 // pm_init_impl.h with four hypotheses instead of one: the reference window is staged and hoisted once per pixel and the four
 // candidates run the same tap loop (box-11 loop / general-window loop / one-tap loop) as tsar_pm_cost_planes, so each candidate's
 // cost, best view and ratio are bit for bit what that call returns for it.
+// The merge form (MERGE, tsar_upsample_merge) scores the pixel's own current plane first, as a fifth candidate ahead of the four, so a
+// coarse plane replaces it only where it scores lower; with a geometric-consistency term installed it runs with variant bit 24.
 #pragma once
 #include "pm_core.h"
 
@@ -11,8 +13,11 @@
 // coarse: [ch][cw] plane map of the coarse level.  Candidates of fine pixel (x, y): coarse (x / 2 + i, y / 2 + j), i, j in {0, 1},
 // clamped to the coarse image, in the order (0,0), (1,0), (0,1), (1,1); the lowest cost wins, the first on a tie.  Writes the
 // winner's plane to n_out and keep_out (the context's resize4), its cost / best view / ratio to c_out / beview_out / ratio_out.
-template <int NB, int HR, bool STRICT, bool QUAD, int V = 0>
-__global__ __launch_bounds__(PM_BLOCK) void pm_upsample_kernel(const DevScene* __restrict__ sc, const float4* __restrict__ coarse, int cw, int ch,
+// MERGE: candidate 0 is own_in[p] (the fine state's plane), the four coarse ones follow; keep_out is not written.  own_in and n_out are
+// different buffers (the launcher writes the context's other ping-pong buffer).
+template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, bool MERGE = false>
+__global__ __launch_bounds__(PM_BLOCK) void pm_upsample_kernel(const DevScene* __restrict__ sc, const float4* __restrict__ own_in,
+                                                               const float4* __restrict__ coarse, int cw, int ch,
                                                                float* __restrict__ c_out, float4* __restrict__ n_out, float4* __restrict__ keep_out,
                                                                int32_t* __restrict__ beview_out, float* __restrict__ ratio_out, int tiles_x,
                                                                int n_tiles, int strip_w) {
@@ -44,44 +49,56 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_upsample_kernel(const DevScene* _
     PixelRef pr;
     if constexpr (LUTW) pr = hoist_reference_lut(sc, tile, tw, own, wts);
     else pr = hoist_reference<HR, TileT>(tile, tw, own, wts, hr, vr);
-    // candidates are loaded where they are scored and the winner is kept as its coarse index (an array of the four planes, indexed in
-    // the rolled loop, would live in scratch)
-    int best_q = cy0 * cw + cx0;
+    // candidates are loaded where they are scored and the winner is kept as its coarse index, -1 = the pixel's own plane (an array of
+    // the candidate planes, indexed in the rolled loop, would live in scratch; one rolled loop keeps one copy of the tap loop)
+    int best_q = MERGE ? -1 : cy0 * cw + cx0;
     float best_c = TSAR_MAXCOST, best_rt = 0.f;
     int best_bv = -1;
     if (pr.textured) {      // an untextured reference window scores MAXCOST / -1 / 0 for every plane: the first candidate wins
         best_c = __builtin_inff();
 #pragma unroll 1
-        for (int k = 0; k < 4; k++) {
-            const int q = ((k & 2) ? cy1 : cy0) * cw + ((k & 1) ? cx1 : cx0);
+        for (int k = MERGE ? -1 : 0; k < 4; k++) {
+            const int q = k < 0 ? -1 : ((k & 2) ? cy1 : cy0) * cw + ((k & 1) ? cx1 : cx0);
             int bv = -1;
             float rt = 0.f;
-            const float c = multiview_cost<NB, HR, STRICT, QUAD, V>(sc, tile, tw, own, wts, pr, x, y, coarse[q], bv, rt);
+            const float c = multiview_cost<NB, HR, STRICT, QUAD, V>(sc, tile, tw, own, wts, pr, x, y, (MERGE && q < 0) ? own_in[p] : coarse[q], bv, rt);
             if (c < best_c) { best_c = c; best_q = q; best_bv = bv; best_rt = rt; }
         }
     }
-    const float4 best_n = coarse[best_q];
+    const float4 best_n = (MERGE && best_q < 0) ? own_in[p] : coarse[best_q];
     n_out[p] = best_n;
-    keep_out[p] = best_n;
+    if constexpr (!MERGE) keep_out[p] = best_n;
     c_out[p] = best_c;
     beview_out[p] = best_bv;
     ratio_out[p] = best_rt;
 }
 
-template <int NB, int HR, bool STRICT, bool QUAD, int V = 0>
+// MERGE (tsar_upsample_merge): reads the state in buf[0], writes buf[1] (the caller swaps them); the plain form writes buf[0] and
+// resize4.  Timed as "pm_upsample_merge" / "pm_upsample".
+template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, bool MERGE = false>
 static int launch_up_t(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
     const DevScene& hs = ctx->hscene;
     const int tiles_x = (hs.w + PM_RW - 1) / PM_RW, tiles_y = (hs.h + UP_RH - 1) / UP_RH;
     const int n_tiles = tiles_x * tiles_y;
     const size_t lds = tile_bytes<QUAD>(PM_RW + 2 * hs.hrad, UP_RH + 2 * hs.vrad + ((V & 1024) ? LUT_TILE_PAD_ROWS : 0)) +
                        ((V & 1024) ? (size_t)(hs.lut_classes + 1) * 1024 : sizeof(float) * (size_t)(hs.hrad + 1) * (hs.vrad + 1) * PM_BLOCK);
-    auto kern = pm_upsample_kernel<NB, HR, STRICT, QUAD, V>;
+    auto kern = pm_upsample_kernel<NB, HR, STRICT, QUAD, V, MERGE>;
     if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const PlaneBuf& out = ctx->buf[MERGE ? 1 : 0];
     {
-        ScopedKernelTimer tm(ctx, "pm_upsample");
-        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(PM_BLOCK), lds, ctx->stream, ctx->dscene, coarse, cw, ch, ctx->buf[0].c, ctx->buf[0].n4,
-                           ctx->resize4, ctx->beview, ctx->ratio, tiles_x, n_tiles, strip_width(ctx->strip_w, tiles_x));
+        ScopedKernelTimer tm(ctx, MERGE ? "pm_upsample_merge" : "pm_upsample");
+        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(PM_BLOCK), lds, ctx->stream, ctx->dscene, MERGE ? ctx->buf[0].n4 : nullptr, coarse, cw, ch, out.c,
+                           out.n4, MERGE ? nullptr : ctx->resize4, ctx->beview, ctx->ratio, tiles_x, n_tiles, strip_width(ctx->strip_w, tiles_x));
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;
+}
+
+// The launchers' entry: the merge form carries the geometric-consistency term (variant bit 24) while one is installed; the plain form
+// never runs with one (tsar_upsample_planes refuses it).
+template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, bool MERGE = false>
+static int launch_up_g(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
+    if constexpr (MERGE)
+        if (ctx->hscene.geom_on) return launch_up_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, true>(ctx, coarse, cw, ch);
+    return launch_up_t<NB, HR, STRICT, QUAD, V, MERGE>(ctx, coarse, cw, ch);
 }

@@ -949,6 +949,98 @@ extern "C" int tsar_get_geom_matrices(tsar_ctx* ctx, int view, float* forward, f
     return TSAR_OK;
 }
 
+// ---- the geometric-consistency pass coarse to fine ------------------------------------------------------------------------------
+// `coarse` holds what tsar_pyramid_views installs from `fine`: ((w + 1) / 2, (h + 1) / 2) views of as many views, on the same device, with
+// fine's cameras and their fx, fy, cx, cy halved
+static bool is_pyramid_of(const tsar_ctx* coarse, const tsar_ctx* fine) {
+    if (!coarse->have_views || !fine->have_views || coarse->device != fine->device) return false;
+    if (coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2 || coarse->n_views != fine->n_views) return false;
+    if (coarse->cams.size() != fine->cams.size()) return false;
+    for (size_t v = 0; v < fine->cams.size(); v++) {
+        tsar_camera c = fine->cams[v];
+        c.K[0] *= 0.5f; c.K[2] *= 0.5f; c.K[4] *= 0.5f; c.K[5] *= 0.5f;
+        if (memcmp(&c, &coarse->cams[v], sizeof c) != 0) return false;
+    }
+    return true;
+}
+
+extern "C" int tsar_geom_pyramid(tsar_ctx* coarse, const tsar_ctx* fine_in) {
+    CHECK_CTX(coarse);
+    tsar_ctx* fine = const_cast<tsar_ctx*>(fine_in);   // its maps are only read; its stream is recorded on
+    if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_geom_pyramid: fine must be another context");
+    if (!fine->hscene.geom_on) return fail(coarse, TSAR_ERR_STATE, "tsar_geom_pyramid: the fine context has no geometric-consistency term");
+    if (!is_pyramid_of(coarse, fine))
+        return fail(coarse, TSAR_ERR_INVALID, "tsar_geom_pyramid: the coarse context must hold fine's views one level down (tsar_pyramid_views)");
+    TSAR_HIP_TRY(coarse, hipStreamSynchronize(coarse->stream));   // no kernel may still read the maps about to be freed
+    free_geom(coarse);
+    const size_t np = (size_t)coarse->w * coarse->h;
+    coarse->geom_maps.assign(coarse->n_views, nullptr);
+    DevScene& sc = coarse->hscene;
+    int rc = stream_after(coarse, fine);
+    for (int v = 1; v < coarse->n_views && rc == TSAR_OK; v++) {
+        const float* src = fine->hscene.geom_depth[v];
+        if (!src) continue;
+        rc = dev_alloc(coarse, &coarse->geom_maps[v], np);
+        if (rc == TSAR_OK) rc = launch_geom_pyramid(coarse, src, fine->w, fine->h, coarse->geom_maps[v]);
+        sc.geom_depth[v] = coarse->geom_maps[v];
+    }
+    if (rc != TSAR_OK) {
+        // (the device block must not keep pointers to the freed maps, so it is uploaded without any term)
+        hipStreamSynchronize(coarse->stream);
+        free_geom(coarse);
+        upload_scene(coarse);
+        return rc;
+    }
+    sc.geom_weight = fine->hscene.geom_weight;
+    sc.geom_clip = fine->hscene.geom_clip;         // the same number of pixels of this level
+    sc.geom_clip_sq = fine->hscene.geom_clip_sq;
+    sc.geom_on = 1;
+    if (coarse->have_state) coarse->cost_consistent = false;
+    coarse->memo_valid_from = coarse->launch_seq + 1;
+    return upload_scene(coarse);           // (synchronises the stream: the maps are complete on return)
+}
+
+extern "C" int tsar_pyramid_planes(tsar_ctx* coarse, const tsar_ctx* fine_in) {
+    CHECK_CTX(coarse);
+    tsar_ctx* fine = const_cast<tsar_ctx*>(fine_in);
+    if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: fine must be another context");
+    if (!fine->have_state) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: the fine context has no plane state");
+    if (!coarse->have_views || fine->device != coarse->device || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
+        return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one on the same device");
+    NEED_SOURCES(coarse);
+    TRY(stream_after(coarse, fine));
+    TRY(launch_pyramid_planes(coarse, fine->buf[0].n4, fine->w, fine->h, coarse->buf[0].n4));
+    // then tsar_pm_rescore: read buf[0], write buf[1], swap
+    TRY(launch_pm_rescore(coarse, coarse->buf[0].n4, coarse->buf[1].c, coarse->buf[1].n4, coarse->beview, coarse->ratio));
+    TSAR_HIP_TRY(coarse, hipStreamSynchronize(coarse->stream));
+    std::swap(coarse->buf[0], coarse->buf[1]);
+    coarse->have_state = true;
+    coarse->have_out = false;
+    coarse->sweeps_done = 0;
+    coarse->cost_consistent = true;
+    coarse->memo_valid_from = coarse->launch_seq + 1;
+    return TSAR_OK;
+}
+
+extern "C" int tsar_upsample_merge(tsar_ctx* fine, const tsar_ctx* coarse_in) {
+    CHECK_CTX(fine);
+    tsar_ctx* coarse = const_cast<tsar_ctx*>(coarse_in);
+    if (!coarse || coarse == fine) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: coarse must be another context");
+    if (!fine->have_state) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: the fine context has no plane state");
+    NEED_SOURCES(fine);
+    if (coarse->device != fine->device || !coarse->have_state || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
+        return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: the coarse context must hold a plane state of ((w + 1) / 2, (h + 1) / 2) on the same device");
+    TRY(stream_after(fine, coarse));
+    TRY(launch_pm_upsample_merge(fine, coarse->buf[0].n4, coarse->w, coarse->h));   // buf[0] -> buf[1]
+    TSAR_HIP_TRY(fine, hipStreamSynchronize(fine->stream));
+    std::swap(fine->buf[0], fine->buf[1]);
+    fine->have_out = false;
+    fine->sweeps_done = 0;              // the sweeps that follow draw like the ones after tsar_pm_init
+    fine->cost_consistent = true;       // every cost is its plane's score on the sweep window
+    fine->memo_valid_from = fine->launch_seq + 1;
+    return TSAR_OK;
+}
+
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);

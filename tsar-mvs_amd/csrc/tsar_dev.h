@@ -261,8 +261,11 @@ int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& same_i
 int launch_pm_cost_planes(tsar_ctx* ctx, const float4* planes, float* cost, int32_t* beview, float* ratio);
 int launch_pm_rescore(tsar_ctx* ctx, const float4* planes, float* cost, float4* n, int32_t* beview, float* ratio);   // pm_init.hip
 int launch_pm_upsample(tsar_ctx* ctx, const float4* coarse, int cw, int ch);                     // pm_upsample.hip
-int launch_pm_upsample_lut(tsar_ctx* ctx, int need, const float4* coarse, int cw, int ch);       // pm_upsample_lut.hip
+int launch_pm_upsample_merge(tsar_ctx* ctx, const float4* coarse, int cw, int ch);               // pm_upsample.hip (buf[0] -> buf[1])
+int launch_pm_upsample_lut(tsar_ctx* ctx, int need, bool merge, const float4* coarse, int cw, int ch);   // pm_upsample_lut.hip
 int launch_pyr_down(tsar_ctx* ctx, const float* src, int w, int h, void* dst, bool u8);        // tsar_pyramid.hip
+int launch_geom_pyramid(tsar_ctx* ctx, const float* src, int w, int h, float* dst);            // tsar_pyramid.hip
+int launch_pyramid_planes(tsar_ctx* ctx, const float4* src, int w, int h, float4* dst);        // tsar_pyramid.hip
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world);
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);

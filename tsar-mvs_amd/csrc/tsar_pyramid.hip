@@ -68,3 +68,55 @@ int launch_pyr_down(tsar_ctx* ctx, const float* src, int w, int h, void* dst, bo
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;
 }
+
+// ---- the geometric-consistency pass coarse to fine (tsar_geom_pyramid / tsar_pyramid_planes) -------------------------------------
+// Coarse pixel (x, y) lies on fine pixel (2x, 2y) (the coarse K is the fine one with fx, fy, cx, cy halved).  Both kernels only move
+// values, one thread per coarse pixel: memory-bound passes over a quarter of the fine map.
+
+// A source view's depth map one level down: Df[2y][2x] if > 0, else the first value > 0 among Df[2y][2x+1], Df[2y+1][2x],
+// Df[2y+1][2x+1] that lies inside the image, else 0 (no estimate).  (NaN is not > 0: it is skipped like a hole.)
+__global__ __launch_bounds__(PYR_BLOCK) void geom_pyramid_kernel(const float* __restrict__ src, int w, int h, float* __restrict__ dst, int cw, int ch) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= cw || y >= ch) return;
+    const int fx = 2 * x, fy = 2 * y;        // inside: cw = (w + 1) / 2, ch = (h + 1) / 2
+    const bool right = fx + 1 < w, below = fy + 1 < h;
+    const float* row0 = src + (size_t)fy * w;
+    float d = row0[fx];
+    if (!(d > 0.0f)) {
+        const float d1 = right ? row0[fx + 1] : 0.0f;
+        const float d2 = below ? row0[w + fx] : 0.0f;
+        const float d3 = right && below ? row0[w + fx + 1] : 0.0f;
+        d = d1 > 0.0f ? d1 : d2 > 0.0f ? d2 : d3 > 0.0f ? d3 : 0.0f;
+    }
+    dst[(size_t)y * cw + x] = d;
+}
+
+// Plane decimation: the coarse plane at (x, y) is the fine plane at (2x, 2y), bit for bit (planes (n, d) are metric, getD_cu).
+__global__ __launch_bounds__(PYR_BLOCK) void pm_pyramid_planes_kernel(const float4* __restrict__ src, int w, float4* __restrict__ dst, int cw, int ch) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= cw || y >= ch) return;
+    dst[(size_t)y * cw + x] = src[(size_t)(2 * y) * w + 2 * x];
+}
+
+// src: a fine depth map [h][w]; dst: [(h + 1) / 2][(w + 1) / 2]; both on ctx's device, written on ctx's stream
+int launch_geom_pyramid(tsar_ctx* ctx, const float* src, int w, int h, float* dst) {
+    const int cw = (w + 1) / 2, ch = (h + 1) / 2;
+    const dim3 grid((cw + 63) / 64, (ch + 3) / 4);
+    {
+        ScopedKernelTimer tm(ctx, "geom_pyramid");
+        hipLaunchKernelGGL(geom_pyramid_kernel, grid, dim3(PYR_BLOCK), 0, ctx->stream, src, w, h, dst, cw, ch);
+    }
+    TSAR_HIP_TRY(ctx, hipGetLastError());
+    return TSAR_OK;
+}
+// src: fine planes [h][w]; dst: [(h + 1) / 2][(w + 1) / 2]
+int launch_pyramid_planes(tsar_ctx* ctx, const float4* src, int w, int h, float4* dst) {
+    const int cw = (w + 1) / 2, ch = (h + 1) / 2;
+    const dim3 grid((cw + 63) / 64, (ch + 3) / 4);
+    {
+        ScopedKernelTimer tm(ctx, "pm_pyramid_planes");
+        hipLaunchKernelGGL(pm_pyramid_planes_kernel, grid, dim3(PYR_BLOCK), 0, ctx->stream, src, w, dst, cw, ch);
+    }
+    TSAR_HIP_TRY(ctx, hipGetLastError());
+    return TSAR_OK;
+}

@@ -21,6 +21,11 @@
 //                      the geometric-consistency term (include/tsar.h tsar_set_geom_depths), rescores, runs N iterations at full
 //                      resolution and writes TSAR_geom_disp.dmb + TSAR_geom_normals.dmb + TSAR_geom.txt (its settings); resumed only
 //                      when that record matches and no input is newer than the outputs; with --fuse the geom maps are fused
+//     [--geom_multi_scale=L (0) [--geom_coarse_iterations=N (--geom_iterations)]]   phase 2 coarse to fine (ACMM): the view's own maps
+//                      and the term go down L pyramid levels (tsar_pyramid_views, tsar_geom_pyramid, tsar_pyramid_planes), N iterations
+//                      run at the coarsest, then each finer level merges the coarser planes into its own (tsar_upsample_merge) and runs
+//                      --geom_iterations iterations; each worker keeps its coarse contexts across views; TSAR_geom.txt gains a line
+//                      with the two settings when L >= 1.  L = 0: the single-scale pass above
 //   --all resumes: a view whose APD/<id>/TSAR_disp.dmb and TSAR_normals.dmb are complete (the reference's header, main.cpp:1817-1860 /
 //                      fileIoUtils.h:333-381, and exactly h*w*nb floats behind it) is skipped — the output files are the per-view
 //                      checkpoints; --force recomputes.  A view that fails on one GPU is retried once on the next
@@ -75,6 +80,8 @@ struct Options {
     bool coarse_iterations_set = false, textureless_merge = false;
     bool geom = false;                               // --geom_consistency: phase 2 of --all (run_geom_view)
     int geom_iterations = 2;
+    int geom_multi_scale = 0, geom_coarse_iterations = -1;   // --geom_multi_scale / --geom_coarse_iterations (-1: --geom_iterations)
+    bool geom_coarse_iterations_set = false;
     float geom_weight = 0.2f, geom_clip = 3.0f;      // ACMM's lambda and tau (include/tsar.h tsar_set_geom_depths)
 };
 
@@ -172,7 +179,7 @@ static void usage() {
            "                   [--depth_min=D --depth_max=D] [--mode=patchmatch|load|tsar] [--all --gpus=N --workers=W] [--seed=S] [--strict] [--fix-quirks] [--texture-filter-8bit] [-color_processing] [--display_outputs] [--timing]\n"
            "                   [--multi_scale=L [--coarse_iterations=N] [--textureless_merge]]\n"
            "       tsar_gipuma --all [--gpus=N] [--force] [--fuse [--num_consistent=N --reproj_error=PX --depth_diff=REL --angle=DEG --used_list=0|1]]\n"
-           "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX]]\n"
+           "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX] [--geom_multi_scale=L [--geom_coarse_iterations=N]]]\n"
            "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n");
 }
 
@@ -201,6 +208,18 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
         else if (starts("--workers=")) o.workers = atoi(a + 10);
         else if (starts("--seed=")) o.seed = strtoull(a + 7, nullptr, 10);
         else if (starts("--mode=")) o.mode = a + 7;
+        else if (starts("--geom_multi_scale=") || starts("--geom_coarse_iterations=")) {
+            const bool ms = starts("--geom_multi_scale=");
+            const char* v = strchr(a, '=') + 1;
+            char* end = nullptr;
+            const long k = strtol(v, &end, 10);
+            if (!*v || *end || k < 0 || k > (ms ? 8 : 1000000)) {
+                printf("Command-line parameter error: %s must be %s\n", a, ms ? "an integer in 0..8" : "a non-negative integer");
+                return -1;
+            }
+            if (ms) o.geom_multi_scale = (int)k;
+            else { o.geom_coarse_iterations = (int)k; o.geom_coarse_iterations_set = true; }
+        }
         else if (starts("--multi_scale=") || starts("--coarse_iterations=")) {
             const bool ms = starts("--multi_scale=");
             const char* v = strchr(a, '=') + 1;
@@ -673,13 +692,20 @@ static double ms_since_exec() {
 // Every view starts from its own phase-1 maps (TSAR_disp.dmb + TSAR_normals.dmb), installs its pair.txt sources' TSAR_disp.dmb as the
 // geometric-consistency term, rescores, runs --geom_iterations iterations (single scale, full resolution) and writes
 // TSAR_geom_disp.dmb + TSAR_geom_normals.dmb (the layout of the phase-1 maps) and TSAR_geom.txt, the settings they were made with.
+// --geom_multi_scale=L >= 1 runs the pass coarse to fine instead (api.run_geom_pass_multiscale's chain) and records a second line.
 static const char* const GEOM_RECORD = "TSAR_geom.txt";
+static int geom_coarse_iterations_of(const Options& o) { return o.geom_coarse_iterations_set ? o.geom_coarse_iterations : o.geom_iterations; }
 static std::string geom_record_of(const Options& o) {
-    char b[320];
+    char b[400];
     snprintf(b, sizeof b, "geom_iterations=%d geom_weight=%.9g geom_clip=%.9g blocksize=%d n_best=%d cost_comb=%d seed=%llu strict=%d fix_quirks=%d texture_filter_8bit=%d cam_scale=%.9g depth_min=%.9g depth_max=%.9g\n",
              o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
              o.fix_quirks ? 1 : 0, o.tex8 ? 1 : 0, (double)o.cam_scale, (double)o.depth_min, (double)o.depth_max);
-    return b;
+    std::string rec = b;
+    if (o.geom_multi_scale > 0) {     // (an L = 0 record is the single-scale one, byte for byte)
+        snprintf(b, sizeof b, "geom_multi_scale=%d geom_coarse_iterations=%d\n", o.geom_multi_scale, geom_coarse_iterations_of(o));
+        rec += b;
+    }
+    return rec;
 }
 static bool mtime_of(const std::string& path, struct timespec& t) {
     struct stat st;
@@ -713,11 +739,19 @@ static bool geom_outputs_current(const Options& o, int ref, const std::vector<in
     return true;
 }
 
-// One view's phase 2 on `device`; ctx is the worker's context (created on first use, kept across its views, dropped after a failure).
-static int run_geom_view(const Options& o, int device, tsar_ctx*& ctx, int ref, const std::vector<int>& srcs, double* seconds) {
+// One view's phase 2 on `device`; ctx is the worker's context and coarse its coarse contexts, finest first (--geom_multi_scale): created
+// on first use, kept across its views, dropped after a failure.
+static int run_geom_view(const Options& o, int device, tsar_ctx*& ctx, std::vector<tsar_ctx*>& coarse, int ref, const std::vector<int>& srcs,
+                         double* seconds) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!ctx && tsar_create(device, &ctx) != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed\n", device); ctx = nullptr; return -1; }
-    auto fail = [&](const char* what) { fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, ctx ? tsar_last_error(ctx) : ""); tsar_destroy(ctx); ctx = nullptr; return -1; };
+    auto drop_coarse = [&]() { for (tsar_ctx* c : coarse) tsar_destroy(c); coarse.clear(); };
+    auto fail = [&](const char* what) { fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, ctx ? tsar_last_error(ctx) : ""); tsar_destroy(ctx); ctx = nullptr; drop_coarse(); return -1; };
+    auto fail_at = [&](const char* what, tsar_ctx* c) {
+        fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, tsar_last_error(c));
+        tsar_destroy(ctx); ctx = nullptr; drop_coarse();
+        return -1;
+    };
     std::vector<int> ids = {ref};
     ids.insert(ids.end(), srcs.begin(), srcs.end());
     const int n = (int)ids.size();
@@ -767,10 +801,35 @@ static int run_geom_view(const Options& o, int device, tsar_ctx*& ctx, int ref, 
               (o.tex8 ? TSAR_FLAG_TEX_FILTER_8BIT : 0);
     if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
     if (tsar_set_views_u8(ctx, n, w, h, ptrs.data(), TSAR_MEM_HOST, cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
+    const int L = o.geom_multi_scale;
+    // coarse to fine: every level's views first, while no term is installed (the coarse contexts still hold the previous view's)
+    while ((int)coarse.size() < L) {
+        tsar_ctx* c = nullptr;
+        if (tsar_create(device, &c) != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed\n", device); tsar_destroy(ctx); ctx = nullptr; drop_coarse(); return -1; }
+        coarse.push_back(c);
+    }
+    for (int k = 0; k < L; k++) {
+        if (tsar_clear_geom(coarse[k]) != TSAR_OK) return fail_at("tsar_clear_geom", coarse[k]);
+        if (tsar_pyramid_views(coarse[k], k ? coarse[k - 1] : ctx) != TSAR_OK) return fail_at("tsar_pyramid_views", coarse[k]);
+    }
     if (tsar_load_planes(ctx, own_d.data(), own_n.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
     if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
-    if (tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
-    if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
+    if (L == 0) {
+        if (tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
+        if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
+    } else {
+        for (int k = 0; k < L; k++) {
+            const tsar_ctx* finer = k ? coarse[k - 1] : ctx;
+            if (tsar_geom_pyramid(coarse[k], finer) != TSAR_OK) return fail_at("tsar_geom_pyramid", coarse[k]);
+            if (tsar_pyramid_planes(coarse[k], finer) != TSAR_OK) return fail_at("tsar_pyramid_planes", coarse[k]);
+        }
+        if (tsar_pm_iterate(coarse[L - 1], geom_coarse_iterations_of(o)) != TSAR_OK) return fail_at("tsar_pm_iterate (coarsest level)", coarse[L - 1]);
+        for (int k = L - 1; k >= 0; k--) {
+            tsar_ctx* finer = k ? coarse[k - 1] : ctx;
+            if (tsar_upsample_merge(finer, coarse[k]) != TSAR_OK) return fail_at("tsar_upsample_merge", finer);
+            if (tsar_pm_iterate(finer, o.geom_iterations) != TSAR_OK) return fail_at("tsar_pm_iterate", finer);
+        }
+    }
     if (tsar_compute_disp(ctx) != TSAR_OK) return fail("tsar_compute_disp");
     const size_t np = (size_t)w * h;
     std::vector<float> depth(np), normal(3 * np);
@@ -802,13 +861,15 @@ static int run_geom_phase(const Options& o, const std::vector<int>& refs, std::m
     for (int g = 0; g < ngpu; g++)
         th.emplace_back([&, g]() {
             tsar_ctx* ctx = nullptr;
+            std::vector<tsar_ctx*> coarse;     // --geom_multi_scale: the worker's coarse contexts, kept across its views
             for (size_t k = g; k < refs.size(); k += ngpu) {
                 gpu_of[k] = g;
                 if (skip[k]) { printf("view %08d: geom outputs present, skipped\n", refs[k]); continue; }
                 double sec = 0;
-                rc[k] = run_geom_view(o, g, ctx, refs[k], pairs[refs[k]], &sec);
+                rc[k] = run_geom_view(o, g, ctx, coarse, refs[k], pairs[refs[k]], &sec);
                 printf("view %08d on gpu %d (geom): %s (%.2f s)\n", refs[k], g, rc[k] == 0 ? "ok" : "FAILED", sec);
             }
+            for (tsar_ctx* c : coarse) tsar_destroy(c);
             tsar_destroy(ctx);
         });
     for (auto& t : th) t.join();
@@ -818,8 +879,10 @@ static int run_geom_phase(const Options& o, const std::vector<int>& refs, std::m
         if (rc[k] != 0) {
             const int g2 = (gpu_of[k] + 1) % ngpu;
             tsar_ctx* ctx = nullptr;
+            std::vector<tsar_ctx*> coarse;
             double sec = 0;
-            rc[k] = run_geom_view(o, g2, ctx, refs[k], pairs[refs[k]], &sec);
+            rc[k] = run_geom_view(o, g2, ctx, coarse, refs[k], pairs[refs[k]], &sec);
+            for (tsar_ctx* c : coarse) tsar_destroy(c);
             tsar_destroy(ctx);
             printf("view %08d on gpu %d (geom, retry): %s (%.2f s)\n", refs[k], g2, rc[k] == 0 ? "ok" : "FAILED", sec);
         }
@@ -839,6 +902,11 @@ int main(int argc, char** argv) {
         if (o.mode != "patchmatch") { fprintf(stderr, "--multi_scale / --coarse_iterations / --textureless_merge work with --mode=patchmatch only\n"); return 1; }
         if (o.multi_scale == 0) { fprintf(stderr, "--coarse_iterations / --textureless_merge need --multi_scale=L with L >= 1\n"); return 1; }
     }
+    if ((o.geom_multi_scale > 0 || o.geom_coarse_iterations_set) && !o.geom) {
+        fprintf(stderr, "--geom_multi_scale / --geom_coarse_iterations work with --geom_consistency only\n");
+        return 1;
+    }
+    if (o.geom_coarse_iterations_set && o.geom_multi_scale == 0) { fprintf(stderr, "--geom_coarse_iterations needs --geom_multi_scale=L with L >= 1\n"); return 1; }
     if (o.geom) {
         if (!o.all) { fprintf(stderr, "--geom_consistency needs --all (phase 2 reads every view's phase-1 maps)\n"); return 1; }
         if (o.mode == "tsar") { fprintf(stderr, "--geom_consistency does not work with --mode=tsar\n"); return 1; }
