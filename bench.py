@@ -8,7 +8,11 @@ ETH3D full resolution 6048x4032, 10 source views, 8 iterations, --blocksize 11, 
 region.  N GPUs = N reference views, one per rank (weak scaling), results gathered to rank 0 over RCCL
 inside the timed region (the "gather before fusion" of the north star).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 6048 --height 4032 --views 10 --iters 8] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 6048 --height 4032 --views 10 --iters 8] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full also measures, after the timed
+steps and on one rank only, what the headline does not need: the strict-arithmetic record with the fast-vs-strict tolerance
+(`strict`, `config.tolerance`), the host-boundary legs (`host_boundary`) and the CPU oracle baseline (`cpu_baseline`).
 """
 import argparse
 import json
@@ -295,7 +299,7 @@ def device_key(ident: dict):
     return ident.get("pci") or ident.get("uuid") or (ident.get("visible"), ident["index"])
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -321,9 +325,17 @@ def main():
                     help="after the timed steps, write the depth / normal / cost maps of the last timed step (rank 0: the gathered maps of all "
                          "ranks) as DIR/<name>.npy in float32; maps beyond %d pixels in all are written at a fixed, seeded sample of pixels "
                          "(bench.dump_outputs), e.g. bench_outputs/" % DUMP_MAX_PIXELS)
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, with one rank, also run the legs the headline does not need: the strict-arithmetic record and "
+                         "config.tolerance, the host-boundary legs and the CPU oracle baseline (each still subject to its --no-* switch)")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -514,13 +526,14 @@ def main():
         if gather_check is not None:
             line["gather_check"] = gather_check
         line["config"]["tolerance"] = None
-        if world == 1 and not args.no_strict_record:
+        full = world == 1 and args.full           # the legs below take runs of their own; a plain run reports the timed steps only
+        if full and not args.no_strict_record:
             # the headline arithmetic's distance from the reference's, measured in this very run: fast maps of the last timed step
             # against the strict maps of the same scene, seed and step
             line["strict"], line["config"]["tolerance"] = strict_mode_record(args, sc, local_rank, fast_maps=tuple(sets[state["last"]]))
-        if world == 1 and not args.no_host_boundary:
+        if full and not args.no_host_boundary:
             line["host_boundary"] = host_boundary(args, sc)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(line), flush=True)
     m.close()
