@@ -19,7 +19,7 @@ LD_PRELOAD=$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0:halt_o
     python -m pytest tests/test_oracle_known_answers.py tests/test_slic_reference_golden.py tests/test_oracle_independent_float64.py tests/test_oracle_independent_sweep.py tests/test_golden.py -x -q -m "not gpu"
 cp "$S/oracle.bak" "$ROOT/oracle/libtsar_oracle.so"; touch "$ROOT/oracle/libtsar_oracle.so"
 (cd "$ROOT/tsar-mvs_amd" && g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -pthread -o tsar_gipuma host/tsar_gipuma.cpp -L. -ltsar_hip -lz -Wl,-rpath,"$ROOT/tsar-mvs_amd")
-ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_io_cli.py tests/test_jpeg_decode.py -q -m "not gpu"
+ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_io_cli.py tests/test_cli_resume_records_cpu.py tests/test_jpeg_decode.py -q -m "not gpu"
 #   3. the JPEG reader (host/tsar_jpeg.h) on damaged files: tools/jpeg_fuzz.cpp, 3000 mutations each of a baseline 4:2:0, a
 #      progressive 4:2:2, a 4:4:4 file with restart markers and optimised tables, and a gray file (written here with Pillow)
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o "$S/jpeg_fuzz" "$ROOT/tools/jpeg_fuzz.cpp"

@@ -50,8 +50,10 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <fstream>
+#include <functional>
 #include <future>
 #include <map>
 #include <math.h>
@@ -208,8 +210,8 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
         else if (starts("--workers=")) o.workers = atoi(a + 10);
         else if (starts("--seed=")) o.seed = strtoull(a + 7, nullptr, 10);
         else if (starts("--mode=")) o.mode = a + 7;
-        else if (starts("--geom_multi_scale=") || starts("--geom_coarse_iterations=")) {
-            const bool ms = starts("--geom_multi_scale=");
+        else if (starts("--multi_scale=") || starts("--coarse_iterations=") || starts("--geom_multi_scale=") || starts("--geom_coarse_iterations=")) {
+            const bool geom = starts("--geom_"), ms = starts(geom ? "--geom_multi_scale=" : "--multi_scale=");
             const char* v = strchr(a, '=') + 1;
             char* end = nullptr;
             const long k = strtol(v, &end, 10);
@@ -217,19 +219,8 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
                 printf("Command-line parameter error: %s must be %s\n", a, ms ? "an integer in 0..8" : "a non-negative integer");
                 return -1;
             }
-            if (ms) o.geom_multi_scale = (int)k;
-            else { o.geom_coarse_iterations = (int)k; o.geom_coarse_iterations_set = true; }
-        }
-        else if (starts("--multi_scale=") || starts("--coarse_iterations=")) {
-            const bool ms = starts("--multi_scale=");
-            const char* v = strchr(a, '=') + 1;
-            char* end = nullptr;
-            const long k = strtol(v, &end, 10);
-            if (!*v || *end || k < 0 || k > (ms ? 8 : 1000000)) {
-                printf("Command-line parameter error: %s must be %s\n", a, ms ? "an integer in 0..8" : "a non-negative integer");
-                return -1;
-            }
-            if (ms) o.multi_scale = (int)k;
+            if (ms) (geom ? o.geom_multi_scale : o.multi_scale) = (int)k;
+            else if (geom) { o.geom_coarse_iterations = (int)k; o.geom_coarse_iterations_set = true; }
             else { o.coarse_iterations = (int)k; o.coarse_iterations_set = true; }
         }
         else if (!strcmp(a, "--textureless_merge")) o.textureless_merge = true;
@@ -342,11 +333,15 @@ static DeviceImageCache g_device_images;
 struct DeviceResult {
     int device = -1, w = 0, h = 0;
     float *depth = nullptr, *normal = nullptr;
-    tsar_camera cam{};
 };
+static void release(DeviceResult& r) {
+    if (r.depth) tsar_device_free(r.device, r.depth);
+    if (r.normal) tsar_device_free(r.device, r.normal);
+    r = DeviceResult{};
+}
 
 // What the refinement modes read per view besides the reference image: the external depth / normal maps and (--mode=tsar)
-// weak.png.  Loaded by helper threads; in --all runs a worker keeps two of these, page-locked, and starts loading view k+1's
+// weak.png.  Loaded by helper threads; in --all runs a worker keeps a ring of these, page-locked, and starts loading the next views'
 // while view k is on the GPU (inflating a full-size weak.png alone takes longer than the view's kernels).
 struct ExternalInputs {
     bool pinned = false;                       // --all: buffers reused by every view of the worker, worth page-locking
@@ -377,36 +372,16 @@ void ExternalInputs::start(const std::string& view_dir, bool want_mask, const st
     if (want_mask) mask = std::async(std::launch::async, [this]() { mask_ok = read_reliable_mask(dir + "weak.png", scale, mw, mh); });
 }
 
-// one reference view: images[0] is the reference, the rest the candidate sources in argv order
-// page-locked result buffers of one worker, allocated once and reused for every view it processes (page-locking 390 MB per view
-// would cost more than the copy it speeds up)
+// one view's result maps on the host and where they go; a worker's sets are allocated once and reused for every view it processes
+// (page-locking 390 MB per view would cost more than the copy it speeds up)
 struct HostResult {
     PinnedFloats depth, normal;
     std::string out_dir;        // where the view's .dmb files go
     int w = 0, h = 0;
-    tsar_ctx** shared_ctx = nullptr;   // the worker's context, kept across its views (device planes are allocated once)
-    std::vector<tsar_ctx*>* shared_coarse = nullptr;   // --multi_scale: the worker's coarse contexts, finest first, kept likewise
-    std::string ms_record;             // --multi_scale: the settings written beside the maps (empty: single scale, no record)
-    bool device_image_cache = false;   // --all: images stay resident on the device across views (a one-view process would only hold every image twice)
 };
-static const char* const MS_RECORD = "TSAR_multiscale.txt";
-static bool write_view_files(const HostResult& r) {   // the two files side by side: a write is a copy into the page cache
-    // the settings record goes first and comes back last: maps that are being replaced never carry the record of other settings
-    unlink((r.out_dir + MS_RECORD).c_str());
-    auto normals = std::async(std::launch::async, [&r]() { return write_dmb(r.out_dir + "TSAR_normals.dmb", r.normal.data(), r.h, r.w, 3); });
-    const bool depth_ok = write_dmb(r.out_dir + "TSAR_disp.dmb", r.depth.data(), r.h, r.w, 1);
-    bool ok = normals.get() && depth_ok;
-    if (ok && !r.ms_record.empty()) {
-        FILE* f = fopen((r.out_dir + MS_RECORD).c_str(), "w");
-        ok = f && fputs(r.ms_record.c_str(), f) >= 0;
-        if (f && fclose(f) != 0) ok = false;
-    }
-    return ok;
-}
 
 // Fault injection for the re-queue path (tests): TSAR_GIPUMA_INJECT_FAILURE=<view id>[:<times>] makes the first <times> (default 1)
 // attempts at that view fail after its context exists, the way a device-side error would (the context is dropped).
-#include <atomic>
 static int g_inject_view = -1;
 static std::atomic<int> g_inject_left{0};
 static void read_injection() {
@@ -416,8 +391,23 @@ static void read_injection() {
     const char* c = strchr(e, ':');
     g_inject_left = c ? atoi(c + 1) : 1;
 }
-static std::string view_dir_of(const Options& o, int ref) { char b[32]; snprintf(b, sizeof b, "%08d", ref); return o.mslp_folder + "APD/" + b + "/"; }
-static std::string view_image_of(const Options& o, int ref) { char b[32]; snprintf(b, sizeof b, "%08d.pgm", ref); return o.images_folder + pnm_name(b, o.color ? ".ppm" : ".pgm"); }
+
+static std::string id8(int id) { char b[32]; snprintf(b, sizeof b, "%08d", id); return b; }
+static std::string view_dir_of(const Options& o, int ref) { return o.mslp_folder + "APD/" + id8(ref) + "/"; }
+static std::string image_path(const Options& o, const std::string& name) { return o.images_folder + pnm_name(name, o.color ? ".ppm" : ".pgm"); }
+static std::string view_image_of(const Options& o, int ref) { return image_path(o, id8(ref) + ".pgm"); }
+static std::string cam_path(const Options& o, const std::string& name) { return o.mslp_folder + "cams/" + stem8(name) + "_cam.txt"; }
+// --all: the image names of a reference view and its pair.txt sources, as the per-view command line gives them
+static std::vector<std::string> names_of(int ref, const std::vector<int>& srcs) {
+    std::vector<std::string> names = {id8(ref) + ".pgm"};
+    for (int s : srcs) names.push_back(id8(s) + ".pgm");
+    return names;
+}
+
+// ---- settings records: what each phase leaves in APD/<id>/ and when --all takes it as done ------------------------------------
+struct MapFiles { const char *depth, *normal, *record; };
+static const MapFiles PHASE1_FILES = {"TSAR_disp.dmb", "TSAR_normals.dmb", "TSAR_multiscale.txt"};
+static const MapFiles GEOM_FILES = {"TSAR_geom_disp.dmb", "TSAR_geom_normals.dmb", "TSAR_geom.txt"};
 // what a multi-scale view records beside its maps (empty for a single-scale run, which leaves no record)
 static std::string ms_record_of(const Options& o) {
     if (o.multi_scale == 0) return "";
@@ -426,24 +416,202 @@ static std::string ms_record_of(const Options& o) {
              o.coarse_iterations_set ? o.coarse_iterations : o.iterations, o.textureless_merge ? 1 : 0);
     return b;
 }
-// the done marker of a view: both output maps complete for the size of its reference image, made with this run's multi-scale settings
-static bool outputs_complete(const Options& o, int ref) {
+static int geom_coarse_iterations_of(const Options& o) { return o.geom_coarse_iterations_set ? o.geom_coarse_iterations : o.geom_iterations; }
+static std::string geom_record_of(const Options& o) {
+    char b[400];
+    snprintf(b, sizeof b, "geom_iterations=%d geom_weight=%.9g geom_clip=%.9g blocksize=%d n_best=%d cost_comb=%d seed=%llu strict=%d fix_quirks=%d texture_filter_8bit=%d cam_scale=%.9g depth_min=%.9g depth_max=%.9g\n",
+             o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
+             o.fix_quirks ? 1 : 0, o.tex8 ? 1 : 0, (double)o.cam_scale, (double)o.depth_min, (double)o.depth_max);
+    std::string rec = b;
+    if (o.geom_multi_scale > 0) {     // (an L = 0 record is the single-scale one, byte for byte)
+        snprintf(b, sizeof b, "geom_multi_scale=%d geom_coarse_iterations=%d\n", o.geom_multi_scale, geom_coarse_iterations_of(o));
+        rec += b;
+    }
+    return rec;
+}
+// both maps complete for the size of the view's reference image, and a record that reads exactly `record` (no file reads as empty)
+static bool maps_current(const Options& o, int ref, const MapFiles& f, const std::string& record) {
     int w = 0, h = 0;
     if (!view_image_size(view_image_of(o, ref), w, h)) return false;
     const std::string d = view_dir_of(o, ref);
-    if (!dmb_complete(d + "TSAR_disp.dmb", h, w, 1) || !dmb_complete(d + "TSAR_normals.dmb", h, w, 3)) return false;
+    if (!dmb_complete(d + f.depth, h, w, 1) || !dmb_complete(d + f.normal, h, w, 3)) return false;
     std::string rec;
-    if (FILE* f = fopen((d + MS_RECORD).c_str(), "r")) {
-        char b[256];
+    if (FILE* fp = fopen((d + f.record).c_str(), "r")) {
+        char b[512];
         size_t k;
-        while ((k = fread(b, 1, sizeof b, f)) > 0) rec.append(b, k);
-        fclose(f);
+        while ((k = fread(b, 1, sizeof b, fp)) > 0) rec.append(b, k);
+        fclose(fp);
     }
-    return rec == ms_record_of(o);
+    return rec == record;
+}
+// the two maps side by side (a write is a copy into the page cache), under their record: the record goes first and comes back
+// last, so maps that are being replaced never carry the record of other settings.  An empty record: none is written.
+static bool write_maps(const HostResult& r, const MapFiles& f, const std::string& record) {
+    unlink((r.out_dir + f.record).c_str());
+    auto normals = std::async(std::launch::async, [&r, &f]() { return write_dmb(r.out_dir + f.normal, r.normal.data(), r.h, r.w, 3); });
+    const bool depth_ok = write_dmb(r.out_dir + f.depth, r.depth.data(), r.h, r.w, 1);
+    bool ok = normals.get() && depth_ok;
+    if (ok && !record.empty()) {
+        FILE* fp = fopen((r.out_dir + f.record).c_str(), "w");
+        ok = fp && fputs(record.c_str(), fp) >= 0;
+        if (fp && fclose(fp) != 0) ok = false;
+    }
+    return ok;
+}
+// the done marker of a phase-1 view: its maps, made with this run's multi-scale settings
+static bool outputs_complete(const Options& o, int ref) { return maps_current(o, ref, PHASE1_FILES, ms_record_of(o)); }
+static bool mtime_of(const std::string& path, struct timespec& t) {
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0) return false;
+    t = st.st_mtim;
+    return true;
+}
+static bool newer(const struct timespec& a, const struct timespec& b) { return a.tv_sec != b.tv_sec ? a.tv_sec > b.tv_sec : a.tv_nsec > b.tv_nsec; }
+// resume of phase 2: the geom maps with the record of this run's settings, and no input (the view's own phase-1 maps, its sources'
+// depth maps) newer than the older of the two outputs
+static bool geom_outputs_current(const Options& o, int ref, const std::vector<int>& srcs) {
+    if (!maps_current(o, ref, GEOM_FILES, geom_record_of(o))) return false;
+    const std::string d = view_dir_of(o, ref);
+    struct timespec t1, t2, ti;
+    if (!mtime_of(d + GEOM_FILES.depth, t1) || !mtime_of(d + GEOM_FILES.normal, t2)) return false;
+    const struct timespec out = newer(t1, t2) ? t2 : t1;
+    std::vector<std::string> inputs = {d + PHASE1_FILES.depth, d + PHASE1_FILES.normal};
+    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + PHASE1_FILES.depth);
+    for (const std::string& in : inputs)
+        if (!mtime_of(in, ti) || newer(ti, out)) return false;
+    return true;
 }
 
-static int run_view(const Options& o, int device, const std::vector<std::string>& names, const std::vector<int>& subset_slots, int ref_id, double* seconds,
-                    DeviceResult* keep = nullptr, HostResult* reuse = nullptr, bool defer_write = false, ExternalInputs* preloaded = nullptr) {
+// The GPU state of one pool thread of --all (or of a one-view process), kept across its views: its context and, coarse to fine, the
+// contexts of the coarser levels (device planes are allocated once); two page-locked result sets its views alternate between (the
+// .dmb files of view k are written by a helper thread while the kernels of view k+1 run: file output is ~0.1 s of a 0.5 s view at
+// ETH3D size); and phase 1's ring of external inputs read ahead.
+struct Worker {
+    const int device;
+    const bool geom;                   // phase 2: its messages say so
+    const bool resident;               // --all: images stay resident on the device across views (a one-view process would only hold every image twice)
+    tsar_ctx* ctx = nullptr;
+    std::vector<tsar_ctx*> coarse;     // the coarser levels, finest first (level(1) = coarse[0])
+    HostResult result[2];
+    std::future<void> writing[2];      // after `result`: a pending write is joined before its set is released
+    std::vector<ExternalInputs> ring;
+    Worker(int device, bool geom, bool resident) : device(device), geom(geom), resident(resident) {}
+    ~Worker() { drop(); }
+    tsar_ctx* level(int k) const { return k ? coarse[k - 1] : ctx; }     // 0: full resolution
+    int create_failed(int rc) const {
+        if (geom) fprintf(stderr, "tsar_create(device %d) failed\n", device);
+        else fprintf(stderr, "tsar_create(device %d) failed: %d\n", device, rc);
+        return rc;
+    }
+    int ensure(int L) {                // levels 1..L, created on first use
+        while ((int)coarse.size() < L) {
+            tsar_ctx* c = nullptr;
+            const int rc = tsar_create(device, &c);
+            if (rc != TSAR_OK) return create_failed(rc);
+            coarse.push_back(c);
+        }
+        return TSAR_OK;
+    }
+    void drop() {                      // after a failed view: the next one starts from fresh contexts
+        for (tsar_ctx* c : coarse) tsar_destroy(c);
+        coarse.clear();
+        tsar_destroy(ctx);
+        ctx = nullptr;
+    }
+    int fail(int ref, const char* what, tsar_ctx* c = nullptr) const {   // a library call of view `ref` failed on c (default: ctx)
+        const char* err = tsar_last_error(c ? c : ctx);
+        if (geom) fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, err);
+        else fprintf(stderr, "%s: %s\n", what, err);
+        return -1;
+    }
+};
+
+// A view's images and cameras as tsar_set_views_u8 takes them (the reference first), and the depth range it is matched in
+struct ViewSet {
+    std::vector<std::shared_ptr<ImageCache::Entry>> gray;
+    std::vector<const uint8_t*> px;    // the resident device copies where the worker keeps them, else the host bytes
+    int mem = TSAR_MEM_HOST;
+    std::vector<tsar_camera> cams;
+    int w = 0, h = 0;
+    float dmin = 0.f, dmax = 0.f;
+    double ms_create = 0.0, ms_decode = 0.0;   // --timing: the two concurrent legs of the start-up, each on its own clock
+};
+// Everything a view needs before its first kernel, side by side: the worker's context if it has none yet (~0.2 s in a fresh process)
+// and the decode of the named images (~45 ms each at ETH3D size, kept in g_images).  Then their sizes are checked, their cameras read
+// and the depth range taken from the reference camera (fileIoUtils.h:150-153) unless the command line gave it.  0, or non-zero after
+// a message.
+static int load_views(const Options& o, Worker& wk, const std::vector<std::string>& names, ViewSet& v) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::future<int> creating;
+    if (!wk.ctx) creating = std::async(std::launch::async, [&wk, &v]() {
+        const auto c0 = std::chrono::steady_clock::now();
+        const int rc = tsar_create(wk.device, &wk.ctx);
+        v.ms_create = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+        return rc;
+    });
+    std::vector<std::future<std::shared_ptr<ImageCache::Entry>>> decoding;
+    for (const std::string& name : names)
+        decoding.push_back(std::async(std::launch::async, [&o, &name]() { return g_images.get(image_path(o, name)); }));
+    for (auto& d : decoding) v.gray.push_back(d.get());
+    v.ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const int create_rc = creating.valid() ? creating.get() : TSAR_OK;
+    if (create_rc != TSAR_OK) return wk.create_failed(create_rc);
+    std::vector<const uint8_t*> host, dev;
+    v.dmin = o.depth_min;
+    v.dmax = o.depth_max;
+    for (size_t i = 0; i < names.size(); i++) {
+        const ImageCache::Entry& e = *v.gray[i];
+        const std::string ip = image_path(o, names[i]);
+        if (!e.ok) { fprintf(stderr, "cannot read image %s: %s\n", ip.c_str(), e.why.c_str()); return -1; }
+        if (i == 0) { v.w = e.w; v.h = e.h; }
+        if (e.w != v.w || e.h != v.h) { fprintf(stderr, "image %s has a different size\n", ip.c_str()); return -1; }
+        host.push_back(e.gray.data());
+        if (wk.resident)               // uploaded once per GPU (falls back to the host bytes)
+            if (const uint8_t* d = g_device_images.get(wk.device, ip, e)) dev.push_back(d);
+        CamFile cf;
+        const std::string cp = cam_path(o, names[i]);
+        if (!read_cam(cp, cf)) { fprintf(stderr, "cannot read camera %s\n", cp.c_str()); return -1; }
+        v.cams.push_back(cf.cam);
+        if (i == 0) {
+            if (v.dmin <= 0) v.dmin = cf.depth_min;
+            if (v.dmax <= 0) v.dmax = cf.depth_max;
+        }
+    }
+    const bool on_device = dev.size() == names.size();
+    v.px = on_device ? dev : host;
+    v.mem = on_device ? TSAR_MEM_DEVICE : TSAR_MEM_HOST;
+    return 0;
+}
+
+// --display_outputs: what the reference always writes beside the maps; here on request (a full-size view's PLY is 0.66 GB)
+static bool write_display_outputs(const HostResult& r, const std::vector<uint8_t>& ref_image, const tsar_camera& cam) {
+    const size_t np = (size_t)r.w * r.h;
+    std::vector<uint16_t> vis(3 * np);
+    for (size_t k = 0; k < 3 * np; k++) {
+        const float v = r.normal[k] * 32767.f + 32767.f;               // convertTo(CV_16U, 32767, 32767): saturate + round
+        vis[k] = (uint16_t)(v <= 0.f ? 0 : v >= 65535.f ? 65535 : (int)lrintf(v));
+    }
+    if (!write_png_rgb16(r.out_dir + "TSAR_normals.png", vis.data(), r.w, r.h)) return false;
+    const std::vector<float> ref_gray(ref_image.begin(), ref_image.end());
+    return write_view_ply(r.out_dir + "TSAR_model.ply", r.depth.data(), r.normal.data(), ref_gray.data(), r.w, r.h, cam);
+}
+
+static tsar_params params_of(const Options& o, int ref_id, float dmin, float dmax) {
+    tsar_params p;
+    tsar_default_params(&p);
+    p.box_hsize = p.box_vsize = o.blocksize;
+    p.n_best = o.n_best; p.cost_comb = o.cost_comb; p.cam_scale = o.cam_scale;
+    p.depth_min = dmin; p.depth_max = dmax;
+    p.seed = o.seed + (uint64_t)ref_id;
+    p.flags = (o.strict ? TSAR_FLAG_STRICT_DIV : 0) | (o.fix_quirks ? (TSAR_FLAG_FIX_DOWN_FAR_SEED | TSAR_FLAG_FIX_RIGHT_FAR_CMP) : 0) |
+              (o.tex8 ? TSAR_FLAG_TEX_FILTER_8BIT : 0);
+    return p;
+}
+
+// Phase 1 of one reference view on the worker's GPU: names[0] is the reference, the rest the candidate sources in argv order.  The
+// maps land in hr and, unless the caller defers that (--all writes them while the next view is matched), in their files.
+static int run_view(const Options& o, Worker& wk, const std::vector<std::string>& names, const std::vector<int>& subset_slots, int ref_id, double* seconds,
+                    HostResult& hr, DeviceResult* keep = nullptr, bool defer_write = false, ExternalInputs* preloaded = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     auto t_last = t0;
     std::string steps;                                            // --timing: "step ms | step ms | ..."
@@ -458,88 +626,34 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
     // The refinement modes never read a source image (load_planes, weak-texture detection, region RANSAC and fill work on the
     // reference view and the plane maps): only the reference image is decoded and handed to the library there.
     const bool tsar_mode = o.mode == "tsar", external = o.mode == "load" || tsar_mode;
-    const int n_all = (int)names.size(), n = external ? 1 : n_all;
+    const int n = external ? 1 : (int)names.size();
     const std::string out_dir = o.mslp_folder + "APD/" + stem8(names[0]) + "/";   // main.cpp:1462, 1813-1830
-    // Everything a process has to do before its first kernel runs side by side: the HIP context (~0.2 s in a fresh process), the
-    // decode of the 1 + N images (~45 ms each at ETH3D size), and — refinement modes — the external maps and weak.png (inflating
-    // a full-size PNG takes ~0.3 s).  In --all runs the context and the images are already there for every view but the first.
-    tsar_ctx** shared = reuse ? reuse->shared_ctx : nullptr;
-    tsar_ctx* ctx = shared ? *shared : nullptr;
-    std::future<int> creating;
-    double ms_create = 0.0, ms_decode = 0.0;                        // --timing: the two concurrent legs of the start-up, each on its own clock
-    if (!ctx) creating = std::async(std::launch::async, [&ctx, device, &ms_create]() {
-        const auto c0 = std::chrono::steady_clock::now();
-        const int rc = tsar_create(device, &ctx);
-        ms_create = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
-        return rc;
-    });
+    // the external maps and weak.png (inflating a full-size PNG takes ~0.3 s) load beside the context and the images
     ExternalInputs own_inputs;
     ExternalInputs& ext = (preloaded && preloaded->started && preloaded->dir == out_dir) ? *preloaded : own_inputs;   // --all: started a view ago
     if (external && !ext.started) ext.start(out_dir, tsar_mode, "");
     struct Consumed { ExternalInputs& e; ~Consumed() { if (e.maps.valid()) e.maps.get(); if (e.mask.valid()) e.mask.get(); e.started = false; } } consumed{ext};
-    std::vector<std::shared_ptr<ImageCache::Entry>> gray(n);
-    {
-        std::vector<std::future<std::shared_ptr<ImageCache::Entry>>> decoding;
-        for (int i = 0; i < n; i++)
-            decoding.push_back(std::async(std::launch::async, [&o, &names, i]() { return g_images.get(o.images_folder + pnm_name(names[i], o.color ? ".ppm" : ".pgm")); }));
-        for (int i = 0; i < n; i++) gray[i] = decoding[i].get();
-        ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    ViewSet v;
+    if (const int rc = load_views(o, wk, std::vector<std::string>(names.begin(), names.begin() + n), v)) return rc;
     // (the map / mask readers are joined where their data is needed — set_views and load_planes run while weak.png is still
     // inflating — or by `consumed` on an early return)
-    const int create_rc = creating.valid() ? creating.get() : TSAR_OK;
-    if (create_rc != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed: %d\n", device, create_rc); return create_rc; }
-    if (shared) *shared = ctx;
-    // a context is destroyed here only when this call owns it, or after a failure (the next view then starts from a fresh one)
-    auto drop_ctx = [&]() { tsar_destroy(ctx); if (shared) *shared = nullptr; };
-    auto fail = [&](const char* what) { fprintf(stderr, "%s: %s\n", what, tsar_last_error(ctx)); drop_ctx(); return -1; };
-    std::vector<const uint8_t*> ptrs(n), dev_ptrs;
-    std::vector<tsar_camera> cams(n);
-    int w = 0, h = 0;
-    float dmin = o.depth_min, dmax = o.depth_max;
-    for (int i = 0; i < n; i++) {
-        const std::string ip = o.images_folder + pnm_name(names[i], o.color ? ".ppm" : ".pgm");
-        if (!gray[i]->ok) { fprintf(stderr, "cannot read image %s: %s\n", ip.c_str(), gray[i]->why.c_str()); drop_ctx(); return -1; }
-        const int wi = gray[i]->w, hi = gray[i]->h;
-        if (i == 0) { w = wi; h = hi; }
-        if (wi != w || hi != h) { fprintf(stderr, "image %s has a different size\n", ip.c_str()); drop_ctx(); return -1; }
-        ptrs[i] = gray[i]->gray.data();
-        if (reuse && reuse->device_image_cache) {                 // --all: resident device copy (falls back to the host buffer)
-            const uint8_t* d = g_device_images.get(device, ip, *gray[i]);
-            if (d) dev_ptrs.push_back(d);
-        }
-        CamFile cf;
-        const std::string cp = o.mslp_folder + "cams/" + stem8(names[i]) + "_cam.txt";
-        if (!read_cam(cp, cf)) { fprintf(stderr, "cannot read camera %s\n", cp.c_str()); drop_ctx(); return -1; }
-        cams[i] = cf.cam;
-        if (i == 0) {   // depth range of the reference view (fileIoUtils.h:150-153) unless given on the command line
-            if (dmin <= 0) dmin = cf.depth_min;
-            if (dmax <= 0) dmax = cf.depth_max;
-        }
-    }
-    tsar_params p;
-    tsar_default_params(&p);
-    p.box_hsize = p.box_vsize = o.blocksize;
-    p.n_best = o.n_best; p.cost_comb = o.cost_comb; p.cam_scale = o.cam_scale;
-    p.depth_min = dmin; p.depth_max = dmax;
-    p.seed = o.seed + (uint64_t)ref_id;
-    p.flags = (o.strict ? TSAR_FLAG_STRICT_DIV : 0) | (o.fix_quirks ? (TSAR_FLAG_FIX_DOWN_FAR_SEED | TSAR_FLAG_FIX_RIGHT_FAR_CMP) : 0) |
-              (o.tex8 ? TSAR_FLAG_TEX_FILTER_8BIT : 0);
+    tsar_ctx* const ctx = wk.ctx;
+    const int w = v.w, h = v.h;
+    auto fail = [&](const char* what, tsar_ctx* c = nullptr) { return wk.fail(ref_id, what, c); };
+    const tsar_params p = params_of(o, ref_id, v.dmin, v.dmax);
     if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
     if (ref_id == g_inject_view && g_inject_left.fetch_sub(1) > 0) {
-        fprintf(stderr, "view %08d on gpu %d: injected failure (TSAR_GIPUMA_INJECT_FAILURE)\n", ref_id, device);
-        drop_ctx();
+        fprintf(stderr, "view %08d on gpu %d: injected failure (TSAR_GIPUMA_INJECT_FAILURE)\n", ref_id, wk.device);
         return -1;
     }
     if (o.timing) { tsar_enable_kernel_timing(ctx, 1); tsar_reset_kernel_timing(ctx); }
     stamp(external ? "context + reference image (external maps and weak.png still loading)" : "context + images + cameras (concurrent)");
     if (o.timing) {
         char buf[96];
-        snprintf(buf, sizeof buf, " [tsar_create %.1f beside decode of %d images %.1f]", ms_create, n, ms_decode);
+        snprintf(buf, sizeof buf, " [tsar_create %.1f beside decode of %d images %.1f]", v.ms_create, n, v.ms_decode);
         steps += buf;
     }
-    const bool resident = (int)dev_ptrs.size() == n;
-    if (tsar_set_views_u8(ctx, n, w, h, resident ? dev_ptrs.data() : ptrs.data(), resident ? TSAR_MEM_DEVICE : TSAR_MEM_HOST, cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
+    if (tsar_set_views_u8(ctx, n, w, h, v.px.data(), v.mem, v.cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
     if (!subset_slots.empty() && !external) {
         std::vector<int32_t> s(subset_slots.begin(), subset_slots.end());
         if (tsar_set_view_subset(ctx, (int)s.size(), s.data()) != TSAR_OK) return fail("tsar_set_view_subset");
@@ -552,41 +666,29 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
     mkdirs(out_dir);
     const size_t np = (size_t)w * h;
     // sizing (and, in --all, page-locking once per worker) of the result buffers happens beside the kernels
-    HostResult local;
-    HostResult& hr = reuse ? *reuse : local;
     std::future<void> sizing;
     if (hr.depth.size() != np) sizing = std::async(std::launch::async, [&hr, np]() { hr.depth.resize(np); hr.normal.resize(3 * np); });
     struct JoinSizing { std::future<void>& f; ~JoinSizing() { if (f.valid()) f.get(); } } join_sizing{sizing};   // on every return path
     if (external) {
         if (ext.maps.valid()) ext.maps.get();
-        if (!ext.depth_ok || ext.dh != h || ext.dw != w || ext.dnb != 1) { fprintf(stderr, "cannot read %sdepths_geom.dmb\n", out_dir.c_str()); drop_ctx(); return -1; }
-        if (!ext.normal_ok || ext.nh != h || ext.nw != w || ext.nnb != 3) { fprintf(stderr, "cannot read %snormals.dmb\n", out_dir.c_str()); drop_ctx(); return -1; }
+        if (!ext.depth_ok || ext.dh != h || ext.dw != w || ext.dnb != 1) { fprintf(stderr, "cannot read %sdepths_geom.dmb\n", out_dir.c_str()); return -1; }
+        if (!ext.normal_ok || ext.nh != h || ext.nw != w || ext.nnb != 3) { fprintf(stderr, "cannot read %snormals.dmb\n", out_dir.c_str()); return -1; }
         if (tsar_load_planes(ctx, ext.depth(), ext.normal(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
         stamp("load_planes");
     } else if (o.multi_scale > 0) {
-        // coarse to fine: the pyramid below ctx, init + coarse iterations at the coarsest level, upsample + iterations at each finer one
-        std::vector<tsar_ctx*> own_coarse;
-        std::vector<tsar_ctx*>& coarse = (reuse && reuse->shared_coarse) ? *reuse->shared_coarse : own_coarse;
-        auto drop_coarse = [&]() { for (tsar_ctx* c : coarse) tsar_destroy(c); coarse.clear(); };
-        auto ms_fail = [&](const char* what, tsar_ctx* c) { fprintf(stderr, "%s: %s\n", what, tsar_last_error(c)); drop_coarse(); drop_ctx(); return -1; };
-        while ((int)coarse.size() < o.multi_scale) {
-            tsar_ctx* c = nullptr;
-            const int rc = tsar_create(device, &c);
-            if (rc != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed: %d\n", device, rc); drop_coarse(); drop_ctx(); return rc; }
-            coarse.push_back(c);
-        }
+        // coarse to fine (api.run_multiscale): the pyramid below ctx, init + coarse iterations at the coarsest level, upsample +
+        // iterations at each finer one
         const int L = o.multi_scale;
-        for (int k = 0; k < L; k++)
-            if (tsar_pyramid_views(coarse[k], k ? coarse[k - 1] : ctx) != TSAR_OK) return ms_fail("tsar_pyramid_views", coarse[k]);
+        if (wk.ensure(L) != TSAR_OK) return -1;
+        for (int k = 1; k <= L; k++)
+            if (tsar_pyramid_views(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_pyramid_views", wk.level(k));
         stamp("pyramid_views");
-        if (tsar_pm_init(coarse[L - 1]) != TSAR_OK) return ms_fail("tsar_pm_init (coarsest level)", coarse[L - 1]);
-        if (tsar_pm_iterate(coarse[L - 1], o.coarse_iterations_set ? o.coarse_iterations : o.iterations) != TSAR_OK) return ms_fail("tsar_pm_iterate (coarsest level)", coarse[L - 1]);
+        if (tsar_pm_init(wk.level(L)) != TSAR_OK) return fail("tsar_pm_init (coarsest level)", wk.level(L));
+        if (tsar_pm_iterate(wk.level(L), o.coarse_iterations_set ? o.coarse_iterations : o.iterations) != TSAR_OK) return fail("tsar_pm_iterate (coarsest level)", wk.level(L));
         for (int k = L - 1; k >= 0; k--) {
-            tsar_ctx* finer = k ? coarse[k - 1] : ctx;
-            if (tsar_upsample_planes(finer, coarse[k]) != TSAR_OK) return ms_fail("tsar_upsample_planes", finer);
-            if (tsar_pm_iterate(finer, o.iterations) != TSAR_OK) return ms_fail("tsar_pm_iterate", finer);
+            if (tsar_upsample_planes(wk.level(k), wk.level(k + 1)) != TSAR_OK) return fail("tsar_upsample_planes", wk.level(k));
+            if (tsar_pm_iterate(wk.level(k), o.iterations) != TSAR_OK) return fail("tsar_pm_iterate", wk.level(k));
         }
-        if (&coarse == &own_coarse) drop_coarse();
         stamp("coarse-to-fine pm_init + pm_iterate");
     } else {
         if (tsar_pm_init(ctx) != TSAR_OK) return fail("tsar_pm_init");
@@ -600,7 +702,7 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
         // (gipuma_getview) -> per-region plane RANSAC (:1520-1730) -> fakecuda -> fillcuda
         if (ext.mask.valid()) ext.mask.get();
         stamp("weak.png (rest of its inflate)");
-        if (!ext.mask_ok || ext.mw != w || ext.mh != h) { fprintf(stderr, "cannot read %sweak.png (8-bit PNG of the image size)\n", out_dir.c_str()); drop_ctx(); return -1; }
+        if (!ext.mask_ok || ext.mw != w || ext.mh != h) { fprintf(stderr, "cannot read %sweak.png (8-bit PNG of the image size)\n", out_dir.c_str()); return -1; }
         if (tsar_set_reliable_mask(ctx, ext.scale.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_set_reliable_mask");
         stamp("set_reliable_mask");
         int n_regions = 0;
@@ -629,15 +731,14 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
     if (tsar_get_result(ctx, depth.data(), normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
     stamp("get_result");
     if (keep) {   // the same maps stay on this GPU for the gather to the fusing device
-        keep->device = device; keep->w = w; keep->h = h; keep->cam = cams[0];
-        keep->depth = (float*)tsar_device_alloc(device, np * 4);
-        keep->normal = (float*)tsar_device_alloc(device, np * 12);
+        keep->device = wk.device; keep->w = w; keep->h = h;
+        keep->depth = (float*)tsar_device_alloc(wk.device, np * 4);
+        keep->normal = (float*)tsar_device_alloc(wk.device, np * 12);
         if (!keep->depth || !keep->normal) return fail("tsar_device_alloc");
         if (tsar_get_result(ctx, keep->depth, keep->normal, nullptr, nullptr, TSAR_MEM_DEVICE) != TSAR_OK) return fail("tsar_get_result (device)");
     }
     hr.out_dir = out_dir; hr.w = w; hr.h = h;
-    hr.ms_record = ms_record_of(o);
-    if (!defer_write && !write_view_files(hr)) return -1;      // deferred: the caller writes while the next view is being matched
+    if (!defer_write && !write_maps(hr, PHASE1_FILES, ms_record_of(o))) return -1;
     if (!defer_write) stamp("write .dmb");
     if (o.timing) {
         printf("view %08d steps (ms): %s\n", ref_id, steps.c_str());
@@ -649,17 +750,7 @@ static int run_view(const Options& o, int device, const std::vector<std::string>
             printf("\n");
         }
     }
-    if (!shared) tsar_destroy(ctx);
-    if (o.display_outputs) {   // the reference always writes these two; here on request (a full-size view's PLY is 0.66 GB)
-        std::vector<uint16_t> vis(3 * np);
-        for (size_t k = 0; k < 3 * np; k++) {
-            const float v = normal[k] * 32767.f + 32767.f;               // convertTo(CV_16U, 32767, 32767): saturate + round
-            vis[k] = (uint16_t)(v <= 0.f ? 0 : v >= 65535.f ? 65535 : (int)lrintf(v));
-        }
-        if (!write_png_rgb16(out_dir + "TSAR_normals.png", vis.data(), w, h)) return -1;
-        const std::vector<float> ref_gray(gray[0]->gray.begin(), gray[0]->gray.end());
-        if (!write_view_ply(out_dir + "TSAR_model.ply", depth.data(), normal.data(), ref_gray.data(), w, h, cams[0])) return -1;
-    }
+    if (o.display_outputs && !write_display_outputs(hr, v.gray[0]->gray, v.cams[0])) return -1;
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (seconds) *seconds = sec;
     FILE* rf = fopen((out_dir + "TSAR_results.txt").c_str(), "a");   // main.cpp:1854-1860
@@ -688,129 +779,42 @@ static double ms_since_exec() {
     return (up - (double)start_ticks / (double)sysconf(_SC_CLK_TCK)) * 1e3;
 }
 
-// ---- --all --geom_consistency: phase 2 ----------------------------------------------------------------------------------------
-// Every view starts from its own phase-1 maps (TSAR_disp.dmb + TSAR_normals.dmb), installs its pair.txt sources' TSAR_disp.dmb as the
-// geometric-consistency term, rescores, runs --geom_iterations iterations (single scale, full resolution) and writes
-// TSAR_geom_disp.dmb + TSAR_geom_normals.dmb (the layout of the phase-1 maps) and TSAR_geom.txt, the settings they were made with.
-// --geom_multi_scale=L >= 1 runs the pass coarse to fine instead (api.run_geom_pass_multiscale's chain) and records a second line.
-static const char* const GEOM_RECORD = "TSAR_geom.txt";
-static int geom_coarse_iterations_of(const Options& o) { return o.geom_coarse_iterations_set ? o.geom_coarse_iterations : o.geom_iterations; }
-static std::string geom_record_of(const Options& o) {
-    char b[400];
-    snprintf(b, sizeof b, "geom_iterations=%d geom_weight=%.9g geom_clip=%.9g blocksize=%d n_best=%d cost_comb=%d seed=%llu strict=%d fix_quirks=%d texture_filter_8bit=%d cam_scale=%.9g depth_min=%.9g depth_max=%.9g\n",
-             o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
-             o.fix_quirks ? 1 : 0, o.tex8 ? 1 : 0, (double)o.cam_scale, (double)o.depth_min, (double)o.depth_max);
-    std::string rec = b;
-    if (o.geom_multi_scale > 0) {     // (an L = 0 record is the single-scale one, byte for byte)
-        snprintf(b, sizeof b, "geom_multi_scale=%d geom_coarse_iterations=%d\n", o.geom_multi_scale, geom_coarse_iterations_of(o));
-        rec += b;
-    }
-    return rec;
-}
-static bool mtime_of(const std::string& path, struct timespec& t) {
-    struct stat st;
-    if (stat(path.c_str(), &st) != 0) return false;
-    t = st.st_mtim;
-    return true;
-}
-static bool newer(const struct timespec& a, const struct timespec& b) { return a.tv_sec != b.tv_sec ? a.tv_sec > b.tv_sec : a.tv_nsec > b.tv_nsec; }
-// resume of phase 2: both geom maps complete, the record of this run's settings, and no input (the view's own phase-1 maps, its
-// sources' depth maps) newer than the older of the two outputs
-static bool geom_outputs_current(const Options& o, int ref, const std::vector<int>& srcs) {
-    int w = 0, h = 0;
-    if (!view_image_size(view_image_of(o, ref), w, h)) return false;
-    const std::string d = view_dir_of(o, ref);
-    if (!dmb_complete(d + "TSAR_geom_disp.dmb", h, w, 1) || !dmb_complete(d + "TSAR_geom_normals.dmb", h, w, 3)) return false;
-    std::string rec;
-    if (FILE* f = fopen((d + GEOM_RECORD).c_str(), "r")) {
-        char b[512];
-        size_t k;
-        while ((k = fread(b, 1, sizeof b, f)) > 0) rec.append(b, k);
-        fclose(f);
-    }
-    if (rec != geom_record_of(o)) return false;
-    struct timespec t1, t2, ti;
-    if (!mtime_of(d + "TSAR_geom_disp.dmb", t1) || !mtime_of(d + "TSAR_geom_normals.dmb", t2)) return false;
-    const struct timespec out = newer(t1, t2) ? t2 : t1;
-    std::vector<std::string> inputs = {d + "TSAR_disp.dmb", d + "TSAR_normals.dmb"};
-    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + "TSAR_disp.dmb");
-    for (const std::string& in : inputs)
-        if (!mtime_of(in, ti) || newer(ti, out)) return false;
-    return true;
-}
-
-// One view's phase 2 on `device`; ctx is the worker's context and coarse its coarse contexts, finest first (--geom_multi_scale): created
-// on first use, kept across its views, dropped after a failure.
-static int run_geom_view(const Options& o, int device, tsar_ctx*& ctx, std::vector<tsar_ctx*>& coarse, int ref, const std::vector<int>& srcs,
-                         double* seconds) {
+// Phase 2 of one view (--geom_consistency): it starts from its own phase-1 maps (TSAR_disp.dmb + TSAR_normals.dmb), installs its
+// pair.txt sources' TSAR_disp.dmb as the geometric-consistency term, rescores, runs --geom_iterations iterations at full resolution
+// and writes TSAR_geom_disp.dmb + TSAR_geom_normals.dmb (the layout of the phase-1 maps) under TSAR_geom.txt, the settings they were
+// made with.  --geom_multi_scale=L >= 1 runs the pass coarse to fine instead (api.run_geom_pass_multiscale's chain).
+static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vector<int>& srcs, double* seconds) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx && tsar_create(device, &ctx) != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed\n", device); ctx = nullptr; return -1; }
-    auto drop_coarse = [&]() { for (tsar_ctx* c : coarse) tsar_destroy(c); coarse.clear(); };
-    auto fail = [&](const char* what) { fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, ctx ? tsar_last_error(ctx) : ""); tsar_destroy(ctx); ctx = nullptr; drop_coarse(); return -1; };
-    auto fail_at = [&](const char* what, tsar_ctx* c) {
-        fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, tsar_last_error(c));
-        tsar_destroy(ctx); ctx = nullptr; drop_coarse();
-        return -1;
-    };
-    std::vector<int> ids = {ref};
-    ids.insert(ids.end(), srcs.begin(), srcs.end());
-    const int n = (int)ids.size();
-    std::vector<std::shared_ptr<ImageCache::Entry>> gray(n);
-    std::vector<const uint8_t*> ptrs(n);
-    std::vector<tsar_camera> cams(n);
-    int w = 0, h = 0;
-    float dmin = o.depth_min, dmax = o.depth_max;
-    for (int i = 0; i < n; i++) {
-        const std::string ip = view_image_of(o, ids[i]);
-        gray[i] = g_images.get(ip);
-        if (!gray[i]->ok) { fprintf(stderr, "cannot read image %s: %s\n", ip.c_str(), gray[i]->why.c_str()); return -1; }
-        if (i == 0) { w = gray[i]->w; h = gray[i]->h; }
-        if (gray[i]->w != w || gray[i]->h != h) { fprintf(stderr, "image %s has a different size\n", ip.c_str()); return -1; }
-        ptrs[i] = gray[i]->gray.data();
-        char cn[32];
-        snprintf(cn, sizeof cn, "%08d", ids[i]);
-        CamFile cf;
-        const std::string cp = o.mslp_folder + "cams/" + cn + "_cam.txt";
-        if (!read_cam(cp, cf)) { fprintf(stderr, "cannot read camera %s\n", cp.c_str()); return -1; }
-        cams[i] = cf.cam;
-        if (i == 0) {   // depth range of the reference view unless given on the command line (as in phase 1)
-            if (dmin <= 0) dmin = cf.depth_min;
-            if (dmax <= 0) dmax = cf.depth_max;
-        }
-    }
+    ViewSet v;
+    if (const int rc = load_views(o, wk, names_of(ref, srcs), v)) return rc;
+    const int n = (int)v.cams.size(), w = v.w, h = v.h;
     // the maps: the view's own phase-1 result and its sources' depths, each of the image size
     const std::string d = view_dir_of(o, ref);
+    auto read_map = [&](const std::string& path, int nb, std::vector<float>& out) {
+        int hh = 0, ww = 0, nn = 0;
+        if (read_dmb(path, out, hh, ww, nn) && hh == h && ww == w && nn == nb) return true;
+        fprintf(stderr, "cannot read %s\n", path.c_str());
+        return false;
+    };
     std::vector<float> own_d, own_n;
     std::vector<std::vector<float>> src_d(n);
-    int hh = 0, ww = 0, nb = 0;
-    if (!read_dmb(d + "TSAR_disp.dmb", own_d, hh, ww, nb) || hh != h || ww != w || nb != 1) { fprintf(stderr, "cannot read %sTSAR_disp.dmb\n", d.c_str()); return -1; }
-    if (!read_dmb(d + "TSAR_normals.dmb", own_n, hh, ww, nb) || hh != h || ww != w || nb != 3) { fprintf(stderr, "cannot read %sTSAR_normals.dmb\n", d.c_str()); return -1; }
+    if (!read_map(d + PHASE1_FILES.depth, 1, own_d) || !read_map(d + PHASE1_FILES.normal, 3, own_n)) return -1;
     std::vector<const float*> maps(n, nullptr);
     for (int i = 1; i < n; i++) {
-        const std::string sp = view_dir_of(o, ids[i]) + "TSAR_disp.dmb";
-        if (!read_dmb(sp, src_d[i], hh, ww, nb) || hh != h || ww != w || nb != 1) { fprintf(stderr, "cannot read %s\n", sp.c_str()); return -1; }
+        if (!read_map(view_dir_of(o, srcs[i - 1]) + PHASE1_FILES.depth, 1, src_d[i])) return -1;
         maps[i] = src_d[i].data();
     }
-    tsar_params p;
-    tsar_default_params(&p);
-    p.box_hsize = p.box_vsize = o.blocksize;
-    p.n_best = o.n_best; p.cost_comb = o.cost_comb; p.cam_scale = o.cam_scale;
-    p.depth_min = dmin; p.depth_max = dmax;
-    p.seed = o.seed + (uint64_t)ref;
-    p.flags = (o.strict ? TSAR_FLAG_STRICT_DIV : 0) | (o.fix_quirks ? (TSAR_FLAG_FIX_DOWN_FAR_SEED | TSAR_FLAG_FIX_RIGHT_FAR_CMP) : 0) |
-              (o.tex8 ? TSAR_FLAG_TEX_FILTER_8BIT : 0);
+    tsar_ctx* const ctx = wk.ctx;
+    auto fail = [&](const char* what, tsar_ctx* c = nullptr) { return wk.fail(ref, what, c); };
+    const tsar_params p = params_of(o, ref, v.dmin, v.dmax);
     if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
-    if (tsar_set_views_u8(ctx, n, w, h, ptrs.data(), TSAR_MEM_HOST, cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
-    const int L = o.geom_multi_scale;
+    if (tsar_set_views_u8(ctx, n, w, h, v.px.data(), v.mem, v.cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
     // coarse to fine: every level's views first, while no term is installed (the coarse contexts still hold the previous view's)
-    while ((int)coarse.size() < L) {
-        tsar_ctx* c = nullptr;
-        if (tsar_create(device, &c) != TSAR_OK) { fprintf(stderr, "tsar_create(device %d) failed\n", device); tsar_destroy(ctx); ctx = nullptr; drop_coarse(); return -1; }
-        coarse.push_back(c);
-    }
-    for (int k = 0; k < L; k++) {
-        if (tsar_clear_geom(coarse[k]) != TSAR_OK) return fail_at("tsar_clear_geom", coarse[k]);
-        if (tsar_pyramid_views(coarse[k], k ? coarse[k - 1] : ctx) != TSAR_OK) return fail_at("tsar_pyramid_views", coarse[k]);
+    const int L = o.geom_multi_scale;
+    if (wk.ensure(L) != TSAR_OK) return -1;
+    for (int k = 1; k <= L; k++) {
+        if (tsar_clear_geom(wk.level(k)) != TSAR_OK) return fail("tsar_clear_geom", wk.level(k));
+        if (tsar_pyramid_views(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_pyramid_views", wk.level(k));
     }
     if (tsar_load_planes(ctx, own_d.data(), own_n.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
     if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
@@ -818,77 +822,261 @@ static int run_geom_view(const Options& o, int device, tsar_ctx*& ctx, std::vect
         if (tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
         if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
     } else {
-        for (int k = 0; k < L; k++) {
-            const tsar_ctx* finer = k ? coarse[k - 1] : ctx;
-            if (tsar_geom_pyramid(coarse[k], finer) != TSAR_OK) return fail_at("tsar_geom_pyramid", coarse[k]);
-            if (tsar_pyramid_planes(coarse[k], finer) != TSAR_OK) return fail_at("tsar_pyramid_planes", coarse[k]);
+        for (int k = 1; k <= L; k++) {
+            if (tsar_geom_pyramid(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_geom_pyramid", wk.level(k));
+            if (tsar_pyramid_planes(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_pyramid_planes", wk.level(k));
         }
-        if (tsar_pm_iterate(coarse[L - 1], geom_coarse_iterations_of(o)) != TSAR_OK) return fail_at("tsar_pm_iterate (coarsest level)", coarse[L - 1]);
+        if (tsar_pm_iterate(wk.level(L), geom_coarse_iterations_of(o)) != TSAR_OK) return fail("tsar_pm_iterate (coarsest level)", wk.level(L));
         for (int k = L - 1; k >= 0; k--) {
-            tsar_ctx* finer = k ? coarse[k - 1] : ctx;
-            if (tsar_upsample_merge(finer, coarse[k]) != TSAR_OK) return fail_at("tsar_upsample_merge", finer);
-            if (tsar_pm_iterate(finer, o.geom_iterations) != TSAR_OK) return fail_at("tsar_pm_iterate", finer);
+            if (tsar_upsample_merge(wk.level(k), wk.level(k + 1)) != TSAR_OK) return fail("tsar_upsample_merge", wk.level(k));
+            if (tsar_pm_iterate(wk.level(k), o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate", wk.level(k));
         }
     }
     if (tsar_compute_disp(ctx) != TSAR_OK) return fail("tsar_compute_disp");
-    const size_t np = (size_t)w * h;
-    std::vector<float> depth(np), normal(3 * np);
-    if (tsar_get_result(ctx, depth.data(), normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
+    HostResult& hr = wk.result[0];
+    hr.out_dir = d; hr.w = w; hr.h = h;
+    hr.depth.resize((size_t)w * h);
+    hr.normal.resize((size_t)3 * w * h);
+    if (tsar_get_result(ctx, hr.depth.data(), hr.normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
     if (tsar_clear_geom(ctx) != TSAR_OK) return fail("tsar_clear_geom");
-    // the record goes last: maps being replaced never carry the record of other settings
-    unlink((d + GEOM_RECORD).c_str());
-    bool ok = write_dmb(d + "TSAR_geom_disp.dmb", depth.data(), h, w, 1) && write_dmb(d + "TSAR_geom_normals.dmb", normal.data(), h, w, 3);
-    if (ok) {
-        FILE* f = fopen((d + GEOM_RECORD).c_str(), "w");
-        ok = f && fputs(geom_record_of(o).c_str(), f) >= 0;
-        if (f && fclose(f) != 0) ok = false;
-    }
+    const bool ok = write_maps(hr, GEOM_FILES, geom_record_of(o));
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return ok ? 0 : -1;
 }
 
-// Phase 2 over every view, dealt round-robin to the GPUs (one worker per GPU); a failed view is retried once on the next GPU with a
-// fresh context.  Returns the number of views without current geom outputs.
-static int run_geom_phase(const Options& o, const std::vector<int>& refs, std::map<int, std::vector<int>>& pairs) {
-    const int ngpu = o.gpus < 1 ? 1 : o.gpus;
+// One phase of --all over every view of pair.txt, dealt round-robin to nthr threads (every view of a scene costs the same); thread t
+// drives GPU t % ngpu with a worker of its own and calls view(worker, k, turn, &seconds) for each view k it is dealt that is not
+// skipped (turn: the thread's count of views dealt so far).  A worker drops its contexts after a failed view.  A view that failed
+// is then tried once more on the NEXT gpu's turn (the same one when there is only one) with a worker of its own, created fresh and
+// destroyed with the view (turn -1) — never the contexts the failure left behind.  Returns each view's status; a skipped view's is
+// what skipped(worker, k) returns (0 without it).
+typedef std::function<int(Worker&, size_t k, int turn, double* seconds)> ViewFn;
+static std::vector<int> run_pool(const Options& o, bool geom, const std::vector<int>& refs, const std::vector<char>& skip, int nthr,
+                                 const ViewFn& view, const std::function<int(Worker&, size_t k)>& skipped = nullptr) {
+    const int ngpu = std::max(1, o.gpus);
     std::vector<int> rc(refs.size(), 0), gpu_of(refs.size(), 0);
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthr; t++)
+        th.emplace_back([&, t]() {
+            Worker wk(t % ngpu, geom, true);
+            int turn = 0;
+            for (size_t k = t; k < refs.size(); k += nthr, turn++) {
+                gpu_of[k] = wk.device;
+                if (skip[k]) {
+                    printf("view %08d: %soutputs present, skipped\n", refs[k], geom ? "geom " : "");
+                    if (skipped) rc[k] = skipped(wk, k);
+                    continue;
+                }
+                double sec = 0;
+                rc[k] = view(wk, k, turn, &sec);
+                if (rc[k] != 0) wk.drop();
+                printf("view %08d on gpu %d%s: %s (%.2f s)\n", refs[k], wk.device, geom ? " (geom)" : "", rc[k] == 0 ? "ok" : "FAILED", sec);
+            }
+        });
+    for (auto& t : th) t.join();
+    for (size_t k = 0; k < refs.size(); k++) {
+        if (skip[k] || rc[k] == 0) continue;
+        const int g2 = (gpu_of[k] + 1) % ngpu;
+        if (!geom) printf("view %08d FAILED on gpu %d: retrying once on gpu %d with a fresh context\n", refs[k], gpu_of[k], g2);
+        double sec = 0;
+        {
+            Worker fresh(g2, geom, true);
+            rc[k] = view(fresh, k, -1, &sec);
+        }
+        printf("view %08d on gpu %d (%sretry): %s (%.2f s)\n", refs[k], g2, geom ? "geom, " : "", rc[k] == 0 ? "ok" : "FAILED", sec);
+    }
+    return rc;
+}
+
+// --fuse: a view's maps read back from its files onto device g (a resumed view's phase-1 maps, or every view's geom maps)
+static bool load_kept(const Options& o, int ref, int g, const MapFiles& f, DeviceResult& r) {
+    std::vector<float> d, nr;
+    int h = 0, w = 0, nb = 0, h2 = 0, w2 = 0, nb2 = 0;
+    const std::string dir = view_dir_of(o, ref);
+    if (!read_dmb(dir + f.depth, d, h, w, nb) || !read_dmb(dir + f.normal, nr, h2, w2, nb2) || h != h2 || w != w2 || nb != 1 || nb2 != 3) return false;
+    r.device = g; r.w = w; r.h = h;
+    r.depth = (float*)tsar_device_alloc(g, d.size() * 4);
+    r.normal = (float*)tsar_device_alloc(g, nr.size() * 4);
+    return r.depth && r.normal && tsar_device_write(g, r.depth, d.data(), d.size() * 4) == TSAR_OK && tsar_device_write(g, r.normal, nr.data(), nr.size() * 4) == TSAR_OK;
+}
+
+// --all phase 1 over every view, dealt to ngpu x --workers threads; a worker's views alternate between its two result sets, whose
+// files a helper thread writes while the next view is matched.  With --fuse each view's maps stay on its GPU in kept[k].  False when
+// a view's outputs are missing.
+static bool run_phase1(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs, std::vector<DeviceResult>& kept) {
+    const int nthr = std::max(1, o.gpus) * std::max(1, o.workers);
+    // resume: the views whose output files are complete are not matched again (decided up front, so that nothing is read ahead for them)
     std::vector<char> skip(refs.size(), 0);
     size_t n_skip = 0;
     if (!o.force)
-        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = geom_outputs_current(o, refs[k], pairs[refs[k]]) ? 1 : 0);
-    if (n_skip) printf("geom: resuming: %zu of %zu views have current TSAR_geom_disp.dmb / TSAR_geom_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
-    std::vector<std::thread> th;
-    for (int g = 0; g < ngpu; g++)
-        th.emplace_back([&, g]() {
-            tsar_ctx* ctx = nullptr;
-            std::vector<tsar_ctx*> coarse;     // --geom_multi_scale: the worker's coarse contexts, kept across its views
-            for (size_t k = g; k < refs.size(); k += ngpu) {
-                gpu_of[k] = g;
-                if (skip[k]) { printf("view %08d: geom outputs present, skipped\n", refs[k]); continue; }
-                double sec = 0;
-                rc[k] = run_geom_view(o, g, ctx, coarse, refs[k], pairs[refs[k]], &sec);
-                printf("view %08d on gpu %d (geom): %s (%.2f s)\n", refs[k], g, rc[k] == 0 ? "ok" : "FAILED", sec);
+        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = outputs_complete(o, refs[k]) ? 1 : 0);
+    if (n_skip) printf("resuming: %zu of %zu views already have complete TSAR_disp.dmb / TSAR_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
+    const std::string record = ms_record_of(o);
+    const bool tsar_mode = o.mode == "tsar", external = o.mode == "load" || tsar_mode;
+    // refinement modes: a ring of (page-locked) input buffers per worker; the maps, weak.png and reference image of its next seven
+    // views are read while view k is on the GPU (one weak.png inflates in ~0.3 s, a view's kernels take ~0.1 s).  (About sixteen
+    // sets in flight per process: eight with one worker, two per worker on an 8-GPU node — each set page-locks 0.39 GB at ETH3D
+    // size, and the inflates run on as many host threads.)
+    const size_t RING = std::max<size_t>(2, std::min<size_t>(8, 16 / (size_t)nthr));
+    std::atomic<int> write_failures{0};
+    auto view = [&](Worker& wk, size_t k, int turn, double* sec) {
+        const int ref = refs[k];
+        DeviceResult* keep = o.fuse ? &kept[k] : nullptr;
+        if (keep) release(*keep);                 // what a failed attempt left there
+        if (turn < 0) return run_view(o, wk, names_of(ref, pairs.at(ref)), {}, ref, sec, wk.result[0], keep);   // a retry: written at once
+        HostResult& hr = wk.result[turn & 1];
+        std::future<void>& writing = wk.writing[turn & 1];
+        if (writing.valid()) writing.get();       // the set's previous files are on disk
+        ExternalInputs* in = nullptr;
+        if (external) {
+            if (wk.ring.empty()) {
+                wk.ring.resize(RING);
+                for (ExternalInputs& e : wk.ring) e.pinned = true;
             }
-            for (tsar_ctx* c : coarse) tsar_destroy(c);
-            tsar_destroy(ctx);
-        });
-    for (auto& t : th) t.join();
-    int missing = 0;
-    for (size_t k = 0; k < refs.size(); k++) {
-        if (skip[k]) continue;
-        if (rc[k] != 0) {
-            const int g2 = (gpu_of[k] + 1) % ngpu;
-            tsar_ctx* ctx = nullptr;
-            std::vector<tsar_ctx*> coarse;
-            double sec = 0;
-            rc[k] = run_geom_view(o, g2, ctx, coarse, refs[k], pairs[refs[k]], &sec);
-            for (tsar_ctx* c : coarse) tsar_destroy(c);
-            tsar_destroy(ctx);
-            printf("view %08d on gpu %d (geom, retry): %s (%.2f s)\n", refs[k], g2, rc[k] == 0 ? "ok" : "FAILED", sec);
+            in = &wk.ring[turn % RING];
+            if (!in->started) in->start(view_dir_of(o, ref), tsar_mode, "");
+            for (size_t j = 1; j < RING; j++) {
+                ExternalInputs& ahead = wk.ring[(turn + j) % RING];
+                const size_t kk = k + j * nthr;
+                if (kk < refs.size() && !skip[kk] && !ahead.started) ahead.start(view_dir_of(o, refs[kk]), tsar_mode, view_image_of(o, refs[kk]));
+            }
         }
+        const int rc = run_view(o, wk, names_of(ref, pairs.at(ref)), {}, ref, sec, hr, keep, /*defer_write*/ true, in);
+        if (rc == 0) writing = std::async(std::launch::async, [&hr, &record, &write_failures]() { if (!write_maps(hr, PHASE1_FILES, record)) write_failures++; });
+        return rc;
+    };
+    // --fuse needs a skipped view's maps on a device all the same: read back from its files
+    auto skipped = [&](Worker& wk, size_t k) {
+        if (!o.fuse || load_kept(o, refs[k], wk.device, PHASE1_FILES, kept[k])) return 0;
+        fprintf(stderr, "view %08d: cannot read its output files back for --fuse\n", refs[k]);
+        return -1;
+    };
+    const std::vector<int> rc = run_pool(o, false, refs, skip, nthr, view, skipped);
+    int missing = 0;
+    for (size_t k = 0; k < refs.size(); k++)
+        if (rc[k] != 0 || !outputs_complete(o, refs[k])) { fprintf(stderr, "view %08d: outputs missing or incomplete\n", refs[k]); missing++; }
+    return missing == 0 && write_failures == 0;       // (a file of an otherwise matched view that could not be written)
+}
+
+// --all --geom_consistency: phase 2 over every view, one worker per GPU.  False when a view has no current geom outputs.
+static bool run_geom_phase(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs) {
+    std::vector<char> skip(refs.size(), 0);
+    size_t n_skip = 0;
+    if (!o.force)
+        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = geom_outputs_current(o, refs[k], pairs.at(refs[k])) ? 1 : 0);
+    if (n_skip) printf("geom: resuming: %zu of %zu views have current TSAR_geom_disp.dmb / TSAR_geom_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
+    const std::vector<int> rc = run_pool(o, true, refs, skip, std::max(1, o.gpus),
+                                         [&](Worker& wk, size_t k, int, double* sec) { return run_geom_view(o, wk, refs[k], pairs.at(refs[k]), sec); });
+    int missing = 0;
+    for (size_t k = 0; k < refs.size(); k++)
         if (rc[k] != 0) { fprintf(stderr, "view %08d: geom outputs missing\n", refs[k]); missing++; }
+    return missing == 0;
+}
+
+// --fuse: every view's maps gathered to GPU 0 (peer copies over xGMI; views matched on GPU 0 are already there), fused there, and the
+// cloud written to APD/APD_TSAR.ply
+static int fuse_views(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs, std::vector<DeviceResult>& kept) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (refs.empty() || kept.empty()) { fprintf(stderr, "--fuse: no view was matched\n"); return 1; }
+    const int n = (int)refs.size(), fw = kept[0].w, fh = kept[0].h;
+    const size_t np = (size_t)fw * fh;
+    std::map<int, int> slot;
+    for (int k = 0; k < n; k++) slot[refs[k]] = k;
+    std::vector<const float*> pd(n), pn(n), pg(n);
+    std::vector<tsar_camera> cams(n);
+    std::vector<void*> owned;                       // device-0 buffers to release
+    auto release_owned = [&]() { for (void* q : owned) tsar_device_free(0, q); };
+    size_t moved = 0;
+    for (int k = 0; k < n; k++) {
+        if (kept[k].w != fw || kept[k].h != fh) { fprintf(stderr, "--fuse: views differ in size\n"); release_owned(); return 1; }
+        float *d = kept[k].depth, *nr = kept[k].normal;
+        if (kept[k].device != 0) {
+            float* d0 = (float*)tsar_device_alloc(0, np * 4);
+            float* n0 = (float*)tsar_device_alloc(0, np * 12);
+            if (d0) owned.push_back(d0);            // released on every error path below
+            if (n0) owned.push_back(n0);
+            if (!d0 || !n0 || tsar_peer_copy(0, d0, kept[k].device, d, np * 4) != TSAR_OK || tsar_peer_copy(0, n0, kept[k].device, nr, np * 12) != TSAR_OK) {
+                fprintf(stderr, "--fuse: gather of view %08d from gpu %d failed\n", refs[k], kept[k].device);
+                release_owned();
+                return 1;
+            }
+            tsar_device_free(kept[k].device, d);
+            tsar_device_free(kept[k].device, nr);
+            d = d0; nr = n0;
+            moved += np * 16;
+        } else {
+            owned.push_back(d); owned.push_back(nr);
+        }
+        auto img = g_images.get(view_image_of(o, refs[k]));
+        float* g0 = (float*)tsar_device_alloc(0, np * 4);
+        if (g0) owned.push_back(g0);
+        const std::vector<float> img_f(img->gray.begin(), img->gray.end());      // the fuser colours its points from float images
+        if (!img->ok || img_f.size() != np || !g0 || tsar_device_write(0, g0, img_f.data(), np * 4) != TSAR_OK) { fprintf(stderr, "--fuse: image of view %08d\n", refs[k]); release_owned(); return 1; }
+        pd[k] = d; pn[k] = nr; pg[k] = g0;
+        CamFile cf;
+        if (!read_cam(cam_path(o, id8(refs[k])), cf)) { fprintf(stderr, "--fuse: camera of view %08d\n", refs[k]); release_owned(); return 1; }
+        cams[k] = cf.cam;
     }
-    return missing;
+    const double t_gather = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<int32_t> off(n + 1, 0), idx;
+    for (int k = 0; k < n; k++) {
+        for (int sv : pairs.at(refs[k]))
+            if (slot.count(sv)) idx.push_back(slot[sv]);
+        off[k + 1] = (int32_t)idx.size();
+    }
+    if (idx.empty()) idx.push_back(0);
+    const int64_t cap = (int64_t)n * fw * fh;
+    std::unique_ptr<float[]> pts(new float[(size_t)cap * 9]);   // not zero-filled: only the fused points' pages are ever touched
+    int64_t cnt = 0;
+    const int rc = tsar_fuse(0, n, fw, fh, cams.data(), pd.data(), pn.data(), pg.data(), TSAR_MEM_DEVICE, off.data(), idx.data(), &o.fusion, pts.get(), cap, &cnt);
+    release_owned();
+    if (rc != TSAR_OK) { fprintf(stderr, "tsar_fuse failed: %d\n", rc); return 1; }
+    if (cnt > cap) cnt = cap;
+    const std::string out = o.mslp_folder + "APD/APD_TSAR.ply";
+    if (!write_cloud_ply(out, pts.get(), cnt)) { fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
+    const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("fused %d views on gpu 0: %lld points -> %s (gather of %.1f MB from other gpus + uploads %.3f s, total %.3f s)\n", n, (long long)cnt, out.c_str(),
+           moved / 1e6, t_gather, t_all);
+    return 0;
+}
+
+// --all: phase 1, then phase 2 once every view has its phase-1 maps (it reads them from the files), then --fuse
+static int run_all(const Options& o, const std::map<int, std::vector<int>>& pairs) {
+    g_pin_results = true;
+    std::vector<int> refs;
+    for (auto& kv : pairs) refs.push_back(kv.first);
+    std::vector<DeviceResult> kept(o.fuse ? refs.size() : 0);
+    bool ok = run_phase1(o, refs, pairs, kept);
+    if (ok && o.geom) ok = run_geom_phase(o, refs, pairs);
+    g_device_images.release();
+    if (!ok) return 1;
+    if (o.geom && o.fuse)        // --fuse fuses the geom maps: they replace the phase-1 maps kept on each view's device
+        for (size_t k = 0; k < refs.size(); k++) {
+            const int g = kept[k].device >= 0 ? kept[k].device : (int)(k % (size_t)std::max(1, o.gpus));
+            release(kept[k]);
+            if (!load_kept(o, refs[k], g, GEOM_FILES, kept[k])) { fprintf(stderr, "view %08d: cannot read its geom maps for --fuse\n", refs[k]); return 1; }
+        }
+    return o.fuse ? fuse_views(o, refs, pairs, kept) : 0;
+}
+
+// the refusals decided from the command line alone: false after the message
+static bool options_valid(const Options& o) {
+    if (o.mslp_folder.empty() || o.images_folder.empty()) { usage(); return false; }
+    if (o.multi_scale > 0 || o.coarse_iterations_set || o.textureless_merge) {
+        if (o.mode != "patchmatch") { fprintf(stderr, "--multi_scale / --coarse_iterations / --textureless_merge work with --mode=patchmatch only\n"); return false; }
+        if (o.multi_scale == 0) { fprintf(stderr, "--coarse_iterations / --textureless_merge need --multi_scale=L with L >= 1\n"); return false; }
+    }
+    if ((o.geom_multi_scale > 0 || o.geom_coarse_iterations_set) && !o.geom) {
+        fprintf(stderr, "--geom_multi_scale / --geom_coarse_iterations work with --geom_consistency only\n");
+        return false;
+    }
+    if (o.geom_coarse_iterations_set && o.geom_multi_scale == 0) { fprintf(stderr, "--geom_coarse_iterations needs --geom_multi_scale=L with L >= 1\n"); return false; }
+    if (o.geom) {
+        if (!o.all) { fprintf(stderr, "--geom_consistency needs --all (phase 2 reads every view's phase-1 maps)\n"); return false; }
+        if (o.mode == "tsar") { fprintf(stderr, "--geom_consistency does not work with --mode=tsar\n"); return false; }
+        if (o.geom_iterations < 0 || !(o.geom_weight >= 0.f) || !(o.geom_clip > 0.f)) { fprintf(stderr, "--geom_iterations must be >= 0, --geom_weight >= 0, --geom_clip > 0\n"); return false; }
+    }
+    return true;
 }
 
 int main(int argc, char** argv) {
@@ -897,225 +1085,15 @@ int main(int argc, char** argv) {
     tsar_default_fusion_params(&o.fusion);
     const int pr = parse_args(argc, argv, o);
     if (pr != 0) return pr < 0 ? 1 : 0;
-    if (o.mslp_folder.empty() || o.images_folder.empty()) { usage(); return 1; }
-    if (o.multi_scale > 0 || o.coarse_iterations_set || o.textureless_merge) {
-        if (o.mode != "patchmatch") { fprintf(stderr, "--multi_scale / --coarse_iterations / --textureless_merge work with --mode=patchmatch only\n"); return 1; }
-        if (o.multi_scale == 0) { fprintf(stderr, "--coarse_iterations / --textureless_merge need --multi_scale=L with L >= 1\n"); return 1; }
-    }
-    if ((o.geom_multi_scale > 0 || o.geom_coarse_iterations_set) && !o.geom) {
-        fprintf(stderr, "--geom_multi_scale / --geom_coarse_iterations work with --geom_consistency only\n");
-        return 1;
-    }
-    if (o.geom_coarse_iterations_set && o.geom_multi_scale == 0) { fprintf(stderr, "--geom_coarse_iterations needs --geom_multi_scale=L with L >= 1\n"); return 1; }
-    if (o.geom) {
-        if (!o.all) { fprintf(stderr, "--geom_consistency needs --all (phase 2 reads every view's phase-1 maps)\n"); return 1; }
-        if (o.mode == "tsar") { fprintf(stderr, "--geom_consistency does not work with --mode=tsar\n"); return 1; }
-        if (o.geom_iterations < 0 || !(o.geom_weight >= 0.f) || !(o.geom_clip > 0.f)) { fprintf(stderr, "--geom_iterations must be >= 0, --geom_weight >= 0, --geom_clip > 0\n"); return 1; }
-    }
+    if (!options_valid(o)) return 1;
     if (o.mslp_folder.back() != '/') o.mslp_folder += '/';
     if (o.images_folder.back() != '/') o.images_folder += '/';
     std::map<int, std::vector<int>> pairs;
     const bool have_pairs = read_pairs(o.mslp_folder + "pair.txt", pairs);
     read_injection();
     if (o.all) {
-        g_pin_results = true;
         if (!have_pairs) { fprintf(stderr, "--all needs %spair.txt\n", o.mslp_folder.c_str()); return 1; }
-        std::vector<int> refs;
-        for (auto& kv : pairs) refs.push_back(kv.first);
-        const int ngpu = o.gpus < 1 ? 1 : o.gpus;
-        const int nthr = ngpu * (o.workers < 1 ? 1 : o.workers);   // worker t drives GPU t % ngpu with its own context
-        std::vector<int> status(nthr, 0);
-        std::vector<DeviceResult> kept(o.fuse ? refs.size() : 0);
-        // resume: the views whose output files are complete are not matched again (decided up front, so that nothing is read ahead for them)
-        std::vector<char> skip(refs.size(), 0);
-        std::vector<int> view_rc(refs.size(), 0), view_gpu(refs.size(), -1);
-        size_t n_skip = 0;
-        if (!o.force)
-            for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = outputs_complete(o, refs[k]) ? 1 : 0);
-        if (n_skip) printf("resuming: %zu of %zu views already have complete TSAR_disp.dmb / TSAR_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
-        // --fuse needs a skipped view's maps on a device all the same: read back from its files
-        auto load_kept = [&](size_t k, int g, bool geom_maps = false) {
-            std::vector<float> d, nr;
-            int h = 0, w = 0, nb = 0, h2 = 0, w2 = 0, nb2 = 0;
-            const std::string dir = view_dir_of(o, refs[k]);
-            const char* dn = geom_maps ? "TSAR_geom_disp.dmb" : "TSAR_disp.dmb";
-            const char* nn = geom_maps ? "TSAR_geom_normals.dmb" : "TSAR_normals.dmb";
-            if (!read_dmb(dir + dn, d, h, w, nb) || !read_dmb(dir + nn, nr, h2, w2, nb2) || h != h2 || w != w2 || nb != 1 || nb2 != 3) return false;
-            DeviceResult& r = kept[k];
-            r.device = g; r.w = w; r.h = h;
-            r.depth = (float*)tsar_device_alloc(g, d.size() * 4);
-            r.normal = (float*)tsar_device_alloc(g, nr.size() * 4);
-            return r.depth && r.normal && tsar_device_write(g, r.depth, d.data(), d.size() * 4) == TSAR_OK && tsar_device_write(g, r.normal, nr.data(), nr.size() * 4) == TSAR_OK;
-        };
-        std::vector<std::thread> th;
-        for (int t = 0; t < nthr; t++)
-            th.emplace_back([&, t]() {
-                const int g = t % ngpu;
-                // two page-locked result sets per worker: the .dmb files of view k are written by a helper thread while the
-                // kernels of view k+1 run (file output is ~0.1 s of a 0.5 s view at ETH3D size)
-                HostResult host_result[2];
-                tsar_ctx* worker_ctx = nullptr;
-                std::vector<tsar_ctx*> worker_coarse;
-                host_result[0].shared_ctx = host_result[1].shared_ctx = &worker_ctx;
-                host_result[0].shared_coarse = host_result[1].shared_coarse = &worker_coarse;
-                host_result[0].device_image_cache = host_result[1].device_image_cache = true;
-                std::future<bool> writing[2];
-                // refinement modes: a ring of (page-locked) input buffers; the maps, weak.png and reference image of the next seven
-                // views are read while view k is on the GPU (one weak.png inflates in ~0.3 s, a view's kernels take ~0.1 s)
-                const bool external = o.mode == "load" || o.mode == "tsar";
-                // (about sixteen sets in flight per process: eight with one worker, two per worker on an 8-GPU node — each set
-                // page-locks 0.39 GB at ETH3D size, and the inflates run on as many host threads)
-                const size_t RING = std::max<size_t>(2, std::min<size_t>(8, 16 / (size_t)nthr));
-                std::vector<ExternalInputs> inputs(RING);
-                for (auto& in : inputs) in.pinned = true;
-                auto view_dir = [&](int ref) { return view_dir_of(o, ref); };
-                auto ref_image = [&](int ref) { return view_image_of(o, ref); };
-                size_t turn = 0;
-                for (size_t k = t; k < refs.size(); k += nthr, turn++) {   // round-robin: every view of a scene costs the same
-                    const int ref = refs[k];
-                    view_gpu[k] = g;
-                    if (skip[k]) {
-                        printf("view %08d: outputs present, skipped\n", ref);
-                        if (o.fuse && !load_kept(k, g)) { fprintf(stderr, "view %08d: cannot read its output files back for --fuse\n", ref); view_rc[k] = -1; }
-                        continue;
-                    }
-                    char buf[32];
-                    std::vector<std::string> names;
-                    snprintf(buf, sizeof buf, "%08d.pgm", ref);
-                    names.push_back(buf);
-                    for (int s : pairs[ref]) { snprintf(buf, sizeof buf, "%08d.pgm", s); names.push_back(buf); }
-                    double sec = 0;
-                    HostResult& hr = host_result[turn & 1];
-                    if (writing[turn & 1].valid() && !writing[turn & 1].get()) status[t] = -1;      // the set's previous files are on disk
-                    if (external) {
-                        if (!inputs[turn % RING].started) inputs[turn % RING].start(view_dir(ref), o.mode == "tsar", "");
-                        for (size_t j = 1; j < RING; j++) {
-                            ExternalInputs& ahead = inputs[(turn + j) % RING];
-                            const size_t kk = k + j * nthr;
-                            if (kk < refs.size() && !skip[kk] && !ahead.started) ahead.start(view_dir(refs[kk]), o.mode == "tsar", ref_image(refs[kk]));
-                        }
-                    }
-                    const int rc = run_view(o, g, names, {}, ref, &sec, o.fuse ? &kept[k] : nullptr, &hr, /*defer_write*/ true, external ? &inputs[turn % RING] : nullptr);
-                    printf("view %08d on gpu %d: %s (%.2f s)\n", ref, g, rc == 0 ? "ok" : "FAILED", sec);
-                    view_rc[k] = rc;               // a failed view does not stop the others; it is retried below
-                    if (rc == 0) writing[turn & 1] = std::async(std::launch::async, [&hr]() { return write_view_files(hr); });
-                }
-                for (auto& f : writing)
-                    if (f.valid() && !f.get()) status[t] = -1;
-                for (tsar_ctx* c : worker_coarse) tsar_destroy(c);
-                tsar_destroy(worker_ctx);
-            });
-        for (auto& t : th) t.join();
-        // re-queue: a view that failed is tried once more on the NEXT gpu's turn (the same one when there is only one) with a
-        // context of its own, created fresh and destroyed with the view — never the worker context the failure left behind
-        for (size_t k = 0; k < refs.size(); k++) {
-            if (view_rc[k] == 0 || skip[k]) continue;
-            const int g2 = (view_gpu[k] + 1) % ngpu;
-            printf("view %08d FAILED on gpu %d: retrying once on gpu %d with a fresh context\n", refs[k], view_gpu[k], g2);
-            if (o.fuse) {
-                if (kept[k].depth) tsar_device_free(kept[k].device, kept[k].depth);
-                if (kept[k].normal) tsar_device_free(kept[k].device, kept[k].normal);
-                kept[k] = DeviceResult{};
-            }
-            char buf[32];
-            std::vector<std::string> names;
-            snprintf(buf, sizeof buf, "%08d.pgm", refs[k]);
-            names.push_back(buf);
-            for (int sv : pairs[refs[k]]) { snprintf(buf, sizeof buf, "%08d.pgm", sv); names.push_back(buf); }
-            double sec = 0;
-            view_rc[k] = run_view(o, g2, names, {}, refs[k], &sec, o.fuse ? &kept[k] : nullptr);
-            printf("view %08d on gpu %d (retry): %s (%.2f s)\n", refs[k], g2, view_rc[k] == 0 ? "ok" : "FAILED", sec);
-        }
-        g_device_images.release();
-        int missing = 0;
-        for (size_t k = 0; k < refs.size(); k++)
-            if (view_rc[k] != 0 || !outputs_complete(o, refs[k])) { fprintf(stderr, "view %08d: outputs missing or incomplete\n", refs[k]); missing++; }
-        for (int s : status)
-            if (s != 0) missing++;      // a file of an otherwise matched view could not be written
-        if (missing) return 1;
-        if (o.geom) {
-            // phase 2 starts once every view has its phase-1 maps; it reads them from the files
-            if (run_geom_phase(o, refs, pairs) != 0) return 1;
-            if (o.fuse)        // --fuse fuses the geom maps: they replace the phase-1 maps kept on each view's device
-                for (size_t k = 0; k < refs.size(); k++) {
-                    const int g = kept[k].device >= 0 ? kept[k].device : (int)(k % (size_t)ngpu);
-                    if (kept[k].depth) tsar_device_free(kept[k].device, kept[k].depth);
-                    if (kept[k].normal) tsar_device_free(kept[k].device, kept[k].normal);
-                    const tsar_camera cam = kept[k].cam;
-                    kept[k] = DeviceResult{};
-                    kept[k].cam = cam;
-                    if (!load_kept(k, g, true)) { fprintf(stderr, "view %08d: cannot read its geom maps for --fuse\n", refs[k]); return 1; }
-                }
-        }
-        if (o.fuse) {
-            // gather: every view's maps to GPU 0 (peer copies over xGMI; views matched on GPU 0 are already there), then fuse
-            const auto t0 = std::chrono::steady_clock::now();
-            if (refs.empty() || kept.empty()) { fprintf(stderr, "--fuse: no view was matched\n"); return 1; }
-            const int n = (int)refs.size(), fw = kept[0].w, fh = kept[0].h;
-            const size_t np = (size_t)fw * fh;
-            std::map<int, int> slot;
-            for (int k = 0; k < n; k++) slot[refs[k]] = k;
-            std::vector<const float*> pd(n), pn(n), pg(n);
-            std::vector<tsar_camera> cams(n);
-            std::vector<void*> owned;                       // device-0 buffers to release
-            auto release = [&]() { for (void* q : owned) tsar_device_free(0, q); };
-            size_t moved = 0;
-            for (int k = 0; k < n; k++) {
-                if (kept[k].w != fw || kept[k].h != fh) { fprintf(stderr, "--fuse: views differ in size\n"); release(); return 1; }
-                float *d = kept[k].depth, *nr = kept[k].normal;
-                if (kept[k].device != 0) {
-                    float* d0 = (float*)tsar_device_alloc(0, np * 4);
-                    float* n0 = (float*)tsar_device_alloc(0, np * 12);
-                    if (d0) owned.push_back(d0);            // released on every error path below
-                    if (n0) owned.push_back(n0);
-                    if (!d0 || !n0 || tsar_peer_copy(0, d0, kept[k].device, d, np * 4) != TSAR_OK || tsar_peer_copy(0, n0, kept[k].device, nr, np * 12) != TSAR_OK) {
-                        fprintf(stderr, "--fuse: gather of view %08d from gpu %d failed\n", refs[k], kept[k].device);
-                        release();
-                        return 1;
-                    }
-                    tsar_device_free(kept[k].device, d);
-                    tsar_device_free(kept[k].device, nr);
-                    d = d0; nr = n0;
-                    moved += np * 16;
-                } else {
-                    owned.push_back(d); owned.push_back(nr);
-                }
-                char buf[32];
-                snprintf(buf, sizeof buf, "%08d.pgm", refs[k]);
-                auto img = g_images.get(o.images_folder + pnm_name(buf, o.color ? ".ppm" : ".pgm"));
-                float* g0 = (float*)tsar_device_alloc(0, np * 4);
-                if (g0) owned.push_back(g0);
-                const std::vector<float> img_f(img->gray.begin(), img->gray.end());      // the fuser colours its points from float images
-                if (!img->ok || img_f.size() != np || !g0 || tsar_device_write(0, g0, img_f.data(), np * 4) != TSAR_OK) { fprintf(stderr, "--fuse: image of view %08d\n", refs[k]); release(); return 1; }
-                pd[k] = d; pn[k] = nr; pg[k] = g0;
-                char cname[32];
-                snprintf(cname, sizeof cname, "%08d", refs[k]);
-                CamFile cf;
-                if (!read_cam(o.mslp_folder + "cams/" + cname + "_cam.txt", cf)) { fprintf(stderr, "--fuse: camera of view %08d\n", refs[k]); release(); return 1; }
-                cams[k] = cf.cam;
-            }
-            const double t_gather = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            std::vector<int32_t> off(n + 1, 0), idx;
-            for (int k = 0; k < n; k++) {
-                for (int sv : pairs[refs[k]])
-                    if (slot.count(sv)) idx.push_back(slot[sv]);
-                off[k + 1] = (int32_t)idx.size();
-            }
-            if (idx.empty()) idx.push_back(0);
-            const int64_t cap = (int64_t)n * fw * fh;
-            std::unique_ptr<float[]> pts(new float[(size_t)cap * 9]);   // not zero-filled: only the fused points' pages are ever touched
-            int64_t cnt = 0;
-            const int rc = tsar_fuse(0, n, fw, fh, cams.data(), pd.data(), pn.data(), pg.data(), TSAR_MEM_DEVICE, off.data(), idx.data(), &o.fusion, pts.get(), cap, &cnt);
-            release();
-            if (rc != TSAR_OK) { fprintf(stderr, "tsar_fuse failed: %d\n", rc); return 1; }
-            if (cnt > cap) cnt = cap;
-            const std::string out = o.mslp_folder + "APD/APD_TSAR.ply";
-            if (!write_cloud_ply(out, pts.get(), cnt)) { fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
-            const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            printf("fused %d views on gpu 0: %lld points -> %s (gather of %.1f MB from other gpus + uploads %.3f s, total %.3f s)\n", n, (long long)cnt, out.c_str(),
-                   moved / 1e6, t_gather, t_all);
-        }
-        return 0;
+        return run_all(o, pairs);
     }
     if (o.images.size() < 2) { usage(); return 1; }
     // camera id from the reference image name, source slots from pair.txt (main.cpp:1347-1376)
@@ -1129,10 +1107,8 @@ int main(int argc, char** argv) {
     // one view per process (the reference's shell loop): the context and the buffers stay alive until the process ends, and the
     // process ends without tearing them down one by one — the files are on disk, the driver reclaims the rest (0.25 s of a 1.4 s
     // invocation at ETH3D size went into freeing 1.5 GB of host buffers, the context and the runtime's own shutdown)
-    static HostResult single;
-    static tsar_ctx* single_ctx = nullptr;
-    single.shared_ctx = &single_ctx;
-    const int rc = run_view(o, 0, o.images, slots, camera_id, &sec, nullptr, &single);
+    static Worker single(0, false, false);
+    const int rc = run_view(o, single, o.images, slots, camera_id, &sec, single.result[0]);
     printf("Total runtime including disk i/o: %gsec\n", sec);
     if (o.timing) printf("process (ms since exec, 10 ms resolution): main entered at %.0f, leaving at %.0f (what the caller waits for beyond that is the teardown of the process's GPU state by the driver)\n",
                          ms_exec_to_main, ms_since_exec());
