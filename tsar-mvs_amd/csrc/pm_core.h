@@ -189,7 +189,7 @@ DEVFN float view_cost_generic(const DevScene* __restrict__ sc, const DevView& vw
     return fmaxf(0.0f, fminf(TSAR_MAXCOST, 1.0f - covar / vrs));
 }
 
-#include "pm_tap_r5.h"     // view_cost_r5: the production loop for box 11 on 8-bit imagery (variants 114 / 122 / 250, + 131072 = buffer loads)
+#include "pm_tap_r5.h"     // view_cost_r5: the production loop for box 11 on 8-bit imagery (variants 114 / 122 / 250, + TSAR_V_BUF = buffer loads)
 #include "pm_core_lut.h"   // view_cost_lut: any window, weights from a shared table (variant bit 10; chunk length in bits 11-13)
 
 // The geometric-consistency term lambda e of view vi for the hypothesis whose depth at (x, y) is D (include/tsar.h states the
@@ -257,9 +257,9 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
         float c;
         // V names the tap loop: bit 10 = the general-window loop (chunk length in bits 11-13), a production variant of the box-11
         // loop (pm_tap_r5.h), 0 = the generic one-tap loop; anything else exists in the experiments build only
-        if constexpr ((VT & 1024) != 0) c = view_cost_lut<STRICT, (VT >> 11) & 7, (VT & 131072) != 0 && !STRICT, (VT & 2097152) != 0 && !STRICT>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
+        if constexpr ((VT & TSAR_V_LUT) != 0) c = view_cost_lut<STRICT, (VT >> 11) & 7, (VT & TSAR_V_BUF) != 0 && !STRICT, (VT & TSAR_V_MIX) != 0 && !STRICT>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
         else if constexpr (QUAD && HR == 5 && r5_production_variant(VT))
-            c = view_cost_r5<STRICT, (VT & 128) != 0 && !STRICT, (VT & 8) != 0, (VT & 131072) != 0, (VT & 2097152) != 0, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
+            c = view_cost_r5<STRICT, (VT & 128) != 0 && !STRICT, (VT & 8) != 0, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
 #ifdef TSAR_EXPERIMENTS
         else if constexpr (QUAD && HR == 5 && r5_diag_variant(VT))
             c = view_cost_r5<false, true, true, true, true, BLK, (VT & 4194304) ? 1 : 2>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);

@@ -1,7 +1,7 @@
 // pm_init_impl.h — the every-pixel kernel (random initialisation / scoring of given planes) and its launcher, as templates:
 // pm_init.hip instantiates the production (box 11) and float-image configurations, pm_init_lut.hip the general-window ones.
 #pragma once
-#include "pm_core.h"
+#include "pm_dispatch.h"
 
 #define FULL_RH 8
 
@@ -14,7 +14,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_full_kernel(const DevScene* __res
     typedef typename TileOf<QUAD>::type TileT;
     const int hr = HR > 0 ? HR : sc->hrad, vr = HR > 0 ? HR : sc->vrad;
     const int tw = PM_RW + 2 * hr, th = FULL_RH + 2 * vr;
-    constexpr bool LUTW = (V & 1024) != 0;      // shared weight table first, then the window (pm_core_lut.h)
+    constexpr bool LUTW = (V & TSAR_V_LUT) != 0;      // shared weight table first, then the window (pm_core_lut.h)
     const size_t lut_bytes = LUTW ? (size_t)(sc->lut_classes + 1) * 1024 : 0;
     TileT* tile = (TileT*)(lds_raw + lut_bytes);
     float* wts = LUTW ? (float*)lds_raw : (float*)(lds_raw + tile_bytes<QUAD>(tw, th)) + threadIdx.x;
@@ -90,8 +90,7 @@ static int launch_full_t(tsar_ctx* ctx, const float4* planes, float* c, float4* 
     const DevScene& hs = ctx->hscene;
     const int tiles_x = (hs.w + PM_RW - 1) / PM_RW, tiles_y = (hs.h + FULL_RH - 1) / FULL_RH;
     const int n_tiles = tiles_x * tiles_y;
-    const size_t lds = tile_bytes<QUAD>(PM_RW + 2 * hs.hrad, FULL_RH + 2 * hs.vrad + ((V & 1024) ? LUT_TILE_PAD_ROWS : 0)) +
-                       ((V & 1024) ? (size_t)(hs.lut_classes + 1) * 1024 : sizeof(float) * (size_t)(hs.hrad + 1) * (hs.vrad + 1) * PM_BLOCK);
+    const size_t lds = tap_loop_lds_bytes(hs, FULL_RH, PM_BLOCK, QUAD, V);
     auto kern = pm_full_kernel<NB, HR, STRICT, QUAD, INIT, V>;
     if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     {
@@ -102,13 +101,15 @@ static int launch_full_t(tsar_ctx* ctx, const float4* planes, float* c, float4* 
     return TSAR_OK;
 }
 
-// The production launchers' entry: with a geometric-consistency term installed the same kernel with variant bit 24; tsar_pm_rescore
-// (ctx->rescoring) runs the initialising form with bit 25 as well (which always carries the term's code: without maps every view's
-// term is 0 and the scores are the photometric ones bit for bit).
-template <int NB, int HR, bool STRICT, bool QUAD, bool INIT, int V = 0>
-static int launch_full_g(tsar_ctx* ctx, const float4* planes, float* c, float4* n, int32_t* bv, float* rt) {
-    if constexpr (INIT)
-        if (ctx->rescoring) return launch_full_t<NB, HR, STRICT, QUAD, true, V | TSAR_V_GEOM | TSAR_V_REDRAW>(ctx, planes, c, n, bv, rt);
-    if (ctx->hscene.geom_on) return launch_full_t<NB, HR, STRICT, QUAD, INIT, V | TSAR_V_GEOM>(ctx, planes, c, n, bv, rt);
-    return launch_full_t<NB, HR, STRICT, QUAD, INIT, V>(ctx, planes, c, n, bv, rt);
+// The production launchers' entry, for a configuration of pm_dispatch.h: with a geometric-consistency term installed the same kernel
+// with variant bit 24; REDRAW (tsar_pm_rescore) runs the initialising form with bit 25 as well (which always carries the term's code:
+// without maps every view's term is 0 and the scores are the photometric ones bit for bit).
+template <class Cfg, bool INIT, bool REDRAW = false>
+static int launch_full_g(Cfg, tsar_ctx* ctx, const float4* planes, float* c, float4* n, int32_t* bv, float* rt) {
+    constexpr int NB = Cfg::NB, HR = Cfg::HR, V = Cfg::V;
+    constexpr bool STRICT = Cfg::STRICT, QUAD = Cfg::QUAD;
+    static_assert(INIT || !REDRAW, "only the initialising form redraws");
+    if constexpr (REDRAW) return launch_full_t<NB, HR, STRICT, QUAD, true, V | TSAR_V_GEOM | TSAR_V_REDRAW>(ctx, planes, c, n, bv, rt);
+    else if (ctx->hscene.geom_on) return launch_full_t<NB, HR, STRICT, QUAD, INIT, V | TSAR_V_GEOM>(ctx, planes, c, n, bv, rt);
+    else return launch_full_t<NB, HR, STRICT, QUAD, INIT, V>(ctx, planes, c, n, bv, rt);
 }

@@ -45,14 +45,14 @@ static int launch_sweep_nh(tsar_ctx* ctx, int colour, const PlaneBuf& a, const P
     const bool buf = ctx->buffer_gather && ctx->sweeps_done >= (strict ? (ctx->buffer_from > 2 ? ctx->buffer_from : 2) : ctx->buffer_from);
     // The production configuration (8-bit quad textures, box 11, <= 4 best views) runs the hand-scheduled tap loop of pm_tap_r5.h in
     // both arithmetic modes: variant 250 in fast mode (row-wise walk), 122 in strict mode (the oracle's column order; also the
-    // column-order fast loop, TSAR_VARIANT=122), 114 where the D16 probe fails; + 131072 with buffer loads.
+    // column-order fast loop, TSAR_VARIANT=122), 114 where the D16 probe fails; + TSAR_V_BUF with buffer loads.
     const int v = ctx->variant;
     if constexpr ((NB == 2 || NB == 4) && HR == 5)
     if (quad && !(ctx->hscene.flags & TSAR_FLAG_TEX_FILTER_8BIT) && (v == 250 || v == 122 || (v == 114 && NB == 2))) {   // (the 8-bit filter mode runs the general-window loop)
-#define SWEEP_R5(S, V, B) (buf ? launch_sweep_g<NB, 5, S, true, (V) | 131072, B>(ctx, colour, a, b, c, sid, dp, dr) : launch_sweep_g<NB, 5, S, true, V, B>(ctx, colour, a, b, c, sid, dp, dr))
+#define SWEEP_R5(S, V, B) (buf ? launch_sweep_g<NB, 5, S, true, (V) | TSAR_V_BUF, B>(ctx, colour, a, b, c, sid, dp, dr) : launch_sweep_g<NB, 5, S, true, V, B>(ctx, colour, a, b, c, sid, dp, dr))
         // fast mode, buffer-load launches: the half-float difference texture (pm_tap_r5.h MIX) when tsar_set_views built it
         const bool mix = buf && !strict && v == 250 && ctx->hscene.n_sel > 0 && ctx->hscene.view[ctx->hscene.sel[0]].dquad != nullptr;
-#define SWEEP_R5_FAST250(B) (mix ? launch_sweep_g<NB, 5, false, true, 250 | 131072 | 2097152, B>(ctx, colour, a, b, c, sid, dp, dr) : SWEEP_R5(false, 250, B))
+#define SWEEP_R5_FAST250(B) (mix ? launch_sweep_g<NB, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_MIX, B>(ctx, colour, a, b, c, sid, dp, dr) : SWEEP_R5(false, 250, B))
         if constexpr (NB == 2) {
             // small images: 128-thread workgroups (see SWEEP_SMALL_IMAGE_TILES); TSAR_BLOCK=128|256 forces a shape (A/B runs)
             const int tiles256 = ((ctx->hscene.w + PM_RW - 1) / PM_RW) * ((ctx->hscene.h + 15) / 16);
@@ -86,13 +86,13 @@ int launch_pm_sweep(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const Pl
         if (rc != TSAR_OK || launched) return rc;
     }
 #endif
-    const int need = hs.cost_comb == TSAR_COMB_BEST_N ? (hs.n_best < hs.n_sel ? hs.n_best : hs.n_sel) : hs.n_sel;
+    const int need = views_in_cost(hs);
     const bool r5 = hs.hrad == 5 && hs.vrad == 5;
     // 8-bit imagery, any window but the box-11 / two-best-views configuration (which has its own tap loop): shared weight
     // table, chunked lines (pm_sweep_lut.hip)
     // (the box-11 loop filters with exact fp32 weights only: the 8-bit filter mode takes the general-window loop at box 11 too)
     const bool own_loop = r5 && need <= 4 && (need <= 2 || ctx->variant == 250 || ctx->variant == 122) && !(hs.flags & TSAR_FLAG_TEX_FILTER_8BIT);   // (TSAR_VARIANT=0 or an experiment: the generic loop below)
-    if (lut_path_applies(ctx) && (!own_loop || lut_path_forced(ctx))) return launch_pm_sweep_lut(ctx, need, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
+    if (lut_path_applies(ctx) && (!own_loop || lut_path_forced(ctx))) return launch_pm_sweep_lut(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
     if (need <= 4 && need > 2 && r5) return launch_sweep_nh<4, 5>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
     if (need <= 2) return r5 ? launch_sweep_nh<2, 5>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine)
                              : launch_sweep_nh<2, 0>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);

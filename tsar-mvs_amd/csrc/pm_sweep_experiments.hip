@@ -7,7 +7,7 @@
 int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& a, const PlaneBuf& b, const PlaneBuf& c, uint32_t sid, int dp, int dr, int* launched) {
     *launched = 0;
     const DevScene& hs = ctx->hscene;
-    const int need = hs.cost_comb == TSAR_COMB_BEST_N ? (hs.n_best < hs.n_sel ? hs.n_best : hs.n_sel) : hs.n_sel;
+    const int need = views_in_cost(hs);
     const bool strict = hs.flags & TSAR_FLAG_STRICT_DIV;
     if (!(hs.use_quad && hs.hrad == 5 && hs.vrad == 5 && need <= 2) || (hs.flags & TSAR_FLAG_TEX_FILTER_8BIT)) return TSAR_OK;
 #define EXP(S, V) case V: *launched = 1; return launch_sweep_t<2, 5, S, true, V>(ctx, colour, a, b, c, sid, dp, dr)
@@ -15,7 +15,7 @@ int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& a, con
     // the wrong-result variants never converge on their own and would be measured in the random-plane regime
     int variant = getenv("TSAR_VARIANT_NOW") ? atoi(getenv("TSAR_VARIANT_NOW")) : ctx->variant;
     // the difference-texture loops read the views' dquad textures: without them (strict-built views, TSAR_MIX_GATHER=0) refuse
-    if ((variant & 2097152) && !(hs.n_sel > 0 && hs.view[hs.sel[0]].dquad != nullptr)) {
+    if ((variant & TSAR_V_MIX) && !(hs.n_sel > 0 && hs.view[hs.sel[0]].dquad != nullptr)) {
         ctx->err = "TSAR_VARIANT: the difference-texture tap loop needs the views' dquad textures (fast mode, TSAR_MIX_GATHER on)";
         return TSAR_ERR_STATE;
     }

@@ -1,7 +1,7 @@
 // pm_sweep_impl.h — the fused propagation + refinement kernel of one red/black half-iteration and its launcher, as templates:
 // pm_sweep.hip instantiates the production (box 11) configurations, pm_sweep_lut*.hip the general-window ones.
 #pragma once
-#include "pm_core.h"
+#include "pm_dispatch.h"
 
 // Workgroup = BLK threads = a region of 32 x BLK/16 pixels, one thread per pixel of the active colour.  BLK = 256 (32 x 16) is
 // the production shape; BLK = 128 (32 x 8) is used for small images, where 256-thread tiles number fewer than the ~1000
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
     const int hr = HR > 0 ? HR : sc->hrad, vr = HR > 0 ? HR : sc->vrad;
     const int tw = RW + 2 * hr, th = SWEEP_RH + 2 * vr;
     // LDS: [reference window][S weights per thread], or (variant bit 10) [shared weight table][reference window]
-    constexpr bool LUTW = (V & 1024) != 0;
+    constexpr bool LUTW = (V & TSAR_V_LUT) != 0;
     const size_t lut_bytes = LUTW ? (size_t)(sc->lut_classes + 1) * 1024 : 0;
     TileT* tile = (TileT*)(lds_raw + lut_bytes);
     float* const wts_base = LUTW ? (float*)lds_raw : (float*)(lds_raw + tile_bytes<QUAD>(tw, th));
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
 
 // the tap loops of 8-bit imagery — box 11's own and the general-window one — have a packed form (CMP) beside the rolled one
 template <int HR, bool QUAD, int V>
-constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~TSAR_V_GEOM)) || (V & 1024) != 0); }
+constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~TSAR_V_GEOM)) || (V & TSAR_V_LUT) != 0); }
 
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
@@ -472,8 +472,7 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
 #else
     constexpr size_t lds_pad = 0;
 #endif
-    size_t lds = tile_bytes<QUAD>(RW + 2 * hs.hrad, SWEEP_RH + 2 * hs.vrad + ((V & 1024) ? LUT_TILE_PAD_ROWS : 0)) + lds_pad +
-                 ((V & 1024) ? (size_t)(hs.lut_classes + 1) * 1024 : sizeof(float) * (size_t)(hs.hrad + 1) * (hs.vrad + 1) * BLK);
+    size_t lds = tap_loop_lds_bytes(hs, SWEEP_RH, BLK, QUAD, V) + lds_pad;
     SweepMemo memo;
     memo.cand = ctx->memo_cand; memo.seq = ctx->memo_seq; memo.changed = ctx->changed_seq;
     memo.launch = ctx->launch_seq; memo.valid_from = ctx->memo_valid_from;

@@ -3,7 +3,7 @@
 // terms of pm_core.h.  Both arithmetic modes run this one function; included by pm_core.h.
 //
 // Template switches (the kernels' variant number V keeps naming them in profiles: 114 = none, 122 = D16, 250 = D16 + ROW,
-// + 131072 = BUF):
+// + TSAR_V_BUF = BUF):
 //   STRICT  the oracle's values bit for bit: correctly rounded quotients (persp_divide_exact), min/max clamp, (w r) s, and the
 //           oracle's summation order (window columns).  Fast mode: v_rcp_f32 + 2 multiplies, v_med3_f32 clamp, (w s) r.
 //   ROW     fast mode only: the window is walked row by row (six taps along x per trip).  A row's six taps of one lane fall into
@@ -310,7 +310,7 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
 }
 
 // The variant numbers the production kernels are instantiated with (and which profiles name): bits 1, 4, 5, 6 always set.
-// + 2097152 (with 250 | 131072): MIX
+// + TSAR_V_MIX (with 250 | TSAR_V_BUF): MIX
 // + 4194304 / + 8388608 (experiments build): DIAG 1 / 2 of the MIX body
-__host__ __device__ constexpr bool r5_diag_variant(int V) { return V == (250 | 131072 | 2097152 | 4194304) || V == (250 | 131072 | 2097152 | 8388608); }
-__host__ __device__ constexpr bool r5_production_variant(int V) { return V == 114 || V == 122 || V == 250 || V == (114 | 131072) || V == (122 | 131072) || V == (250 | 131072) || V == (250 | 131072 | 2097152); }
+__host__ __device__ constexpr bool r5_diag_variant(int V) { return V == (250 | TSAR_V_BUF | TSAR_V_MIX | 4194304) || V == (250 | TSAR_V_BUF | TSAR_V_MIX | 8388608); }
+__host__ __device__ constexpr bool r5_production_variant(int V) { return V == 114 || V == 122 || V == 250 || V == (114 | TSAR_V_BUF) || V == (122 | TSAR_V_BUF) || V == (250 | TSAR_V_BUF) || V == (250 | TSAR_V_BUF | TSAR_V_MIX); }

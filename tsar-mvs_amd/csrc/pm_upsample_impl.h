@@ -6,7 +6,7 @@
 // The merge form (MERGE, tsar_upsample_merge) scores the pixel's own current plane first, as a fifth candidate ahead of the four, so a
 // coarse plane replaces it only where it scores lower; with a geometric-consistency term installed it runs with variant bit 24.
 #pragma once
-#include "pm_core.h"
+#include "pm_dispatch.h"
 
 #define UP_RH 8
 
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_upsample_kernel(const DevScene* _
     typedef typename TileOf<QUAD>::type TileT;
     const int hr = HR > 0 ? HR : sc->hrad, vr = HR > 0 ? HR : sc->vrad;
     const int tw = PM_RW + 2 * hr, th = UP_RH + 2 * vr;
-    constexpr bool LUTW = (V & 1024) != 0;
+    constexpr bool LUTW = (V & TSAR_V_LUT) != 0;
     const size_t lut_bytes = LUTW ? (size_t)(sc->lut_classes + 1) * 1024 : 0;
     TileT* tile = (TileT*)(lds_raw + lut_bytes);
     float* wts = LUTW ? (float*)lds_raw : (float*)(lds_raw + tile_bytes<QUAD>(tw, th)) + threadIdx.x;
@@ -80,8 +80,7 @@ static int launch_up_t(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
     const DevScene& hs = ctx->hscene;
     const int tiles_x = (hs.w + PM_RW - 1) / PM_RW, tiles_y = (hs.h + UP_RH - 1) / UP_RH;
     const int n_tiles = tiles_x * tiles_y;
-    const size_t lds = tile_bytes<QUAD>(PM_RW + 2 * hs.hrad, UP_RH + 2 * hs.vrad + ((V & 1024) ? LUT_TILE_PAD_ROWS : 0)) +
-                       ((V & 1024) ? (size_t)(hs.lut_classes + 1) * 1024 : sizeof(float) * (size_t)(hs.hrad + 1) * (hs.vrad + 1) * PM_BLOCK);
+    const size_t lds = tap_loop_lds_bytes(hs, UP_RH, PM_BLOCK, QUAD, V);
     auto kern = pm_upsample_kernel<NB, HR, STRICT, QUAD, V, MERGE>;
     if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const PlaneBuf& out = ctx->buf[MERGE ? 1 : 0];
@@ -94,10 +93,12 @@ static int launch_up_t(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
     return TSAR_OK;
 }
 
-// The launchers' entry: the merge form carries the geometric-consistency term (variant bit 24) while one is installed; the plain form
-// never runs with one (tsar_upsample_planes refuses it).
-template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, bool MERGE = false>
-static int launch_up_g(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
+// The launchers' entry, for a configuration of pm_dispatch.h: the merge form carries the geometric-consistency term (variant bit 24)
+// while one is installed; the plain form never runs with one (tsar_upsample_planes refuses it).
+template <class Cfg, bool MERGE>
+static int launch_up_g(Cfg, tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
+    constexpr int NB = Cfg::NB, HR = Cfg::HR, V = Cfg::V;
+    constexpr bool STRICT = Cfg::STRICT, QUAD = Cfg::QUAD;
     if constexpr (MERGE)
         if (ctx->hscene.geom_on) return launch_up_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, true>(ctx, coarse, cw, ch);
     return launch_up_t<NB, HR, STRICT, QUAD, V, MERGE>(ctx, coarse, cw, ch);

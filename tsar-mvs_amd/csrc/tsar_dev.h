@@ -78,6 +78,10 @@ struct DevScene {
     int geom_on;                                   // a term is installed: the launchers pick the variant-bit-24 kernels
 };
 
+// Variant bits of the tap loops beside the box-11 loop's own numbers (114 / 122 / 250, pm_tap_r5.h)
+#define TSAR_V_LUT 1024           // bit 10: the general-window loop, weights from the shared table (pm_core_lut.h; chunk length in bits 11-13)
+#define TSAR_V_BUF 131072         // bit 17: gathers as structured buffer loads (pm_tap_r5.h BUF)
+#define TSAR_V_MIX 2097152        // bit 21, with TSAR_V_BUF: gathers from the half-float difference texture (pm_tap_r5.h MIX)
 // Variant bits of the geometric-consistency kernels (the remaining bits name the tap loop as before)
 #define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term)
 #define TSAR_V_REDRAW 33554432    // bit 25, with INIT: pm_full_kernel keeps the given plane where it is a valid hypothesis (tsar_pm_rescore)
@@ -151,7 +155,6 @@ struct tsar_ctx {
     const float* final_text = nullptr;   // device lines->text while tsar_pm_iterate_final runs (the kernels' `final` mode), else null
     // geometric consistency (tsar_set_geom_depths): the source views' depth maps, owned; hscene.geom_depth points into them
     std::vector<float*> geom_maps;
-    bool rescoring = false;           // tsar_pm_rescore's launch of the every-pixel kernel (variant bit 25) is under way
     // timing
     int variant = 2;             // TSAR_VARIANT=n: code-generation variant of the fast-mode tap loop (pm_core.h view_cost); tsar_create picks 250 (med3/fract + D16 window loads + clamp-free loop for in-image windows + wave priority + SGPR-pinned texture base and line-top weight loads + row-wise window walk in fast mode; strict mode runs it as 122, the oracle's column order) when the D16 probe passes, else 114
     bool mix_gather = true;      // TSAR_MIX_GATHER=0: keep the byte texture for the buffer-load launches too (pm_tap_r5.h MIX off)
@@ -240,9 +243,9 @@ int launch_pm_init(tsar_ctx* ctx);
 bool probe_d16_hi_zeroes(tsar_ctx* ctx);   // pm_sweep.hip
 int launch_pm_sweep(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
                     uint32_t stream_id, int do_prop, int do_refine);
-int launch_pm_sweep_lut(tsar_ctx* ctx, int need, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out, uint32_t stream_id,
+int launch_pm_sweep_lut(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out, uint32_t stream_id,
                         int do_prop, int do_refine);       // pm_sweep_lut.hip
-int launch_pm_full_lut(tsar_ctx* ctx, int need, bool init, const float4* planes, float* c, float4* n, int32_t* bv, float* rt);   // pm_init_lut.hip
+int launch_pm_full_lut(tsar_ctx* ctx, bool init, bool redraw, const float4* planes, float* c, float4* n, int32_t* bv, float* rt);   // pm_init_lut.hip
 int lut_chunk_taps(int taps_per_line);
 // the general-window tap loop serves 8-bit imagery (quad textures), both filter modes, whose window has few enough
 // distance classes for the LDS table; TSAR_LUT=0 switches it off (the one-tap-at-a-time loop then runs), TSAR_LUT=2 also sends
@@ -262,7 +265,7 @@ int launch_pm_cost_planes(tsar_ctx* ctx, const float4* planes, float* cost, int3
 int launch_pm_rescore(tsar_ctx* ctx, const float4* planes, float* cost, float4* n, int32_t* beview, float* ratio);   // pm_init.hip
 int launch_pm_upsample(tsar_ctx* ctx, const float4* coarse, int cw, int ch);                     // pm_upsample.hip
 int launch_pm_upsample_merge(tsar_ctx* ctx, const float4* coarse, int cw, int ch);               // pm_upsample.hip (buf[0] -> buf[1])
-int launch_pm_upsample_lut(tsar_ctx* ctx, int need, bool merge, const float4* coarse, int cw, int ch);   // pm_upsample_lut.hip
+int launch_pm_upsample_lut(tsar_ctx* ctx, bool merge, const float4* coarse, int cw, int ch);   // pm_upsample_lut.hip
 int launch_pyr_down(tsar_ctx* ctx, const float* src, int w, int h, void* dst, bool u8);        // tsar_pyramid.hip
 int launch_geom_pyramid(tsar_ctx* ctx, const float* src, int w, int h, float* dst);            // tsar_pyramid.hip
 int launch_pyramid_planes(tsar_ctx* ctx, const float4* src, int w, int h, float4* dst);        // tsar_pyramid.hip
