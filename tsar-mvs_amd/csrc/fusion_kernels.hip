@@ -106,15 +106,13 @@ __global__ __launch_bounds__(FU_BLOCK) void fuse_view_kernel(int view, int w, in
 extern "C" int tsar_fuse_ctx(tsar_ctx* ctx, int n_views, int w, int h, const tsar_camera* cams, const float* const* depth, const float* const* normal_world,
                              const float* const* gray, int mem, const int32_t* src_off, const int32_t* src_idx, const tsar_fusion_params* prm,
                              float* points_out, int64_t cap, int64_t* n_points_out) {
-    if (!ctx) return TSAR_ERR_INVALID;
-    auto bad = [&](const char* msg) { ctx->err = msg; return TSAR_ERR_INVALID; };
-    if (n_views < 2 || w < 1 || h < 1 || !cams || !depth || !normal_world || !gray || !src_off || !src_idx || !prm || !n_points_out) return bad("tsar_fuse: null argument, fewer than two views or an empty image");
-    if (mem != TSAR_MEM_DEVICE && mem != TSAR_MEM_HOST) return bad("tsar_fuse: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return TSAR_ERR_HIP; }
+    CHECK_CTX(ctx);
+    if (n_views < 2 || w < 1 || h < 1 || !cams || !depth || !normal_world || !gray || !src_off || !src_idx || !prm || !n_points_out)
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_fuse: null argument, fewer than two views or an empty image");
+    if (mem != TSAR_MEM_DEVICE && mem != TSAR_MEM_HOST) return fail(ctx, TSAR_ERR_INVALID, "tsar_fuse: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
     const size_t np = (size_t)w * h;
     hipStream_t st = ctx->stream;
     ScratchScope scratch(ctx);
-    auto dmalloc = [&](size_t bytes) -> void* { return scratch.alloc(bytes); };
     auto done = [&](int rc) {
         if (hipStreamSynchronize(st) != hipSuccess && rc == TSAR_OK) rc = TSAR_ERR_HIP;
         scratch.release();
@@ -129,7 +127,7 @@ extern "C" int tsar_fuse_ctx(tsar_ctx* ctx, int n_views, int w, int h, const tsa
         if (!depth[v] || !normal_world[v] || !gray[v]) return done(TSAR_ERR_INVALID);
         if (mem == TSAR_MEM_DEVICE) { hd[v] = depth[v]; hn[v] = normal_world[v]; hg[v] = gray[v]; }
         else {
-            float *dd = (float*)dmalloc(np * 4), *dn = (float*)dmalloc(np * 12), *dg = (float*)dmalloc(np * 4);
+            float *dd = (float*)scratch.alloc(np * 4), *dn = (float*)scratch.alloc(np * 12), *dg = (float*)scratch.alloc(np * 4);
             if (!dd || !dn || !dg) return done(TSAR_ERR_NOMEM);
             hipMemcpyAsync(dd, depth[v], np * 4, hipMemcpyHostToDevice, st);
             hipMemcpyAsync(dn, normal_world[v], np * 12, hipMemcpyHostToDevice, st);
@@ -139,13 +137,13 @@ extern "C" int tsar_fuse_ctx(tsar_ctx* ctx, int n_views, int w, int h, const tsa
     }
     std::vector<FuCam> hc(n_views);
     for (int v = 0; v < n_views; v++) { memcpy(hc[v].K, cams[v].K, 36); memcpy(hc[v].R, cams[v].R, 36); memcpy(hc[v].t, cams[v].t, 12); }
-    FuCam* d_cams = (FuCam*)dmalloc(sizeof(FuCam) * n_views);
-    const float **d_depth = (const float**)dmalloc(8 * n_views), **d_normal = (const float**)dmalloc(8 * n_views), **d_gray = (const float**)dmalloc(8 * n_views);
+    FuCam* d_cams = (FuCam*)scratch.alloc(sizeof(FuCam) * n_views);
+    const float **d_depth = (const float**)scratch.alloc(8 * n_views), **d_normal = (const float**)scratch.alloc(8 * n_views), **d_gray = (const float**)scratch.alloc(8 * n_views);
     const int n_src_total = src_off[n_views];
-    int32_t* d_src = (int32_t*)dmalloc((size_t)(n_src_total > 0 ? n_src_total : 1) * 4);
-    uint8_t *mask = (uint8_t*)dmalloc((size_t)n_views * np), *pending = (uint8_t*)dmalloc((size_t)n_views * np), *keep = (uint8_t*)dmalloc(np);
-    FuRec *rec = (FuRec*)dmalloc(np * sizeof(FuRec)), *compact = (FuRec*)dmalloc(np * sizeof(FuRec));
-    unsigned int* d_count = (unsigned int*)dmalloc(4);
+    int32_t* d_src = (int32_t*)scratch.alloc((size_t)(n_src_total > 0 ? n_src_total : 1) * 4);
+    uint8_t *mask = (uint8_t*)scratch.alloc((size_t)n_views * np), *pending = (uint8_t*)scratch.alloc((size_t)n_views * np), *keep = (uint8_t*)scratch.alloc(np);
+    FuRec *rec = (FuRec*)scratch.alloc(np * sizeof(FuRec)), *compact = (FuRec*)scratch.alloc(np * sizeof(FuRec));
+    unsigned int* d_count = (unsigned int*)scratch.alloc(4);
     if (!d_cams || !d_depth || !d_normal || !d_gray || !d_src || !mask || !pending || !keep || !rec || !compact || !d_count) return done(TSAR_ERR_NOMEM);
     hipMemcpyAsync(d_cams, hc.data(), sizeof(FuCam) * n_views, hipMemcpyHostToDevice, st);
     hipMemcpyAsync((void*)d_depth, hd.data(), 8 * n_views, hipMemcpyHostToDevice, st);
@@ -156,7 +154,7 @@ extern "C" int tsar_fuse_ctx(tsar_ctx* ctx, int n_views, int w, int h, const tsa
     hipMemsetAsync(pending, 0, (size_t)n_views * np, st);
     size_t tmp_bytes = 0;
     if (rocprim::select(nullptr, tmp_bytes, rec, keep, compact, d_count, np, st) != hipSuccess) return done(TSAR_ERR_HIP);
-    void* tmp = dmalloc(tmp_bytes);
+    void* tmp = scratch.alloc(tmp_bytes);
     if (!tmp) return done(TSAR_ERR_NOMEM);
     const float cos_angle = (float)cos((double)prm->angle_deg * 3.14159265358979323846 / 180.0);
     int64_t n_out = 0;

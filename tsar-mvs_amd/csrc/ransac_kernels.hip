@@ -551,9 +551,9 @@ __global__ __launch_bounds__(RS_BLOCK) void ransac_refine_chain_mw_kernel(const 
 }
 
 extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, float* inlier_ratio_out) {
-    if (!ctx) return TSAR_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return TSAR_ERR_HIP; }
-    if (!ctx->have_views || ctx->n_regions < 1) { ctx->err = "tsar_set_views / tsar_set_regions have not been called"; return TSAR_ERR_STATE; }
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    NEED_REGIONS(ctx);
     const int nreg = ctx->n_regions;
     const size_t np = (size_t)ctx->w * ctx->h;
     hipStream_t st = ctx->stream;
@@ -562,35 +562,34 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
     auto TR = [&](const char* what) { if (trace) { hipStreamSynchronize(st); auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[ransac] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tr0).count()); tr0 = n; } };
     std::vector<float> text(nreg);
     std::vector<int32_t> slot_of_region(nreg, -1), region_of_slot;
-    if (hipMemcpy(text.data(), ctx->region_text, (size_t)nreg * 4, hipMemcpyDeviceToHost) != hipSuccess) { ctx->err = "D2H failed"; return TSAR_ERR_HIP; }
+    if (hipMemcpy(text.data(), ctx->region_text, (size_t)nreg * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, TSAR_ERR_HIP, "D2H failed");
     for (int r = 0; r < nreg; r++)
         if (text[r] == -1.0f) { slot_of_region[r] = (int)region_of_slot.size(); region_of_slot.push_back(r); }
     const int nslot = (int)region_of_slot.size();
     TR("text D2H + slots");
     ScratchScope scratch(ctx);           // temporaries come out of the context's arena (tsar_dev.h)
-    auto dmalloc = [&](size_t bytes) -> void* { return scratch.alloc(bytes); };
     auto done = [&](int rc, const char* msg) { if (msg) ctx->err = msg; hipStreamSynchronize(st); scratch.release(); return rc; };
-    float* d_ratio = (float*)dmalloc((size_t)nreg * 4);
+    float* d_ratio = (float*)scratch.alloc((size_t)nreg * 4);
     if (!d_ratio) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
     hipMemsetAsync(d_ratio, 0, (size_t)nreg * 4, st);
     if (nslot > 0) {
-        int32_t* d_slot_of_region = (int32_t*)dmalloc((size_t)nreg * 4);
-        int32_t* d_region_of_slot = (int32_t*)dmalloc((size_t)nslot * 4);
-        uint32_t* d_pix = (uint32_t*)dmalloc(np * 4);
-        uint32_t* d_nsel = (uint32_t*)dmalloc(4);
-        int* d_counts = (int*)dmalloc((size_t)nslot * 4);
+        int32_t* d_slot_of_region = (int32_t*)scratch.alloc((size_t)nreg * 4);
+        int32_t* d_region_of_slot = (int32_t*)scratch.alloc((size_t)nslot * 4);
+        uint32_t* d_pix = (uint32_t*)scratch.alloc(np * 4);
+        uint32_t* d_nsel = (uint32_t*)scratch.alloc(4);
+        int* d_counts = (int*)scratch.alloc((size_t)nslot * 4);
         if (!d_slot_of_region || !d_region_of_slot || !d_pix || !d_nsel || !d_counts) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
         hipMemcpyAsync(d_slot_of_region, slot_of_region.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, st);
         hipMemcpyAsync(d_region_of_slot, region_of_slot.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
         hipMemsetAsync(d_counts, 0, (size_t)nslot * 4, st);
         TR("allocs + uploads");
         // (1) raster-order list of reliable pixels inside textureless regions (main.cpp:1527-1536)
-        uint8_t* d_flag = (uint8_t*)dmalloc(np);
+        uint8_t* d_flag = (uint8_t*)scratch.alloc(np);
         if (!d_flag) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
         size_t tmp_bytes = 0;
         rocprim::counting_iterator<uint32_t> first(0);
         if (rocprim::select(nullptr, tmp_bytes, first, d_flag, d_pix, d_nsel, np, st) != hipSuccess) return done(TSAR_ERR_HIP, "rocprim::select sizing failed");
-        void* d_tmp = dmalloc(tmp_bytes);
+        void* d_tmp = scratch.alloc(tmp_bytes);
         if (!d_tmp) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
         {
             ScopedKernelTimer tm(ctx, "ransac_select");
@@ -603,10 +602,10 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
         TR("select");
         std::vector<int> counts(nslot, 0), slot_start(nslot, 0), pts_start(nslot, 0), pts_count(nslot, 0);
         float* d_pts = nullptr;
-        int *d_slot_start = (int*)dmalloc((size_t)nslot * 4), *d_pts_start = (int*)dmalloc((size_t)nslot * 4), *d_pts_count = (int*)dmalloc((size_t)nslot * 4);
+        int *d_slot_start = (int*)scratch.alloc((size_t)nslot * 4), *d_pts_start = (int*)scratch.alloc((size_t)nslot * 4), *d_pts_count = (int*)scratch.alloc((size_t)nslot * 4);
         if (!d_slot_start || !d_pts_start || !d_pts_count) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
         if (nsel > 0) {
-            uint32_t *d_keys = (uint32_t*)dmalloc((size_t)nsel * 4), *d_keys2 = (uint32_t*)dmalloc((size_t)nsel * 4), *d_pix2 = (uint32_t*)dmalloc((size_t)nsel * 4);
+            uint32_t *d_keys = (uint32_t*)scratch.alloc((size_t)nsel * 4), *d_keys2 = (uint32_t*)scratch.alloc((size_t)nsel * 4), *d_pix2 = (uint32_t*)scratch.alloc((size_t)nsel * 4);
             if (!d_keys || !d_keys2 || !d_pix2) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
             hipLaunchKernelGGL(ransac_keys_kernel, dim3((nsel + 255) / 256), dim3(256), 0, st, d_pix, (int)nsel, ctx->canny, d_slot_of_region, d_keys, d_counts);
             // (2) stable sort by region keeps raster order inside each region
@@ -614,7 +613,7 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
             while ((1 << bits) < nslot) bits++;
             size_t sort_bytes = 0;
             if (rocprim::radix_sort_pairs(nullptr, sort_bytes, d_keys, d_keys2, d_pix, d_pix2, nsel, 0, bits, st) != hipSuccess) return done(TSAR_ERR_HIP, "radix sort sizing failed");
-            void* d_sort_tmp = dmalloc(sort_bytes);
+            void* d_sort_tmp = scratch.alloc(sort_bytes);
             if (!d_sort_tmp) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
             {
                 ScopedKernelTimer tm(ctx, "ransac_sort");
@@ -629,7 +628,7 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
                 pts_count[s] = counts[s] > 50000 ? RS_MAXPTS : counts[s];      // main.cpp:1540-1549
                 pts_start[s] = pacc; pacc += pts_count[s];
             }
-            d_pts = (float*)dmalloc((size_t)(pacc > 0 ? pacc : 1) * 12);
+            d_pts = (float*)scratch.alloc((size_t)(pacc > 0 ? pacc : 1) * 12);
             if (!d_pts) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
             hipMemcpyAsync(d_slot_start, slot_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
             hipMemcpyAsync(d_counts, counts.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
@@ -640,13 +639,13 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
                                    d_counts, d_pts_start, d_pts);
             }
         } else {
-            d_pts = (float*)dmalloc(12);
+            d_pts = (float*)scratch.alloc(12);
             hipMemcpyAsync(d_pts_start, pts_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
         }
         hipMemcpyAsync(d_pts_count, pts_count.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
         TR("points");
-        RansacState* d_state = (RansacState*)dmalloc((size_t)nslot * sizeof(RansacState));
-        int* d_cnt = (int*)dmalloc((size_t)nslot * RS_PHASE * sizeof(int));
+        RansacState* d_state = (RansacState*)scratch.alloc((size_t)nslot * sizeof(RansacState));
+        int* d_cnt = (int*)scratch.alloc((size_t)nslot * RS_PHASE * sizeof(int));
         if (!d_state || !d_cnt) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
         // stage 2, measured on six ~50 000-point regions: the history tree with lookahead 1 / 2 / 3 -> 25.9 / 26.4 / 33.7 ms (the passes
         // are bound by the CU's FP64 rate, so the extra planes of a tree cost what the saved passes return); the speculative chain of
@@ -674,7 +673,7 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
             if (wgs > n_cu / (nslot > 0 ? nslot : 1)) wgs = n_cu / (nslot > 0 ? nslot : 1);
             bool fitted = false;
             if (lookahead < 1 && wgs >= 2) {
-                int* d_sync = (int*)dmalloc((size_t)nslot * RS_SYNC_INTS * 4 + 4);
+                int* d_sync = (int*)scratch.alloc((size_t)nslot * RS_SYNC_INTS * 4 + 4);
                 if (!d_sync) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
                 int* d_failed = d_sync + (size_t)nslot * RS_SYNC_INTS;
                 hipMemsetAsync(d_sync, 0, (size_t)nslot * RS_SYNC_INTS * 4 + 4, st);

@@ -206,8 +206,6 @@ __global__ __launch_bounds__(SL_BLOCK) void slic_connect_kernel(const int32_t* _
     out[(size_t)y * w + x] = dc >= 16 ? dl : cl;
 }
 
-static int fail(tsar_ctx* ctx, int code, const char* msg) { ctx->err = msg; return code; }
-
 extern "C" void tsar_default_slic_settings(tsar_slic_settings* s) {   // main.cpp:608-615
     if (!s) return;
     s->spixel_size = 20;
@@ -218,8 +216,7 @@ extern "C" void tsar_default_slic_settings(tsar_slic_settings* s) {   // main.cp
 }
 
 extern "C" int tsar_slic(tsar_ctx* ctx, const uint8_t* bgra, int w, int h, const tsar_slic_settings* st, int32_t* labels_out, int mem) {
-    if (!ctx) return TSAR_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, TSAR_ERR_HIP, "hipSetDevice failed");
+    CHECK_CTX(ctx);
     if (!bgra || !st || !labels_out) return fail(ctx, TSAR_ERR_INVALID, "bgra/settings/labels_out is NULL");
     const int S = st->spixel_size;
     if (S < 4 || S > 256 || w < S || h < S || st->no_iters < 0 || st->color_space < 0 || st->color_space > 2)
@@ -267,8 +264,7 @@ extern "C" int tsar_slic(tsar_ctx* ctx, const uint8_t* bgra, int w, int h, const
 // laid out like the reference's spixel_info (gSLICr_spixel_info.h:11-17) = Spixel above.
 extern "C" int tsar_selftest_slic_stage(tsar_ctx* ctx, int stage, int w, int h, int mw, int mh, const tsar_slic_settings* st, const void* in0,
                                         const void* in1, void* inout) {
-    if (!ctx) return TSAR_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, TSAR_ERR_HIP, "hipSetDevice failed");
+    CHECK_CTX(ctx);
     if (!st || !in0 || !inout || stage < 0 || stage > 4 || w < 1 || h < 1) return fail(ctx, TSAR_ERR_INVALID, "bad stage arguments");
     const int S = st->spixel_size;
     if (S < 4 || S > 256) return fail(ctx, TSAR_ERR_INVALID, "bad superpixel size");

@@ -284,23 +284,21 @@ __global__ void tx_upsample_kernel(const int32_t* __restrict__ lab4, int w4, int
 // (equivalent to tsar_set_regions).  labels_out [h][w] int32 (optional), n_regions_out, and host copies of
 // text/size (optional, capacity `cap` entries).
 extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int mem, int* n_regions_out, float* text_out, float* size_out, int cap) {
-    if (!ctx) return TSAR_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return TSAR_ERR_HIP; }
-    if (!ctx->have_views) { ctx->err = "tsar_set_views has not been called"; return TSAR_ERR_STATE; }
-    if (!ctx->hscene.use_quad) { ctx->err = "weak-texture detection needs 8-bit imagery"; return TSAR_ERR_INVALID; }
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (!ctx->hscene.use_quad) return fail(ctx, TSAR_ERR_INVALID, "weak-texture detection needs 8-bit imagery");
     const int w = ctx->w, h = ctx->h, w2 = w / 2, h2 = h / 2, w4 = w2 / 2, h4 = h2 / 2;
-    if (w4 < 3 || h4 < 3) { ctx->err = "image too small for weak-texture detection"; return TSAR_ERR_INVALID; }
+    if (w4 < 3 || h4 < 3) return fail(ctx, TSAR_ERR_INVALID, "image too small for weak-texture detection");
     const int n4 = w4 * h4;
     hipStream_t st = ctx->stream;
     const bool trace = ctx->trace_host;     // host-side steps on stderr (diagnostics)
     auto tr0 = std::chrono::steady_clock::now();
     auto TR = [&](const char* what) { if (trace) { hipStreamSynchronize(st); auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[weak_texture] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tr0).count()); tr0 = n; } };
     ScratchScope scratch(ctx);           // temporaries come out of the context's arena (tsar_dev.h)
-    auto dmalloc = [&](size_t bytes) -> void* { return scratch.alloc(bytes); };
     auto done = [&](int rc, const char* msg) { if (msg) ctx->err = msg; hipStreamSynchronize(st); scratch.release(); return rc; };
-    uint8_t *g0 = (uint8_t*)dmalloc((size_t)w * h), *g2 = (uint8_t*)dmalloc((size_t)w2 * h2), *g4 = (uint8_t*)dmalloc(n4), *edge = (uint8_t*)dmalloc(n4);
-    int *parent = (int*)dmalloc((size_t)n4 * 4), *is_root = (int*)dmalloc((size_t)n4 * 4), *rank = (int*)dmalloc((size_t)n4 * 4);
-    int32_t* lab4 = (int32_t*)dmalloc((size_t)n4 * 4);
+    uint8_t *g0 = (uint8_t*)scratch.alloc((size_t)w * h), *g2 = (uint8_t*)scratch.alloc((size_t)w2 * h2), *g4 = (uint8_t*)scratch.alloc(n4), *edge = (uint8_t*)scratch.alloc(n4);
+    int *parent = (int*)scratch.alloc((size_t)n4 * 4), *is_root = (int*)scratch.alloc((size_t)n4 * 4), *rank = (int*)scratch.alloc((size_t)n4 * 4);
+    int32_t* lab4 = (int32_t*)scratch.alloc((size_t)n4 * 4);
     if (!g0 || !g2 || !g4 || !edge || !parent || !is_root || !rank || !lab4) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
     const dim3 b(TX_BLOCK);
     auto grid2 = [](int ww, int hh) { return dim3((ww + 31) / 32, (hh + 7) / 8); };
@@ -314,12 +312,12 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
     TR("allocs + pyramid + edges");
     if (!(ctx->hscene.flags & TSAR_FLAG_NO_LINE_CLOSING)) {
         // first labelling (before the border fix) -> large components -> close gaps in their straight boundaries
-        int* cnt0 = (int*)dmalloc((size_t)n4 * 4);
-        int* wlist = (int*)dmalloc((size_t)TX_MAX_WEAK * 4 + 4);
+        int* cnt0 = (int*)scratch.alloc((size_t)n4 * 4);
+        int* wlist = (int*)scratch.alloc((size_t)TX_MAX_WEAK * 4 + 4);
         const int rmax = w4 + h4 + 2, nrho = 2 * rmax + 1;
-        int* acc = (int*)dmalloc((size_t)180 * nrho * 4);
-        uint8_t* bmask = (uint8_t*)dmalloc(n4);
-        float* tabs = (float*)dmalloc(360 * 4);
+        int* acc = (int*)scratch.alloc((size_t)180 * nrho * 4);
+        uint8_t* bmask = (uint8_t*)scratch.alloc(n4);
+        float* tabs = (float*)scratch.alloc(360 * 4);
         if (!cnt0 || !wlist || !acc || !bmask || !tabs) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
         float htab[360];
         for (int t = 0; t < 180; t++) {
@@ -360,7 +358,7 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
     TR("second labelling");
     size_t tmp_bytes = 0;
     if (rocprim::exclusive_scan(nullptr, tmp_bytes, is_root, rank, 0, (size_t)n4, rocprim::plus<int>(), st) != hipSuccess) return done(TSAR_ERR_HIP, "scan sizing failed");
-    void* tmp = dmalloc(tmp_bytes);
+    void* tmp = scratch.alloc(tmp_bytes);
     if (!tmp) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
     if (rocprim::exclusive_scan(tmp, tmp_bytes, is_root, rank, 0, (size_t)n4, rocprim::plus<int>(), st) != hipSuccess) return done(TSAR_ERR_HIP, "scan failed");
     int last_rank = 0, last_flag = 0;
@@ -369,7 +367,7 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
     if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "weak-texture kernels failed");
     TR("scan + count D2H");
     const int labelnum = last_rank + last_flag + 1;                          // + label 0 (edge pixels)
-    int* stats = (int*)dmalloc((size_t)labelnum * 7 * 4);
+    int* stats = (int*)scratch.alloc((size_t)labelnum * 7 * 4);
     if (!stats) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
     int *count = stats, *sumx = stats + labelnum, *sumy = stats + 2 * labelnum, *xmin = stats + 3 * labelnum, *xmax = stats + 4 * labelnum,
         *ymin = stats + 5 * labelnum, *ymax = stats + 6 * labelnum;

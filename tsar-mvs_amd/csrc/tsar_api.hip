@@ -43,17 +43,7 @@ static void drain_timers(tsar_ctx* ctx) {
 }
 
 // ---- helpers -------------------------------------------------------------------------------------
-static int fail(tsar_ctx* ctx, int code, const char* msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-template <typename T>
-static int dev_alloc(tsar_ctx* ctx, T** p, size_t n) {
-    if (*p) { hipFree(*p); *p = nullptr; }
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-    if (e != hipSuccess) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? TSAR_ERR_NOMEM : TSAR_ERR_HIP; }
-    return TSAR_OK;
-}
+// (fail, CHECK_CTX, NEED_*, TRY, dev_alloc and DevTmp: tsar_dev.h, shared with the operators' own files)
 template <typename T>
 static void dev_free(T*& p) {
     if (p) hipFree(p);
@@ -61,21 +51,12 @@ static void dev_free(T*& p) {
 }
 static hipMemcpyKind in_kind(int mem) { return mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
 static hipMemcpyKind out_kind(int mem) { return mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
-#define CHECK_CTX(ctx) \
-    if (!(ctx)) return TSAR_ERR_INVALID; \
-    if (hipSetDevice((ctx)->device) != hipSuccess) return fail(ctx, TSAR_ERR_HIP, "hipSetDevice failed")
-#define NEED_VIEWS(ctx) if (!(ctx)->have_views) return fail(ctx, TSAR_ERR_STATE, "tsar_set_views has not been called")
-// matching scores planes against source views; a context holding the reference view only serves the textureless-refinement
-// operators (load_planes, weak-texture detection, region RANSAC, fill)
-#define NEED_SOURCES(ctx) if ((ctx)->hscene.n_sel < 1) return fail(ctx, TSAR_ERR_STATE, "no source views: tsar_set_views was given the reference view only")
-#define NEED_STATE(ctx) if (!(ctx)->have_state) return fail(ctx, TSAR_ERR_STATE, "no plane state: call tsar_pm_init, tsar_load_planes or tsar_set_plane first")
-#define TRY(expr) do { int rc_ = (expr); if (rc_ != TSAR_OK) return rc_; } while (0)
 
 template <typename T>
 struct TmpIn {   // device view of a caller buffer (copies host buffers in)
     tsar_ctx* ctx;
     const T* d = nullptr;
-    T* owned = nullptr;
+    DevTmp<T> owned;
     int rc = TSAR_OK;
     // scratch: take the staging buffer from the context's arena (tsar_dev.h ScratchScope) instead of a hipMalloc per call
     TmpIn(tsar_ctx* c, const T* src, size_t n, int mem, ScratchScope* scratch = nullptr) : ctx(c) {
@@ -86,14 +67,14 @@ struct TmpIn {   // device view of a caller buffer (copies host buffers in)
             staging = (T*)scratch->alloc(n * sizeof(T));
             if (!staging) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
         } else {
-            rc = dev_alloc(ctx, &owned, n);
-            staging = owned;
+            rc = owned.alloc(ctx, n);
+            staging = owned.p;
         }
         if (rc == TSAR_OK && hipMemcpyAsync(staging, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "H2D failed");
         d = staging;
     }
     ~TmpIn() {
-        if (owned) { hipStreamSynchronize(ctx->stream); hipFree(owned); }
+        if (owned.p) hipStreamSynchronize(ctx->stream);
     }
 };
 
@@ -320,7 +301,7 @@ static void free_planes(tsar_ctx* ctx) {
 
 extern "C" int tsar_destroy(tsar_ctx* ctx) {
     if (!ctx) return TSAR_OK;
-    hipSetDevice(ctx->device);
+    (void)enter_ctx(ctx);                  // (a device that cannot be selected still gets its host side released)
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     drain_timers(ctx);
     free_views(ctx);
@@ -370,11 +351,7 @@ extern "C" int tsar_set_params(tsar_ctx* ctx, const tsar_params* p) {
     ctx->params = *p;
     ctx->have_params = true;
     fill_scene_params(ctx);
-    if (ctx->have_views) {
-        // depth range / scale feed the derived camera block: the views must be set again
-        ctx->have_views = false;
-        ctx->have_state = false;
-    }
+    if (ctx->have_views) ctx->views_reset();   // depth range / scale feed the derived camera block: the views must be set again
     return TSAR_OK;
 }
 
@@ -409,9 +386,9 @@ static int probe_exact_sqrt(tsar_ctx* ctx) {
     return ctx->exact_sqrt_probe;
 }
 
-// tsar_set_views (elem = 4: float32 images) and tsar_set_views_u8 (elem = 1: the 8-bit decode itself, widened on the device)
-static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* const* gray, int elem, int mem, const tsar_camera* cams) {
-    CHECK_CTX(ctx);
+// ---- tsar_set_views (elem = 4: float32 images) and tsar_set_views_u8 (elem = 1: the 8-bit decode itself, widened on the device), in
+// four steps: the arguments, the images and textures, the window, the state planes ----
+static int check_views_args(tsar_ctx* ctx, int n_views, int w, int h, const void* const* gray, const tsar_camera* cams) {
     if (!ctx->have_params) return fail(ctx, TSAR_ERR_STATE, "tsar_set_params must be called before tsar_set_views");
     if (ctx->params.flags & TSAR_FLAG_STRICT_DIV) {
         const int pr = probe_exact_divide(ctx);
@@ -425,10 +402,11 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     if (!gray || !cams) return fail(ctx, TSAR_ERR_INVALID, "gray/cams is NULL");
     for (int v = 0; v < n_views; v++)
         if (!gray[v]) return fail(ctx, TSAR_ERR_INVALID, "gray[v] is NULL");
-    ctx->have_views = false;
-    ctx->have_state = false;
-    ctx->have_out = false;
-    ctx->have_resize = false;
+    return TSAR_OK;
+}
+
+// images, quad textures (and whether the imagery is 8-bit: use_quad), difference textures, derived cameras
+static int upload_views(tsar_ctx* ctx, int n_views, int w, int h, const void* const* gray, int elem, int mem, const tsar_camera* cams) {
     free_geom(ctx);                        // depth maps of the previous views' sources: not this scene's
     // The image and quad-texture buffers of the previous views are kept when the size is the same (a worker matching view after
     // view of a scene): 2 x n_views hipMalloc + hipFree of ~100 MB each cost 55 ms per call at ETH3D size, more than the copies.
@@ -441,13 +419,9 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     if ((int)ctx->img.size() < n_views) ctx->img.resize(n_views, nullptr);
     if ((int)ctx->quad.size() < n_views) ctx->quad.resize(n_views, nullptr);
     if ((int)ctx->dquad.size() < n_views) ctx->dquad.resize(n_views, nullptr);
-    struct DevInt {   // freed on every exit path
-        int* p = nullptr;
-        ~DevInt() { if (p) hipFree(p); }
-    } dflag_owner;
-    TRY(dev_alloc(ctx, &dflag_owner.p, 1));
-    int* const dflag = dflag_owner.p;
-    hipMemsetAsync(dflag, 0, sizeof(int), ctx->stream);
+    DevTmp<int> dflag;
+    TRY(dflag.alloc(ctx, 1));
+    hipMemsetAsync(dflag.p, 0, sizeof(int), ctx->stream);
     for (int v = 0; v < n_views; v++) {
         if (!ctx->img[v]) TRY(dev_alloc(ctx, &ctx->img[v], np));
         if (!ctx->quad[v]) TRY(dev_alloc(ctx, &ctx->quad[v], (size_t)(w + 2) * (h + 2)));
@@ -462,10 +436,10 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
             TSAR_HIP_TRY(ctx, hipMemcpyAsync(stage, gray[v], np, hipMemcpyHostToDevice, ctx->stream));
             TRY(launch_expand_u8(ctx, stage, ctx->img[v], np));
         }
-        TRY(launch_build_quad(ctx, ctx->img[v], ctx->quad[v], w, h, dflag));
+        TRY(launch_build_quad(ctx, ctx->img[v], ctx->quad[v], w, h, dflag.p));
     }
     int hflag = 0;
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(&hflag, dflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(&hflag, dflag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     sc.use_quad = hflag ? 0 : 1;
     if (sc.use_quad) {   // the 8-bit tap loops are the only users of sqrt_rsq_exact: probed for the contexts that will run them
@@ -490,13 +464,18 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     derive_cameras(ctx, cams);
     ctx->cams.assign(cams, cams + n_views);
     ctx->views_u8 = elem == 1;
-    // Can the matching kernels run this window?  8-bit imagery shares one weight table per workgroup (pm_core_lut.h): any box whose
-    // taps have <= TSAR_LUT_MAX_CLASSES distinct distances (every square box; rectangular ones unless their radii have mixed
-    // parity, e.g. 63 x 61 -> 202).  Everything else keeps the hoisted bilateral weights per thread in LDS, (hrad+1)(vrad+1) taps
-    // x 256 threads x 4 B beside the reference window, which bounds the box at 23.  Checked for the sweeps' window and, for even
-    // boxes, gipuma_init_cu2's own (init_window_differs); a context with the reference view alone never matches (refinement
-    // operators only) and takes any box.
-    auto window_problem = [&](bool for_init) -> const char* {
+    return TSAR_OK;
+}
+
+// Can the matching kernels run this window?  Null, or the reason why not.  8-bit imagery shares one weight table per workgroup
+// (pm_core_lut.h): any box whose taps have <= TSAR_LUT_MAX_CLASSES distinct distances (every square box; rectangular ones unless
+// their radii have mixed parity, e.g. 63 x 61 -> 202).  Everything else keeps the hoisted bilateral weights per thread in LDS,
+// (hrad+1)(vrad+1) taps x 256 threads x 4 B beside the reference window, which bounds the box at 23.  Checked for the sweeps' window
+// and, for even boxes, gipuma_init_cu2's own (init_window_differs); a context with the reference view alone never matches
+// (refinement operators only) and takes any box.  Leaves the scene block describing the sweeps' window.
+static const char* window_problem(tsar_ctx* ctx) {
+    DevScene& sc = ctx->hscene;
+    auto problem_of = [&](bool for_init) -> const char* {
         fill_scene_params(ctx, for_init);
         if (lut_path_applies(ctx)) return nullptr;
         const size_t lds = (size_t)(sc.hrad + 1) * (sc.vrad + 1) * 1024 + (size_t)(32 + 2 * sc.hrad) * (16 + 2 * sc.vrad) * 4 + 16;
@@ -505,13 +484,15 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
         if (sc.lut_classes == 0) return "this rectangular box has more than 144 distinct tap distances (radii of mixed parity): the shared weight table cannot hold them and the per-thread table does not fit LDS; use radii of equal parity, or a box of at most 23";
         return "box too large for fast mode on this device: the D16 LDS-load probe failed, so the general-window loop is not available; use TSAR_FLAG_STRICT_DIV, or a box of at most 23";
     };
-    const char* problem = n_views > 1 ? window_problem(false) : nullptr;
-    if (!problem && n_views > 1 && init_window_differs(ctx)) problem = window_problem(true);
+    const char* problem = ctx->n_views > 1 ? problem_of(false) : nullptr;
+    if (!problem && ctx->n_views > 1 && init_window_differs(ctx)) problem = problem_of(true);
     fill_scene_params(ctx);
-    if (problem) return fail(ctx, TSAR_ERR_INVALID, problem);
-    sc.n_sel = std::min(n_views - 1, TSAR_MAX_SELECTED);   // default subset: the first 32 source views at most (tsar_set_view_subset picks others)
-    for (int i = 0; i < sc.n_sel; i++) sc.sel[i] = i + 1;
-    // state planes (LineState::resize linestate.h:71-110)
+    return problem;
+}
+
+// state planes (LineState::resize linestate.h:71-110): kept from the previous views of the same size, cleared
+static int alloc_state_planes(tsar_ctx* ctx) {
+    const size_t np = (size_t)ctx->w * ctx->h;
     for (int b = 0; b < 2; b++) {
         if (!ctx->buf[b].c) TRY(dev_alloc(ctx, &ctx->buf[b].c, np));
         if (!ctx->buf[b].n4) TRY(dev_alloc(ctx, &ctx->buf[b].n4, np));
@@ -526,6 +507,19 @@ static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* 
     if (!ctx->out4) TRY(dev_alloc(ctx, &ctx->out4, np));
     TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->beview, 0, np * sizeof(int32_t), ctx->stream));
     TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->canny, 0, np * sizeof(int32_t), ctx->stream));
+    return TSAR_OK;
+}
+
+static int set_views_impl(tsar_ctx* ctx, int n_views, int w, int h, const void* const* gray, int elem, int mem, const tsar_camera* cams) {
+    CHECK_CTX(ctx);
+    TRY(check_views_args(ctx, n_views, w, h, gray, cams));
+    ctx->views_reset();
+    TRY(upload_views(ctx, n_views, w, h, gray, elem, mem, cams));
+    if (const char* problem = window_problem(ctx)) return fail(ctx, TSAR_ERR_INVALID, problem);
+    DevScene& sc = ctx->hscene;
+    sc.n_sel = std::min(n_views - 1, TSAR_MAX_SELECTED);   // default subset: the first 32 source views at most (tsar_set_view_subset picks others)
+    for (int i = 0; i < sc.n_sel; i++) sc.sel[i] = i + 1;
+    TRY(alloc_state_planes(ctx));
     TRY(upload_scene(ctx));
     ctx->have_views = true;
     return TSAR_OK;
@@ -546,9 +540,7 @@ extern "C" int tsar_set_view_subset(tsar_ctx* ctx, int n, const int32_t* view_id
         if (view_idx[i] < 1 || view_idx[i] >= ctx->n_views) return fail(ctx, TSAR_ERR_INVALID, "view index must be in 1..n_views-1");
     ctx->hscene.n_sel = n;
     for (int i = 0; i < n; i++) ctx->hscene.sel[i] = view_idx[i];
-    // stored costs were scored under the previous subset: the sweep may no longer skip a neighbour that carries the
-    // pixel's own plane (pm_sweep.hip same_bits shortcut); the reference re-scores it and may accept
-    if (ctx->have_state) ctx->cost_consistent = false;
+    ctx->costs_voided();                   // scored under the previous subset
     return upload_scene(ctx);
 }
 
@@ -574,12 +566,9 @@ extern "C" int tsar_pm_init(tsar_ctx* ctx) {
         if (rc == TSAR_OK) rc = rc2;
     }
     TRY(rc);
-    ctx->have_state = true;
-    ctx->have_out = false;
-    ctx->sweeps_done = 0;
     // c[p] is the score of n4[p] on the SWEEP window only if init ran on that window: otherwise a neighbour's identical plane may
     // well score lower than the stored cost, and the sweeps must not skip it
-    ctx->cost_consistent = !own_window;
+    ctx->state_scored(!own_window);
     return TSAR_OK;
 }
 
@@ -591,12 +580,18 @@ static int pm_sweeps(tsar_ctx* ctx, int n_sweeps, int first_colour, int do_prop,
     ctx->memo_valid_from = ctx->launch_seq + 1;
     ctx->call_launch = 0;
     if (ctx->memo_mode && n_sweeps > 2 && !ctx->memo_cand) {
+        // all three buffers or none: a failure part of the way leaves memo_cand null, and the next call tries again
         const size_t np = (size_t)ctx->w * ctx->h;
-        TRY(dev_alloc(ctx, &ctx->memo_cand, np * 8));
-        TRY(dev_alloc(ctx, &ctx->memo_seq, np));
-        TRY(dev_alloc(ctx, &ctx->changed_seq, np));
-        TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->memo_seq, 0, np * sizeof(uint32_t), ctx->stream));
-        TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->changed_seq, 0, np * sizeof(uint32_t), ctx->stream));
+        DevTmp<int32_t> cand;
+        DevTmp<uint32_t> seq, changed;
+        TRY(cand.alloc(ctx, np * 8));
+        TRY(seq.alloc(ctx, np));
+        TRY(changed.alloc(ctx, np));
+        TSAR_HIP_TRY(ctx, hipMemsetAsync(seq.p, 0, np * sizeof(uint32_t), ctx->stream));
+        TSAR_HIP_TRY(ctx, hipMemsetAsync(changed.p, 0, np * sizeof(uint32_t), ctx->stream));
+        ctx->memo_cand = cand.release();
+        ctx->memo_seq = seq.release();
+        ctx->changed_seq = changed.release();
     }
     for (int s = 0; s < n_sweeps; s++) {
         ctx->launch_seq++;
@@ -640,7 +635,7 @@ extern "C" int tsar_pm_iterate(tsar_ctx* ctx, int iters) {
     if (iters < 0) return fail(ctx, TSAR_ERR_INVALID, "iters must be >= 0");
     TRY(pm_sweeps(ctx, 2 * iters, 0, 1, 1));   // black then red, gipuma.cu:1744-1754
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_out = false;
+    ctx->result_voided();
     return TSAR_OK;
 }
 
@@ -663,7 +658,7 @@ extern "C" int tsar_pm_iterate_final(tsar_ctx* ctx, int iters, const float* text
         ctx->final_text = nullptr;
         if (rc == TSAR_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "sweep failed");
     }
-    ctx->have_out = false;
+    ctx->result_voided();
     return rc;
 }
 
@@ -675,7 +670,7 @@ extern "C" int tsar_pm_sweep(tsar_ctx* ctx, int colour, int do_prop, int do_refi
     NEED_STATE(ctx);
     TRY(pm_sweeps(ctx, 1, colour & 1, do_prop, do_refine));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_out = false;
+    ctx->result_voided();
     return TSAR_OK;
 }
 extern "C" int tsar_set_sweep_counter(tsar_ctx* ctx, int n) {
@@ -690,28 +685,25 @@ extern "C" int tsar_pm_cost_planes(tsar_ctx* ctx, const float* planes, int mem, 
     NEED_SOURCES(ctx);
     if (!planes || !cost_out) return fail(ctx, TSAR_ERR_INVALID, "planes/cost_out is NULL");
     const size_t np = (size_t)ctx->w * ctx->h;
-    float4* dpl = nullptr;
-    float *dc = nullptr, *drt = nullptr;
-    int32_t* dbv = nullptr;
-    int rc = TSAR_OK;
     if (mem == TSAR_MEM_DEVICE) {
-        rc = launch_pm_cost_planes(ctx, (const float4*)planes, cost_out, beview_out, ratio_out);
-        if (rc == TSAR_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "sync failed");
-        return rc;
+        TRY(launch_pm_cost_planes(ctx, (const float4*)planes, cost_out, beview_out, ratio_out));
+        TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return TSAR_OK;
     }
-    if ((rc = dev_alloc(ctx, &dpl, np)) == TSAR_OK && (rc = dev_alloc(ctx, &dc, np)) == TSAR_OK && (rc = dev_alloc(ctx, &drt, np)) == TSAR_OK &&
-        (rc = dev_alloc(ctx, &dbv, np)) == TSAR_OK) {
-        if (hipMemcpyAsync(dpl, planes, np * 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "H2D failed");
-        if (rc == TSAR_OK) rc = launch_pm_cost_planes(ctx, dpl, dc, dbv, drt);
-        if (rc == TSAR_OK) {
-            hipMemcpyAsync(cost_out, dc, np * 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (beview_out) hipMemcpyAsync(beview_out, dbv, np * 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (ratio_out) hipMemcpyAsync(ratio_out, drt, np * 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "kernel or copy failed");
-        }
-    }
-    dev_free(dpl); dev_free(dc); dev_free(drt); dev_free(dbv);
-    return rc;
+    DevTmp<float4> dpl;                    // (per call, not from the scratch arena: a diagnostic does not grow what the context keeps)
+    DevTmp<float> dc, drt;
+    DevTmp<int32_t> dbv;
+    TRY(dpl.alloc(ctx, np));
+    TRY(dc.alloc(ctx, np));
+    TRY(drt.alloc(ctx, np));
+    TRY(dbv.alloc(ctx, np));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(dpl.p, planes, np * 16, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch_pm_cost_planes(ctx, dpl.p, dc.p, dbv.p, drt.p));
+    hipMemcpyAsync(cost_out, dc.p, np * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (beview_out) hipMemcpyAsync(beview_out, dbv.p, np * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (ratio_out) hipMemcpyAsync(ratio_out, drt.p, np * 4, hipMemcpyDeviceToHost, ctx->stream);
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (a failed copy shows here)
+    return TSAR_OK;
 }
 
 extern "C" int tsar_set_plane(tsar_ctx* ctx, const float* planes, const float* cost, int mem) {
@@ -722,9 +714,7 @@ extern "C" int tsar_set_plane(tsar_ctx* ctx, const float* planes, const float* c
     TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[0].n4, planes, np * 16, in_kind(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[0].c, cost, np * 4, in_kind(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cost_consistent = false;
-    ctx->have_state = true;
-    ctx->have_out = false;
+    ctx->state_given();
     return TSAR_OK;
 }
 extern "C" int tsar_get_plane(tsar_ctx* ctx, float* planes, float* cost, int32_t* beview, float* ratio, int mem) {
@@ -751,9 +741,7 @@ extern "C" int tsar_load_planes(tsar_ctx* ctx, const float* depth, const float* 
     TRY(d.rc); TRY(n.rc);
     TRY(launch_get_disp(ctx, d.d, n.d));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cost_consistent = false;
-    ctx->have_state = true;
-    ctx->have_out = false;
+    ctx->state_given();
     return TSAR_OK;
 }
 extern "C" int tsar_compute_disp(tsar_ctx* ctx) {
@@ -761,7 +749,7 @@ extern "C" int tsar_compute_disp(tsar_ctx* ctx) {
     NEED_STATE(ctx);
     TRY(launch_compute_disp(ctx));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_out = true;
+    ctx->result_computed();
     return TSAR_OK;
 }
 extern "C" int tsar_compute_disp_final(tsar_ctx* ctx, const float* resize_planes, const float* text, int mem) {
@@ -771,10 +759,10 @@ extern "C" int tsar_compute_disp_final(tsar_ctx* ctx, const float* resize_planes
     const size_t np = (size_t)ctx->w * ctx->h;
     TmpIn<float> r(ctx, resize_planes, 4 * np, mem), t(ctx, text, np, mem);
     TRY(r.rc); TRY(t.rc);
-    ctx->cost_consistent = false;
+    ctx->costs_voided();
     TRY(launch_compute_disp_final(ctx, (const float4*)r.d, t.d));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_out = true;
+    ctx->result_computed();
     return TSAR_OK;
 }
 // ---- coarse-to-fine ------------------------------------------------------------------------------
@@ -789,10 +777,17 @@ static int stream_after(tsar_ctx* waiter, tsar_ctx* producer) {
     return TSAR_OK;
 }
 
+// The two-context calls.  `other` is a second context at all: not null, not the context itself
+static bool is_other_ctx(const tsar_ctx* ctx, const tsar_ctx* other) { return other && other != ctx; }
+// `coarse` holds views one pyramid level below `fine`'s, ((w + 1) / 2, (h + 1) / 2), on the same device
+static bool is_level_below(const tsar_ctx* coarse, const tsar_ctx* fine) {
+    return coarse->device == fine->device && coarse->have_views && coarse->w == (fine->w + 1) / 2 && coarse->h == (fine->h + 1) / 2;
+}
+
 extern "C" int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine_in) {
     CHECK_CTX(coarse);
     tsar_ctx* fine = const_cast<tsar_ctx*>(fine_in);   // its views are only read; its stream is recorded on
-    if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: fine must be another context");
+    if (!is_other_ctx(coarse, fine)) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: fine must be another context");
     if (fine->device != coarse->device) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the two contexts are on different devices");
     if (!fine->have_views) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the fine context has no views");
     if (fine->hscene.geom_on || coarse->hscene.geom_on)
@@ -827,25 +822,21 @@ extern "C" int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine_in) {
 extern "C" int tsar_upsample_planes(tsar_ctx* fine, const tsar_ctx* coarse_in) {
     CHECK_CTX(fine);
     tsar_ctx* coarse = const_cast<tsar_ctx*>(coarse_in);
-    if (!coarse || coarse == fine) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: coarse must be another context");
+    if (!is_other_ctx(fine, coarse)) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: coarse must be another context");
     NEED_VIEWS(fine);
     NEED_SOURCES(fine);
-    if (coarse->device != fine->device) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the two contexts are on different devices");
     if (fine->hscene.geom_on || coarse->hscene.geom_on)
         return fail(fine, TSAR_ERR_STATE, "tsar_upsample_planes: coarse-to-fine with a geometric-consistency term is not supported (tsar_clear_geom first)");
-    if (!coarse->have_views || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
-        return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one (tsar_pyramid_views)");
+    if (!is_level_below(coarse, fine))
+        return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one on the same device (tsar_pyramid_views)");
     if (!coarse->have_state) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context has no plane state");
     if (!fine->resize4) TRY(dev_alloc(fine, &fine->resize4, (size_t)fine->w * fine->h));
     fine->have_resize = false;
     TRY(stream_after(fine, coarse));
     TRY(launch_pm_upsample(fine, coarse->buf[0].n4, coarse->w, coarse->h));
     TSAR_HIP_TRY(fine, hipStreamSynchronize(fine->stream));
-    fine->have_state = true;
-    fine->have_out = false;
+    fine->state_scored(true);
     fine->have_resize = true;
-    fine->sweeps_done = 0;              // the sweeps that follow draw like the ones after tsar_pm_init
-    fine->cost_consistent = true;       // every cost is its plane's score on the sweep window
     return TSAR_OK;
 }
 
@@ -857,10 +848,10 @@ extern "C" int tsar_compute_disp_final_upsampled(tsar_ctx* ctx, const float* tex
     const size_t np = (size_t)ctx->w * ctx->h;
     TmpIn<float> t(ctx, text, np, mem);
     TRY(t.rc);
-    ctx->cost_consistent = false;
+    ctx->costs_voided();
     TRY(launch_compute_disp_final(ctx, ctx->resize4, t.d));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_out = true;
+    ctx->result_computed();
     return TSAR_OK;
 }
 
@@ -874,6 +865,33 @@ extern "C" int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem)
 }
 
 // ---- geometric consistency -----------------------------------------------------------------------
+// Installs a geometric-consistency term: one map per source view that has one, owned by the context.  fill(v, &map) allocates
+// (dev_alloc) and fills view v's [h][w] map on the context's stream, or leaves it null: no term for that view.  On failure the
+// device block must not keep pointers to freed maps, so it is uploaded without any term.
+template <typename Fill>
+static int install_geom_term(tsar_ctx* ctx, float weight, float clip, Fill fill) {
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // no kernel may still read the maps about to be freed
+    free_geom(ctx);
+    ctx->geom_maps.assign(ctx->n_views, nullptr);
+    DevScene& sc = ctx->hscene;
+    for (int v = 1; v < ctx->n_views; v++) {
+        const int rc = fill(v, &ctx->geom_maps[v]);
+        if (rc != TSAR_OK) {
+            hipStreamSynchronize(ctx->stream);
+            free_geom(ctx);
+            upload_scene(ctx);
+            return rc;
+        }
+        sc.geom_depth[v] = ctx->geom_maps[v];
+    }
+    sc.geom_weight = weight;
+    sc.geom_clip = clip;
+    sc.geom_clip_sq = clip * clip;
+    sc.geom_on = 1;
+    ctx->costs_voided();                   // scored without this term, or with other maps
+    return upload_scene(ctx);              // (synchronises the stream: the maps are complete on return)
+}
+
 extern "C" int tsar_set_geom_depths(tsar_ctx* ctx, int n_views, const float* const* depth, int mem, float weight, float clip) {
     CHECK_CTX(ctx);
     NEED_VIEWS(ctx);
@@ -883,31 +901,14 @@ extern "C" int tsar_set_geom_depths(tsar_ctx* ctx, int n_views, const float* con
     if (!(weight >= 0.0f) || !(weight < 1e30f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: weight must be finite and >= 0");
     if (!(clip > 0.0f) || !(clip <= 1048576.0f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: clip must be in (0, 2^20] pixels");
     if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_geom_depths: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // no kernel may still read the maps about to be freed
-    free_geom(ctx);
     const size_t np = (size_t)ctx->w * ctx->h;
-    ctx->geom_maps.assign(n_views, nullptr);
-    DevScene& sc = ctx->hscene;
-    for (int v = 1; v < n_views; v++) {
-        if (!depth[v]) continue;
-        // (failure: the device block must not keep pointers to the freed maps, so it is uploaded without any term)
-        if (dev_alloc(ctx, &ctx->geom_maps[v], np) != TSAR_OK) { free_geom(ctx); upload_scene(ctx); return TSAR_ERR_NOMEM; }
-        if (hipMemcpyAsync(ctx->geom_maps[v], depth[v], np * sizeof(float), in_kind(mem), ctx->stream) != hipSuccess) {
-            hipStreamSynchronize(ctx->stream);
-            free_geom(ctx);
-            upload_scene(ctx);
+    return install_geom_term(ctx, weight, clip, [&](int v, float** map) -> int {
+        if (!depth[v]) return TSAR_OK;
+        if (dev_alloc(ctx, map, np) != TSAR_OK) return TSAR_ERR_NOMEM;
+        if (hipMemcpyAsync(*map, depth[v], np * sizeof(float), in_kind(mem), ctx->stream) != hipSuccess)
             return fail(ctx, TSAR_ERR_HIP, "tsar_set_geom_depths: copy of a depth map failed");
-        }
-        sc.geom_depth[v] = ctx->geom_maps[v];
-    }
-    sc.geom_weight = weight;
-    sc.geom_clip = clip;
-    sc.geom_clip_sq = clip * clip;
-    sc.geom_on = 1;
-    // stored costs were scored without this term (or with other maps): void them and the memo, as tsar_set_view_subset does
-    if (ctx->have_state) ctx->cost_consistent = false;
-    ctx->memo_valid_from = ctx->launch_seq + 1;
-    return upload_scene(ctx);              // (synchronises the stream: the copies above are complete on return)
+        return TSAR_OK;
+    });
 }
 
 extern "C" int tsar_clear_geom(tsar_ctx* ctx) {
@@ -915,9 +916,18 @@ extern "C" int tsar_clear_geom(tsar_ctx* ctx) {
     if (!ctx->hscene.geom_on && ctx->geom_maps.empty()) return TSAR_OK;
     if (ctx->stream) TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     free_geom(ctx);
-    if (ctx->have_state) ctx->cost_consistent = false;
-    ctx->memo_valid_from = ctx->launch_seq + 1;
+    ctx->costs_voided();                   // scored with the term
     return ctx->dscene ? upload_scene(ctx) : TSAR_OK;
+}
+
+// buf[0]'s planes scored with the context's cost (invalid ones redrawn as tsar_pm_init draws) into buf[1], which becomes the state:
+// the kernel's plane pointers are restrict-qualified, so it cannot run in place
+static int rescore_state(tsar_ctx* ctx) {
+    TRY(launch_pm_rescore(ctx, ctx->buf[0].n4, ctx->buf[1].c, ctx->buf[1].n4, ctx->beview, ctx->ratio));
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::swap(ctx->buf[0], ctx->buf[1]);
+    ctx->state_scored(true);               // every c[p] is n4[p]'s score under the context's cost, on the sweep window
+    return TSAR_OK;
 }
 
 extern "C" int tsar_pm_rescore(tsar_ctx* ctx) {
@@ -925,15 +935,7 @@ extern "C" int tsar_pm_rescore(tsar_ctx* ctx) {
     NEED_VIEWS(ctx);
     NEED_SOURCES(ctx);
     NEED_STATE(ctx);
-    // read buf[0], write buf[1] (the kernel's plane pointers are restrict-qualified), then buf[1] is the state
-    TRY(launch_pm_rescore(ctx, ctx->buf[0].n4, ctx->buf[1].c, ctx->buf[1].n4, ctx->beview, ctx->ratio));
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::swap(ctx->buf[0], ctx->buf[1]);
-    ctx->sweeps_done = 0;                  // the sweeps that follow draw like the ones after tsar_pm_init (whatever the context ran before)
-    ctx->cost_consistent = true;           // every c[p] is n4[p]'s score under the context's cost, on the sweep window
-    ctx->memo_valid_from = ctx->launch_seq + 1;
-    ctx->have_out = false;
-    return TSAR_OK;
+    return rescore_state(ctx);
 }
 
 extern "C" int tsar_get_geom_matrices(tsar_ctx* ctx, int view, float* forward, float* back) {
@@ -953,9 +955,8 @@ extern "C" int tsar_get_geom_matrices(tsar_ctx* ctx, int view, float* forward, f
 // `coarse` holds what tsar_pyramid_views installs from `fine`: ((w + 1) / 2, (h + 1) / 2) views of as many views, on the same device, with
 // fine's cameras and their fx, fy, cx, cy halved
 static bool is_pyramid_of(const tsar_ctx* coarse, const tsar_ctx* fine) {
-    if (!coarse->have_views || !fine->have_views || coarse->device != fine->device) return false;
-    if (coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2 || coarse->n_views != fine->n_views) return false;
-    if (coarse->cams.size() != fine->cams.size()) return false;
+    if (!fine->have_views || !is_level_below(coarse, fine)) return false;
+    if (coarse->n_views != fine->n_views || coarse->cams.size() != fine->cams.size()) return false;
     for (size_t v = 0; v < fine->cams.size(); v++) {
         tsar_camera c = fine->cams[v];
         c.K[0] *= 0.5f; c.K[2] *= 0.5f; c.K[4] *= 0.5f; c.K[5] *= 0.5f;
@@ -967,84 +968,55 @@ static bool is_pyramid_of(const tsar_ctx* coarse, const tsar_ctx* fine) {
 extern "C" int tsar_geom_pyramid(tsar_ctx* coarse, const tsar_ctx* fine_in) {
     CHECK_CTX(coarse);
     tsar_ctx* fine = const_cast<tsar_ctx*>(fine_in);   // its maps are only read; its stream is recorded on
-    if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_geom_pyramid: fine must be another context");
+    if (!is_other_ctx(coarse, fine)) return fail(coarse, TSAR_ERR_INVALID, "tsar_geom_pyramid: fine must be another context");
     if (!fine->hscene.geom_on) return fail(coarse, TSAR_ERR_STATE, "tsar_geom_pyramid: the fine context has no geometric-consistency term");
     if (!is_pyramid_of(coarse, fine))
         return fail(coarse, TSAR_ERR_INVALID, "tsar_geom_pyramid: the coarse context must hold fine's views one level down (tsar_pyramid_views)");
-    TSAR_HIP_TRY(coarse, hipStreamSynchronize(coarse->stream));   // no kernel may still read the maps about to be freed
-    free_geom(coarse);
     const size_t np = (size_t)coarse->w * coarse->h;
-    coarse->geom_maps.assign(coarse->n_views, nullptr);
-    DevScene& sc = coarse->hscene;
-    int rc = stream_after(coarse, fine);
-    for (int v = 1; v < coarse->n_views && rc == TSAR_OK; v++) {
-        const float* src = fine->hscene.geom_depth[v];
-        if (!src) continue;
-        rc = dev_alloc(coarse, &coarse->geom_maps[v], np);
-        if (rc == TSAR_OK) rc = launch_geom_pyramid(coarse, src, fine->w, fine->h, coarse->geom_maps[v]);
-        sc.geom_depth[v] = coarse->geom_maps[v];
-    }
-    if (rc != TSAR_OK) {
-        // (the device block must not keep pointers to the freed maps, so it is uploaded without any term)
-        hipStreamSynchronize(coarse->stream);
-        free_geom(coarse);
-        upload_scene(coarse);
-        return rc;
-    }
-    sc.geom_weight = fine->hscene.geom_weight;
-    sc.geom_clip = fine->hscene.geom_clip;         // the same number of pixels of this level
-    sc.geom_clip_sq = fine->hscene.geom_clip_sq;
-    sc.geom_on = 1;
-    if (coarse->have_state) coarse->cost_consistent = false;
-    coarse->memo_valid_from = coarse->launch_seq + 1;
-    return upload_scene(coarse);           // (synchronises the stream: the maps are complete on return)
+    const DevScene& fs = fine->hscene;
+    bool ordered = false;                  // coarse's stream after fine's, before the first map is read
+    return install_geom_term(coarse, fs.geom_weight, fs.geom_clip /* the same number of pixels of this level */, [&](int v, float** map) -> int {
+        if (!ordered) TRY(stream_after(coarse, fine));
+        ordered = true;
+        if (!fs.geom_depth[v]) return TSAR_OK;
+        TRY(dev_alloc(coarse, map, np));
+        return launch_geom_pyramid(coarse, fs.geom_depth[v], fine->w, fine->h, *map);
+    });
 }
 
 extern "C" int tsar_pyramid_planes(tsar_ctx* coarse, const tsar_ctx* fine_in) {
     CHECK_CTX(coarse);
     tsar_ctx* fine = const_cast<tsar_ctx*>(fine_in);
-    if (!fine || fine == coarse) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: fine must be another context");
+    if (!is_other_ctx(coarse, fine)) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: fine must be another context");
     if (!fine->have_state) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: the fine context has no plane state");
-    if (!coarse->have_views || fine->device != coarse->device || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
+    if (!is_level_below(coarse, fine))
         return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one on the same device");
     NEED_SOURCES(coarse);
     TRY(stream_after(coarse, fine));
     TRY(launch_pyramid_planes(coarse, fine->buf[0].n4, fine->w, fine->h, coarse->buf[0].n4));
-    // then tsar_pm_rescore: read buf[0], write buf[1], swap
-    TRY(launch_pm_rescore(coarse, coarse->buf[0].n4, coarse->buf[1].c, coarse->buf[1].n4, coarse->beview, coarse->ratio));
-    TSAR_HIP_TRY(coarse, hipStreamSynchronize(coarse->stream));
-    std::swap(coarse->buf[0], coarse->buf[1]);
-    coarse->have_state = true;
-    coarse->have_out = false;
-    coarse->sweeps_done = 0;
-    coarse->cost_consistent = true;
-    coarse->memo_valid_from = coarse->launch_seq + 1;
-    return TSAR_OK;
+    return rescore_state(coarse);
 }
 
 extern "C" int tsar_upsample_merge(tsar_ctx* fine, const tsar_ctx* coarse_in) {
     CHECK_CTX(fine);
     tsar_ctx* coarse = const_cast<tsar_ctx*>(coarse_in);
-    if (!coarse || coarse == fine) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: coarse must be another context");
+    if (!is_other_ctx(fine, coarse)) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: coarse must be another context");
     if (!fine->have_state) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: the fine context has no plane state");
     NEED_SOURCES(fine);
-    if (coarse->device != fine->device || !coarse->have_state || coarse->w != (fine->w + 1) / 2 || coarse->h != (fine->h + 1) / 2)
+    if (!coarse->have_state || !is_level_below(coarse, fine))
         return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_merge: the coarse context must hold a plane state of ((w + 1) / 2, (h + 1) / 2) on the same device");
     TRY(stream_after(fine, coarse));
     TRY(launch_pm_upsample_merge(fine, coarse->buf[0].n4, coarse->w, coarse->h));   // buf[0] -> buf[1]
     TSAR_HIP_TRY(fine, hipStreamSynchronize(fine->stream));
     std::swap(fine->buf[0], fine->buf[1]);
-    fine->have_out = false;
-    fine->sweeps_done = 0;              // the sweeps that follow draw like the ones after tsar_pm_init
-    fine->cost_consistent = true;       // every cost is its plane's score on the sweep window
-    fine->memo_valid_from = fine->launch_seq + 1;
+    fine->state_scored(true);              // every cost is its plane's score on the sweep window
     return TSAR_OK;
 }
 
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);
-    ctx->cost_consistent = false;
+    ctx->costs_voided();
     TRY(launch_depth_to_plane(ctx));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSAR_OK;
@@ -1140,7 +1112,7 @@ extern "C" int tsar_set_regions(tsar_ctx* ctx, const int32_t* labels, int n_regi
 }
 extern "C" int tsar_set_region_planes(tsar_ctx* ctx, const float* region_planes) {
     CHECK_CTX(ctx);
-    if (ctx->n_regions < 1) return fail(ctx, TSAR_ERR_STATE, "tsar_set_regions has not been called");
+    NEED_REGIONS(ctx);
     if (!region_planes) return fail(ctx, TSAR_ERR_INVALID, "region_planes is NULL");
     TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->region_n4, region_planes, (size_t)ctx->n_regions * 16, hipMemcpyHostToDevice, ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1149,7 +1121,7 @@ extern "C" int tsar_set_region_planes(tsar_ctx* ctx, const float* region_planes)
 extern "C" int tsar_fake_depth(tsar_ctx* ctx, float* fakedepth_out, int mem) {
     CHECK_CTX(ctx);
     NEED_VIEWS(ctx);
-    if (ctx->n_regions < 1) return fail(ctx, TSAR_ERR_STATE, "tsar_set_regions has not been called");
+    NEED_REGIONS(ctx);
     TRY(launch_fake_depth(ctx));
     if (fakedepth_out) TSAR_HIP_TRY(ctx, hipMemcpyAsync(fakedepth_out, ctx->fakedepth, (size_t)ctx->w * ctx->h * 4, out_kind(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1158,12 +1130,12 @@ extern "C" int tsar_fake_depth(tsar_ctx* ctx, float* fakedepth_out, int mem) {
 extern "C" int tsar_fill_textureless(tsar_ctx* ctx) {   // gipuma_fill gipuma.cu:1819-1850
     CHECK_CTX(ctx);
     NEED_STATE(ctx);
-    if (ctx->n_regions < 1) return fail(ctx, TSAR_ERR_STATE, "tsar_set_regions has not been called");
-    ctx->cost_consistent = false;
+    NEED_REGIONS(ctx);
+    ctx->costs_voided();
     TRY(launch_update_scale(ctx));
     TRY(launch_compute_disp(ctx));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_out = true;
+    ctx->result_computed();
     return TSAR_OK;
 }
 
@@ -1249,7 +1221,7 @@ extern "C" int tsar_selftest_divide(tsar_ctx* ctx, const float* X, const float* 
     ScratchScope scratch(ctx);
     float* d[5];
     for (auto& p : d)
-        if (!(p = (float*)scratch.alloc(n * sizeof(float)))) { scratch.release(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
+        if (!(p = (float*)scratch.alloc(n * sizeof(float)))) return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed");
     const float* src[3] = {X, Y, Z};
     int rc = TSAR_OK;
     for (int k = 0; k < 3 && rc == TSAR_OK; k++)
@@ -1259,7 +1231,20 @@ extern "C" int tsar_selftest_divide(tsar_ctx* ctx, const float* X, const float* 
                           hipMemcpyAsync(v_out, d[4], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
         rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    scratch.release();
+    return rc;                             // (the scratch goes back on return: the stream is idle)
+}
+// The counter self-tests: n zeroed 64-bit device counters from the scratch arena, launch(counters), the counters copied to out[n].
+template <typename Launch>
+static int run_counters(tsar_ctx* ctx, int n, uint64_t* out, Launch launch) {
+    ScratchScope scratch(ctx);             // (released on return, after the synchronise below)
+    const size_t bytes = (size_t)n * sizeof(unsigned long long);
+    unsigned long long* dc = (unsigned long long*)scratch.alloc(bytes);
+    if (!dc) return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed");
+    int rc = TSAR_OK;
+    if (hipMemsetAsync(dc, 0, bytes, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemsetAsync failed");
+    if (rc == TSAR_OK) rc = launch(dc);
+    if (rc == TSAR_OK && hipMemcpyAsync(out, dc, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
     return rc;
 }
 extern "C" int tsar_selftest_divide_random(tsar_ctx* ctx, int log2_triples, uint64_t seed, int mode, int guarded, uint64_t* mismatches_out,
@@ -1267,18 +1252,14 @@ extern "C" int tsar_selftest_divide_random(tsar_ctx* ctx, int log2_triples, uint
     CHECK_CTX(ctx);
     if (log2_triples < 6 || log2_triples > 36 || mode < 0 || mode > 2 || !mismatches_out) return fail(ctx, TSAR_ERR_INVALID, "log2_triples in 6..36, mode in 0..2");
     if (!guarded && mode == 2) return fail(ctx, TSAR_ERR_INVALID, "the unguarded form is only defined inside the guard (modes 0, 1)");
-    ScratchScope scratch(ctx);
-    unsigned long long* dc = (unsigned long long*)scratch.alloc(2 * sizeof(unsigned long long));
-    if (!dc) { scratch.release(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
-    unsigned long long hc[2] = {0, 0};
-    int rc = TSAR_OK;
-    if (hipMemsetAsync(dc, 0, sizeof hc, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemsetAsync failed");
-    // launches of 2^30 triples at most (~0.1 s each)
-    for (int done = 0; rc == TSAR_OK && done < (1 << (log2_triples > 30 ? log2_triples - 30 : 0)); done++)
-        rc = launch_selftest_divide_random(ctx, log2_triples > 30 ? 30 : log2_triples, seed + 0x9E3779B97F4A7C15ull * (uint64_t)done, mode, guarded, dc);
-    if (rc == TSAR_OK && hipMemcpyAsync(hc, dc, sizeof hc, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    scratch.release();
+    uint64_t hc[2] = {0, 0};
+    const int rc = run_counters(ctx, 2, hc, [&](unsigned long long* dc) {
+        // launches of 2^30 triples at most (~0.1 s each)
+        int rc = TSAR_OK;
+        for (int done = 0; rc == TSAR_OK && done < (1 << (log2_triples > 30 ? log2_triples - 30 : 0)); done++)
+            rc = launch_selftest_divide_random(ctx, log2_triples > 30 ? 30 : log2_triples, seed + 0x9E3779B97F4A7C15ull * (uint64_t)done, mode, guarded, dc);
+        return rc;
+    });
     *mismatches_out = hc[0];
     if (outside_guard_out) *outside_guard_out = hc[1];
     return rc;
@@ -1286,16 +1267,8 @@ extern "C" int tsar_selftest_divide_random(tsar_ctx* ctx, int log2_triples, uint
 extern "C" int tsar_selftest_sqrt(tsar_ctx* ctx, int mode, uint64_t seed, uint64_t* mismatches_out) {
     CHECK_CTX(ctx);
     if (mode < 0 || mode > 3 || !mismatches_out) return fail(ctx, TSAR_ERR_INVALID, "mode in 0..3");
-    ScratchScope scratch(ctx);
-    unsigned long long* dc = (unsigned long long*)scratch.alloc(sizeof(unsigned long long));
-    if (!dc) { scratch.release(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
-    unsigned long long hc = 0;
-    int rc = TSAR_OK;
-    if (hipMemsetAsync(dc, 0, sizeof hc, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemsetAsync failed");
-    if (rc == TSAR_OK) rc = launch_selftest_sqrt(ctx, mode, seed, dc);
-    if (rc == TSAR_OK && hipMemcpyAsync(&hc, dc, sizeof hc, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    scratch.release();
+    uint64_t hc = 0;
+    const int rc = run_counters(ctx, 1, &hc, [&](unsigned long long* dc) { return launch_selftest_sqrt(ctx, mode, seed, dc); });
     *mismatches_out = hc;
     return rc;
 }
@@ -1305,30 +1278,12 @@ extern "C" int tsar_selftest_sweep_repeat(tsar_ctx* ctx, int colour, void* memo_
     if (!memo_dev || !out8) return fail(ctx, TSAR_ERR_INVALID, "memo_dev / out8 is NULL");
     NEED_VIEWS(ctx);
     NEED_STATE(ctx);
-    ScratchScope scratch(ctx);
-    unsigned long long* dc = (unsigned long long*)scratch.alloc(8 * sizeof(unsigned long long));
-    if (!dc) { scratch.release(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
-    int rc = TSAR_OK;
-    if (hipMemsetAsync(dc, 0, 64, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemsetAsync failed");
-    if (rc == TSAR_OK) rc = launch_sweep_repeat(ctx, colour & 1, (unsigned long long*)memo_dev, dc);
-    if (rc == TSAR_OK && hipMemcpyAsync(out8, dc, 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    scratch.release();
-    return rc;
+    return run_counters(ctx, 8, out8, [&](unsigned long long* dc) { return launch_sweep_repeat(ctx, colour & 1, (unsigned long long*)memo_dev, dc); });
 }
 extern "C" int tsar_selftest_sweep_census(tsar_ctx* ctx, int colour, uint64_t* out8) {
     CHECK_CTX(ctx);
     NEED_VIEWS(ctx);
     NEED_STATE(ctx);
     if (!out8) return fail(ctx, TSAR_ERR_INVALID, "out8 is NULL");
-    ScratchScope scratch(ctx);
-    unsigned long long* dc = (unsigned long long*)scratch.alloc(8 * sizeof(unsigned long long));
-    if (!dc) { scratch.release(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
-    int rc = TSAR_OK;
-    if (hipMemsetAsync(dc, 0, 64, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemsetAsync failed");
-    if (rc == TSAR_OK) rc = launch_sweep_census(ctx, colour & 1, dc);
-    if (rc == TSAR_OK && hipMemcpyAsync(out8, dc, 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    scratch.release();
-    return rc;
+    return run_counters(ctx, 8, out8, [&](unsigned long long* dc) { return launch_sweep_census(ctx, colour & 1, dc); });
 }

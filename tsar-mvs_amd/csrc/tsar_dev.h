@@ -126,7 +126,11 @@ struct tsar_ctx {
     int32_t *beview = nullptr, *canny = nullptr;
     float4* out4 = nullptr;      // result of compute_disp: (n_world, depth)
     bool have_out = false;
-    bool cost_consistent = false;   // c[p] is the multi-view score of n4[p] for every pixel (init / sweep produced the state)
+    // c[p] is the score of n4[p] under the context's current cost (views, subset, sweep window, geometric term) for every pixel: the
+    // sweep then skips a neighbour that carries the pixel's own plane (pm_sweep_impl.h same_bits).  Left standing over a cost that is
+    // not its plane's score, it makes the sweep skip what the reference scores and may accept.  Read by the sweep launcher and the
+    // sweep census self-tests, all behind NEED_STATE, and written by both transitions that create a state: voiding needs no guard.
+    bool cost_consistent = false;
     // regions (cannylines)
     int n_regions = 0;
     float *region_text = nullptr, *region_size = nullptr;
@@ -138,13 +142,15 @@ struct tsar_ctx {
     // that launch, and the number of the last launch that changed the pixel's plane.  A candidate that is the same neighbour as last
     // time, with a plane unchanged since, was scored at this pixel then and rejected (or taken and since improved on): the pixel's cost
     // never rises, so it is rejected again and need not be scored — the reference's results, bit for bit, with fewer evaluations.
-    // Valid among the launches of ONE tsar_pm_iterate call only (nothing else touches the state in between).
+    // Valid among the launches of ONE sweep call only (tsar_pm_iterate, tsar_pm_iterate_final, tsar_pm_sweep; nothing else touches
+    // the state in between): pm_sweeps (tsar_api.hip) voids it at the start of every call, and is the only writer of memo_valid_from
+    // and the only allocator of the three buffers, which exist all or none (memo_cand non-null means all three do).
     int32_t* memo_cand = nullptr;     // [h][w][8]
     uint32_t* memo_seq = nullptr;     // [h][w]
     uint32_t* changed_seq = nullptr;  // [h][w]
     uint32_t launch_seq = 0;          // sweep launches of this context so far (never reset)
-    uint32_t memo_valid_from = 1;     // memos written before this launch are void
-    int call_launch = 0;              // launches since the current tsar_pm_iterate call began
+    uint32_t memo_valid_from = 1;     // memos written before this launch are void (read by launch_sweep_t, pm_sweep_impl.h)
+    int call_launch = 0;              // launches since the current sweep call began
     int memo_mode = 1;                // TSAR_MEMO=0: off
     int compact_from = 6;             // TSAR_COMPACT_FROM=n (-1: never): from launch n of a call on, a wave packs its surviving hypotheses (pm_sweep_impl.h)
     // coarse-to-fine mode (tsar_pyramid_views / tsar_upsample_planes)
@@ -179,6 +185,57 @@ struct tsar_ctx {
     bool timing = false;
     std::vector<KernelTimer> timers;
     ScratchArena scratch;
+
+    // ---- what a call does to the plane state: the only writers of have_state, have_out, cost_consistent and sweeps_done (beside
+    // pm_sweeps' count and tsar_set_sweep_counter) ----
+    // a state whose costs are its planes' scores (init, rescore, upsampling, merge); `consistent`: scored on the sweeps' window (false
+    // only for tsar_pm_init on an even box, whose window is one tap ring larger).  The sweeps that follow draw like the first ones.
+    void state_scored(bool consistent) { have_state = true; have_out = false; sweeps_done = 0; cost_consistent = consistent; }
+    // a state the caller gave (planes with any costs): the sweep counter runs on
+    void state_given() { have_state = true; have_out = false; cost_consistent = false; }
+    // the stored costs are no longer the planes' scores: the cost changed (view subset, geometric term) or planes were rewritten
+    void costs_voided() { cost_consistent = false; }
+    // the result buffer (out4) follows / no longer follows the planes
+    void result_computed() { have_out = true; }
+    void result_voided() { have_out = false; }
+    // new parameters or new views: nothing derived from the previous views stands
+    void views_reset() { have_views = have_state = have_out = have_resize = false; }
+};
+
+// ---- entry guards of the C ABI (every extern "C" function that takes a context) ------------------------------------------------
+static inline int fail(tsar_ctx* ctx, int code, const char* msg) { if (ctx) ctx->err = msg; return code; }
+static inline int enter_ctx(tsar_ctx* ctx) {   // the calling thread works on the context's device from here on
+    if (!ctx) return TSAR_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, TSAR_ERR_HIP, "hipSetDevice failed");
+    return TSAR_OK;
+}
+#define CHECK_CTX(ctx) TRY(enter_ctx(ctx))
+#define NEED_VIEWS(ctx) if (!(ctx)->have_views) return fail(ctx, TSAR_ERR_STATE, "tsar_set_views has not been called")
+// matching scores planes against source views; a context holding the reference view only serves the textureless-refinement
+// operators (load_planes, weak-texture detection, region RANSAC, fill)
+#define NEED_SOURCES(ctx) if ((ctx)->hscene.n_sel < 1) return fail(ctx, TSAR_ERR_STATE, "no source views: tsar_set_views was given the reference view only")
+#define NEED_STATE(ctx) if (!(ctx)->have_state) return fail(ctx, TSAR_ERR_STATE, "no plane state: call tsar_pm_init, tsar_load_planes or tsar_set_plane first")
+#define NEED_REGIONS(ctx) if ((ctx)->n_regions < 1) return fail(ctx, TSAR_ERR_STATE, "tsar_set_regions has not been called")
+#define TRY(expr) do { int rc_ = (expr); if (rc_ != TSAR_OK) return rc_; } while (0)
+
+template <typename T>
+static int dev_alloc(tsar_ctx* ctx, T** p, size_t n) {
+    if (*p) { hipFree(*p); *p = nullptr; }
+    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
+    if (e != hipSuccess) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? TSAR_ERR_NOMEM : TSAR_ERR_HIP; }
+    return TSAR_OK;
+}
+// A device buffer that lives for one call: freed on every exit path unless release()d to a longer-lived owner.  (hipFree waits
+// for the device, so work still queued on the buffer is complete before it goes.)
+template <typename T>
+struct DevTmp {
+    T* p = nullptr;
+    DevTmp() = default;
+    DevTmp(const DevTmp&) = delete;
+    DevTmp& operator=(const DevTmp&) = delete;
+    ~DevTmp() { if (p) hipFree(p); }
+    int alloc(tsar_ctx* ctx, size_t n) { return dev_alloc(ctx, &p, n); }
+    T* release() { T* q = p; p = nullptr; return q; }
 };
 
 // One operator call's view of the arena: alloc() hands out 256-byte-aligned pieces; what does not fit is a plain hipMalloc for

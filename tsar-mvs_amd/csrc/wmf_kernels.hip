@@ -440,20 +440,15 @@ __global__ __launch_bounds__(WMF_BLOCK, 2) void wmf_fill_kernel(const DevScene* 
 // iters launches of gipuma_WMF (final_pass = 0; the reference's loop runs 4, gipuma.cu:1809-1812) or of
 // gipuma_WMF_Final (final_pass = 1; 6 in the reference, :1844-1847)
 extern "C" int tsar_wmf(tsar_ctx* ctx, int iters, int final_pass) {
-    if (!ctx) return TSAR_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return TSAR_ERR_HIP; }
-    if (!ctx->have_state) { ctx->err = "no plane state"; return TSAR_ERR_STATE; }
-    if (iters < 1 || iters > (final_pass ? 6 : 4)) { ctx->err = "tsar_wmf: iters must be 1..4 (detect) or 1..6 (final)"; return TSAR_ERR_INVALID; }
-    if (final_pass && ctx->n_regions < 1) { ctx->err = "tsar_set_regions has not been called"; return TSAR_ERR_STATE; }
+    CHECK_CTX(ctx);
+    NEED_STATE(ctx);
+    if (iters < 1 || iters > (final_pass ? 6 : 4)) return fail(ctx, TSAR_ERR_INVALID, "tsar_wmf: iters must be 1..4 (detect) or 1..6 (final)");
+    if (final_pass) NEED_REGIONS(ctx);
     const size_t np = (size_t)ctx->w * ctx->h;
     ScratchScope scratch(ctx);             // the launch-start snapshots come out of the context's scratch arena
     float* scale_snap = (float*)scratch.alloc(np * 4);
     float* depth_snap = final_pass ? (float*)scratch.alloc(np * 4) : nullptr;
-    if (!scale_snap || (final_pass && !depth_snap)) {
-        scratch.release();
-        ctx->err = "device allocation failed";
-        return TSAR_ERR_NOMEM;
-    }
+    if (!scale_snap || (final_pass && !depth_snap)) return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed");
     const dim3 grid((unsigned)((np + WMF_PIX - 1) / WMF_PIX)), block(WMF_BLOCK);
     int rc = TSAR_OK;
     for (int it = 0; it < iters && rc == TSAR_OK; it++) {
@@ -471,8 +466,7 @@ extern "C" int tsar_wmf(tsar_ctx* ctx, int iters, int final_pass) {
         if (hipGetLastError() != hipSuccess) { ctx->err = "wmf launch failed"; rc = TSAR_ERR_HIP; }
     }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) { ctx->err = "wmf kernel failed"; rc = TSAR_ERR_HIP; }
-    scratch.release();
-    ctx->have_out = false;
-    if (final_pass) ctx->cost_consistent = false;
+    ctx->result_voided();
+    if (final_pass) ctx->costs_voided();   // the final pass rewrites planes
     return rc;
 }
