@@ -322,6 +322,33 @@ int tsar_geom_pyramid(tsar_ctx* coarse, const tsar_ctx* fine);
 int tsar_pyramid_planes(tsar_ctx* coarse, const tsar_ctx* fine);
 int tsar_upsample_merge(tsar_ctx* fine, const tsar_ctx* coarse);
 
+/* The geometric-consistency check on its own: which pixels of a depth map of the reference view do the source views' maps confirm?
+ * What tsar_fuse decides per point, as a per-pixel count, a mask and a filtered map (the reference's pipeline reads such a mask, weak.png,
+ * from a closed binary, main.cpp:1499-1514).  Needs views and an installed term: tsar_set_geom_depths supplies the source maps and the
+ * two matrices (a weight of 0 installs maps for checking only).
+ * depth [h][w]: the map to check; NULL = the context's own result (tsar_get_result's depth: tsar_compute_disp or tsar_fill_textureless
+ * must have run, TSAR_ERR_STATE otherwise).  count_out [h][w] uint8 and depth_out [h][w] float32 may each be NULL (depth_out may be
+ * `depth` itself); `mem` applies to all three pointers.  The call always writes lines->scale, 1 where the pixel is kept, else 0
+ * (tsar_get_reliable_mask returns it: what tsar_set_reliable_mask would install), and changes nothing else: planes, stored costs, the
+ * propagation memo, the sweep counter, the result planes and the term stay as they are.  Timed as "geom_check".
+ * The arithmetic, the same in both arithmetic modes: float32, every operation one IEEE-754 operation rounded to nearest (no fused
+ * multiply-add).  For pixel (x, y) with D = depth[y][x]:
+ *   candidate = D > 0 and D < inf (NaN fails both); a pixel that is no candidate gets count 0
+ *   for every view v = 1 .. n_views - 1 that has a map, in view order (the view subset does not matter): the chain of
+ *   tsar_set_geom_depths above with this D, the F and B tsar_get_geom_matrices returns, exactly as written there, up to inside, D_v,
+ *   p_0, p_1, p_2, x', y' and e2 (no square root);  r2 = reproj_error * reproj_error;  dd = depth_diff * D;
+ *     ok_v = inside and D_v > 0 and p_2 > 0 and e2 < r2 and |p_2 - D| < dd      (p_2: the source point's depth in the reference camera)
+ *   count = sum of ok_v;  keep = count >= min_consistent;  depth_out = keep ? D : 0;  scale = keep ? 1 : 0
+ * TSAR_ERR_STATE: no term installed.  TSAR_ERR_INVALID: p NULL; reproj_error or depth_diff not finite or <= 0; reproj_error > 2^20;
+ * min_consistent outside [1, 31]. */
+typedef struct tsar_geom_check_params {
+    float reproj_error;       /* px,       default 2.0  (tsar_fusion_params' value) */
+    float depth_diff;         /* relative, default 0.01 (tsar_fusion_params' value) */
+    int32_t min_consistent;   /* default 2, in [1, 31] */
+} tsar_geom_check_params;
+void tsar_default_geom_check_params(tsar_geom_check_params* p);
+int tsar_geom_check(tsar_ctx* ctx, const float* depth, const tsar_geom_check_params* p, uint8_t* count_out, float* depth_out, int mem);
+
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */
 int tsar_get_result(tsar_ctx* ctx, float* depth, float* normal_world, float* cost, float* confid,

@@ -53,6 +53,10 @@ class FusionParams(C.Structure):
                 ("used_list", C.c_int32)]
 
 
+class GeomCheckParams(C.Structure):
+    _fields_ = [("reproj_error", C.c_float), ("depth_diff", C.c_float), ("min_consistent", C.c_int32)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -69,6 +73,7 @@ ABI_SYMBOLS = [
     "tsar_pyramid_views", "tsar_upsample_planes", "tsar_compute_disp_final_upsampled", "tsar_get_view_image",
     "tsar_set_geom_depths", "tsar_clear_geom", "tsar_pm_rescore", "tsar_get_geom_matrices",
     "tsar_geom_pyramid", "tsar_pyramid_planes", "tsar_upsample_merge",
+    "tsar_default_geom_check_params", "tsar_geom_check",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -124,6 +129,9 @@ def load_library(path: str = LIB_PATH):
     L.tsar_geom_pyramid.argtypes = [C.c_void_p, C.c_void_p]
     L.tsar_pyramid_planes.argtypes = [C.c_void_p, C.c_void_p]
     L.tsar_upsample_merge.argtypes = [C.c_void_p, C.c_void_p]
+    L.tsar_default_geom_check_params.restype = None
+    L.tsar_default_geom_check_params.argtypes = [C.POINTER(GeomCheckParams)]
+    L.tsar_geom_check.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(GeomCheckParams), C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -400,6 +408,36 @@ class Matcher:
         """each pixel keeps the cheapest of its own plane and its four nearest coarse planes, the own plane winning ties
         (tsar_upsample_merge)"""
         self._chk(self.L.tsar_upsample_merge(self._ctx, coarse._ctx))
+
+    # ---- the geometric-consistency check on its own ----
+    def geom_check(self, depth=None, reproj_error: float = 2.0, depth_diff: float = 0.01, min_consistent: int = 2, want=("count", "depth")):
+        """which pixels of `depth` ([h, w], the reference view's map; None = the context's own result) do the installed source maps
+        confirm (tsar_geom_check; set_geom_depths installs the maps, weight 0 for checking only)?  Returns a dict with "count" ([h, w]
+        uint8: the number of consistent source views) and / or "depth" ([h, w] float32: `depth` where count >= min_consistent, else 0),
+        as `want` names them: numpy arrays, or torch tensors on depth's device when depth is a torch device tensor.  The mask itself
+        is left in the context (get_reliable_mask)."""
+        p = GeomCheckParams(float(reproj_error), float(depth_diff), int(min_consistent))
+        on_device = depth is not None and _is_torch(depth) and depth.is_cuda
+        if depth is not None and not on_device:
+            depth = np.ascontiguousarray(depth.numpy() if _is_torch(depth) else depth, np.float32)
+        if depth is not None:
+            assert tuple(depth.shape) == (self.h, self.w), "the depth map has shape %s, the views are %dx%d" % (tuple(depth.shape), self.w, self.h)
+        res = {}
+        if on_device:
+            import torch
+            assert depth.dtype == torch.float32
+            if "count" in want:
+                res["count"] = torch.empty((self.h, self.w), dtype=torch.uint8, device=depth.device)
+            if "depth" in want:
+                res["depth"] = torch.empty((self.h, self.w), dtype=torch.float32, device=depth.device)
+        else:
+            if "count" in want:
+                res["count"] = np.empty((self.h, self.w), np.uint8)
+            if "depth" in want:
+                res["depth"] = np.empty((self.h, self.w), np.float32)
+        d, kind = _ptr(depth)
+        self._chk(self.L.tsar_geom_check(self._ctx, d, C.byref(p), _ptr(res.get("count"))[0], _ptr(res.get("depth"))[0], kind))
+        return res
 
     def get_result(self, want=("depth", "normal", "cost", "confid"), pinned=False, out=None):
         """pinned=True: the result arrays are page-locked (tsar_host_alloc), so the D2H copies run at PCIe rate.

@@ -1013,6 +1013,46 @@ extern "C" int tsar_upsample_merge(tsar_ctx* fine, const tsar_ctx* coarse_in) {
     return TSAR_OK;
 }
 
+// ---- the geometric-consistency check on its own (geom_check_kernels.hip) ---------------------------------------------------------
+extern "C" void tsar_default_geom_check_params(tsar_geom_check_params* p) {
+    if (!p) return;
+    p->reproj_error = 2.0f;                // tsar_default_fusion_params' values
+    p->depth_diff = 0.01f;
+    p->min_consistent = 2;
+}
+
+// Reads the map and the term, writes ctx->scale and the caller's outputs: no transition of the plane state (tsar_dev.h) is involved
+extern "C" int tsar_geom_check(tsar_ctx* ctx, const float* depth, const tsar_geom_check_params* p, uint8_t* count_out, float* depth_out, int mem) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (!ctx->hscene.geom_on) return fail(ctx, TSAR_ERR_STATE, "tsar_geom_check: no geometric-consistency term installed (tsar_set_geom_depths supplies the source maps)");
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_check: params is NULL");
+    if (!(p->reproj_error > 0.0f) || !(p->reproj_error <= 1048576.0f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_check: reproj_error must be in (0, 2^20] pixels");
+    if (!(p->depth_diff > 0.0f) || !(p->depth_diff < __builtin_inff())) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_check: depth_diff must be finite and > 0");
+    if (p->min_consistent < 1 || p->min_consistent > 31) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_check: min_consistent must be in 1..31");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_check: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (!depth && !(ctx->have_state && ctx->have_out)) return fail(ctx, TSAR_ERR_STATE, "tsar_geom_check: depth is NULL and the context has no result (call tsar_compute_disp / tsar_fill_textureless first)");
+    const size_t np = (size_t)ctx->w * ctx->h;
+    const float* own = (const float*)ctx->out4 + 3;        // the result plane is (n_world, depth) per pixel
+    if (mem == TSAR_MEM_DEVICE) {
+        TRY(launch_geom_check(ctx, depth ? depth : own, depth ? 1 : 4, p, count_out, depth_out));
+        TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return TSAR_OK;
+    }
+    ScratchScope scratch(ctx);             // host buffers are staged in the context's scratch arena (released after the sync below)
+    TmpIn<float> d(ctx, depth, np, mem, &scratch);
+    int rc = d.rc;
+    uint8_t* dc = nullptr;
+    float* dd = nullptr;
+    if (rc == TSAR_OK && count_out && !(dc = (uint8_t*)scratch.alloc(np))) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
+    if (rc == TSAR_OK && depth_out && !(dd = (float*)scratch.alloc(np * 4))) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
+    if (rc == TSAR_OK) rc = launch_geom_check(ctx, depth ? d.d : own, depth ? 1 : 4, p, dc, dd);
+    if (rc == TSAR_OK && count_out && hipMemcpyAsync(count_out, dc, np, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "D2H failed");
+    if (rc == TSAR_OK && depth_out && hipMemcpyAsync(depth_out, dd, np * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "D2H failed");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
+    return rc;
+}
+
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);

@@ -326,6 +326,8 @@ int launch_pm_upsample_lut(tsar_ctx* ctx, bool merge, const float4* coarse, int 
 int launch_pyr_down(tsar_ctx* ctx, const float* src, int w, int h, void* dst, bool u8);        // tsar_pyramid.hip
 int launch_geom_pyramid(tsar_ctx* ctx, const float* src, int w, int h, float* dst);            // tsar_pyramid.hip
 int launch_pyramid_planes(tsar_ctx* ctx, const float4* src, int w, int h, float4* dst);        // tsar_pyramid.hip
+int launch_geom_check(tsar_ctx* ctx, const float* depth, int depth_stride, const tsar_geom_check_params* p, uint8_t* count_out,
+                      float* depth_out);                                                       // geom_check_kernels.hip (writes ctx->scale)
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world);
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);

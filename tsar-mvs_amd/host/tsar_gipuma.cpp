@@ -26,6 +26,14 @@
 //                      run at the coarsest, then each finer level merges the coarser planes into its own (tsar_upsample_merge) and runs
 //                      --geom_iterations iterations; each worker keeps its coarse contexts across views; TSAR_geom.txt gains a line
 //                      with the two settings when L >= 1.  L = 0: the single-scale pass above
+//   --all --consistency_filter[=K (2)] [--filter_reproj_error=PX (2)] [--filter_depth_diff=REL (0.01)]   a last phase after the matching
+//                      phases, before --fuse: each view's depth map of the phase that ran last (TSAR_geom_disp.dmb with
+//                      --geom_consistency, else TSAR_disp.dmb) is checked against its pair.txt sources' maps of the same phase
+//                      (include/tsar.h tsar_geom_check: the maps are installed with weight 0); a pixel is kept when at least K sources
+//                      confirm it.  Writes TSAR_filtered_disp.dmb (0 where dropped), TSAR_consistent.png (8-bit gray, 255 where kept:
+//                      read_reliable_mask / --check-mask= decode it to exactly the mask, so it can serve as a weak.png) and
+//                      TSAR_filter.txt (the settings and the maps checked); resumed only when that record matches and no input map is
+//                      newer than the outputs.  --fuse fuses what it fuses without the switch
 //   --all resumes: a view whose APD/<id>/TSAR_disp.dmb and TSAR_normals.dmb are complete (the reference's header, main.cpp:1817-1860 /
 //                      fileIoUtils.h:333-381, and exactly h*w*nb floats behind it) is skipped — the output files are the per-view
 //                      checkpoints; --force recomputes.  A view that fails on one GPU is retried once on the next
@@ -85,6 +93,9 @@ struct Options {
     int geom_multi_scale = 0, geom_coarse_iterations = -1;   // --geom_multi_scale / --geom_coarse_iterations (-1: --geom_iterations)
     bool geom_coarse_iterations_set = false;
     float geom_weight = 0.2f, geom_clip = 3.0f;      // ACMM's lambda and tau (include/tsar.h tsar_set_geom_depths)
+    bool filter = false;                             // --consistency_filter[=K]: the last phase of --all (run_filter_view)
+    bool filter_option_set = false;                  // a --filter_* switch was given
+    tsar_geom_check_params check{};                  // K, --filter_reproj_error, --filter_depth_diff (include/tsar.h tsar_geom_check)
 };
 
 #include "tsar_io.h"
@@ -182,7 +193,9 @@ static void usage() {
            "                   [--multi_scale=L [--coarse_iterations=N] [--textureless_merge]]\n"
            "       tsar_gipuma --all [--gpus=N] [--force] [--fuse [--num_consistent=N --reproj_error=PX --depth_diff=REL --angle=DEG --used_list=0|1]]\n"
            "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX] [--geom_multi_scale=L [--geom_coarse_iterations=N]]]\n"
-           "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n");
+           "                   [--consistency_filter[=K] [--filter_reproj_error=PX] [--filter_depth_diff=REL]]\n"
+           "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n"
+           "       tsar_gipuma --check-mask=MASK.png | --encode-mask=DEPTH.dmb:MASK.png | --decode-image=IN[:OUT.pgm]     (no GPU)\n");
 }
 
 static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946: same spellings, unknown options only warn
@@ -234,6 +247,19 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
             printf("mask %d x %d reliable %zu checksum %zu\n", mw, mh, ones, wsum);
             return 1;
         }
+        else if (starts("--encode-mask=")) {         // diagnostics, no GPU: the mask of a filtered depth map (kept = depth > 0) the way --consistency_filter writes TSAR_consistent.png
+            std::string in = a + 14, out;
+            const size_t colon = in.rfind(':');
+            if (colon != std::string::npos) { out = in.substr(colon + 1); in = in.substr(0, colon); }
+            std::vector<float> depth;
+            int dh = 0, dw = 0, dnb = 0;
+            if (out.empty() || !read_dmb(in, depth, dh, dw, dnb) || dnb != 1) { printf("cannot read %s as a depth map (--encode-mask=DEPTH.dmb:MASK.png)\n", in.c_str()); return -1; }
+            size_t ones = 0;
+            for (float& d : depth) { d = d > 0.0f ? 1.0f : 0.0f; ones += d == 1.0f; }
+            if (!write_mask_png(out, depth.data(), dw, dh)) { printf("cannot write %s\n", out.c_str()); return -1; }
+            printf("mask %d x %d reliable %zu -> %s\n", dw, dh, ones, out.c_str());
+            return 1;
+        }
         else if (starts("--decode-image=")) {        // no GPU: decode an image the way a run would, --decode-image=IN[:OUT.pgm] [-color_processing first]
             std::string in = a + 15, out;
             const size_t colon = in.rfind(':');
@@ -257,6 +283,16 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
         else if (starts("--geom_iterations=")) o.geom_iterations = atoi(a + 18);
         else if (starts("--geom_weight=")) o.geom_weight = (float)atof(a + 14);
         else if (starts("--geom_clip=")) o.geom_clip = (float)atof(a + 12);
+        else if (!strcmp(a, "--consistency_filter")) o.filter = true;
+        else if (starts("--consistency_filter=")) {
+            char* end = nullptr;
+            const long k = strtol(a + 21, &end, 10);
+            if (!a[21] || *end || k < 1 || k > 31) { printf("Command-line parameter error: --consistency_filter=K must be an integer in 1..31\n"); return -1; }
+            o.filter = true;
+            o.check.min_consistent = (int)k;
+        }
+        else if (starts("--filter_reproj_error=")) { o.check.reproj_error = (float)atof(a + 22); o.filter_option_set = true; }
+        else if (starts("--filter_depth_diff=")) { o.check.depth_diff = (float)atof(a + 20); o.filter_option_set = true; }
         else if (!strcmp(a, "--fuse")) o.fuse = true;
         else if (!strcmp(a, "--force")) o.force = true;                        // --all: recompute views whose outputs are already there
         else if (starts("--num_consistent=")) o.fusion.num_consistent = atoi(a + 17);
@@ -429,20 +465,36 @@ static std::string geom_record_of(const Options& o) {
     }
     return rec;
 }
+// the filter phase: the maps it checks are those of the matching phase that ran last
+static const char* const FILTER_DEPTH = "TSAR_filtered_disp.dmb";
+static const char* const FILTER_MASK = "TSAR_consistent.png";
+static const char* const FILTER_RECORD = "TSAR_filter.txt";
+static const MapFiles& filter_input_files(const Options& o) { return o.geom ? GEOM_FILES : PHASE1_FILES; }
+static std::string filter_record_of(const Options& o, const std::vector<int>& srcs) {
+    char b[256];
+    snprintf(b, sizeof b, "min_consistent=%d reproj_error=%.9g depth_diff=%.9g cam_scale=%.9g checked=%s sources=", o.check.min_consistent,
+             (double)o.check.reproj_error, (double)o.check.depth_diff, (double)o.cam_scale, filter_input_files(o).depth);
+    std::string rec = b;
+    for (size_t i = 0; i < srcs.size(); i++) rec += (i ? "," : "") + id8(srcs[i]);
+    return rec + "\n";
+}
+static std::string read_text_file(const std::string& path) {          // (no file reads as empty)
+    std::string txt;
+    if (FILE* fp = fopen(path.c_str(), "r")) {
+        char b[512];
+        size_t k;
+        while ((k = fread(b, 1, sizeof b, fp)) > 0) txt.append(b, k);
+        fclose(fp);
+    }
+    return txt;
+}
 // both maps complete for the size of the view's reference image, and a record that reads exactly `record` (no file reads as empty)
 static bool maps_current(const Options& o, int ref, const MapFiles& f, const std::string& record) {
     int w = 0, h = 0;
     if (!view_image_size(view_image_of(o, ref), w, h)) return false;
     const std::string d = view_dir_of(o, ref);
     if (!dmb_complete(d + f.depth, h, w, 1) || !dmb_complete(d + f.normal, h, w, 3)) return false;
-    std::string rec;
-    if (FILE* fp = fopen((d + f.record).c_str(), "r")) {
-        char b[512];
-        size_t k;
-        while ((k = fread(b, 1, sizeof b, fp)) > 0) rec.append(b, k);
-        fclose(fp);
-    }
-    return rec == record;
+    return read_text_file(d + f.record) == record;
 }
 // the two maps side by side (a write is a copy into the page cache), under their record: the record goes first and comes back
 // last, so maps that are being replaced never carry the record of other settings.  An empty record: none is written.
@@ -482,24 +534,41 @@ static bool geom_outputs_current(const Options& o, int ref, const std::vector<in
     return true;
 }
 
+// resume of the filter phase: the filtered map complete, the mask there, the record of this run's settings and maps, and no input map
+// (the view's own, its sources') newer than the older of the two outputs
+static bool filter_outputs_current(const Options& o, int ref, const std::vector<int>& srcs) {
+    int w = 0, h = 0;
+    if (!view_image_size(view_image_of(o, ref), w, h)) return false;
+    const std::string d = view_dir_of(o, ref);
+    if (!dmb_complete(d + FILTER_DEPTH, h, w, 1) || read_text_file(d + FILTER_RECORD) != filter_record_of(o, srcs)) return false;
+    struct timespec t1, t2, ti;
+    if (!mtime_of(d + FILTER_DEPTH, t1) || !mtime_of(d + FILTER_MASK, t2)) return false;
+    const struct timespec out = newer(t1, t2) ? t2 : t1;
+    std::vector<std::string> inputs = {d + filter_input_files(o).depth};
+    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + filter_input_files(o).depth);
+    for (const std::string& in : inputs)
+        if (!mtime_of(in, ti) || newer(ti, out)) return false;
+    return true;
+}
+
 // The GPU state of one pool thread of --all (or of a one-view process), kept across its views: its context and, coarse to fine, the
 // contexts of the coarser levels (device planes are allocated once); two page-locked result sets its views alternate between (the
 // .dmb files of view k are written by a helper thread while the kernels of view k+1 run: file output is ~0.1 s of a 0.5 s view at
 // ETH3D size); and phase 1's ring of external inputs read ahead.
 struct Worker {
     const int device;
-    const bool geom;                   // phase 2: its messages say so
+    const char* const phase;           // null: phase 1; "geom" / "filter": the later phases, whose messages say so
     const bool resident;               // --all: images stay resident on the device across views (a one-view process would only hold every image twice)
     tsar_ctx* ctx = nullptr;
     std::vector<tsar_ctx*> coarse;     // the coarser levels, finest first (level(1) = coarse[0])
     HostResult result[2];
     std::future<void> writing[2];      // after `result`: a pending write is joined before its set is released
     std::vector<ExternalInputs> ring;
-    Worker(int device, bool geom, bool resident) : device(device), geom(geom), resident(resident) {}
+    Worker(int device, const char* phase, bool resident) : device(device), phase(phase), resident(resident) {}
     ~Worker() { drop(); }
     tsar_ctx* level(int k) const { return k ? coarse[k - 1] : ctx; }     // 0: full resolution
     int create_failed(int rc) const {
-        if (geom) fprintf(stderr, "tsar_create(device %d) failed\n", device);
+        if (phase) fprintf(stderr, "tsar_create(device %d) failed\n", device);
         else fprintf(stderr, "tsar_create(device %d) failed: %d\n", device, rc);
         return rc;
     }
@@ -520,7 +589,7 @@ struct Worker {
     }
     int fail(int ref, const char* what, tsar_ctx* c = nullptr) const {   // a library call of view `ref` failed on c (default: ctx)
         const char* err = tsar_last_error(c ? c : ctx);
-        if (geom) fprintf(stderr, "view %08d (geom): %s: %s\n", ref, what, err);
+        if (phase) fprintf(stderr, "view %08d (%s): %s: %s\n", ref, phase, what, err);
         else fprintf(stderr, "%s: %s\n", what, err);
         return -1;
     }
@@ -844,6 +913,55 @@ static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vecto
     return ok ? 0 : -1;
 }
 
+// The filter phase of one view (--consistency_filter): its depth map of the matching phase that ran last is checked against its
+// pair.txt sources' maps of that phase (tsar_geom_check; the maps are installed as a term of weight 0, which only the check reads), and
+// TSAR_filtered_disp.dmb + TSAR_consistent.png are written under TSAR_filter.txt, the settings and maps they were made with.
+static int run_filter_view(const Options& o, Worker& wk, int ref, const std::vector<int>& srcs, double* seconds) {
+    const auto t0 = std::chrono::steady_clock::now();
+    ViewSet v;
+    if (const int rc = load_views(o, wk, names_of(ref, srcs), v)) return rc;
+    const int n = (int)v.cams.size(), w = v.w, h = v.h;
+    const MapFiles& in = filter_input_files(o);
+    const std::string d = view_dir_of(o, ref);
+    auto read_map = [&](const std::string& path, std::vector<float>& out) {
+        int hh = 0, ww = 0, nn = 0;
+        if (read_dmb(path, out, hh, ww, nn) && hh == h && ww == w && nn == 1) return true;
+        fprintf(stderr, "cannot read %s\n", path.c_str());
+        return false;
+    };
+    std::vector<float> own_d;
+    std::vector<std::vector<float>> src_d(n);
+    if (!read_map(d + in.depth, own_d)) return -1;
+    std::vector<const float*> maps(n, nullptr);
+    for (int i = 1; i < n; i++) {
+        if (!read_map(view_dir_of(o, srcs[i - 1]) + in.depth, src_d[i])) return -1;
+        maps[i] = src_d[i].data();
+    }
+    tsar_ctx* const ctx = wk.ctx;
+    auto fail = [&](const char* what) { return wk.fail(ref, what); };
+    const tsar_params p = params_of(o, ref, v.dmin, v.dmax);
+    if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
+    if (tsar_set_views_u8(ctx, n, w, h, v.px.data(), v.mem, v.cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
+    if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, 0.0f, 3.0f) != TSAR_OK) return fail("tsar_set_geom_depths");
+    std::vector<float> filtered((size_t)w * h), mask((size_t)w * h);
+    if (tsar_geom_check(ctx, own_d.data(), &o.check, nullptr, filtered.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_geom_check");
+    if (tsar_get_reliable_mask(ctx, mask.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_reliable_mask");
+    if (tsar_clear_geom(ctx) != TSAR_OK) return fail("tsar_clear_geom");
+    // the record goes first and comes back last, so outputs that are being replaced never carry the record of other settings
+    unlink((d + FILTER_RECORD).c_str());
+    bool ok = write_dmb(d + FILTER_DEPTH, filtered.data(), h, w, 1) && write_mask_png(d + FILTER_MASK, mask.data(), w, h);
+    if (ok) {
+        FILE* fp = fopen((d + FILTER_RECORD).c_str(), "w");
+        ok = fp && fputs(filter_record_of(o, srcs).c_str(), fp) >= 0;
+        if (fp && fclose(fp) != 0) ok = false;
+    }
+    size_t kept = 0;
+    for (float m : mask) kept += m == 1.0f;
+    if (ok) printf("view %08d (filter): %zu of %zu pixels of %s kept\n", ref, kept, mask.size(), in.depth);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return ok ? 0 : -1;
+}
+
 // One phase of --all over every view of pair.txt, dealt round-robin to nthr threads (every view of a scene costs the same); thread t
 // drives GPU t % ngpu with a worker of its own and calls view(worker, k, turn, &seconds) for each view k it is dealt that is not
 // skipped (turn: the thread's count of views dealt so far).  A worker drops its contexts after a failed view.  A view that failed
@@ -851,39 +969,40 @@ static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vecto
 // destroyed with the view (turn -1) — never the contexts the failure left behind.  Returns each view's status; a skipped view's is
 // what skipped(worker, k) returns (0 without it).
 typedef std::function<int(Worker&, size_t k, int turn, double* seconds)> ViewFn;
-static std::vector<int> run_pool(const Options& o, bool geom, const std::vector<int>& refs, const std::vector<char>& skip, int nthr,
+static std::vector<int> run_pool(const Options& o, const char* phase, const std::vector<int>& refs, const std::vector<char>& skip, int nthr,
                                  const ViewFn& view, const std::function<int(Worker&, size_t k)>& skipped = nullptr) {
     const int ngpu = std::max(1, o.gpus);
     std::vector<int> rc(refs.size(), 0), gpu_of(refs.size(), 0);
+    const std::string label = phase ? std::string(" (") + phase + ")" : "";
     std::vector<std::thread> th;
     for (int t = 0; t < nthr; t++)
         th.emplace_back([&, t]() {
-            Worker wk(t % ngpu, geom, true);
+            Worker wk(t % ngpu, phase, true);
             int turn = 0;
             for (size_t k = t; k < refs.size(); k += nthr, turn++) {
                 gpu_of[k] = wk.device;
                 if (skip[k]) {
-                    printf("view %08d: %soutputs present, skipped\n", refs[k], geom ? "geom " : "");
+                    printf("view %08d: %s%soutputs present, skipped\n", refs[k], phase ? phase : "", phase ? " " : "");
                     if (skipped) rc[k] = skipped(wk, k);
                     continue;
                 }
                 double sec = 0;
                 rc[k] = view(wk, k, turn, &sec);
                 if (rc[k] != 0) wk.drop();
-                printf("view %08d on gpu %d%s: %s (%.2f s)\n", refs[k], wk.device, geom ? " (geom)" : "", rc[k] == 0 ? "ok" : "FAILED", sec);
+                printf("view %08d on gpu %d%s: %s (%.2f s)\n", refs[k], wk.device, label.c_str(), rc[k] == 0 ? "ok" : "FAILED", sec);
             }
         });
     for (auto& t : th) t.join();
     for (size_t k = 0; k < refs.size(); k++) {
         if (skip[k] || rc[k] == 0) continue;
         const int g2 = (gpu_of[k] + 1) % ngpu;
-        if (!geom) printf("view %08d FAILED on gpu %d: retrying once on gpu %d with a fresh context\n", refs[k], gpu_of[k], g2);
+        if (!phase) printf("view %08d FAILED on gpu %d: retrying once on gpu %d with a fresh context\n", refs[k], gpu_of[k], g2);
         double sec = 0;
         {
-            Worker fresh(g2, geom, true);
+            Worker fresh(g2, phase, true);
             rc[k] = view(fresh, k, -1, &sec);
         }
-        printf("view %08d on gpu %d (%sretry): %s (%.2f s)\n", refs[k], g2, geom ? "geom, " : "", rc[k] == 0 ? "ok" : "FAILED", sec);
+        printf("view %08d on gpu %d (%s%sretry): %s (%.2f s)\n", refs[k], g2, phase ? phase : "", phase ? ", " : "", rc[k] == 0 ? "ok" : "FAILED", sec);
     }
     return rc;
 }
@@ -951,7 +1070,7 @@ static bool run_phase1(const Options& o, const std::vector<int>& refs, const std
         fprintf(stderr, "view %08d: cannot read its output files back for --fuse\n", refs[k]);
         return -1;
     };
-    const std::vector<int> rc = run_pool(o, false, refs, skip, nthr, view, skipped);
+    const std::vector<int> rc = run_pool(o, nullptr, refs, skip, nthr, view, skipped);
     int missing = 0;
     for (size_t k = 0; k < refs.size(); k++)
         if (rc[k] != 0 || !outputs_complete(o, refs[k])) { fprintf(stderr, "view %08d: outputs missing or incomplete\n", refs[k]); missing++; }
@@ -965,11 +1084,26 @@ static bool run_geom_phase(const Options& o, const std::vector<int>& refs, const
     if (!o.force)
         for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = geom_outputs_current(o, refs[k], pairs.at(refs[k])) ? 1 : 0);
     if (n_skip) printf("geom: resuming: %zu of %zu views have current TSAR_geom_disp.dmb / TSAR_geom_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
-    const std::vector<int> rc = run_pool(o, true, refs, skip, std::max(1, o.gpus),
+    const std::vector<int> rc = run_pool(o, "geom", refs, skip, std::max(1, o.gpus),
                                          [&](Worker& wk, size_t k, int, double* sec) { return run_geom_view(o, wk, refs[k], pairs.at(refs[k]), sec); });
     int missing = 0;
     for (size_t k = 0; k < refs.size(); k++)
         if (rc[k] != 0) { fprintf(stderr, "view %08d: geom outputs missing\n", refs[k]); missing++; }
+    return missing == 0;
+}
+
+// --all --consistency_filter: the filter phase over every view, one worker per GPU.  False when a view has no current filter outputs.
+static bool run_filter_phase(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs) {
+    std::vector<char> skip(refs.size(), 0);
+    size_t n_skip = 0;
+    if (!o.force)
+        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = filter_outputs_current(o, refs[k], pairs.at(refs[k])) ? 1 : 0);
+    if (n_skip) printf("filter: resuming: %zu of %zu views have current TSAR_filtered_disp.dmb / TSAR_consistent.png and are skipped (--force recomputes them)\n", n_skip, refs.size());
+    const std::vector<int> rc = run_pool(o, "filter", refs, skip, std::max(1, o.gpus),
+                                         [&](Worker& wk, size_t k, int, double* sec) { return run_filter_view(o, wk, refs[k], pairs.at(refs[k]), sec); });
+    int missing = 0;
+    for (size_t k = 0; k < refs.size(); k++)
+        if (rc[k] != 0) { fprintf(stderr, "view %08d: filter outputs missing\n", refs[k]); missing++; }
     return missing == 0;
 }
 
@@ -1040,7 +1174,8 @@ static int fuse_views(const Options& o, const std::vector<int>& refs, const std:
     return 0;
 }
 
-// --all: phase 1, then phase 2 once every view has its phase-1 maps (it reads them from the files), then --fuse
+// --all: phase 1, then phase 2 once every view has its phase-1 maps (it reads them from the files), then the filter phase over the
+// maps of whichever ran last (while the images are still resident on the devices), then --fuse
 static int run_all(const Options& o, const std::map<int, std::vector<int>>& pairs) {
     g_pin_results = true;
     std::vector<int> refs;
@@ -1048,6 +1183,7 @@ static int run_all(const Options& o, const std::map<int, std::vector<int>>& pair
     std::vector<DeviceResult> kept(o.fuse ? refs.size() : 0);
     bool ok = run_phase1(o, refs, pairs, kept);
     if (ok && o.geom) ok = run_geom_phase(o, refs, pairs);
+    if (ok && o.filter) ok = run_filter_phase(o, refs, pairs);
     g_device_images.release();
     if (!ok) return 1;
     if (o.geom && o.fuse)        // --fuse fuses the geom maps: they replace the phase-1 maps kept on each view's device
@@ -1076,6 +1212,16 @@ static bool options_valid(const Options& o) {
         if (o.mode == "tsar") { fprintf(stderr, "--geom_consistency does not work with --mode=tsar\n"); return false; }
         if (o.geom_iterations < 0 || !(o.geom_weight >= 0.f) || !(o.geom_clip > 0.f)) { fprintf(stderr, "--geom_iterations must be >= 0, --geom_weight >= 0, --geom_clip > 0\n"); return false; }
     }
+    if (o.filter_option_set && !o.filter) { fprintf(stderr, "--filter_reproj_error / --filter_depth_diff work with --consistency_filter only\n"); return false; }
+    if (o.filter) {
+        if (!o.all) { fprintf(stderr, "--consistency_filter needs --all (the filter reads every view's depth map)\n"); return false; }
+        if (o.mode != "patchmatch") { fprintf(stderr, "--consistency_filter does not work with --mode=tsar or --mode=load\n"); return false; }
+        const tsar_geom_check_params& c = o.check;
+        if (c.min_consistent < 1 || c.min_consistent > 31 || !(c.reproj_error > 0.f) || !(c.reproj_error <= 1048576.f) || !(c.depth_diff > 0.f) || !(c.depth_diff < INFINITY)) {
+            fprintf(stderr, "--consistency_filter=K must be in 1..31, --filter_reproj_error in (0, 2^20] pixels, --filter_depth_diff finite and > 0\n");
+            return false;
+        }
+    }
     return true;
 }
 
@@ -1083,6 +1229,7 @@ int main(int argc, char** argv) {
     const double ms_exec_to_main = ms_since_exec();
     Options o;
     tsar_default_fusion_params(&o.fusion);
+    tsar_default_geom_check_params(&o.check);
     const int pr = parse_args(argc, argv, o);
     if (pr != 0) return pr < 0 ? 1 : 0;
     if (!options_valid(o)) return 1;
@@ -1107,7 +1254,7 @@ int main(int argc, char** argv) {
     // one view per process (the reference's shell loop): the context and the buffers stay alive until the process ends, and the
     // process ends without tearing them down one by one — the files are on disk, the driver reclaims the rest (0.25 s of a 1.4 s
     // invocation at ETH3D size went into freeing 1.5 GB of host buffers, the context and the runtime's own shutdown)
-    static Worker single(0, false, false);
+    static Worker single(0, nullptr, false);
     const int rc = run_view(o, single, o.images, slots, camera_id, &sec, single.result[0]);
     printf("Total runtime including disk i/o: %gsec\n", sec);
     if (o.timing) printf("process (ms since exec, 10 ms resolution): main entered at %.0f, leaving at %.0f (what the caller waits for beyond that is the teardown of the process's GPU state by the driver)\n",

@@ -331,6 +331,38 @@ static inline bool read_reliable_mask(const std::string& path, std::vector<float
     return true;
 }
 
+// TSAR_consistent.png: a reliability mask (lines->scale) as an 8-bit gray PNG, 255 where scale == 1 and 0 elsewhere — white is one of
+// the colours read_reliable_mask takes as reliable, so the file decodes to exactly the mask and can serve as a weak.png
+static inline bool write_mask_png(const std::string& path, const float* scale, int w, int h) {
+    std::vector<unsigned char> raw((size_t)h * (1 + (size_t)w));
+    for (int y = 0; y < h; y++) {
+        unsigned char* row = &raw[(size_t)y * (1 + (size_t)w)];
+        row[0] = 0;                                          // filter type none
+        for (int x = 0; x < w; x++) row[1 + x] = scale[(size_t)y * w + x] == 1.0f ? 255 : 0;
+    }
+    uLongf clen = compressBound((uLong)raw.size());
+    std::vector<unsigned char> comp(clen);
+    if (compress2(comp.data(), &clen, raw.data(), (uLong)raw.size(), 1) != Z_OK) return false;
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    auto chunk = [&](const char* tag, const unsigned char* data, uint32_t len) {
+        unsigned char hdr[8] = {(unsigned char)(len >> 24), (unsigned char)(len >> 16), (unsigned char)(len >> 8), (unsigned char)len, (unsigned char)tag[0], (unsigned char)tag[1], (unsigned char)tag[2], (unsigned char)tag[3]};
+        fwrite(hdr, 1, 8, f);
+        if (len) fwrite(data, 1, len, f);
+        uLong crc = crc32(0L, hdr + 4, 4);
+        if (len) crc = crc32(crc, data, len);
+        const unsigned char c[4] = {(unsigned char)(crc >> 24), (unsigned char)(crc >> 16), (unsigned char)(crc >> 8), (unsigned char)crc};
+        fwrite(c, 1, 4, f);
+    };
+    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    fwrite(sig, 1, 8, f);
+    const unsigned char ihdr[13] = {(unsigned char)(w >> 24), (unsigned char)(w >> 16), (unsigned char)(w >> 8), (unsigned char)w, (unsigned char)(h >> 24), (unsigned char)(h >> 16), (unsigned char)(h >> 8), (unsigned char)h, 8, 0, 0, 0, 0};
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", comp.data(), (uint32_t)clen);
+    chunk("IEND", nullptr, 0);
+    return fclose(f) == 0;
+}
+
 // fused cloud, binary little-endian: x y z nx ny nz red green blue per point (records of 9 floats from tsar_fuse)
 static bool write_cloud_ply(const std::string& path, const float* pts, int64_t n) {
     FILE* f = fopen(path.c_str(), "wb");
