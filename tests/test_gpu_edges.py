@@ -193,7 +193,7 @@ def test_perspective_divide_at_the_operand_guard(strict):
     m.close()
 
 
-# ---- the fast path's clamp-free decision from the window's centre and a bound on its extent (pm_tap_r5.h:52-71) -------------------
+# ---- the fast path's clamp-free decision from the window's centre and a bound on its extent (pm_tap_r5.h view_cost_r5, the !STRICT branch) -------------------
 def _rot(yaw, pitch, roll):
     cy, sy, cp, sp, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
     Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
@@ -214,7 +214,7 @@ def _scene_rotated():
 
 
 def _centre_extent_margins(Hm):
-    """the decision of pm_tap_r5.h:52-71 restated in numpy (fp32): per pixel, the four distances by which the window bound clears
+    """the decision of pm_tap_r5.h (view_cost_r5, the !STRICT branch) restated in numpy (fp32): per pixel, the four distances by which the window bound clears
     (>= 0) or misses (< 0) the source image's clamp-free region; H is the 3x3 plane homography of one view"""
     f32 = np.float32
     Hm = np.asarray(Hm, f32).ravel()

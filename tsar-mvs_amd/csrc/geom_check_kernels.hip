@@ -10,7 +10,7 @@
 // (persp_divide_exact's correctly rounded quotients, no contraction: -ffp-contract=off and no fma_ here).
 #include "tsar_device_math.h"
 
-// the maps are HBM pointers by construction (pm_core.h says why that is worth saying): the loads become global_load
+// the maps are HBM pointers by construction (pm_tap_common.h says why that is worth saying): the loads become global_load
 typedef const float __attribute__((address_space(1)))* gc_f32_ptr;
 
 #define GC_BLOCK 256      // 64 x 4 pixels

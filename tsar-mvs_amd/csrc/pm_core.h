@@ -1,5 +1,7 @@
-// pm_core.h — the matching cost and the per-pixel PatchMatch step, shared by the init / sweep /
-// cost-evaluation kernels (pm_init.hip, pm_sweep.hip).
+// pm_core.h — the matching cost and the per-pixel PatchMatch step, shared by the init / sweep / upsampling /
+// cost-evaluation kernels (pm_init_impl.h, pm_sweep_impl.h, pm_upsample_impl.h).  The cost of one view is one of three tap loops —
+// view_cost_generic here, view_cost_r5 (pm_tap_r5.h), view_cost_lut (pm_core_lut.h) — built from the per-tap pieces of
+// pm_tap_common.h; multiview_cost combines the views.
 //
 // Mapping (MI355X-first): one thread owns one pixel and walks its hypotheses; a
 // 256-thread workgroup owns a 32-wide pixel region.  Per workgroup, once per launch:
@@ -22,11 +24,7 @@
 #define PM_BLOCK 256
 #define PM_RW 32  // region width in pixels (all kernels)
 
-// Image pointers come out of the DevScene table in memory, so the compiler only knows them as generic
-// ("flat") pointers; flat loads count on both vmcnt and lgkmcnt and serialise against the LDS reads of
-// the tap loop.  They are HBM pointers by construction: say so, and the gathers become global_load.
-typedef const uint32_t __attribute__((address_space(1)))* global_u32_ptr;
-typedef const float __attribute__((address_space(1)))* global_f32_ptr;
+#include "pm_tap_common.h"   // the per-tap pieces every tap loop below is made of
 
 // DIFF (fast arithmetic only, oracle S7 (6)): the blend as (t00 + ax d1) + ay (d2 + ax d3) over the texel differences
 template <bool QUAD, bool DIFF = false>
@@ -54,22 +52,8 @@ DEVFN float sample_bilinear(const DevView& vw, int w, int h, int qpitch, float u
         const global_f32_ptr r1 = (global_f32_ptr)vw.img + (size_t)y1 * w;
         t00 = r0[x0]; t10 = r0[x1]; t01 = r1[x0]; t11 = r1[x1];
     }
-    if (DIFF) {
-        const float d1 = t10 - t00, d2 = t01 - t00, d3 = (t11 - t01) - d1;
-        return fma_(ay, fma_(ax, d3, d2), fma_(ax, d1, t00));
-    }
-    const float top = fma_(ax, t10 - t00, t00);
-    const float bot = fma_(ax, t11 - t01, t01);
-    return fma_(ay, bot - top, top);
+    return blend_texels<DIFF>(t00, t10, t01, t11, ax, ay);
 }
-
-// Per-pixel quantities that do not depend on the hypothesis.
-struct PixelRef {
-    float inv_wsum;   // 1 / sum(w)
-    float mean_ref;   // sum(w r) / sum(w)
-    float var_ref;    // E[r^2] - E[r]^2
-    bool textured;    // var_ref >= kMinVar
-};
 
 // Stage the reference window of this workgroup's region in LDS.  tile is (RW + 2hr) x (RH + 2vr).
 // Reference-window texel type: 8-bit imagery (QUAD path) keeps the window as 16-bit entries holding the upper half
@@ -124,14 +108,7 @@ DEVFN PixelRef hoist_reference(const TileT* tile, int tw, int own, float* wts, i
             ++tap;
         }
     }
-    PixelRef pr;
-    pr.inv_wsum = 1.0f / wsum;
-    sum_ref *= pr.inv_wsum;
-    sum_ref_ref *= pr.inv_wsum;
-    pr.mean_ref = sum_ref;
-    pr.var_ref = sum_ref_ref - sum_ref * sum_ref;
-    pr.textured = !(pr.var_ref < 1e-5f);
-    return pr;
+    return pixel_ref_from_sums(sum_ref, sum_ref_ref, 1.0f / wsum);
 }
 
 // pmCost gipuma.cu:229-298 for one source view, given the hoisted reference terms: any window, both arithmetic modes, float or
@@ -150,35 +127,22 @@ DEVFN float view_cost_generic(const DevScene* __restrict__ sc, const DevView& vw
     int tap = 0;
 #pragma unroll 1
     for (int i = -hr; i <= hr; i += 2) {
-        const float xi = (float)(x + i);
-        // getCorrespondingPoint_cu gipuma.cu:161-171 (matvecmul4noz, config.h:150-162): (m[0] x + m[1] y) + m[2] — strict mode keeps the
-        // text's association, the constant added LAST (oracle S4: mul, fma, add); the fast arithmetic folds it into the column term
-        // (oracle S7 (7): two fused operations per coordinate)
-        const float bx = STRICT ? H[0] * xi : fma_(H[0], xi, H[2]), by = STRICT ? H[3] * xi : fma_(H[3], xi, H[5]), bz = STRICT ? H[6] * xi : fma_(H[6], xi, H[8]);
+        float bx, by, bz;
+        tap_line_base<STRICT>(H, (float)(x + i), bx, by, bz);
 #pragma unroll
         for (int j = -vr; j <= vr; j += 2) {
-            const float yj = (float)(y + j);
-            float X = fma_(H[1], yj, bx), Y = fma_(H[4], yj, by), Z = fma_(H[7], yj, bz);
-            if (STRICT) { X += H[2]; Y += H[5]; Z += H[8]; }
-            float u, v;
-            if (STRICT) {
-                persp_divide_exact<true>(X, Y, Z, u, v);         // = X / Z, Y / Z bit for bit (tsar_device_math.h)
-            } else {
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                u = X * rz;
-                v = Y * rz;
-            }
+            float X, Y, Z, u, v;
+            tap_homogeneous<STRICT>(H, (float)(y + j), bx, by, bz, X, Y, Z);
+            tap_divide<STRICT, true>(X, Y, Z, u, v);
             const float s = sample_bilinear<QUAD, !STRICT>(vw, w, h, qp, u, v, (sc->flags & TSAR_FLAG_TEX_FILTER_8BIT) != 0);
             const float r = tile_value(tile[own + j * tw + i]);
             const float wt = wts[tap * BLK];
-            const float ws = wt * s;
-            sum_src += ws;
-            sum_src_src = fma_(ws, s, sum_src_src);
-            if (STRICT) sum_ref_src = fma_(wt * r, s, sum_ref_src);      // (w r) s, the oracle's order
-            else sum_ref_src = fma_(ws, r, sum_ref_src);
+            const TapSums t = tap_accumulate<STRICT>(TapSums{sum_src, sum_src_src, sum_ref_src}, wt, r, s);
+            sum_src = t.src; sum_src_src = t.src_src; sum_ref_src = t.ref_src;
             ++tap;
         }
     }
+    // (the tail of ncc_cost, pm_tap_common.h, with the compiler's sqrtf: float imagery has no bound on the variances)
     sum_src *= pr.inv_wsum;
     sum_src_src *= pr.inv_wsum;
     sum_ref_src *= pr.inv_wsum;

@@ -1,5 +1,5 @@
-// pm_core_lut.h — the matching cost for ANY window (box 1..63, square or not) on 8-bit imagery: the production tap loop of
-// pm_core.h (view_cost, variant 250 / 122) is written for the scripts' box 11; every other box — the reference binary's own
+// pm_core_lut.h — the matching cost for ANY window (box 1..63, square or not) on 8-bit imagery: the production tap loop
+// (view_cost_r5, pm_tap_r5.h) is written for the scripts' box 11; every other box — the reference binary's own
 // default is 19 (algorithmparameters.h:25) — used to fall to a one-tap-at-a-time loop whose S hoisted weights per thread
 // (100 KiB of LDS per workgroup at box 19) left one wave per SIMD.  Included by pm_core.h.
 //
@@ -56,14 +56,7 @@ DEVFN PixelRef hoist_reference_lut(const DevScene* __restrict__ sc, const unsign
             wsum += wt;
         }
     }
-    PixelRef pr;
-    pr.inv_wsum = 1.0f / wsum;
-    sum_ref *= pr.inv_wsum;
-    sum_ref_ref *= pr.inv_wsum;
-    pr.mean_ref = sum_ref;
-    pr.var_ref = sum_ref_ref - sum_ref * sum_ref;
-    pr.textured = !(pr.var_ref < 1e-5f);
-    return pr;
+    return pixel_ref_from_sums(sum_ref, sum_ref_ref, 1.0f / wsum);
 }
 
 // pmCost (gipuma.cu:229-298) for one source view, any window, 8-bit quad textures.
@@ -81,7 +74,7 @@ DEVFN void lut_wait_lds(float (&r)[CH], uint32_t after) {
 template <bool STRICT, int CH, bool BUF = false, bool MIX = false>
 DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, const unsigned short* tile, int tw, int own, const float* lut,
                           const PixelRef& pr, int x, int y, const float4& n4) {
-    constexpr bool ROW = !STRICT;                           // fast mode walks window rows (see pm_core.h, variant bit 7)
+    constexpr bool ROW = !STRICT;                           // fast mode walks window rows (pm_tap_r5.h ROW)
     const int hr = sc->hrad, vr = sc->vrad;
     const int rt = ROW ? hr : vr, rl = ROW ? vr : hr;       // radius along / across the lines
     const int w = sc->w, h = sc->h, qp = sc->quad_pitch;
@@ -89,17 +82,17 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
     if (STRICT) plane_homography(sc->ref, vw, n4, H, sc->k_sparse != 0);
     else plane_homography_fast(sc->ref, vw, n4, H);
     // clamp-free loop when the four corner taps of every active lane land inside the source image with Z > 0 and a pixel of
-    // margin (pm_core.h, variant bit 4): wave-uniform, identical results.  In fast mode the padding slots of a row's last chunk
+    // margin (pm_tap_r5.h): wave-uniform, identical results.  In fast mode the padding slots of a row's last chunk
     // are sampled where they fall, beyond the window's right edge: the corners include them.
     const int xr = ROW ? 2 * (sc->lut_pad_taps - 1) - hr : hr;
     bool inside = true;
     float zmin = __builtin_inff(), zmax = 0.0f;
     if (!STRICT) {
-        // fast mode: the decision from the window's centre and a bound on its extent (pm_tap_r5.h): one reciprocal instead of four.
+        // fast mode: the decision from the window's centre and a bound on its extent (derived in pm_tap_r5.h): one reciprocal instead of four.
         // |dx| <= max(hr, xr) (the padding slots reach further right than the window), |dy| <= vr
         const float ex = (float)max(hr, xr), ey = (float)vr;
-        const float xc = (float)x, yc = (float)y;
-        const float Xc = fma_(H[1], yc, fma_(H[0], xc, H[2])), Yc = fma_(H[4], yc, fma_(H[3], xc, H[5])), Zc = fma_(H[7], yc, fma_(H[6], xc, H[8]));
+        float Xc, Yc, Zc;
+        pixel_homogeneous(H, (float)x, (float)y, Xc, Yc, Zc);
         const float a = fma_(ex, fabsf(H[0]), ey * fabsf(H[1])), b = fma_(ex, fabsf(H[3]), ey * fabsf(H[4])), c = fma_(ex, fabsf(H[6]), ey * fabsf(H[7]));
         const float Zmin = Zc - c;
         const float r = __builtin_amdgcn_rcpf(Zmin * Zc);
@@ -110,14 +103,14 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
     } else
 #pragma unroll
     for (int c = 0; c < 4; c++) {
-        const float xi = (float)(x + ((c & 1) ? xr : -hr)), yj = (float)(y + ((c & 2) ? vr : -vr));
-        const float X = fma_(H[1], yj, fma_(H[0], xi, H[2])), Y = fma_(H[4], yj, fma_(H[3], xi, H[5])), Z = fma_(H[7], yj, fma_(H[6], xi, H[8]));
+        float X, Y, Z;
+        pixel_homogeneous(H, (float)(x + ((c & 1) ? xr : -hr)), (float)(y + ((c & 2) ? vr : -vr)), X, Y, Z);
         const float rz = __builtin_amdgcn_rcpf(Z);
         const float u = X * rz, v = Y * rz;
         inside = inside && Z > 0.0f && u >= 1.0f && u <= (float)(w - 2) && v >= 1.0f && v <= (float)(h - 2);
         if (STRICT) { zmin = fminf(zmin, Z); zmax = fmaxf(zmax, Z); }
     }
-    if (STRICT) {       // the clamp-free strict loop runs persp_divide_exact without its per-tap guard: see view_cost (pm_core.h) for the bounds
+    if (STRICT) {       // the clamp-free strict loop runs persp_divide_exact without its per-tap guard: the bounds are proved in pm_tap_r5.h
         const float cm = (float)(max(w, h) + 32);
         const float sz = fma_(fabsf(H[6]) + fabsf(H[7]), cm, fabsf(H[8]));
         const float sx = fma_(fabsf(H[0]) + fabsf(H[1]), cm, fabsf(H[2]));
@@ -125,31 +118,14 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
         inside = inside && zmin >= 3.814697265625e-06f && zmax <= 131072.0f && sz * cm <= 524288.0f * zmin && fmaxf(sx, sy) <= 262144.0f * zmin;
     }
     const bool need_clamp = !__all(inside);
-    // quad-texture base with the border offset folded in, pinned in an SGPR pair for the whole view (pm_core.h, variant bit 6):
-    // offsets are unsigned from entry (1, 1), so positions are clamped to [0, w - 1] x [0, h - 1] — the same samples, bit for
-    // bit, as the oracle's clamp to [-1, w] (edge replication)
-    const uint64_t qa = (uint64_t)(uintptr_t)vw.quad + (uint32_t)((qp + 1) << 2);
-    uint32_t qb_lo = __builtin_amdgcn_readfirstlane((uint32_t)qa), qb_hi = __builtin_amdgcn_readfirstlane((uint32_t)(qa >> 32));
-    asm volatile("" : "+s"(qb_lo), "+s"(qb_hi));
-    // BUF (fast mode, from the second sweep of a run on): the gathers as structured buffer loads through a stride-4 resource
-    // descriptor — see pm_core.h, variant bit 17
-    typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
-    u32x4s rsrc = {0u, 0u, 0u, 0u};
+    // the view's quad texture (pm_tap_common.h): the base pinned for the whole view; BUF (fast mode, from the second sweep of a run on)
+    // / MIX the descriptor of the structured buffer loads
     static_assert(!MIX || (BUF && !STRICT), "the half-float difference texture serves the fast arithmetic's blend through buffer loads");
-    if constexpr (MIX) {                                    // 8-byte entries of the difference texture (pm_tap_r5.h MIX), same pitch and border
-        const uint64_t da = (uint64_t)(uintptr_t)vw.dquad + 2 * (uint64_t)(uint32_t)((qp + 1) << 2);
-        rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)da);
-        rsrc.y = __builtin_amdgcn_readfirstlane(((uint32_t)(da >> 32) & 0xffffu) | (8u << 16));
-        rsrc.z = __builtin_amdgcn_readfirstlane((uint32_t)(qp * (h + 1) - 1));
-        rsrc.w = 0x00020000u;
-        asm volatile("" : "+s"(rsrc));
-    } else if constexpr (BUF) {
-        rsrc.x = qb_lo;
-        rsrc.y = __builtin_amdgcn_readfirstlane((qb_hi & 0xffffu) | (4u << 16));
-        rsrc.z = __builtin_amdgcn_readfirstlane((uint32_t)(qp * (h + 1) - 1));
-        rsrc.w = 0x00020000u;
-        asm volatile("" : "+s"(rsrc));
-    }
+    uint32_t qb_lo, qb_hi;
+    pin_quad_base(quad_origin<false>(vw, quad_border_bytes(qp)), qb_lo, qb_hi);
+    u32x4s rsrc = {0u, 0u, 0u, 0u};
+    if constexpr (MIX) rsrc = quad_descriptor<true>(quad_origin<true>(vw, quad_border_bytes(qp)), h + 1, qp);
+    else if constexpr (BUF) rsrc = quad_descriptor<false>(((uint64_t)qb_hi << 32) | qb_lo, h + 1, qp);
     const float cen = tile_value(tile[own]);
     const float fa = (float)(ROW ? x : y), fl = (float)(ROW ? y : x);
     const float uhi = (float)(w - 1), vhi = (float)(h - 1);
@@ -163,7 +139,7 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
         uint64_t q2[CH];                                    // MIX: the tap's four halfs
         float yj0 = 0.f;
         if constexpr (ROW) {
-            // the chunk's reference texels, each loaded into bits 31:16 of a register = its fp32 value (pm_core.h, variant bit 3);
+            // the chunk's reference texels, each loaded into bits 31:16 of a register = its fp32 value (pm_tap_r5.h D16);
             // the wait for them is lut_wait_lds below, after the gathers are on their way
             const uint32_t a0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned short*)(trow + 2 * c0);
 #pragma unroll
@@ -177,42 +153,14 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
 #pragma unroll
         for (int jj = 0; jj < CH; jj++) {                   // phase 1: tap positions -> byte offsets; phase 2: gathers
             const float yj = ROW ? yj0 + (float)(2 * jj) : fa + (float)(2 * min(c0 + jj, rt) - rt);
-            float X = fma_(H[ROW ? 0 : 1], yj, bx), Y = fma_(H[ROW ? 3 : 4], yj, by), Z = fma_(H[ROW ? 6 : 7], yj, bz);
-            if (STRICT) { X += H[2]; Y += H[5]; Z += H[8]; }      // strict: (m[0] x + m[1] y) + m[2], the constant last (pm_core.h view_cost_generic)
-            float u, v;
-            int iu, iv;
-            if (STRICT) {                                   // the oracle's operations: IEEE divides, min/max clamp, floor / subtract
-                persp_divide_exact<CLAMP>(X, Y, Z, u, v);   // = X / Z, Y / Z bit for bit (tsar_device_math.h); clamp-free: guard shown by the corner test
-                if (CLAMP) {
-                    u = fminf(fmaxf(u, 0.0f), uhi);
-                    v = fminf(fmaxf(v, 0.0f), vhi);
-                }
-                // u, v >= 0 (clamped, or inside the image by the corner test): fract = u - floor(u) exactly
-                ax[jj] = __builtin_amdgcn_fractf(u);
-                ay[jj] = __builtin_amdgcn_fractf(v);
-                asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iu) : "v"(u));
-                asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iv) : "v"(v));
-            } else {
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                u = X * rz;
-                v = Y * rz;
-                if (CLAMP) {
-                    u = __builtin_amdgcn_fmed3f(u, 0.0f, uhi);
-                    v = __builtin_amdgcn_fmed3f(v, 0.0f, vhi);
-                }
-                ax[jj] = __builtin_amdgcn_fractf(u);
-                ay[jj] = __builtin_amdgcn_fractf(v);
-                asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iu) : "v"(u));
-                asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iv) : "v"(v));
-            }
+            float X, Y, Z;
+            tap_homogeneous<STRICT, ROW>(H, yj, bx, by, bz, X, Y, Z);
             int lin;
-            asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(lin) : "v"(iv), "s"(qp), "v"(iu));
-            if constexpr (MIX) {
+            tap_position<STRICT, CLAMP>(X, Y, Z, uhi, vhi, qp, ax[jj], ay[jj], lin);
+            if constexpr (BUF) {
                 off_last = (uint32_t)lin;
-                asm volatile("buffer_load_dwordx2 %0, %1, %2, 0 idxen" : "=v"(q2[jj]) : "v"(lin), "s"(rsrc));
-            } else if constexpr (BUF) {
-                off_last = (uint32_t)lin;
-                asm volatile("buffer_load_dword %0, %1, %2, 0 idxen" : "=v"(q[jj]) : "v"(lin), "s"(rsrc));
+                if constexpr (MIX) q2[jj] = buffer_gather<true>(lin, rsrc);
+                else q[jj] = buffer_gather<false>(lin, rsrc);
             } else {
                 off_last = (uint32_t)lin << 2;
                 q[jj] = *(global_u32_ptr)((const char __attribute__((address_space(1)))*)(uintptr_t)(((uint64_t)qb_hi << 32) | qb_lo) + off_last);
@@ -233,37 +181,17 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int jj = 0; jj < CH; jj++) {                   // phase 3: unpack, blend, accumulate
-            float t00, t10, t01, t11;
             float s;
             if constexpr (MIX) {
                 asm("s_waitcnt vmcnt(%3)" : "+v"(q2[jj]), "+v"(sum_src_src) : "v"(q2[CH - 1]), "n"(CH - 1 - jj));
-                const uint32_t lo = (uint32_t)q2[jj], hi = (uint32_t)(q2[jj] >> 32);
-                float ta, tb;
-                asm("v_fma_mix_f32 %0, %1, %2, %2 op_sel:[0,1,0] op_sel_hi:[0,1,1]" : "=v"(ta) : "v"(ax[jj]), "v"(lo));          // ax * d1 + t00: the top row's interpolation
-                asm("v_fma_mix_f32 %0, %1, %2, %2 op_sel:[0,1,0] op_sel_hi:[0,1,1]" : "=v"(tb) : "v"(ax[jj]), "v"(hi));          // ax * d3 + d2: bottom row minus top row, rounded once
-                s = fma_(ay[jj], tb, ta);
+                s = blend_dquad(q2[jj], ax[jj], ay[jj]);
             } else {
-            if constexpr (BUF)      // the asm-issued gathers return in order: tap jj has CH - 1 - jj behind it (waits chained, pm_core.h)
-                asm("s_waitcnt vmcnt(%3)" : "+v"(q[jj]), "+v"(sum_src_src) : "v"(q[CH - 1]), "n"(CH - 1 - jj));
-            asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00) : "v"(q[jj]));
-            asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t10) : "v"(q[jj]));
-            asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(t01) : "v"(q[jj]));
-            asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(t11) : "v"(q[jj]));
-            if (STRICT) {
-                const float top = fma_(ax[jj], t10 - t00, t00);
-                const float bot = fma_(ax[jj], t11 - t01, t01);
-                s = fma_(ay[jj], bot - top, top);
-            } else {                                            // fast arithmetic (oracle S7 (6)), see pm_tap_r5.h
-                const float d1 = t10 - t00, d2 = t01 - t00, d3 = (t11 - t01) - d1;
-                s = fma_(ay[jj], fma_(ax[jj], d3, d2), fma_(ax[jj], d1, t00));
+                if constexpr (BUF)      // the asm-issued gathers return in order: tap jj has CH - 1 - jj behind it; why the waits take these operands: pm_tap_r5.h, at its BUF waits
+                    asm("s_waitcnt vmcnt(%3)" : "+v"(q[jj]), "+v"(sum_src_src) : "v"(q[CH - 1]), "n"(CH - 1 - jj));
+                s = blend_quad<!STRICT>(q[jj], ax[jj], ay[jj]);
             }
-            }
-            const float wt = wv[jj];
-            const float ws = wt * s;
-            sum_src += ws;
-            sum_src_src = fma_(ws, s, sum_src_src);
-            if (STRICT) sum_ref_src = fma_(wt * r[jj], s, sum_ref_src);   // (w r) s, the oracle's order
-            else sum_ref_src = fma_(ws, r[jj], sum_ref_src);              // (w s) r: one multiply fewer per tap
+            const TapSums t = tap_accumulate<STRICT>(TapSums{sum_src, sum_src_src, sum_ref_src}, wv[jj], r[jj], s);
+            sum_src = t.src; sum_src_src = t.src_src; sum_ref_src = t.ref_src;
         }
     };
     auto lines = [&](auto clamp_tag) {
@@ -275,8 +203,8 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
         for (int l = 0; l <= rl; l++) {
             const int ol = 2 * l - rl;
             const float xi = fl + (float)ol;
-            const float bx = STRICT ? H[0] * xi : fma_(H[ROW ? 1 : 0], xi, H[2]), by = STRICT ? H[3] * xi : fma_(H[ROW ? 4 : 3], xi, H[5]),
-                        bz = STRICT ? H[6] * xi : fma_(H[ROW ? 7 : 6], xi, H[8]);
+            float bx, by, bz;
+            tap_line_base<STRICT, ROW>(H, xi, bx, by, bz);
             const unsigned short* trow = tile + own + (ROW ? ol * tw - rt : ol - rt * tw);
 #pragma unroll 1
             for (int c0 = 0; c0 <= rt; c0 += CH) {
@@ -292,14 +220,5 @@ DEVFN float view_cost_lut(const DevScene* __restrict__ sc, const DevView& vw, co
     };
     if (need_clamp) lines(std::true_type());
     else lines(std::false_type());
-    sum_src *= pr.inv_wsum;
-    sum_src_src *= pr.inv_wsum;
-    sum_ref_src *= pr.inv_wsum;
-    const float var_src = sum_src_src - sum_src * sum_src;
-    if (var_src < 1e-5f) return TSAR_MAXCOST;
-    const float covar = sum_ref_src - pr.mean_ref * sum_src;
-    // both variances are >= 1e-5 here and at most 255^2 (8-bit imagery): their product lies inside sqrt_rsq_exact's range by
-    // construction, so the correctly rounded root needs no guard (and none of the six v_cndmask of the compiler's sqrtf)
-    const float vrs = sqrt_rsq_exact(pr.var_ref * var_src);
-    return fmaxf(0.0f, fminf(TSAR_MAXCOST, 1.0f - covar / vrs));
+    return ncc_cost(pr, TapSums{sum_src, sum_src_src, sum_ref_src});
 }

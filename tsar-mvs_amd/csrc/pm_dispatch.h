@@ -82,3 +82,16 @@ static inline size_t tap_loop_lds_bytes(const DevScene& hs, int region_rows, int
     return (quad ? tile_bytes<true>(tw, th) : tile_bytes<false>(tw, th)) +
            (lut ? (size_t)(hs.lut_classes + 1) * 1024 : sizeof(float) * (size_t)(hs.hrad + 1) * (hs.vrad + 1) * block);
 }
+
+// The launch shape of a tap-loop kernel: the tile grid of the image, the dynamic LDS (+ extra_lds the caller adds behind it), and
+// the kernel's limit raised where that exceeds the 64 KiB a kernel may use unasked.
+struct TapGrid { int tiles_x, n_tiles; size_t lds; };
+template <class K>
+static int tap_grid(tsar_ctx* ctx, K kern, int region_rows, int block, bool quad, int v, size_t extra_lds, TapGrid& g) {
+    const DevScene& hs = ctx->hscene;
+    g.tiles_x = (hs.w + PM_RW - 1) / PM_RW;
+    g.n_tiles = g.tiles_x * ((hs.h + region_rows - 1) / region_rows);
+    g.lds = tap_loop_lds_bytes(hs, region_rows, block, quad, v) + extra_lds;
+    if (g.lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+    return TSAR_OK;
+}

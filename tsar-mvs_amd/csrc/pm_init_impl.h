@@ -87,15 +87,12 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_full_kernel(const DevScene* __res
 
 template <int NB, int HR, bool STRICT, bool QUAD, bool INIT, int V = 0>
 static int launch_full_t(tsar_ctx* ctx, const float4* planes, float* c, float4* n, int32_t* bv, float* rt) {
-    const DevScene& hs = ctx->hscene;
-    const int tiles_x = (hs.w + PM_RW - 1) / PM_RW, tiles_y = (hs.h + FULL_RH - 1) / FULL_RH;
-    const int n_tiles = tiles_x * tiles_y;
-    const size_t lds = tap_loop_lds_bytes(hs, FULL_RH, PM_BLOCK, QUAD, V);
     auto kern = pm_full_kernel<NB, HR, STRICT, QUAD, INIT, V>;
-    if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TapGrid g;
+    if (const int rc = tap_grid(ctx, kern, FULL_RH, PM_BLOCK, QUAD, V, 0, g)) return rc;
     {
         ScopedKernelTimer tm(ctx, (INIT && (V & TSAR_V_REDRAW)) ? "pm_rescore" : INIT ? "pm_init" : "pm_cost_planes");
-        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(PM_BLOCK), lds, ctx->stream, ctx->dscene, planes, c, n, bv, rt, tiles_x, n_tiles, strip_width(ctx->strip_w, tiles_x));
+        hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(PM_BLOCK), g.lds, ctx->stream, ctx->dscene, planes, c, n, bv, rt, g.tiles_x, g.n_tiles, strip_width(ctx->strip_w, g.tiles_x));
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;

@@ -462,40 +462,32 @@ constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_producti
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
                           uint32_t stream_id, int do_prop, int do_refine) {
-    const DevScene& hs = ctx->hscene;
-    constexpr int RW = PM_RW;
-    constexpr int SWEEP_RH = 2 * BLK / RW;
-    const int tiles_x = (hs.w + RW - 1) / RW, tiles_y = (hs.h + SWEEP_RH - 1) / SWEEP_RH;
-    const int n_tiles = tiles_x * tiles_y;
+    constexpr int SWEEP_RH = 2 * BLK / PM_RW;
 #ifdef TSAR_EXPERIMENTS
     const size_t lds_pad = ctx->lds_pad;       // occupancy experiments: unused LDS per workgroup
 #else
     constexpr size_t lds_pad = 0;
 #endif
-    size_t lds = tap_loop_lds_bytes(hs, SWEEP_RH, BLK, QUAD, V) + lds_pad;
     SweepMemo memo;
     memo.cand = ctx->memo_cand; memo.seq = ctx->memo_seq; memo.changed = ctx->changed_seq;
     memo.launch = ctx->launch_seq; memo.valid_from = ctx->memo_valid_from;
     memo.mode = (ctx->memo_mode && ctx->memo_cand && ctx->cost_consistent && !ctx->final_text) ? 1 : 0;
-    memo.slot_off = 0;
     bool packed = false;
     if constexpr (sweep_has_packed_form<HR, QUAD, V>())
         packed = memo.mode && do_prop && ctx->compact_from >= 0 && ctx->call_launch >= ctx->compact_from;
     auto kern = pm_sweep_kernel<NB, HR, STRICT, QUAD, V, BLK, false>;
-    if constexpr (sweep_has_packed_form<HR, QUAD, V>()) {
-        if (packed) {
-            kern = pm_sweep_kernel<NB, HR, STRICT, QUAD, V, BLK, true>;
-            memo.slot_off = (int)lds;
-            lds += 6 * (size_t)BLK;
-        }
-    }
-    if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if constexpr (sweep_has_packed_form<HR, QUAD, V>())
+        if (packed) kern = pm_sweep_kernel<NB, HR, STRICT, QUAD, V, BLK, true>;
+    const size_t slots = packed ? 6 * (size_t)BLK : 0;      // the packed form's hand-over slots, behind everything else
+    TapGrid g;
+    if (const int rc = tap_grid(ctx, kern, SWEEP_RH, BLK, QUAD, V, lds_pad + slots, g)) return rc;
+    memo.slot_off = packed ? (int)(g.lds - slots) : 0;
     {
         ScopedKernelTimer tm(ctx, (V & TSAR_V_GEOM) ? "pm_sweep_geom" : "pm_sweep");
         ScopedKernelTimer tm_packed(ctx, packed ? "pm_sweep_packed" : nullptr);      // (the packed launches a second time under their own name)
-        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(BLK), lds, ctx->stream, ctx->dscene, colour, same_in.c, same_in.n4, other.c,
-                           other.n4, same_out.c, same_out.n4, ctx->ratio, ctx->beview, stream_id, do_prop, do_refine, tiles_x, n_tiles,
-                           ctx->cost_consistent ? 1 : 0, strip_width(ctx->strip_w, tiles_x), ctx->final_text, memo);
+        hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(BLK), g.lds, ctx->stream, ctx->dscene, colour, same_in.c, same_in.n4, other.c,
+                           other.n4, same_out.c, same_out.n4, ctx->ratio, ctx->beview, stream_id, do_prop, do_refine, g.tiles_x, g.n_tiles,
+                           ctx->cost_consistent ? 1 : 0, strip_width(ctx->strip_w, g.tiles_x), ctx->final_text, memo);
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;

@@ -1,6 +1,7 @@
 // pm_tap_r5.h — the production tap loop: pmCost (gipuma.cu:229-298) of one source view for the scripts' window (--blocksize=11:
 // radius 5, taps at {-5,-3,-1,1,3,5}^2, scripts/courtyard.sh:10-15) on 8-bit imagery (quad textures), given the hoisted reference
-// terms of pm_core.h.  Both arithmetic modes run this one function; included by pm_core.h.
+// terms of pm_core.h.  Both arithmetic modes run this one function, built from the per-tap pieces of pm_tap_common.h; included by
+// pm_core.h.
 //
 // Template switches (the kernels' variant number V keeps naming them in profiles: 114 = none, 122 = D16, 250 = D16 + ROW,
 // + TSAR_V_BUF = BUF):
@@ -16,11 +17,12 @@
 //   BUF     the gathers as structured buffer loads (buffer_load_dword ... idxen) through a stride-4 resource descriptor: the texture
 //           addresser scales the element index, the per-tap shift goes away (-0.65 % on a converged launch, +4 ms on the first
 //           sweep of a view, so the launcher uses it from the second sweep on in fast mode, the third in strict mode).  No compiler builtin reaches idxen: the loads are
-//           issued by asm and their vmcnt waits are written out.
+//           issued by asm and their vmcnt waits are written out (buffer_gather, pm_tap_common.h; the waits below).
 //   MIX     with BUF, fast mode: the gather reads 8 bytes from the view's half-float difference texture (t00, t10 - t00, t01 - t00,
 //           t11 - t10 - t01 + t00; plane_kernels.hip build_dquad_kernel) and the fast arithmetic's blend (t00 + ax d1) + ay (d2 + ax d3)
-//           is two v_fma_mix_f32 on the halfs in place and one v_fma_f32: no byte converts, no subtractions (-9 issue units of a tap's 34).  Same
-//           values bit for bit as the byte-texture form of that blend, which the global-load launches (init, the first two sweeps) keep.
+//           is two v_fma_mix_f32 on the halfs in place and one v_fma_f32 (blend_dquad, pm_tap_common.h): no byte converts, no subtractions
+//           (-9 issue units of a tap's 34).  Same values bit for bit as the byte-texture form of that blend, which the global-load
+//           launches (init, the first two sweeps) keep.
 //           (Strict mode can form the reference's blend from the same halfs bit-exactly — t10 - t00 is stored, t01 and t11 - t01 are
 //           one exact v_fma_mix_f32 each, -4.5 issue units per tap — and was measured SLOWER, 48.1 -> 51.6 ms per launch: its
 //           column-order walk touches six texture rows per lane and trip, and 8-byte entries double that footprint.  Not kept.)
@@ -41,15 +43,15 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
     static_assert(!(STRICT && ROW), "the row-wise walk changes the summation order: fast mode only");
     static_assert(!MIX || (BUF && !STRICT), "the half-float difference texture serves the fast arithmetic's blend through buffer loads");
     const int w = sc->w, h = sc->h, qp = sc->quad_pitch;
-    const int qorg = (qp + 1) << 2;          // byte offset of quad entry (0 + 1, 0 + 1)
+    const int qorg = quad_border_bytes(qp);
     float H[9];
     if (STRICT) plane_homography(sc->ref, vw, n4, H, sc->k_sparse != 0);
     else plane_homography_fast(sc->ref, vw, n4, H);
     float sum_src = 0.f, sum_src_src = 0.f, sum_ref_src = 0.f;
-    // Clamp-free loop: if the four corner taps of every active lane's window land inside the source image with Z > 0 (the window
-    // then maps into the convex quadrilateral they span), no tap needs the clamp and the wave runs a tap loop without it.
-    // Wave-uniform decision, identical results.  The texture is addressed from entry (1, 1) with an unsigned offset, so the
-    // clamp-free loop must never see floor(u) = -1: the corners keep one pixel of margin (rounding moves a tap by ~1e-4 pixel).
+    // Clamp-free loop: if every active lane's window lands inside the source image with Z > 0, no tap needs the clamp and the wave
+    // runs a tap loop without it.  Wave-uniform decision, identical results.  Strict mode decides on the four corner taps
+    // (the window then maps into the convex quadrilateral they span).  The texture is addressed from entry (1, 1) with an unsigned offset, so the
+    // clamp-free loop must never see floor(u) = -1: both tests keep a pixel of margin (rounding moves a tap by ~1e-4 pixel).
     bool need_clamp;
     if (!STRICT) {
         // Fast mode: the same decision from the window's CENTRE and a bound on its extent — one reciprocal instead of four and ~20
@@ -60,8 +62,8 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
         // pixel for the rounding of this bound itself: its terms are evaluated to ~1e-6 relative on distances of a few pixels and
         // positions of a few thousand).  More conservative than the corner test by the slack of the bound: waves whose windows come
         // within ~2 extents of the border take the clamp loop, which returns the same bits.
-        const float xc = (float)x, yc = (float)y;
-        const float Xc = fma_(H[1], yc, fma_(H[0], xc, H[2])), Yc = fma_(H[4], yc, fma_(H[3], xc, H[5])), Zc = fma_(H[7], yc, fma_(H[6], xc, H[8]));
+        float Xc, Yc, Zc;
+        pixel_homogeneous(H, (float)x, (float)y, Xc, Yc, Zc);
         const float a = fabsf(H[0]) + fabsf(H[1]), b = fabsf(H[3]) + fabsf(H[4]), c = fabsf(H[6]) + fabsf(H[7]);
         const float Zmin = fma_(-5.0f, c, Zc);
         const float r = __builtin_amdgcn_rcpf(Zmin * Zc);
@@ -75,55 +77,34 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
         float zmin = __builtin_inff(), zmax = 0.0f;
 #pragma unroll
         for (int c = 0; c < 4; c++) {
-            const float xi = (float)(x + ((c & 1) ? 5 : -5)), yj = (float)(y + ((c & 2) ? 5 : -5));
-            const float X = fma_(H[1], yj, fma_(H[0], xi, H[2])), Y = fma_(H[4], yj, fma_(H[3], xi, H[5])), Z = fma_(H[7], yj, fma_(H[6], xi, H[8]));
+            float X, Y, Z;
+            pixel_homogeneous(H, (float)(x + ((c & 1) ? 5 : -5)), (float)(y + ((c & 2) ? 5 : -5)), X, Y, Z);
             const float rz = __builtin_amdgcn_rcpf(Z);
             const float u = X * rz, v = Y * rz;
             inside = inside && Z > 0.0f && u >= 1.0f && u <= (float)(w - 1) - 1.0f && v >= 1.0f && v <= (float)(h - 1) - 1.0f;
-            if (STRICT) { zmin = fminf(zmin, Z); zmax = fmaxf(zmax, Z); }
+            zmin = fminf(zmin, Z); zmax = fmaxf(zmax, Z);
         }
-        if (STRICT) {
-            // The clamp-free loop of strict mode also drops the per-tap operand guard of persp_divide_exact, so "inside" must imply
-            // that X, Y, Z of EVERY tap lie in [2^-20, 2^38].  With cm >= |x|, |y| of any tap: Z is affine in the tap position, so at
-            // every tap it lies between the corner values up to the rounding of its three-term evaluation, dZ <= 3 * 2^-24 * sz with
-            // sz = (|H6| + |H7|) cm + |H8|.  sz cm <= 2^19 zmin bounds dZ / Z by 3 * 2^-5 / cm <= 1.2 % (cm >= 8), so Z stays in
-            // [2^-19, 2^18] for zmin >= 2^-18, zmax <= 2^17.  u = X / Z of a tap lies in the hull of the corners' true u (Z > 0: the
-            // map is projective), which are >= 1 - 0.15: computed u >= 1, and a computed corner is off by u dZ / Z <= cm * 3 * 2^-24
-            // * 2^19 / cm = 0.094 plus dX / Z <= 3 * 2^-24 * sx / zmin <= 0.047 for sx = (|H0| + |H1|) cm + |H2| <= 2^18 zmin.  Hence
-            // X >= 0.8 zmin >= 2^-20 and |X| <= sx <= 2^35; the same for Y.
-            const float cm = (float)(max(w, h) + 32);
-            const float sz = fma_(fabsf(H[6]) + fabsf(H[7]), cm, fabsf(H[8]));
-            const float sx = fma_(fabsf(H[0]) + fabsf(H[1]), cm, fabsf(H[2]));
-            const float sy = fma_(fabsf(H[3]) + fabsf(H[4]), cm, fabsf(H[5]));
-            inside = inside && zmin >= 3.814697265625e-06f && zmax <= 131072.0f && sz * cm <= 524288.0f * zmin && fmaxf(sx, sy) <= 262144.0f * zmin;
-        }
+        // The clamp-free loop of strict mode also drops the per-tap operand guard of persp_divide_exact, so "inside" must imply
+        // that X, Y, Z of EVERY tap lie in [2^-20, 2^38].  With cm >= |x|, |y| of any tap: Z is affine in the tap position, so at
+        // every tap it lies between the corner values up to the rounding of its three-term evaluation, dZ <= 3 * 2^-24 * sz with
+        // sz = (|H6| + |H7|) cm + |H8|.  sz cm <= 2^19 zmin bounds dZ / Z by 3 * 2^-5 / cm <= 1.2 % (cm >= 8), so Z stays in
+        // [2^-19, 2^18] for zmin >= 2^-18, zmax <= 2^17.  u = X / Z of a tap lies in the hull of the corners' true u (Z > 0: the
+        // map is projective), which are >= 1 - 0.15: computed u >= 1, and a computed corner is off by u dZ / Z <= cm * 3 * 2^-24
+        // * 2^19 / cm = 0.094 plus dX / Z <= 3 * 2^-24 * sx / zmin <= 0.047 for sx = (|H0| + |H1|) cm + |H2| <= 2^18 zmin.  Hence
+        // X >= 0.8 zmin >= 2^-20 and |X| <= sx <= 2^35; the same for Y.
+        const float cm = (float)(max(w, h) + 32);
+        const float sz = fma_(fabsf(H[6]) + fabsf(H[7]), cm, fabsf(H[8]));
+        const float sx = fma_(fabsf(H[0]) + fabsf(H[1]), cm, fabsf(H[2]));
+        const float sy = fma_(fabsf(H[3]) + fabsf(H[4]), cm, fabsf(H[5]));
+        inside = inside && zmin >= 3.814697265625e-06f && zmax <= 131072.0f && sz * cm <= 524288.0f * zmin && fmaxf(sx, sy) <= 262144.0f * zmin;
         need_clamp = !__all(inside);
     }
-    // quad base + border offset, opaque to the optimiser so that it stays in two SGPRs across the view (the compiler otherwise
-    // re-loads it with s_load in every line and waits for it, and for the line's LDS loads, right before issuing the gathers)
+    // the view's quad texture: pinned base for the global loads, descriptor for the buffer-load forms (which address through it alone:
+    // no second pointer load per view)
     uint32_t qb_lo = 0, qb_hi = 0;
-    if (!BUF) {                              // (the buffer-load forms address through the descriptor below: no second pointer load per view)
-        const uint64_t qa = (uint64_t)(uintptr_t)vw.quad + (uint32_t)qorg;
-        qb_lo = __builtin_amdgcn_readfirstlane((uint32_t)qa);
-        qb_hi = __builtin_amdgcn_readfirstlane((uint32_t)(qa >> 32));
-        asm volatile("" : "+s"(qb_lo), "+s"(qb_hi));
-    }
-    typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
     u32x4s rsrc = {0u, 0u, 0u, 0u};
-    if (BUF) {
-        if (MIX) {                           // 8-byte entries of the difference texture, same pitch and border
-            const uint64_t da = (uint64_t)(uintptr_t)vw.dquad + 2 * (uint64_t)(uint32_t)qorg;
-            rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)da);
-            rsrc.y = __builtin_amdgcn_readfirstlane(((uint32_t)(da >> 32) & 0xffffu) | (8u << 16));  // base[47:32] | stride 8
-        } else {
-        const uint64_t qa = (uint64_t)(uintptr_t)vw.quad + (uint32_t)qorg;
-        rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)qa);
-        rsrc.y = __builtin_amdgcn_readfirstlane(((uint32_t)(qa >> 32) & 0xffffu) | (4u << 16));      // base[47:32] | stride 4
-        }
-        rsrc.z = __builtin_amdgcn_readfirstlane((uint32_t)(qp * (h + 1) - 1));                       // records from entry (1, 1) on
-        rsrc.w = 0x00020000u;                                                                         // 32-bit data format (gfx9 family)
-        asm volatile("" : "+s"(rsrc));
-    }
+    if (!BUF) pin_quad_base(quad_origin<false>(vw, qorg), qb_lo, qb_hi);
+    else rsrc = quad_descriptor<MIX>(quad_origin<MIX>(vw, qorg), h + 1, qp);
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     // one line of the window: `i` is the column offset (the row offset when ROW) and the six taps run along the other axis
     // unr_tag: the caller's loop over the six lines is fully unrolled (`i` is a constant after inlining): the line's LDS loads then
@@ -133,10 +114,8 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
         constexpr bool UNR = decltype(unr_tag)::value;
         static_assert(!UNR || (ROW && D16), "the unrolled form is written for the row-wise walk with D16 window loads");
         const float xi = (float)((ROW ? y : x) + i);
-        // strict mode: the text's association (m[0] x + m[1] y) + m[2] of getCorrespondingPoint_cu (gipuma.cu:161-171, config.h:150-162),
-        // the constant added last (pm_core.h view_cost_generic); fast: folded into the line term (oracle S7 (7))
-        const float bx = STRICT ? H[0] * xi : fma_(H[ROW ? 1 : 0], xi, H[2]), by = STRICT ? H[3] * xi : fma_(H[ROW ? 4 : 3], xi, H[5]),
-                    bz = STRICT ? H[6] * xi : fma_(H[ROW ? 7 : 6], xi, H[8]);
+        float bx, by, bz;
+        tap_line_base<STRICT, ROW>(H, xi, bx, by, bz);
         const int line = (i + 5) >> 1;                // 0..5: which column (or row) this is
         float rcol[6];
         f32x2 wcol[3];
@@ -167,39 +146,11 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
 #pragma unroll
         for (int jj = 0; jj < 6; jj++) {                        // phase 1: tap positions -> element index; phase 2: gathers
             const float yj = (float)((ROW ? x : y) + 2 * jj - 5);
-            float X = fma_(H[ROW ? 0 : 1], yj, bx), Y = fma_(H[ROW ? 3 : 4], yj, by), Z = fma_(H[ROW ? 6 : 7], yj, bz);
-            if (STRICT) { X += H[2]; Y += H[5]; Z += H[8]; }
-            float u, v;
-            // Clamp range.  The oracle clamps to [-1, w] (tex2D at u + .5 with clamp addressing).  The offset is unsigned from entry
-            // (1, 1), so floor(u) must be >= 0: clamp to [0, w - 1] instead.  The sample is the same bit for bit: for u in [-1, 0)
-            // both texels of the pair are T(0) (edge replication), so the blend returns T(0) whatever the fraction — exactly what
-            // u = 0 returns (fraction 0); likewise beyond w - 1, and per axis.
+            float X, Y, Z;
+            tap_homogeneous<STRICT, ROW>(H, yj, bx, by, bz, X, Y, Z);
             const float uhi = (float)(w - 1), vhi = (float)(h - 1);
-            if (STRICT) {                                       // the oracle's values: correctly rounded quotients, min/max clamp
-                persp_divide_exact<CLAMP>(X, Y, Z, u, v);       // clamp-free loop: the operand guard is shown by the corner test
-                if (CLAMP) {
-                    u = fminf(fmaxf(u, 0.0f), uhi);
-                    v = fminf(fmaxf(v, 0.0f), vhi);
-                }
-            } else {
-                const float rz = __builtin_amdgcn_rcpf(Z);
-                u = X * rz;
-                v = Y * rz;
-                if (CLAMP) {
-                    u = __builtin_amdgcn_fmed3f(u, 0.0f, uhi);
-                    v = __builtin_amdgcn_fmed3f(v, 0.0f, vhi);
-                }
-            }
-            // u, v >= 0 here (clamped to [0, w - 1], or inside the image by the corner test): v_fract_f32 = u - floor(u) exactly (the
-            // difference is representable), v_cvt_flr_i32_f32 = (int)floor(u) — the oracle's floor / subtract / convert
-            int iu, iv;
-            ax[jj] = __builtin_amdgcn_fractf(u);
-            ay[jj] = __builtin_amdgcn_fractf(v);
-            asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iu) : "v"(u));
-            asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iv) : "v"(v));
-            // element index of quad entry (iv + 1, iu + 1) from entry (1, 1): one 24-bit multiply-add
             int lin;
-            asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(lin) : "v"(iv), "s"(qp), "v"(iu));
+            tap_position<STRICT, CLAMP>(X, Y, Z, uhi, vhi, qp, ax[jj], ay[jj], lin);
             if (MIX && DIAG == 1) {
                 q2[jj] = ((uint64_t)(uint32_t)~lin << 32) | (uint32_t)lin;      // (two different dwords: identical ones would let the compiler merge the blend's two mixed FMAs)
             } else if (MIX && DIAG == 2) {
@@ -207,9 +158,9 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
                 asm("v_bfe_u32 %0, %1, 0, 12" : "=v"(la) : "v"(lin));
                 asm volatile("ds_read_b64 %0, %1" : "=v"(q2[jj]) : "v"(la << 3));
             } else if (MIX) {
-                asm volatile("buffer_load_dwordx2 %0, %1, %2, 0 idxen" : "=v"(q2[jj]) : "v"(lin), "s"(rsrc));
+                q2[jj] = buffer_gather<true>(lin, rsrc);
             } else if (BUF) {
-                asm volatile("buffer_load_dword %0, %1, %2, 0 idxen" : "=v"(q[jj]) : "v"(lin), "s"(rsrc));
+                q[jj] = buffer_gather<false>(lin, rsrc);
             } else {                                            // base already holds the border offset: the byte offset is a plain shift
                 const uint32_t off2 = (uint32_t)lin << 2;
                 q[jj] = *(global_u32_ptr)((const char __attribute__((address_space(1)))*)(uintptr_t)(((uint64_t)qb_hi << 32) | qb_lo) + off2);
@@ -220,7 +171,6 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int jj = 0; jj < 6; jj++) {                        // phase 3: unpack, blend, accumulate
-            float t00, t10, t01, t11;                           // the four texels: one convert each, no shifts/masks
             if (MIX && DIAG == 1) {
             } else if (MIX && DIAG == 2) {                      // LDS returns in order: tap jj has 5 - jj reads behind it
                 if (jj == 0) asm("s_waitcnt lgkmcnt(5)" : "+v"(q2[0]), "+v"(rcol[0]), "+v"(rcol[1]), "+v"(rcol[2]), "+v"(rcol[3]), "+v"(rcol[4]), "+v"(rcol[5]),
@@ -245,28 +195,8 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
                 if (jj == 5) asm("s_waitcnt vmcnt(0)" : "+v"(q[5]), "+v"(sum_src_src));
             }
             float s;
-            if (MIX) {
-                // (t00 + ax d1) + ay (d2 + ax d3) with the halfs read in place: two mixed-precision FMAs on the gathered dwords and one
-                // plain FMA, one fp32 rounding each — the same values as the fp32 chain below (the halfs are exact integers)
-                const uint32_t lo = (uint32_t)q2[jj], hi = (uint32_t)(q2[jj] >> 32);
-                float ta, tb;
-                asm("v_fma_mix_f32 %0, %1, %2, %2 op_sel:[0,1,0] op_sel_hi:[0,1,1]" : "=v"(ta) : "v"(ax[jj]), "v"(lo));          // ax * d1 + t00: the top row's interpolation
-                asm("v_fma_mix_f32 %0, %1, %2, %2 op_sel:[0,1,0] op_sel_hi:[0,1,1]" : "=v"(tb) : "v"(ax[jj]), "v"(hi));          // ax * d3 + d2: bottom row minus top row, rounded once
-                s = fma_(ay[jj], tb, ta);
-            } else {
-            asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(t00) : "v"(q[jj]));
-            asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(t10) : "v"(q[jj]));
-            asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(t01) : "v"(q[jj]));
-            asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(t11) : "v"(q[jj]));
-            if (STRICT) {                                       // the reference's blend: two horizontal interpolations, one vertical
-                const float top = fma_(ax[jj], t10 - t00, t00);
-                const float bot = fma_(ax[jj], t11 - t01, t01);
-                s = fma_(ay[jj], bot - top, top);
-            } else {                                            // fast arithmetic (oracle S7 (6)): (t00 + ax d1) + ay (d2 + ax d3), exact integer differences
-                const float d1 = t10 - t00, d2 = t01 - t00, d3 = (t11 - t01) - d1;
-                s = fma_(ay[jj], fma_(ax[jj], d3, d2), fma_(ax[jj], d1, t00));
-            }
-            }
+            if (MIX) s = blend_dquad(q2[jj], ax[jj], ay[jj]);
+            else s = blend_quad<!STRICT>(q[jj], ax[jj], ay[jj]);
             // one wait per line, at its first tap: every LDS load of the line (six texels when they are D16 loads, three weight
             // pairs) was issued before the gathers, in order, and has long returned when the first gather does
             if (jj == 0 && DIAG != 2) {
@@ -278,11 +208,8 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
             }
             const float r = D16 ? rcol[jj] : tile_value(ROW ? tile[own + i * tw + (2 * jj - 5)] : tile[own + (2 * jj - 5) * tw + i]);
             const float wt = wcol[jj >> 1][jj & 1];
-            const float ws = wt * s;
-            sum_src += ws;
-            sum_src_src = fma_(ws, s, sum_src_src);
-            if (STRICT) sum_ref_src = fma_(wt * r, s, sum_ref_src);   // (w r) s, the oracle's order
-            else sum_ref_src = fma_(ws, r, sum_ref_src);              // (w s) r: one multiply fewer per tap
+            const TapSums t = tap_accumulate<STRICT>(TapSums{sum_src, sum_src_src, sum_ref_src}, wt, r, s);
+            sum_src = t.src; sum_src_src = t.src_src; sum_ref_src = t.ref_src;
         }
     };
     if (need_clamp) {
@@ -297,16 +224,7 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
 #pragma unroll 1
         for (int i = -5; i <= 5; i += 2) line6(i, std::false_type(), std::false_type());
     }
-    sum_src *= pr.inv_wsum;
-    sum_src_src *= pr.inv_wsum;
-    sum_ref_src *= pr.inv_wsum;
-    const float var_src = sum_src_src - sum_src * sum_src;
-    if (var_src < 1e-5f) return TSAR_MAXCOST;
-    const float covar = sum_ref_src - pr.mean_ref * sum_src;
-    // both variances are >= 1e-5 here and at most 255^2 (8-bit imagery): their product lies inside sqrt_rsq_exact's range by
-    // construction, so the correctly rounded root needs no guard (and none of the six v_cndmask of the compiler's sqrtf)
-    const float vrs = sqrt_rsq_exact(pr.var_ref * var_src);
-    return fmaxf(0.0f, fminf(TSAR_MAXCOST, 1.0f - covar / vrs));
+    return ncc_cost(pr, TapSums{sum_src, sum_src_src, sum_ref_src});
 }
 
 // The variant numbers the production kernels are instantiated with (and which profiles name): bits 1, 4, 5, 6 always set.

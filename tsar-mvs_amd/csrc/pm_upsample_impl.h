@@ -77,17 +77,14 @@ __global__ __launch_bounds__(PM_BLOCK) void pm_upsample_kernel(const DevScene* _
 // resize4.  Timed as "pm_upsample_merge" / "pm_upsample".
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, bool MERGE = false>
 static int launch_up_t(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
-    const DevScene& hs = ctx->hscene;
-    const int tiles_x = (hs.w + PM_RW - 1) / PM_RW, tiles_y = (hs.h + UP_RH - 1) / UP_RH;
-    const int n_tiles = tiles_x * tiles_y;
-    const size_t lds = tap_loop_lds_bytes(hs, UP_RH, PM_BLOCK, QUAD, V);
     auto kern = pm_upsample_kernel<NB, HR, STRICT, QUAD, V, MERGE>;
-    if (lds > 64 * 1024) TSAR_HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TapGrid g;
+    if (const int rc = tap_grid(ctx, kern, UP_RH, PM_BLOCK, QUAD, V, 0, g)) return rc;
     const PlaneBuf& out = ctx->buf[MERGE ? 1 : 0];
     {
         ScopedKernelTimer tm(ctx, MERGE ? "pm_upsample_merge" : "pm_upsample");
-        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(PM_BLOCK), lds, ctx->stream, ctx->dscene, MERGE ? ctx->buf[0].n4 : nullptr, coarse, cw, ch, out.c,
-                           out.n4, MERGE ? nullptr : ctx->resize4, ctx->beview, ctx->ratio, tiles_x, n_tiles, strip_width(ctx->strip_w, tiles_x));
+        hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(PM_BLOCK), g.lds, ctx->stream, ctx->dscene, MERGE ? ctx->buf[0].n4 : nullptr, coarse, cw, ch, out.c,
+                           out.n4, MERGE ? nullptr : ctx->resize4, ctx->beview, ctx->ratio, g.tiles_x, g.n_tiles, strip_width(ctx->strip_w, g.tiles_x));
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());
     return TSAR_OK;

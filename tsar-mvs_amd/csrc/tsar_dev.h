@@ -60,7 +60,7 @@ struct DevScene {
     DevRef ref;
     int sel[TSAR_MAX_VIEWS];   // view indices in pair.txt order
     DevView view[TSAR_MAX_VIEWS];
-    // Shared weight table of the general-window tap loop (pm_core.h view_cost_lut; 8-bit imagery): the bilateral weight
+    // Shared weight table of the general-window tap loop (pm_core_lut.h view_cost_lut; 8-bit imagery): the bilateral weight
     // exp(-sqrt(i^2 + j^2) / 50 - |r - centre| / 18) of a tap depends on its distance class (the distinct i^2 + j^2 of the
     // window) and on an integer 0..255, so a workgroup keeps one 256-entry row per class in LDS instead of S weights per thread.
     int lut_classes;                               // rows of the table; row lut_classes is all zero (padding taps of a line's last chunk)
@@ -162,7 +162,7 @@ struct tsar_ctx {
     // geometric consistency (tsar_set_geom_depths): the source views' depth maps, owned; hscene.geom_depth points into them
     std::vector<float*> geom_maps;
     // timing
-    int variant = 2;             // TSAR_VARIANT=n: code-generation variant of the fast-mode tap loop (pm_core.h view_cost); tsar_create picks 250 (med3/fract + D16 window loads + clamp-free loop for in-image windows + wave priority + SGPR-pinned texture base and line-top weight loads + row-wise window walk in fast mode; strict mode runs it as 122, the oracle's column order) when the D16 probe passes, else 114
+    int variant = 2;             // TSAR_VARIANT=n: code-generation variant of the fast-mode tap loop (pm_tap_r5.h view_cost_r5); tsar_create picks 250 (med3/fract + D16 window loads + clamp-free loop for in-image windows + wave priority + SGPR-pinned texture base and line-top weight loads + row-wise window walk in fast mode; strict mode runs it as 122, the oracle's column order) when the D16 probe passes, else 114
     bool mix_gather = true;      // TSAR_MIX_GATHER=0: keep the byte texture for the buffer-load launches too (pm_tap_r5.h MIX off)
     bool buffer_gather = true;   // TSAR_BUFFER_GATHER=0: the fast tap loop's gathers as global loads + a shift instead of structured buffer loads
     int strip_w = -1;            // TSAR_STRIP=n: width in tiles of the strips the sweep walks (pm_core.h strip_tile), 0 = row-major,
