@@ -101,6 +101,9 @@ extern "C" {
                                                   gipuma.cu:161-171), (w r) s, window columns, the reference's homography and blend
                                                   (bit-exact against the CPU oracle; ~28 % slower than the default arithmetic, whose
                                                   seven rounding-level liberties oracle/tsar_oracle.c S7 lists) */
+#define TSAR_FLAG_FIX_PLANE_FIT      (1u << 3) /* tsar_ransac_regions: the plane through three points with its first component
+                                                   as the cross product has it, (y2-y1)(z3-z1) - (z2-z1)(y3-y1).  The reference's
+                                                   calcLinePara writes (y3-y1) in both products (main.cpp:159); default off. */
 #define TSAR_FLAG_NO_LINE_CLOSING    (1u << 4) /* tsar_detect_weak_texture: skip the Hough boundary closing of large regions
                                                   (main.cpp:385-435; on by default like the reference's HoughLinesP step) */
 
@@ -398,6 +401,8 @@ void tsar_default_fusion_params(tsar_fusion_params* p);
  * source views of view v are src_idx[src_off[v] .. src_off[v+1]) (pair.txt as CSR).  points_out: up to `cap`
  * records of 9 floats (x y z, nx ny nz, gray, number of agreeing views, reference view), in view order then
  * raster order; *n_points_out is the number found (may exceed cap).
+ * `mem` names where the maps lie, and points_out with them: host maps deliver into a host buffer, device maps into a device
+ * buffer (the copy into points_out is issued as device-to-host or device-to-device accordingly).
  * tsar_fuse_ctx runs on the context's device and stream and takes every temporary from the context's scratch arena (no device
  * allocation from the second call of a size on); tsar_fuse is the context-free form for a one-shot fuser process: it creates a
  * context on `device` for the duration of the call. */

@@ -256,8 +256,15 @@ def test_convergence_to_ground_truth(mid_scene):
     m.close()
 
 
-def test_plane_depth_kernels_bit_exact(small_scene):
-    sc = small_scene
+# the small streaming kernels (get_disp, compute_disp[_final], depth_to_plane, getview, update_scale, fake_depth, lrdiff): 96 x 64 is
+# exactly 24 workgroups of 256 pixels; 101 x 75 = 7575 pixels ends on a partial one, with rows that do not align with waves
+@pytest.fixture(scope="module", params=["96x64", "101x75"])
+def stream_scene(request, small_scene):
+    return small_scene if request.param == "96x64" else synth.make_scene(101, 75, 3, seed=7)
+
+
+def test_plane_depth_kernels_bit_exact(stream_scene):
+    sc = stream_scene
     orc = _oracle(sc)
     gt_d = sc.gt_depth.numpy()
     n_cam = sc.gt_normal.numpy()
@@ -287,8 +294,8 @@ def test_plane_depth_kernels_bit_exact(small_scene):
     m.close()
 
 
-def test_textureless_fill_bit_exact(small_scene):
-    sc = small_scene
+def test_textureless_fill_bit_exact(stream_scene):
+    sc = stream_scene
     h, w = sc.h, sc.w
     orc = _oracle(sc, seed=4)
     orc.pm_init()
@@ -318,8 +325,8 @@ def test_textureless_fill_bit_exact(small_scene):
     m.close()
 
 
-def test_lrdiff_confidence(small_scene):
-    sc = small_scene
+def test_lrdiff_confidence(stream_scene):
+    sc = stream_scene
     orc = _oracle(sc, seed=6)
     orc.pm_init()
     orc.pm_iterate(1)
@@ -336,11 +343,11 @@ def test_lrdiff_confidence(small_scene):
     m.close()
 
 
-def test_compute_disp_final_bit_exact(small_scene):
+def test_compute_disp_final_bit_exact(stream_scene):
     """gipuma_compute_disp_final (reference gipuma.cu:757-808) on the case that drives every branch: text 0 / 1 / -1,
     disparity difference above and below the threshold of 6, clamps at depthMin and depthMax, MAXCOST export"""
     from test_oracle_known_answers import _merge_case
-    sc = small_scene
+    sc = stream_scene
     orc = _oracle(sc)
     rs, text, exp_d, took = _merge_case(sc, orc)
     m = api.matcher_from_scene(sc)

@@ -20,6 +20,7 @@ TSAR_ERR_INVALID, TSAR_ERR_HIP, TSAR_ERR_STATE, TSAR_ERR_NOMEM = -1, -2, -3, -4
 MEM_HOST, MEM_DEVICE = 0, 1
 COMB_ALL, COMB_BEST_N, COMB_ANGLE, COMB_GOOD = 0, 1, 2, 3
 FLAG_FIX_DOWN_FAR_SEED, FLAG_FIX_RIGHT_FAR_CMP, FLAG_STRICT_DIV = 1, 2, 4
+FLAG_FIX_PLANE_FIT = 8
 FLAG_NO_LINE_CLOSING = 16
 FLAG_TEX_FILTER_8BIT = 32
 FLAG_FIX_INIT_RADIUS = 64
@@ -694,18 +695,21 @@ def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_
     return coarse
 
 
-def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = None, cap: int | None = None, device: int = 0, matcher=None):
+def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = None, cap: int | None = None, device: int = 0, matcher=None,
+         return_count: bool = False):
     """Fuse per-view depth [h, w] / world-normal [h, w, 3] maps into a point cloud (tsar_fuse; with `matcher`, tsar_fuse_ctx on that
     context: its stream, temporaries from its scratch arena).
     pairs: {view: [source views]} or list of lists.  Returns an [n, 9] float32 array:
-    x y z, nx ny nz, gray, number of agreeing views, reference view."""
+    x y z, nx ny nz, gray, number of agreeing views, reference view — a numpy array, or, when the maps are torch device tensors, a
+    torch tensor on their device (include/tsar.h: `mem` names where the maps and points_out lie).  At most `cap` points are returned;
+    return_count=True returns (points, number of points found), which may exceed cap."""
     L = load_library()
     n = len(depths)
     h, w = int(depths[0].shape[0]), int(depths[0].shape[1])
     if params is None:
         params = FusionParams()
         L.tsar_default_fusion_params(C.byref(params))
-    keep, kinds = [], set()
+    keep, kinds, devices = [], set(), set()
 
     def ptrs(seq, shape):
         arr = (C.c_void_p * n)()
@@ -713,13 +717,18 @@ def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = N
             if not _is_torch(a):
                 a = np.ascontiguousarray(a, np.float32)
                 keep.append(a)
+            else:
+                assert str(a.dtype) == "torch.float32"
+                if a.is_cuda:
+                    devices.add(a.device)
             assert tuple(a.shape) == shape
             p, kind = _ptr(a)
             arr[i] = p
             kinds.add(kind)
         return arr
     pd, pn, pg = ptrs(depths, (h, w)), ptrs(normals, (h, w, 3)), ptrs(grays, (h, w))
-    assert len(kinds) == 1
+    assert len(kinds) == 1, "all maps must live in the same memory space"
+    mem = kinds.pop()
     cams = (Camera * n)()
     K = np.asarray(K, np.float32).reshape(n, 9); R = np.asarray(R, np.float32).reshape(n, 9); t = np.asarray(t, np.float32).reshape(n, 3)
     for i in range(n):
@@ -730,14 +739,24 @@ def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = N
     idx = np.asarray([s for x in lists for s in x] or [0], np.int32)
     if cap is None:
         cap = n * h * w
-    out = np.empty((cap, 9), np.float32)
+    if mem == MEM_DEVICE:
+        # device maps: the cloud is delivered on their device as well, never into a host array
+        import torch
+        assert len(devices) == 1, "all maps must live on one device"
+        out = torch.empty((max(cap, 1), 9), dtype=torch.float32, device=devices.pop())
+        out_ptr = _ptr(out)[0]
+    else:
+        out = np.empty((cap, 9), np.float32)
+        out_ptr = out.ctypes.data_as(C.c_void_p)
     cnt = C.c_int64(0)
-    tail = (n, w, h, cams, pd, pn, pg, kinds.pop(), off.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), C.byref(params),
-            out.ctypes.data_as(C.c_void_p), cap, C.byref(cnt))
+    tail = (n, w, h, cams, pd, pn, pg, mem, off.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), C.byref(params),
+            out_ptr, cap, C.byref(cnt))
     rc = L.tsar_fuse_ctx(matcher._ctx, *tail) if matcher is not None else L.tsar_fuse(device, *tail)
     if rc != TSAR_OK:
         raise TsarError(rc, L.tsar_last_error(matcher._ctx).decode() if matcher is not None else "tsar_fuse failed")
-    return out[: min(cnt.value, cap)].copy()
+    pts = out[: min(cnt.value, cap)]
+    pts = pts.clone() if mem == MEM_DEVICE else pts.copy()
+    return (pts, int(cnt.value)) if return_count else pts
 
 
 def pinned_empty(shape, dtype=np.float32):

@@ -21,7 +21,6 @@
 
 #include "tsar_device_math.h"
 
-#define TSAR_FLAG_FIX_PLANE_FIT (1u << 3)
 #define RS_BLOCK 1024
 #define RS_MAXPTS 49999
 
