@@ -102,7 +102,7 @@ __global__ __launch_bounds__(FU_BLOCK) void fuse_view_kernel(int view, int w, in
 }
 
 // On a context: its stream, and every temporary (uploaded maps, marks, records, rocPRIM scratch) out of its scratch arena — a host
-// that fuses scene after scene (or the tests, call after call) allocates nothing from the second call on (tsar_dev.h ScratchScope).
+// that fuses scene after scene (or the tests, call after call) allocates nothing from the second call on (tsar_dev.h CallFrame).
 extern "C" int tsar_fuse_ctx(tsar_ctx* ctx, int n_views, int w, int h, const tsar_camera* cams, const float* const* depth, const float* const* normal_world,
                              const float* const* gray, int mem, const int32_t* src_off, const int32_t* src_idx, const tsar_fusion_params* prm,
                              float* points_out, int64_t cap, int64_t* n_points_out) {
@@ -112,76 +112,62 @@ extern "C" int tsar_fuse_ctx(tsar_ctx* ctx, int n_views, int w, int h, const tsa
     if (mem != TSAR_MEM_DEVICE && mem != TSAR_MEM_HOST) return fail(ctx, TSAR_ERR_INVALID, "tsar_fuse: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
     const size_t np = (size_t)w * h;
     hipStream_t st = ctx->stream;
-    ScratchScope scratch(ctx);
-    auto done = [&](int rc) {
-        if (hipStreamSynchronize(st) != hipSuccess && rc == TSAR_OK) rc = TSAR_ERR_HIP;
-        scratch.release();
-        if (rc == TSAR_ERR_NOMEM) ctx->err = "tsar_fuse: device allocation failed";
-        else if (rc == TSAR_ERR_HIP) ctx->err = "tsar_fuse: HIP call failed";
-        else if (rc == TSAR_ERR_INVALID) ctx->err = "tsar_fuse: a view's maps are NULL or a source index is out of range";
-        return rc;
-    };
+    CallFrame f(ctx, "tsar_fuse");
+    const char* bad_view = "tsar_fuse: a view's maps are NULL or a source index is out of range";
     // inputs
     std::vector<const float*> hd(n_views), hn(n_views), hg(n_views);
     for (int v = 0; v < n_views; v++) {
-        if (!depth[v] || !normal_world[v] || !gray[v]) return done(TSAR_ERR_INVALID);
-        if (mem == TSAR_MEM_DEVICE) { hd[v] = depth[v]; hn[v] = normal_world[v]; hg[v] = gray[v]; }
-        else {
-            float *dd = (float*)scratch.alloc(np * 4), *dn = (float*)scratch.alloc(np * 12), *dg = (float*)scratch.alloc(np * 4);
-            if (!dd || !dn || !dg) return done(TSAR_ERR_NOMEM);
-            hipMemcpyAsync(dd, depth[v], np * 4, hipMemcpyHostToDevice, st);
-            hipMemcpyAsync(dn, normal_world[v], np * 12, hipMemcpyHostToDevice, st);
-            hipMemcpyAsync(dg, gray[v], np * 4, hipMemcpyHostToDevice, st);
-            hd[v] = dd; hn[v] = dn; hg[v] = dg;
-        }
+        if (!depth[v] || !normal_world[v] || !gray[v]) return f.fail(TSAR_ERR_INVALID, bad_view);
+        hd[v] = f.in(depth[v], np, mem);
+        hn[v] = f.in(normal_world[v], 3 * np, mem);
+        hg[v] = f.in(gray[v], np, mem);
     }
     std::vector<FuCam> hc(n_views);
     for (int v = 0; v < n_views; v++) { memcpy(hc[v].K, cams[v].K, 36); memcpy(hc[v].R, cams[v].R, 36); memcpy(hc[v].t, cams[v].t, 12); }
-    FuCam* d_cams = (FuCam*)scratch.alloc(sizeof(FuCam) * n_views);
-    const float **d_depth = (const float**)scratch.alloc(8 * n_views), **d_normal = (const float**)scratch.alloc(8 * n_views), **d_gray = (const float**)scratch.alloc(8 * n_views);
+    FuCam* d_cams = f.tmp<FuCam>(n_views);
+    const float **d_depth = f.tmp<const float*>(n_views), **d_normal = f.tmp<const float*>(n_views), **d_gray = f.tmp<const float*>(n_views);
     const int n_src_total = src_off[n_views];
-    int32_t* d_src = (int32_t*)scratch.alloc((size_t)(n_src_total > 0 ? n_src_total : 1) * 4);
-    uint8_t *mask = (uint8_t*)scratch.alloc((size_t)n_views * np), *pending = (uint8_t*)scratch.alloc((size_t)n_views * np), *keep = (uint8_t*)scratch.alloc(np);
-    FuRec *rec = (FuRec*)scratch.alloc(np * sizeof(FuRec)), *compact = (FuRec*)scratch.alloc(np * sizeof(FuRec));
-    unsigned int* d_count = (unsigned int*)scratch.alloc(4);
-    if (!d_cams || !d_depth || !d_normal || !d_gray || !d_src || !mask || !pending || !keep || !rec || !compact || !d_count) return done(TSAR_ERR_NOMEM);
-    hipMemcpyAsync(d_cams, hc.data(), sizeof(FuCam) * n_views, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync((void*)d_depth, hd.data(), 8 * n_views, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync((void*)d_normal, hn.data(), 8 * n_views, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync((void*)d_gray, hg.data(), 8 * n_views, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_src, src_idx, (size_t)n_src_total * 4, hipMemcpyHostToDevice, st);
-    hipMemsetAsync(mask, 0, (size_t)n_views * np, st);
-    hipMemsetAsync(pending, 0, (size_t)n_views * np, st);
+    int32_t* d_src = f.tmp<int32_t>(n_src_total > 0 ? n_src_total : 1);
+    uint8_t *mask = f.tmp<uint8_t>((size_t)n_views * np), *pending = f.tmp<uint8_t>((size_t)n_views * np), *keep = f.tmp<uint8_t>(np);
+    FuRec *rec = f.tmp<FuRec>(np), *compact = f.tmp<FuRec>(np);
+    unsigned int* d_count = f.tmp<unsigned int>(1);
+    f.copy(d_cams, hc.data(), sizeof(FuCam) * n_views, hipMemcpyHostToDevice);
+    f.copy((void*)d_depth, hd.data(), 8 * n_views, hipMemcpyHostToDevice);
+    f.copy((void*)d_normal, hn.data(), 8 * n_views, hipMemcpyHostToDevice);
+    f.copy((void*)d_gray, hg.data(), 8 * n_views, hipMemcpyHostToDevice);
+    f.copy(d_src, src_idx, (size_t)(n_src_total > 0 ? n_src_total : 0) * 4, hipMemcpyHostToDevice);
+    f.zero(mask, (size_t)n_views * np);
+    f.zero(pending, (size_t)n_views * np);
     size_t tmp_bytes = 0;
-    if (rocprim::select(nullptr, tmp_bytes, rec, keep, compact, d_count, np, st) != hipSuccess) return done(TSAR_ERR_HIP);
-    void* tmp = scratch.alloc(tmp_bytes);
-    if (!tmp) return done(TSAR_ERR_NOMEM);
+    if (!f.ok() || !f.hip(rocprim::select(nullptr, tmp_bytes, rec, keep, compact, d_count, np, st), "rocprim::select sizing")) return f.finish();
+    void* tmp = f.tmp<char>(tmp_bytes);
+    if (!f.ok()) return f.finish();
     const float cos_angle = (float)cos((double)prm->angle_deg * 3.14159265358979323846 / 180.0);
     int64_t n_out = 0;
     for (int v = 0; v < n_views; v++) {
         const int ns = src_off[v + 1] - src_off[v];
         for (int k = 0; k < ns; k++)
-            if (src_idx[src_off[v] + k] < 0 || src_idx[src_off[v] + k] >= n_views) return done(TSAR_ERR_INVALID);
+            if (src_idx[src_off[v] + k] < 0 || src_idx[src_off[v] + k] >= n_views) return f.fail(TSAR_ERR_INVALID, bad_view);
         hipLaunchKernelGGL(fuse_view_kernel, dim3((unsigned)((np + FU_BLOCK - 1) / FU_BLOCK)), dim3(FU_BLOCK), 0, st, v, w, h, d_cams, d_depth, d_normal, d_gray,
                            d_src + src_off[v], ns, mask, pending, prm->num_consistent, prm->reproj_error, prm->depth_diff, cos_angle, prm->used_list ? 1 : 0, rec, keep);
-        if (rocprim::select(tmp, tmp_bytes, rec, keep, compact, d_count, np, st) != hipSuccess) return done(TSAR_ERR_HIP);
+        f.hip(rocprim::select(tmp, tmp_bytes, rec, keep, compact, d_count, np, st), "rocprim::select");
         unsigned int cnt = 0;
-        hipMemcpyAsync(&cnt, d_count, 4, hipMemcpyDeviceToHost, st);
-        if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP);
+        f.copy(&cnt, d_count, 4, hipMemcpyDeviceToHost);
+        if (!f.sync()) return f.finish();
         if (points_out && n_out < cap) {
             const int64_t take = (int64_t)cnt < cap - n_out ? (int64_t)cnt : cap - n_out;
-            hipMemcpyAsync(points_out + 9 * n_out, compact, (size_t)take * sizeof(FuRec), mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
+            f.copy(points_out + 9 * n_out, compact, (size_t)take * sizeof(FuRec), kind_from_dev(mem));
         }
         n_out += cnt;
         if (prm->used_list) {   // marks of this view become visible to the next one; only its source views can have changed
             for (int k = 0; k < ns; k++) {
                 const size_t o = (size_t)src_idx[src_off[v] + k] * np;
-                hipMemcpyAsync(mask + o, pending + o, np, hipMemcpyDeviceToDevice, st);
+                f.copy(mask + o, pending + o, np, hipMemcpyDeviceToDevice);
             }
         }
     }
     *n_points_out = n_out;
-    return done(TSAR_OK);
+    return f.finish();
 }
 
 // Context-free form (the fuser binary's one call per scene): a context of its own for the duration of the call.

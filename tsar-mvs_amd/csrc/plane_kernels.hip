@@ -280,20 +280,17 @@ __global__ __launch_bounds__(EW_BLOCK) void label_range_kernel(const int32_t* __
     if ((threadIdx.x & 63) == 0) { atomicMin(&lohi[0], lo); atomicMax(&lohi[1], hi); }
 }
 int launch_label_range(tsar_ctx* ctx, const int32_t* labels, size_t n, int32_t* lo, int32_t* hi) {
-    int32_t* d = nullptr;
-    if (hipMalloc((void**)&d, 2 * sizeof(int32_t)) != hipSuccess) { ctx->err = "hipMalloc failed"; return TSAR_ERR_NOMEM; }
+    CallFrame f(ctx, "label range check", nullptr, /*grow_arena=*/false);   // (eight bytes do not count as an overflow of the arena)
     const int32_t init[2] = {INT32_MAX, INT32_MIN};
     int32_t out[2] = {0, 0};
     const size_t blocks = (n + EW_BLOCK - 1) / EW_BLOCK;
-    hipError_t e = hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    int32_t* d = f.out(out, 2, TSAR_MEM_HOST);
+    f.copy(d, init, sizeof init, hipMemcpyHostToDevice);
+    if (f.ok()) {
         hipLaunchKernelGGL(label_range_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(EW_BLOCK), 0, ctx->stream, labels, n, d);
-        e = hipGetLastError();
+        f.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof out, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d);
-    if (e != hipSuccess) { ctx->err = std::string("label range check: ") + hipGetErrorString(e); return TSAR_ERR_HIP; }
+    TRY(f.finish());
     *lo = out[0];
     *hi = out[1];
     return TSAR_OK;

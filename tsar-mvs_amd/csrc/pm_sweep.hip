@@ -24,12 +24,14 @@ __global__ void d16_probe_kernel(uint32_t* out) {
     out[threadIdx.x] = r;
 }
 bool probe_d16_hi_zeroes(tsar_ctx* ctx) {
-    uint32_t* d = nullptr;
+    CallFrame f(ctx, "d16 probe", nullptr, /*grow_arena=*/false);   // (tsar_create has made the stream; the arena is still empty and stays so)
     uint32_t h[64];
-    if (hipMalloc((void**)&d, sizeof h) != hipSuccess) return false;
-    hipLaunchKernelGGL(d16_probe_kernel, dim3(1), dim3(64), 0, ctx->stream, d);
-    bool ok = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
-    hipFree(d);
+    uint32_t* d = f.out(h, 64, TSAR_MEM_HOST);
+    if (f.ok()) {
+        hipLaunchKernelGGL(d16_probe_kernel, dim3(1), dim3(64), 0, ctx->stream, d);
+        f.launched();
+    }
+    bool ok = f.finish() == TSAR_OK;
     for (int i = 0; ok && i < 64; i++) ok = h[i] == ((0x4300u + i) << 16);
     return ok;
 }

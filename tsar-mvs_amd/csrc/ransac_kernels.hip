@@ -12,7 +12,6 @@
 //
 // Deterministic choices (the reference uses rand() and a time-seeded shuffle): raster-order point
 // lists, even subsampling to 49999 points above 50000, Philox draws keyed by (draw, stage, region).
-#include <chrono>
 #include <mutex>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -556,96 +555,88 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
     const int nreg = ctx->n_regions;
     const size_t np = (size_t)ctx->w * ctx->h;
     hipStream_t st = ctx->stream;
-    const bool trace = ctx->trace_host;
-    auto tr0 = std::chrono::steady_clock::now();
-    auto TR = [&](const char* what) { if (trace) { hipStreamSynchronize(st); auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[ransac] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tr0).count()); tr0 = n; } };
+    CallFrame f(ctx, __func__, "[ransac]");   // temporaries come out of the context's arena (tsar_dev.h)
     std::vector<float> text(nreg);
     std::vector<int32_t> slot_of_region(nreg, -1), region_of_slot;
-    if (hipMemcpy(text.data(), ctx->region_text, (size_t)nreg * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, TSAR_ERR_HIP, "D2H failed");
+    if (!f.hip(hipMemcpy(text.data(), ctx->region_text, (size_t)nreg * 4, hipMemcpyDeviceToHost), "hipMemcpy")) return f.finish();
     for (int r = 0; r < nreg; r++)
         if (text[r] == -1.0f) { slot_of_region[r] = (int)region_of_slot.size(); region_of_slot.push_back(r); }
     const int nslot = (int)region_of_slot.size();
-    TR("text D2H + slots");
-    ScratchScope scratch(ctx);           // temporaries come out of the context's arena (tsar_dev.h)
-    auto done = [&](int rc, const char* msg) { if (msg) ctx->err = msg; hipStreamSynchronize(st); scratch.release(); return rc; };
-    float* d_ratio = (float*)scratch.alloc((size_t)nreg * 4);
-    if (!d_ratio) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
-    hipMemsetAsync(d_ratio, 0, (size_t)nreg * 4, st);
+    f.trace("text D2H + slots");
+    float* d_ratio = f.tmp<float>(nreg);
+    f.zero(d_ratio, (size_t)nreg * 4);
     if (nslot > 0) {
-        int32_t* d_slot_of_region = (int32_t*)scratch.alloc((size_t)nreg * 4);
-        int32_t* d_region_of_slot = (int32_t*)scratch.alloc((size_t)nslot * 4);
-        uint32_t* d_pix = (uint32_t*)scratch.alloc(np * 4);
-        uint32_t* d_nsel = (uint32_t*)scratch.alloc(4);
-        int* d_counts = (int*)scratch.alloc((size_t)nslot * 4);
-        if (!d_slot_of_region || !d_region_of_slot || !d_pix || !d_nsel || !d_counts) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
-        hipMemcpyAsync(d_slot_of_region, slot_of_region.data(), (size_t)nreg * 4, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(d_region_of_slot, region_of_slot.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
-        hipMemsetAsync(d_counts, 0, (size_t)nslot * 4, st);
-        TR("allocs + uploads");
+        int32_t* d_slot_of_region = f.tmp<int32_t>(nreg);
+        int32_t* d_region_of_slot = f.tmp<int32_t>(nslot);
+        uint32_t* d_pix = f.tmp<uint32_t>(np);
+        uint32_t* d_nsel = f.tmp<uint32_t>(1);
+        int* d_counts = f.tmp<int>(nslot);
+        f.copy(d_slot_of_region, slot_of_region.data(), (size_t)nreg * 4, hipMemcpyHostToDevice);
+        f.copy(d_region_of_slot, region_of_slot.data(), (size_t)nslot * 4, hipMemcpyHostToDevice);
+        f.zero(d_counts, (size_t)nslot * 4);
+        f.trace("allocs + uploads");
         // (1) raster-order list of reliable pixels inside textureless regions (main.cpp:1527-1536)
-        uint8_t* d_flag = (uint8_t*)scratch.alloc(np);
-        if (!d_flag) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+        uint8_t* d_flag = f.tmp<uint8_t>(np);
         size_t tmp_bytes = 0;
         rocprim::counting_iterator<uint32_t> first(0);
-        if (rocprim::select(nullptr, tmp_bytes, first, d_flag, d_pix, d_nsel, np, st) != hipSuccess) return done(TSAR_ERR_HIP, "rocprim::select sizing failed");
-        void* d_tmp = scratch.alloc(tmp_bytes);
-        if (!d_tmp) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+        if (!f.ok() || !f.hip(rocprim::select(nullptr, tmp_bytes, first, d_flag, d_pix, d_nsel, np, st), "rocprim::select sizing")) return f.finish();
+        void* d_tmp = f.tmp<char>(tmp_bytes);
+        if (!f.ok()) return f.finish();
         {
             ScopedKernelTimer tm(ctx, "ransac_select");
             hipLaunchKernelGGL(ransac_flag_kernel, dim3(2048), dim3(256), 0, st, ctx->canny, ctx->scale, d_slot_of_region, np, d_flag);
-            if (rocprim::select(d_tmp, tmp_bytes, first, d_flag, d_pix, d_nsel, np, st) != hipSuccess) return done(TSAR_ERR_HIP, "rocprim::select failed");
+            f.hip(rocprim::select(d_tmp, tmp_bytes, first, d_flag, d_pix, d_nsel, np, st), "rocprim::select");
         }
         uint32_t nsel = 0;
-        hipMemcpyAsync(&nsel, d_nsel, 4, hipMemcpyDeviceToHost, st);
-        if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "select failed");
-        TR("select");
+        f.copy(&nsel, d_nsel, 4, hipMemcpyDeviceToHost);
+        if (!f.sync()) return f.finish();
+        f.trace("select");
         std::vector<int> counts(nslot, 0), slot_start(nslot, 0), pts_start(nslot, 0), pts_count(nslot, 0);
         float* d_pts = nullptr;
-        int *d_slot_start = (int*)scratch.alloc((size_t)nslot * 4), *d_pts_start = (int*)scratch.alloc((size_t)nslot * 4), *d_pts_count = (int*)scratch.alloc((size_t)nslot * 4);
-        if (!d_slot_start || !d_pts_start || !d_pts_count) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+        int *d_slot_start = f.tmp<int>(nslot), *d_pts_start = f.tmp<int>(nslot), *d_pts_count = f.tmp<int>(nslot);
         if (nsel > 0) {
-            uint32_t *d_keys = (uint32_t*)scratch.alloc((size_t)nsel * 4), *d_keys2 = (uint32_t*)scratch.alloc((size_t)nsel * 4), *d_pix2 = (uint32_t*)scratch.alloc((size_t)nsel * 4);
-            if (!d_keys || !d_keys2 || !d_pix2) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+            uint32_t *d_keys = f.tmp<uint32_t>(nsel), *d_keys2 = f.tmp<uint32_t>(nsel), *d_pix2 = f.tmp<uint32_t>(nsel);
+            if (!f.ok()) return f.finish();
             hipLaunchKernelGGL(ransac_keys_kernel, dim3((nsel + 255) / 256), dim3(256), 0, st, d_pix, (int)nsel, ctx->canny, d_slot_of_region, d_keys, d_counts);
             // (2) stable sort by region keeps raster order inside each region
             int bits = 1;
             while ((1 << bits) < nslot) bits++;
             size_t sort_bytes = 0;
-            if (rocprim::radix_sort_pairs(nullptr, sort_bytes, d_keys, d_keys2, d_pix, d_pix2, nsel, 0, bits, st) != hipSuccess) return done(TSAR_ERR_HIP, "radix sort sizing failed");
-            void* d_sort_tmp = scratch.alloc(sort_bytes);
-            if (!d_sort_tmp) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+            if (!f.hip(rocprim::radix_sort_pairs(nullptr, sort_bytes, d_keys, d_keys2, d_pix, d_pix2, nsel, 0, bits, st), "rocprim::radix_sort_pairs sizing")) return f.finish();
+            void* d_sort_tmp = f.tmp<char>(sort_bytes);
+            if (!f.ok()) return f.finish();
             {
                 ScopedKernelTimer tm(ctx, "ransac_sort");
-                if (rocprim::radix_sort_pairs(d_sort_tmp, sort_bytes, d_keys, d_keys2, d_pix, d_pix2, nsel, 0, bits, st) != hipSuccess) return done(TSAR_ERR_HIP, "radix sort failed");
+                f.hip(rocprim::radix_sort_pairs(d_sort_tmp, sort_bytes, d_keys, d_keys2, d_pix, d_pix2, nsel, 0, bits, st), "rocprim::radix_sort_pairs");
             }
-            hipMemcpyAsync(counts.data(), d_counts, (size_t)nslot * 4, hipMemcpyDeviceToHost, st);
-            if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "sort failed");
-            TR("keys + sort + counts D2H");
+            f.copy(counts.data(), d_counts, (size_t)nslot * 4, hipMemcpyDeviceToHost);
+            if (!f.sync()) return f.finish();
+            f.trace("keys + sort + counts D2H");
             int acc = 0, pacc = 0;
             for (int s = 0; s < nslot; s++) {
                 slot_start[s] = acc; acc += counts[s];
                 pts_count[s] = counts[s] > 50000 ? RS_MAXPTS : counts[s];      // main.cpp:1540-1549
                 pts_start[s] = pacc; pacc += pts_count[s];
             }
-            d_pts = (float*)scratch.alloc((size_t)(pacc > 0 ? pacc : 1) * 12);
-            if (!d_pts) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
-            hipMemcpyAsync(d_slot_start, slot_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
-            hipMemcpyAsync(d_counts, counts.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
-            hipMemcpyAsync(d_pts_start, pts_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
+            d_pts = f.tmp<float>((size_t)(pacc > 0 ? pacc : 1) * 3);
+            f.copy(d_slot_start, slot_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice);
+            f.copy(d_counts, counts.data(), (size_t)nslot * 4, hipMemcpyHostToDevice);
+            f.copy(d_pts_start, pts_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice);
+            if (!f.ok()) return f.finish();
             {
                 ScopedKernelTimer tm(ctx, "ransac_points");
                 hipLaunchKernelGGL(ransac_points_kernel, dim3((nsel + 255) / 256), dim3(256), 0, st, ctx->dscene, d_pix2, d_keys2, (int)nsel, ctx->depth, d_slot_start,
                                    d_counts, d_pts_start, d_pts);
             }
         } else {
-            d_pts = (float*)scratch.alloc(12);
-            hipMemcpyAsync(d_pts_start, pts_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
+            d_pts = f.tmp<float>(3);              // (no point: never read)
+            f.copy(d_pts_start, pts_start.data(), (size_t)nslot * 4, hipMemcpyHostToDevice);
         }
-        hipMemcpyAsync(d_pts_count, pts_count.data(), (size_t)nslot * 4, hipMemcpyHostToDevice, st);
-        TR("points");
-        RansacState* d_state = (RansacState*)scratch.alloc((size_t)nslot * sizeof(RansacState));
-        int* d_cnt = (int*)scratch.alloc((size_t)nslot * RS_PHASE * sizeof(int));
-        if (!d_state || !d_cnt) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+        f.copy(d_pts_count, pts_count.data(), (size_t)nslot * 4, hipMemcpyHostToDevice);
+        f.trace("points");
+        RansacState* d_state = f.tmp<RansacState>(nslot);
+        int* d_cnt = f.tmp<int>((size_t)nslot * RS_PHASE);
+        if (!f.ok()) return f.finish();
         // stage 2, measured on six ~50 000-point regions: the history tree with lookahead 1 / 2 / 3 -> 25.9 / 26.4 / 33.7 ms (the passes
         // are bound by the CU's FP64 rate, so the extra planes of a tree cost what the saved passes return); the speculative chain of
         // 8 steps 17.5 ms; the chain on 8 CUs per region 5.3 ms (the default).
@@ -672,16 +663,17 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
             if (wgs > n_cu / (nslot > 0 ? nslot : 1)) wgs = n_cu / (nslot > 0 ? nslot : 1);
             bool fitted = false;
             if (lookahead < 1 && wgs >= 2) {
-                int* d_sync = (int*)scratch.alloc((size_t)nslot * RS_SYNC_INTS * 4 + 4);
-                if (!d_sync) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+                int* d_sync = f.tmp<int>((size_t)nslot * RS_SYNC_INTS + 1);
                 int* d_failed = d_sync + (size_t)nslot * RS_SYNC_INTS;
-                hipMemsetAsync(d_sync, 0, (size_t)nslot * RS_SYNC_INTS * 4 + 4, st);
+                f.zero(d_sync, (size_t)nslot * RS_SYNC_INTS * 4 + 4);
                 // diagnostics: TSAR_RANSAC_FORCE_FALLBACK=1 pre-sets `failed` (the give-up path: every workgroup leaves, the
                 // single-workgroup kernel below produces the result); TSAR_RANSAC_POLL_LIMIT=n bounds a wait (default 2^15 polls
                 // of ~0.3 us: ~10 ms, three orders of magnitude above a pass)
                 const bool force_fallback = ctx->ransac_force_fallback;
                 int poll_limit = ctx->ransac_poll_limit;
-                if (force_fallback) { const int one = 1; hipMemcpyAsync(d_failed, &one, 4, hipMemcpyHostToDevice, st); }
+                const int one = 1;
+                if (force_fallback) f.copy(d_failed, &one, 4, hipMemcpyHostToDevice);
+                if (!f.ok()) return f.finish();
                 const void* mw = chain == 4 ? (const void*)ransac_refine_chain_mw_kernel<4> : (chain == 16 ? (const void*)ransac_refine_chain_mw_kernel<16> : (const void*)ransac_refine_chain_mw_kernel<8>);
                 const float* a_pts = d_pts; const int *a_ps = d_pts_start, *a_pc = d_pts_count, *a_rs = d_region_of_slot, *a_cnt = d_cnt;
                 uint32_t a_k0 = ctx->hscene.seed_lo, a_k1 = ctx->hscene.seed_hi, a_fl = ctx->hscene.flags;
@@ -704,25 +696,24 @@ extern "C" int tsar_ransac_regions(tsar_ctx* ctx, float* region_planes_out, floa
                                      : hipLaunchKernel(mw, dim3(nslot * wgs), dim3(RS_BLOCK), args, 0, st);
                 if (le == hipSuccess) {
                     int h_failed = 1;
-                    hipMemcpyAsync(&h_failed, d_failed, 4, hipMemcpyDeviceToHost, st);
-                    if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "ransac kernel failed");
+                    f.copy(&h_failed, d_failed, 4, hipMemcpyDeviceToHost);
+                    if (!f.sync()) return f.finish();
                     fitted = h_failed == 0;                   // else: the workgroups were not resident together; one per region below
                 } else {
                     (void)hipGetLastError();                  // the grid could not be placed as a whole (or no cooperative launches here): one workgroup per region below
                 }
                 if (coop) coop_lock.unlock();
-                if (trace) fprintf(stderr, "[ransac] stage 2 on %d workgroups per region: %s%s\n", wgs, coop ? "cooperative launch" : "plain launch", fitted ? "" : " -> fallback to one workgroup per region");
+                if (ctx->trace_host) fprintf(stderr, "[ransac] stage 2 on %d workgroups per region: %s%s\n", wgs, coop ? "cooperative launch" : "plain launch", fitted ? "" : " -> fallback to one workgroup per region");
             }
             if (!fitted)
                 hipLaunchKernelGGL(refine, dim3(nslot), dim3(RS_BLOCK), 0, st, d_pts, d_pts_start, d_pts_count, d_region_of_slot, ctx->hscene.seed_lo,
                                    ctx->hscene.seed_hi, ctx->hscene.flags, d_state, d_cnt, ctx->region_n4, d_ratio);
         }
-        if (hipGetLastError() != hipSuccess) return done(TSAR_ERR_HIP, "ransac launch failed");
-        TR("fit");
+        if (!f.launched()) return f.finish();
+        f.trace("fit");
     }
-    if (region_planes_out) hipMemcpyAsync(region_planes_out, ctx->region_n4, (size_t)nreg * 16, hipMemcpyDeviceToHost, st);
-    if (inlier_ratio_out) hipMemcpyAsync(inlier_ratio_out, d_ratio, (size_t)nreg * 4, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "ransac kernel failed");
-    TR("outputs D2H");
-    return done(TSAR_OK, nullptr);
+    if (region_planes_out) f.copy(region_planes_out, ctx->region_n4, (size_t)nreg * 16, hipMemcpyDeviceToHost);
+    if (inlier_ratio_out) f.copy(inlier_ratio_out, d_ratio, (size_t)nreg * 4, hipMemcpyDeviceToHost);
+    f.trace("outputs D2H");
+    return f.finish();
 }

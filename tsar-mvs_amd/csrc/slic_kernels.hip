@@ -225,20 +225,17 @@ extern "C" int tsar_slic(tsar_ctx* ctx, const uint8_t* bgra, int w, int h, const
     const int mw = w / S, mh = h / S;                                  // (int)ceil(int / int), GPU.cu:70-71
     const int nblk = (int)ceilf((float)(S * S * 9) / 256.0f);          // no_grid_per_center GPU.cu:77-79
     const int bpl = S * 3 / 16 < 1 ? 1 : S * 3 / 16;                   // no_blocks_per_line GPU.cu:160
-    // temporaries from the context's scratch arena (tsar_dev.h ScratchScope): five hipMalloc + hipFree per call cost 22 ms of
+    // temporaries from the context's scratch arena (tsar_dev.h CallFrame): five hipMalloc + hipFree per call cost 22 ms of
     // wall time around 1.3 ms of kernels at 1512 x 1008 (profiles/r02)
-    ScratchScope scratch(ctx);
-    int rc = TSAR_OK;
-    auto cleanup = [&]() { hipStreamSynchronize(ctx->stream); scratch.release(); };
-#define SL_TRY(e) do { if ((e) != hipSuccess) { ctx->err = #e " failed"; cleanup(); return TSAR_ERR_HIP; } } while (0)
-    uchar4* d_in = (uchar4*)scratch.alloc(np * 4);
-    float4* d_lab = (float4*)scratch.alloc(np * 16);
-    int32_t* d_idx = (int32_t*)scratch.alloc(np * 4);
-    int32_t* d_tmp = st->do_enforce_connectivity ? (int32_t*)scratch.alloc(np * 4) : nullptr;
-    Spixel* d_sp = (Spixel*)scratch.alloc((size_t)mw * mh * sizeof(Spixel));
-    if (!d_in || !d_lab || !d_idx || !d_sp || (st->do_enforce_connectivity && !d_tmp)) { cleanup(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
-    SL_TRY(hipMemcpyAsync(d_in, bgra, np * 4, mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    SL_TRY(hipMemsetAsync(d_idx, 0, np * 4, ctx->stream));
+    CallFrame f(ctx, __func__);
+    uchar4* d_in = f.tmp<uchar4>(np);
+    float4* d_lab = f.tmp<float4>(np);
+    int32_t* d_idx = f.tmp<int32_t>(np);
+    int32_t* d_tmp = st->do_enforce_connectivity ? f.tmp<int32_t>(np) : nullptr;
+    Spixel* d_sp = f.tmp<Spixel>((size_t)mw * mh);
+    f.copy(d_in, bgra, np * 4, kind_to_dev(mem));
+    f.zero(d_idx, np * 4);
+    if (!f.ok()) return f.finish();
     const dim3 g1((unsigned)((np + SL_BLOCK - 1) / SL_BLOCK)), g2((w + 31) / 32, (h + 7) / 8), b(SL_BLOCK);
     { ScopedKernelTimer tm(ctx, "slic_cvt"); hipLaunchKernelGGL(slic_cvt_kernel, g1, b, 0, ctx->stream, d_in, d_lab, (int)np, st->color_space); }
     { ScopedKernelTimer tm(ctx, "slic_init"); hipLaunchKernelGGL(slic_init_kernel, dim3((mw * mh + 255) / 256), dim3(256), 0, ctx->stream, d_lab, d_sp, w, h, mw, mh, S); }
@@ -252,11 +249,9 @@ extern "C" int tsar_slic(tsar_ctx* ctx, const uint8_t* bgra, int w, int h, const
         { ScopedKernelTimer tm(ctx, "slic_connect"); hipLaunchKernelGGL(slic_connect_kernel, g2, b, 0, ctx->stream, d_idx, d_tmp, w, h); }
         { ScopedKernelTimer tm(ctx, "slic_connect"); hipLaunchKernelGGL(slic_connect_kernel, g2, b, 0, ctx->stream, d_tmp, d_idx, w, h); }
     }
-    SL_TRY(hipGetLastError());
-    SL_TRY(hipMemcpyAsync(labels_out, d_idx, np * 4, mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    SL_TRY(hipStreamSynchronize(ctx->stream));
-    cleanup();
-    return rc;
+    f.launched();
+    f.copy(labels_out, d_idx, np * 4, kind_from_dev(mem));
+    return f.finish();
 }
 
 // The stages of tsar_slic one at a time on caller-supplied HOST inputs (include/tsar.h "self-tests"): lets a test hold each kernel
@@ -272,19 +267,18 @@ extern "C" int tsar_selftest_slic_stage(tsar_ctx* ctx, int stage, int w, int h, 
     if (stage == 2 && !in1) return fail(ctx, TSAR_ERR_INVALID, "stage 2 needs centres");
     if (stage == 3 && (!in1 || mw != w / S || mh != h / S)) return fail(ctx, TSAR_ERR_INVALID, "stage 3 needs labels and the engine's own map size");
     const size_t np = (size_t)w * h, nc = (size_t)mw * mh;
-    ScratchScope scratch(ctx);
-    auto cleanup = [&]() { hipStreamSynchronize(ctx->stream); scratch.release(); };
+    CallFrame f(ctx, __func__);
     const dim3 g1((unsigned)((np + SL_BLOCK - 1) / SL_BLOCK)), g2((w + 31) / 32, (h + 7) / 8), b(SL_BLOCK);
     const size_t in0_bytes = stage == 0 ? np * 4 : stage == 4 ? np * 4 : np * 16;
     const size_t in1_bytes = stage == 2 ? nc * sizeof(Spixel) : stage == 3 ? np * 4 : 0;
     const size_t io_bytes = stage == 0 ? np * 16 : (stage == 1 || stage == 3) ? nc * sizeof(Spixel) : np * 4;
-    void* d0 = scratch.alloc(in0_bytes);
-    void* d1 = in1_bytes ? scratch.alloc(in1_bytes) : nullptr;
-    void* dio = scratch.alloc(io_bytes);
-    if (!d0 || !dio || (in1_bytes && !d1)) { cleanup(); return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed"); }
-    SL_TRY(hipMemcpyAsync(d0, in0, in0_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (in1_bytes) SL_TRY(hipMemcpyAsync(d1, in1, in1_bytes, hipMemcpyHostToDevice, ctx->stream));
-    SL_TRY(hipMemcpyAsync(dio, inout, io_bytes, hipMemcpyHostToDevice, ctx->stream));   // stage 2 keeps labels no centre claims
+    void* d0 = f.tmp<char>(in0_bytes);
+    void* d1 = in1_bytes ? f.tmp<char>(in1_bytes) : nullptr;
+    void* dio = f.tmp<char>(io_bytes);
+    f.copy(d0, in0, in0_bytes, hipMemcpyHostToDevice);
+    if (in1_bytes) f.copy(d1, in1, in1_bytes, hipMemcpyHostToDevice);
+    f.copy(dio, inout, io_bytes, hipMemcpyHostToDevice);   // stage 2 keeps labels no centre claims
+    if (!f.ok()) return f.finish();
     switch (stage) {
     case 0: hipLaunchKernelGGL(slic_cvt_kernel, g1, b, 0, ctx->stream, (const uchar4*)d0, (float4*)dio, (int)np, st->color_space); break;
     case 1: hipLaunchKernelGGL(slic_init_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d0, (Spixel*)dio, w, h, mw, mh, S); break;
@@ -296,9 +290,7 @@ extern "C" int tsar_selftest_slic_stage(tsar_ctx* ctx, int stage, int w, int h, 
     }
     default: hipLaunchKernelGGL(slic_connect_kernel, g2, b, 0, ctx->stream, (const int32_t*)d0, (int32_t*)dio, w, h); break;
     }
-    SL_TRY(hipGetLastError());
-    SL_TRY(hipMemcpyAsync(inout, dio, io_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SL_TRY(hipStreamSynchronize(ctx->stream));
-    cleanup();
-    return TSAR_OK;
+    f.launched();
+    f.copy(inout, dio, io_bytes, hipMemcpyDeviceToHost);
+    return f.finish();
 }

@@ -12,7 +12,6 @@
 // Deviations: the HoughLinesP boundary closing (main.cpp:391-435) is OpenCV-internal and
 // randomised and is not reproduced; components are the true 4-connected ones, whereas Connect()'s parent
 // overwrite can lose a link in rare shapes.
-#include <chrono>
 #include <rocprim/device/device_scan.hpp>
 
 #include "tsar_dev.h"
@@ -291,15 +290,11 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
     if (w4 < 3 || h4 < 3) return fail(ctx, TSAR_ERR_INVALID, "image too small for weak-texture detection");
     const int n4 = w4 * h4;
     hipStream_t st = ctx->stream;
-    const bool trace = ctx->trace_host;     // host-side steps on stderr (diagnostics)
-    auto tr0 = std::chrono::steady_clock::now();
-    auto TR = [&](const char* what) { if (trace) { hipStreamSynchronize(st); auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[weak_texture] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tr0).count()); tr0 = n; } };
-    ScratchScope scratch(ctx);           // temporaries come out of the context's arena (tsar_dev.h)
-    auto done = [&](int rc, const char* msg) { if (msg) ctx->err = msg; hipStreamSynchronize(st); scratch.release(); return rc; };
-    uint8_t *g0 = (uint8_t*)scratch.alloc((size_t)w * h), *g2 = (uint8_t*)scratch.alloc((size_t)w2 * h2), *g4 = (uint8_t*)scratch.alloc(n4), *edge = (uint8_t*)scratch.alloc(n4);
-    int *parent = (int*)scratch.alloc((size_t)n4 * 4), *is_root = (int*)scratch.alloc((size_t)n4 * 4), *rank = (int*)scratch.alloc((size_t)n4 * 4);
-    int32_t* lab4 = (int32_t*)scratch.alloc((size_t)n4 * 4);
-    if (!g0 || !g2 || !g4 || !edge || !parent || !is_root || !rank || !lab4) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+    CallFrame f(ctx, __func__, "[weak_texture]");   // temporaries come out of the context's arena (tsar_dev.h); host-side steps on stderr
+    uint8_t *g0 = f.tmp<uint8_t>((size_t)w * h), *g2 = f.tmp<uint8_t>((size_t)w2 * h2), *g4 = f.tmp<uint8_t>(n4), *edge = f.tmp<uint8_t>(n4);
+    int *parent = f.tmp<int>(n4), *is_root = f.tmp<int>(n4), *rank = f.tmp<int>(n4);
+    int32_t* lab4 = f.tmp<int32_t>(n4);
+    if (!f.ok()) return f.finish();
     const dim3 b(TX_BLOCK);
     auto grid2 = [](int ww, int hh) { return dim3((ww + 31) / 32, (hh + 7) / 8); };
     {
@@ -309,16 +304,15 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
         hipLaunchKernelGGL(tx_pyrdown_kernel, grid2(w4, h4), b, 0, st, g2, w2, h2, g4);
         hipLaunchKernelGGL(tx_roberts_kernel, grid2(w4, h4), b, 0, st, g4, w4, h4, edge);
     }
-    TR("allocs + pyramid + edges");
+    f.trace("allocs + pyramid + edges");
     if (!(ctx->hscene.flags & TSAR_FLAG_NO_LINE_CLOSING)) {
         // first labelling (before the border fix) -> large components -> close gaps in their straight boundaries
-        int* cnt0 = (int*)scratch.alloc((size_t)n4 * 4);
-        int* wlist = (int*)scratch.alloc((size_t)TX_MAX_WEAK * 4 + 4);
+        int* cnt0 = f.tmp<int>(n4);
+        int* wlist = f.tmp<int>(TX_MAX_WEAK + 1);
         const int rmax = w4 + h4 + 2, nrho = 2 * rmax + 1;
-        int* acc = (int*)scratch.alloc((size_t)180 * nrho * 4);
-        uint8_t* bmask = (uint8_t*)scratch.alloc(n4);
-        float* tabs = (float*)scratch.alloc(360 * 4);
-        if (!cnt0 || !wlist || !acc || !bmask || !tabs) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+        int* acc = f.tmp<int>((size_t)180 * nrho);
+        uint8_t* bmask = f.tmp<uint8_t>(n4);
+        float* tabs = f.tmp<float>(360);
         float htab[360];
         for (int t = 0; t < 180; t++) {
             const double a = (double)t * 3.14159265358979323846 / 180.0;
@@ -326,27 +320,29 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
             htab[180 + t] = (float)sin(a);
         }
         ScopedKernelTimer tm(ctx, "weak_texture_closing");
-        hipMemcpyAsync(tabs, htab, sizeof htab, hipMemcpyHostToDevice, st);
-        hipMemsetAsync(cnt0, 0, (size_t)n4 * 4, st);
-        hipMemsetAsync(wlist, 0, (size_t)TX_MAX_WEAK * 4 + 4, st);
+        f.copy(tabs, htab, sizeof htab, hipMemcpyHostToDevice);
+        f.zero(cnt0, (size_t)n4 * 4);
+        f.zero(wlist, (size_t)TX_MAX_WEAK * 4 + 4);
+        if (!f.ok()) return f.finish();
         hipLaunchKernelGGL(tx_ccl_init_kernel, dim3((n4 + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, edge, parent, n4);
         hipLaunchKernelGGL(tx_ccl_merge_kernel, grid2(w4, h4), b, 0, st, edge, parent, w4, h4);
         hipLaunchKernelGGL(tx_ccl_flatten_kernel, dim3((n4 + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, edge, parent, is_root, n4);
         hipLaunchKernelGGL(tx_root_count_kernel, dim3((n4 + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, parent, cnt0, n4);
         hipLaunchKernelGGL(tx_weak_roots_kernel, dim3((n4 + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, cnt0, n4, wlist + 1, wlist);
         std::vector<int> hl(TX_MAX_WEAK + 1);
-        hipMemcpyAsync(hl.data(), wlist, (size_t)TX_MAX_WEAK * 4 + 4, hipMemcpyDeviceToHost, st);
-        if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "weak-texture kernels failed");
-        TR("first labelling + large components D2H");
+        f.copy(hl.data(), wlist, (size_t)TX_MAX_WEAK * 4 + 4, hipMemcpyDeviceToHost);
+        if (!f.sync()) return f.finish();
+        f.trace("first labelling + large components D2H");
         const int nweak = hl[0] < TX_MAX_WEAK ? hl[0] : TX_MAX_WEAK;
         for (int k = 0; k < nweak; k++) {                     // independent of each other: masks come from the first labelling
-            hipMemsetAsync(acc, 0, (size_t)180 * nrho * 4, st);
-            hipMemsetAsync(bmask, 0, (size_t)n4, st);
+            f.zero(acc, (size_t)180 * nrho * 4);
+            f.zero(bmask, (size_t)n4);
+            if (!f.ok()) return f.finish();
             hipLaunchKernelGGL(tx_hough_vote_kernel, grid2(w4, h4), b, 0, st, parent, hl[1 + k], w4, h4, tabs, tabs + 180, bmask, acc, nrho, rmax);
             hipLaunchKernelGGL(tx_hough_segments_kernel, dim3((nrho + TX_BLOCK - 1) / TX_BLOCK, 180), b, 0, st, acc, nrho, rmax, tabs, tabs + 180, bmask, edge, w4, h4);
         }
     }
-    TR("line closing");
+    f.trace("line closing");
     {
         ScopedKernelTimer tm(ctx, "weak_texture_label");
         hipLaunchKernelGGL(tx_border_rows_kernel, dim3((h4 + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, edge, w4, h4);
@@ -355,41 +351,37 @@ extern "C" int tsar_detect_weak_texture(tsar_ctx* ctx, int32_t* labels_out, int 
         hipLaunchKernelGGL(tx_ccl_merge_kernel, grid2(w4, h4), b, 0, st, edge, parent, w4, h4);
         hipLaunchKernelGGL(tx_ccl_flatten_kernel, dim3((n4 + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, edge, parent, is_root, n4);
     }
-    TR("second labelling");
+    f.trace("second labelling");
     size_t tmp_bytes = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, is_root, rank, 0, (size_t)n4, rocprim::plus<int>(), st) != hipSuccess) return done(TSAR_ERR_HIP, "scan sizing failed");
-    void* tmp = scratch.alloc(tmp_bytes);
-    if (!tmp) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
-    if (rocprim::exclusive_scan(tmp, tmp_bytes, is_root, rank, 0, (size_t)n4, rocprim::plus<int>(), st) != hipSuccess) return done(TSAR_ERR_HIP, "scan failed");
+    if (!f.hip(rocprim::exclusive_scan(nullptr, tmp_bytes, is_root, rank, 0, (size_t)n4, rocprim::plus<int>(), st), "rocprim::exclusive_scan sizing")) return f.finish();
+    void* tmp = f.tmp<char>(tmp_bytes);
+    if (!f.ok()) return f.finish();
+    f.hip(rocprim::exclusive_scan(tmp, tmp_bytes, is_root, rank, 0, (size_t)n4, rocprim::plus<int>(), st), "rocprim::exclusive_scan");
     int last_rank = 0, last_flag = 0;
-    hipMemcpyAsync(&last_rank, rank + (n4 - 1), 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(&last_flag, is_root + (n4 - 1), 4, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return done(TSAR_ERR_HIP, "weak-texture kernels failed");
-    TR("scan + count D2H");
+    f.copy(&last_rank, rank + (n4 - 1), 4, hipMemcpyDeviceToHost);
+    f.copy(&last_flag, is_root + (n4 - 1), 4, hipMemcpyDeviceToHost);
+    if (!f.sync()) return f.finish();
+    f.trace("scan + count D2H");
     const int labelnum = last_rank + last_flag + 1;                          // + label 0 (edge pixels)
-    int* stats = (int*)scratch.alloc((size_t)labelnum * 7 * 4);
-    if (!stats) return done(TSAR_ERR_NOMEM, "hipMalloc failed");
+    int* stats = f.tmp<int>((size_t)labelnum * 7);
     int *count = stats, *sumx = stats + labelnum, *sumy = stats + 2 * labelnum, *xmin = stats + 3 * labelnum, *xmax = stats + 4 * labelnum,
         *ymin = stats + 5 * labelnum, *ymax = stats + 6 * labelnum;
-    hipMemsetAsync(stats, 0, (size_t)labelnum * 3 * 4, st);
+    f.zero(stats, (size_t)labelnum * 3 * 4);
+    if (!f.ok()) return f.finish();
     hipLaunchKernelGGL(tx_stats_init_kernel, dim3((labelnum + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, xmin, xmax, ymin, ymax, labelnum, w4, h4);
     hipLaunchKernelGGL(tx_label_stats_kernel, grid2(w4, h4), b, 0, st, parent, rank, lab4, w4, h4, count, sumx, sumy, xmin, xmax, ymin, ymax);
-    TR("label statistics");
-    // install as the context's regions
-    hipFree(ctx->region_text); hipFree(ctx->region_size); hipFree(ctx->region_n4);
-    ctx->region_text = nullptr; ctx->region_size = nullptr; ctx->region_n4 = nullptr;
-    if (hipMalloc((void**)&ctx->region_text, (size_t)labelnum * 4) != hipSuccess || hipMalloc((void**)&ctx->region_size, (size_t)labelnum * 4) != hipSuccess ||
-        hipMalloc((void**)&ctx->region_n4, (size_t)labelnum * 16) != hipSuccess)
-        return done(TSAR_ERR_NOMEM, "hipMalloc failed");
-    hipMemsetAsync(ctx->region_n4, 0, (size_t)labelnum * 16, st);
+    f.trace("label statistics");
+    // install as the context's regions (n_regions is 0 until the tables and the labels are queued)
+    f.take(install_regions(ctx, labelnum));
+    if (!f.ok()) return f.finish();
     hipLaunchKernelGGL(tx_classify_kernel, dim3((labelnum + TX_BLOCK - 1) / TX_BLOCK), b, 0, st, count, xmin, xmax, ymin, ymax, ctx->region_text, ctx->region_size, labelnum);
     hipLaunchKernelGGL(tx_upsample_kernel, grid2(w, h), b, 0, st, lab4, w4, h4, w, h, ctx->canny);
-    if (hipGetLastError() != hipSuccess) return done(TSAR_ERR_HIP, "weak-texture launch failed");
+    if (!f.launched()) return f.finish();
     ctx->n_regions = labelnum;
-    if (labels_out) hipMemcpyAsync(labels_out, ctx->canny, (size_t)w * h * 4, mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
-    if (text_out) hipMemcpyAsync(text_out, ctx->region_text, (size_t)(labelnum < cap ? labelnum : cap) * 4, hipMemcpyDeviceToHost, st);
-    if (size_out) hipMemcpyAsync(size_out, ctx->region_size, (size_t)(labelnum < cap ? labelnum : cap) * 4, hipMemcpyDeviceToHost, st);
+    if (labels_out) f.copy(labels_out, ctx->canny, (size_t)w * h * 4, kind_from_dev(mem));
+    if (text_out) f.copy(text_out, ctx->region_text, (size_t)(labelnum < cap ? labelnum : cap) * 4, hipMemcpyDeviceToHost);
+    if (size_out) f.copy(size_out, ctx->region_size, (size_t)(labelnum < cap ? labelnum : cap) * 4, hipMemcpyDeviceToHost);
     if (n_regions_out) *n_regions_out = labelnum;
-    TR("region tables + classify + upsample + outputs");
-    return done(hipStreamSynchronize(st) == hipSuccess ? TSAR_OK : TSAR_ERR_HIP, nullptr);
+    f.trace("region tables + classify + upsample + outputs");
+    return f.finish();
 }

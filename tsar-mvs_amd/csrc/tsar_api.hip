@@ -43,41 +43,13 @@ static void drain_timers(tsar_ctx* ctx) {
 }
 
 // ---- helpers -------------------------------------------------------------------------------------
-// (fail, CHECK_CTX, NEED_*, TRY, dev_alloc and DevTmp: tsar_dev.h, shared with the operators' own files)
+// (fail, CHECK_CTX, NEED_*, TRY, dev_alloc, DevTmp, the copy kinds, install_regions and CallFrame — what a call that stages buffers
+// or needs temporaries is written with — : tsar_dev.h, shared with the operators' own files)
 template <typename T>
 static void dev_free(T*& p) {
     if (p) hipFree(p);
     p = nullptr;
 }
-static hipMemcpyKind in_kind(int mem) { return mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
-static hipMemcpyKind out_kind(int mem) { return mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
-
-template <typename T>
-struct TmpIn {   // device view of a caller buffer (copies host buffers in)
-    tsar_ctx* ctx;
-    const T* d = nullptr;
-    DevTmp<T> owned;
-    int rc = TSAR_OK;
-    // scratch: take the staging buffer from the context's arena (tsar_dev.h ScratchScope) instead of a hipMalloc per call
-    TmpIn(tsar_ctx* c, const T* src, size_t n, int mem, ScratchScope* scratch = nullptr) : ctx(c) {
-        if (!src) return;
-        if (mem == TSAR_MEM_DEVICE) { d = src; return; }
-        T* staging = nullptr;
-        if (scratch) {
-            staging = (T*)scratch->alloc(n * sizeof(T));
-            if (!staging) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
-        } else {
-            rc = owned.alloc(ctx, n);
-            staging = owned.p;
-        }
-        if (rc == TSAR_OK && hipMemcpyAsync(staging, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "H2D failed");
-        d = staging;
-    }
-    ~TmpIn() {
-        if (owned.p) hipStreamSynchronize(ctx->stream);
-    }
-};
-
 static void inv3(const double* m, double* o) {
     const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
     const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
@@ -421,12 +393,12 @@ static int upload_views(tsar_ctx* ctx, int n_views, int w, int h, const void* co
     if ((int)ctx->dquad.size() < n_views) ctx->dquad.resize(n_views, nullptr);
     DevTmp<int> dflag;
     TRY(dflag.alloc(ctx, 1));
-    hipMemsetAsync(dflag.p, 0, sizeof(int), ctx->stream);
+    TSAR_HIP_TRY(ctx, hipMemsetAsync(dflag.p, 0, sizeof(int), ctx->stream));
     for (int v = 0; v < n_views; v++) {
         if (!ctx->img[v]) TRY(dev_alloc(ctx, &ctx->img[v], np));
         if (!ctx->quad[v]) TRY(dev_alloc(ctx, &ctx->quad[v], (size_t)(w + 2) * (h + 2)));
         if (elem == 4) {
-            TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->img[v], gray[v], np * sizeof(float), in_kind(mem), ctx->stream));
+            TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->img[v], gray[v], np * sizeof(float), kind_to_dev(mem), ctx->stream));
         } else if (mem == TSAR_MEM_DEVICE) {
             TRY(launch_expand_u8(ctx, (const uint8_t*)gray[v], ctx->img[v], np));
         } else {
@@ -648,16 +620,12 @@ extern "C" int tsar_pm_iterate_final(tsar_ctx* ctx, int iters, const float* text
     NEED_STATE(ctx);
     if (iters < 0) return fail(ctx, TSAR_ERR_INVALID, "iters must be >= 0");
     if (!text) return fail(ctx, TSAR_ERR_INVALID, "text is NULL");
-    const size_t np = (size_t)ctx->w * ctx->h;
-    int rc = TSAR_OK;
-    {
-        TmpIn<float> t(ctx, text, np, mem);
-        TRY(t.rc);
-        ctx->final_text = t.d;
-        rc = pm_sweeps(ctx, 2 * iters, 0, 1, 1);
-        ctx->final_text = nullptr;
-        if (rc == TSAR_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "sweep failed");
-    }
+    CallFrame f(ctx, __func__, nullptr, /*grow_arena=*/false);
+    ctx->final_text = f.in(text, (size_t)ctx->w * ctx->h, mem);
+    if (!f.ok()) { ctx->final_text = nullptr; return f.finish(); }   // nothing was swept
+    f.take(pm_sweeps(ctx, 2 * iters, 0, 1, 1));
+    ctx->final_text = nullptr;
+    const int rc = f.finish();
     ctx->result_voided();
     return rc;
 }
@@ -685,25 +653,13 @@ extern "C" int tsar_pm_cost_planes(tsar_ctx* ctx, const float* planes, int mem, 
     NEED_SOURCES(ctx);
     if (!planes || !cost_out) return fail(ctx, TSAR_ERR_INVALID, "planes/cost_out is NULL");
     const size_t np = (size_t)ctx->w * ctx->h;
-    if (mem == TSAR_MEM_DEVICE) {
-        TRY(launch_pm_cost_planes(ctx, (const float4*)planes, cost_out, beview_out, ratio_out));
-        TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return TSAR_OK;
-    }
-    DevTmp<float4> dpl;                    // (per call, not from the scratch arena: a diagnostic does not grow what the context keeps)
-    DevTmp<float> dc, drt;
-    DevTmp<int32_t> dbv;
-    TRY(dpl.alloc(ctx, np));
-    TRY(dc.alloc(ctx, np));
-    TRY(drt.alloc(ctx, np));
-    TRY(dbv.alloc(ctx, np));
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(dpl.p, planes, np * 16, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch_pm_cost_planes(ctx, dpl.p, dc.p, dbv.p, drt.p));
-    hipMemcpyAsync(cost_out, dc.p, np * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (beview_out) hipMemcpyAsync(beview_out, dbv.p, np * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (ratio_out) hipMemcpyAsync(ratio_out, drt.p, np * 4, hipMemcpyDeviceToHost, ctx->stream);
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (a failed copy shows here)
-    return TSAR_OK;
+    CallFrame f(ctx, __func__, nullptr, /*grow_arena=*/false);   // a diagnostic does not grow what the context keeps
+    const float4* dpl = (const float4*)f.in(planes, 4 * np, mem);
+    float* dc = f.out(cost_out, np, mem);
+    int32_t* dbv = f.out(beview_out, np, mem);
+    float* drt = f.out(ratio_out, np, mem);
+    if (f.ok()) f.take(launch_pm_cost_planes(ctx, dpl, dc, dbv, drt));
+    return f.finish();
 }
 
 extern "C" int tsar_set_plane(tsar_ctx* ctx, const float* planes, const float* cost, int mem) {
@@ -711,8 +667,8 @@ extern "C" int tsar_set_plane(tsar_ctx* ctx, const float* planes, const float* c
     NEED_VIEWS(ctx);
     if (!planes || !cost) return fail(ctx, TSAR_ERR_INVALID, "planes/cost is NULL");
     const size_t np = (size_t)ctx->w * ctx->h;
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[0].n4, planes, np * 16, in_kind(mem), ctx->stream));
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[0].c, cost, np * 4, in_kind(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[0].n4, planes, np * 16, kind_to_dev(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->buf[0].c, cost, np * 4, kind_to_dev(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->state_given();
     return TSAR_OK;
@@ -721,10 +677,10 @@ extern "C" int tsar_get_plane(tsar_ctx* ctx, float* planes, float* cost, int32_t
     CHECK_CTX(ctx);
     NEED_STATE(ctx);
     const size_t np = (size_t)ctx->w * ctx->h;
-    if (planes) TSAR_HIP_TRY(ctx, hipMemcpyAsync(planes, ctx->buf[0].n4, np * 16, out_kind(mem), ctx->stream));
-    if (cost) TSAR_HIP_TRY(ctx, hipMemcpyAsync(cost, ctx->buf[0].c, np * 4, out_kind(mem), ctx->stream));
-    if (beview) TSAR_HIP_TRY(ctx, hipMemcpyAsync(beview, ctx->beview, np * 4, out_kind(mem), ctx->stream));
-    if (ratio) TSAR_HIP_TRY(ctx, hipMemcpyAsync(ratio, ctx->ratio, np * 4, out_kind(mem), ctx->stream));
+    if (planes) TSAR_HIP_TRY(ctx, hipMemcpyAsync(planes, ctx->buf[0].n4, np * 16, kind_from_dev(mem), ctx->stream));
+    if (cost) TSAR_HIP_TRY(ctx, hipMemcpyAsync(cost, ctx->buf[0].c, np * 4, kind_from_dev(mem), ctx->stream));
+    if (beview) TSAR_HIP_TRY(ctx, hipMemcpyAsync(beview, ctx->beview, np * 4, kind_from_dev(mem), ctx->stream));
+    if (ratio) TSAR_HIP_TRY(ctx, hipMemcpyAsync(ratio, ctx->ratio, np * 4, kind_from_dev(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSAR_OK;
 }
@@ -736,11 +692,10 @@ extern "C" int tsar_load_planes(tsar_ctx* ctx, const float* depth, const float* 
     NEED_VIEWS(ctx);
     if (!depth || !normal_world) return fail(ctx, TSAR_ERR_INVALID, "depth/normal_world is NULL");
     const size_t np = (size_t)ctx->w * ctx->h;
-    ScratchScope scratch(ctx);             // host maps are staged through the context's scratch arena (released after the sync below)
-    TmpIn<float> d(ctx, depth, np, mem, &scratch), n(ctx, normal_world, 3 * np, mem, &scratch);
-    TRY(d.rc); TRY(n.rc);
-    TRY(launch_get_disp(ctx, d.d, n.d));
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CallFrame f(ctx, __func__);
+    const float *d = f.in(depth, np, mem), *n = f.in(normal_world, 3 * np, mem);
+    if (f.ok()) f.take(launch_get_disp(ctx, d, n));
+    TRY(f.finish());
     ctx->state_given();
     return TSAR_OK;
 }
@@ -757,11 +712,12 @@ extern "C" int tsar_compute_disp_final(tsar_ctx* ctx, const float* resize_planes
     NEED_STATE(ctx);
     if (!resize_planes || !text) return fail(ctx, TSAR_ERR_INVALID, "resize_planes/text is NULL");
     const size_t np = (size_t)ctx->w * ctx->h;
-    TmpIn<float> r(ctx, resize_planes, 4 * np, mem), t(ctx, text, np, mem);
-    TRY(r.rc); TRY(t.rc);
+    CallFrame f(ctx, __func__, nullptr, /*grow_arena=*/false);
+    const float *r = f.in(resize_planes, 4 * np, mem), *t = f.in(text, np, mem);
+    if (!f.ok()) return f.finish();        // nothing was launched: the state stands
     ctx->costs_voided();
-    TRY(launch_compute_disp_final(ctx, (const float4*)r.d, t.d));
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    f.take(launch_compute_disp_final(ctx, (const float4*)r, t));
+    TRY(f.finish());
     ctx->result_computed();
     return TSAR_OK;
 }
@@ -801,20 +757,18 @@ extern "C" int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine_in) {
     std::vector<tsar_camera> cams(fine->cams);
     for (tsar_camera& c : cams) { c.K[0] *= 0.5f; c.K[2] *= 0.5f; c.K[4] *= 0.5f; c.K[5] *= 0.5f; }   // exact: a power of two
     const bool u8 = fine->views_u8;
-    int rc = stream_after(coarse, fine);
     {
-        ScratchScope scratch(coarse);
+        CallFrame f(coarse, __func__);     // the levels are staged in the coarse context's arena until its views are installed
+        f.take(stream_after(coarse, fine));
         std::vector<const void*> lv(n, nullptr);
-        for (int v = 0; v < n && rc == TSAR_OK; v++) {
-            void* dst = scratch.alloc((size_t)cw * ch * (u8 ? 1 : sizeof(float)));
-            if (!dst) { rc = fail(coarse, TSAR_ERR_NOMEM, "hipMalloc failed"); break; }
-            rc = launch_pyr_down(coarse, fine->img[v], fine->w, fine->h, dst, u8);
+        for (int v = 0; v < n && f.ok(); v++) {
+            void* dst = f.tmp<char>((size_t)cw * ch * (u8 ? 1 : sizeof(float)));
+            if (f.ok()) f.take(launch_pyr_down(coarse, fine->img[v], fine->w, fine->h, dst, u8));
             lv[v] = dst;
         }
-        if (rc == TSAR_OK) rc = set_views_impl(coarse, n, cw, ch, lv.data(), u8 ? 1 : 4, TSAR_MEM_DEVICE, cams.data());
-        hipStreamSynchronize(coarse->stream);     // the staging buffers go back to the arena
+        if (f.ok()) f.take(set_views_impl(coarse, n, cw, ch, lv.data(), u8 ? 1 : 4, TSAR_MEM_DEVICE, cams.data()));
+        TRY(f.finish());
     }
-    TRY(rc);
     if (fine->hscene.n_sel >= 1) TRY(tsar_set_view_subset(coarse, fine->hscene.n_sel, fine->hscene.sel));
     return TSAR_OK;
 }
@@ -845,12 +799,12 @@ extern "C" int tsar_compute_disp_final_upsampled(tsar_ctx* ctx, const float* tex
     NEED_STATE(ctx);
     if (!text) return fail(ctx, TSAR_ERR_INVALID, "text is NULL");
     if (!ctx->have_resize) return fail(ctx, TSAR_ERR_INVALID, "tsar_compute_disp_final_upsampled: no upsampled planes kept (call tsar_upsample_planes first)");
-    const size_t np = (size_t)ctx->w * ctx->h;
-    TmpIn<float> t(ctx, text, np, mem);
-    TRY(t.rc);
+    CallFrame f(ctx, __func__, nullptr, /*grow_arena=*/false);
+    const float* t = f.in(text, (size_t)ctx->w * ctx->h, mem);
+    if (!f.ok()) return f.finish();        // nothing was launched: the state stands
     ctx->costs_voided();
-    TRY(launch_compute_disp_final(ctx, ctx->resize4, t.d));
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    f.take(launch_compute_disp_final(ctx, ctx->resize4, t));
+    TRY(f.finish());
     ctx->result_computed();
     return TSAR_OK;
 }
@@ -859,7 +813,7 @@ extern "C" int tsar_get_view_image(tsar_ctx* ctx, int view, float* out, int mem)
     CHECK_CTX(ctx);
     NEED_VIEWS(ctx);
     if (!out || view < 0 || view >= ctx->n_views) return fail(ctx, TSAR_ERR_INVALID, "tsar_get_view_image: view out of range or out is NULL");
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->img[view], (size_t)ctx->w * ctx->h * sizeof(float), out_kind(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->img[view], (size_t)ctx->w * ctx->h * sizeof(float), kind_from_dev(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSAR_OK;
 }
@@ -905,7 +859,7 @@ extern "C" int tsar_set_geom_depths(tsar_ctx* ctx, int n_views, const float* con
     return install_geom_term(ctx, weight, clip, [&](int v, float** map) -> int {
         if (!depth[v]) return TSAR_OK;
         if (dev_alloc(ctx, map, np) != TSAR_OK) return TSAR_ERR_NOMEM;
-        if (hipMemcpyAsync(*map, depth[v], np * sizeof(float), in_kind(mem), ctx->stream) != hipSuccess)
+        if (hipMemcpyAsync(*map, depth[v], np * sizeof(float), kind_to_dev(mem), ctx->stream) != hipSuccess)
             return fail(ctx, TSAR_ERR_HIP, "tsar_set_geom_depths: copy of a depth map failed");
         return TSAR_OK;
     });
@@ -1034,23 +988,12 @@ extern "C" int tsar_geom_check(tsar_ctx* ctx, const float* depth, const tsar_geo
     if (!depth && !(ctx->have_state && ctx->have_out)) return fail(ctx, TSAR_ERR_STATE, "tsar_geom_check: depth is NULL and the context has no result (call tsar_compute_disp / tsar_fill_textureless first)");
     const size_t np = (size_t)ctx->w * ctx->h;
     const float* own = (const float*)ctx->out4 + 3;        // the result plane is (n_world, depth) per pixel
-    if (mem == TSAR_MEM_DEVICE) {
-        TRY(launch_geom_check(ctx, depth ? depth : own, depth ? 1 : 4, p, count_out, depth_out));
-        TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return TSAR_OK;
-    }
-    ScratchScope scratch(ctx);             // host buffers are staged in the context's scratch arena (released after the sync below)
-    TmpIn<float> d(ctx, depth, np, mem, &scratch);
-    int rc = d.rc;
-    uint8_t* dc = nullptr;
-    float* dd = nullptr;
-    if (rc == TSAR_OK && count_out && !(dc = (uint8_t*)scratch.alloc(np))) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
-    if (rc == TSAR_OK && depth_out && !(dd = (float*)scratch.alloc(np * 4))) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
-    if (rc == TSAR_OK) rc = launch_geom_check(ctx, depth ? d.d : own, depth ? 1 : 4, p, dc, dd);
-    if (rc == TSAR_OK && count_out && hipMemcpyAsync(count_out, dc, np, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "D2H failed");
-    if (rc == TSAR_OK && depth_out && hipMemcpyAsync(depth_out, dd, np * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "D2H failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    return rc;
+    CallFrame f(ctx, __func__);
+    const float* d = f.in(depth, np, mem);
+    uint8_t* dc = f.out(count_out, np, mem);
+    float* dd = f.out(depth_out, np, mem);
+    if (f.ok()) f.take(launch_geom_check(ctx, depth ? d : own, depth ? 1 : 4, p, dc, dd));
+    return f.finish();
 }
 
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
@@ -1066,27 +1009,12 @@ extern "C" int tsar_get_result(tsar_ctx* ctx, float* depth, float* normal_world,
     NEED_STATE(ctx);
     if (!ctx->have_out) return fail(ctx, TSAR_ERR_STATE, "call tsar_compute_disp / tsar_fill_textureless first");
     const size_t np = (size_t)ctx->w * ctx->h;
-    if (depth || normal_world) {
-        if (mem == TSAR_MEM_DEVICE) {
-            TRY(launch_split_out4(ctx, depth, normal_world));
-        } else {
-            ScratchScope scratch(ctx);     // the split maps are staged in the context's scratch arena
-            float *dd = nullptr, *dn = nullptr;
-            int rc = TSAR_OK;
-            if (depth && !(dd = (float*)scratch.alloc(np * 4))) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
-            if (rc == TSAR_OK && normal_world && !(dn = (float*)scratch.alloc(np * 12))) rc = fail(ctx, TSAR_ERR_NOMEM, "hipMalloc failed");
-            if (rc == TSAR_OK) rc = launch_split_out4(ctx, dd, dn);
-            if (rc == TSAR_OK && depth && hipMemcpyAsync(depth, dd, np * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "D2H failed");
-            if (rc == TSAR_OK && normal_world && hipMemcpyAsync(normal_world, dn, np * 12, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "D2H failed");
-            hipStreamSynchronize(ctx->stream);
-            scratch.release();
-            TRY(rc);
-        }
-    }
-    if (cost) TSAR_HIP_TRY(ctx, hipMemcpyAsync(cost, ctx->buf[0].c, np * 4, out_kind(mem), ctx->stream));
-    if (confid) TSAR_HIP_TRY(ctx, hipMemcpyAsync(confid, ctx->confid, np * 4, out_kind(mem), ctx->stream));
-    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TSAR_OK;
+    CallFrame f(ctx, __func__);
+    float *dd = f.out(depth, np, mem), *dn = f.out(normal_world, 3 * np, mem);    // the result plane is split into maps of its own
+    if ((depth || normal_world) && f.ok()) f.take(launch_split_out4(ctx, dd, dn));
+    if (cost) f.copy(cost, ctx->buf[0].c, np * 4, kind_from_dev(mem));
+    if (confid) f.copy(confid, ctx->confid, np * 4, kind_from_dev(mem));
+    return f.finish();
 }
 
 // ---- TSAR refinement -----------------------------------------------------------------------------
@@ -1094,7 +1022,7 @@ extern "C" int tsar_set_reliable_mask(tsar_ctx* ctx, const float* scale, int mem
     CHECK_CTX(ctx);
     NEED_VIEWS(ctx);
     if (!scale) return fail(ctx, TSAR_ERR_INVALID, "scale is NULL");
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->scale, scale, (size_t)ctx->w * ctx->h * 4, in_kind(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->scale, scale, (size_t)ctx->w * ctx->h * 4, kind_to_dev(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSAR_OK;
 }
@@ -1102,7 +1030,7 @@ extern "C" int tsar_get_reliable_mask(tsar_ctx* ctx, float* scale, int mem) {
     CHECK_CTX(ctx);
     NEED_VIEWS(ctx);
     if (!scale) return fail(ctx, TSAR_ERR_INVALID, "scale is NULL");
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(scale, ctx->scale, (size_t)ctx->w * ctx->h * 4, out_kind(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(scale, ctx->scale, (size_t)ctx->w * ctx->h * 4, kind_from_dev(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSAR_OK;
 }
@@ -1138,14 +1066,11 @@ extern "C" int tsar_set_regions(tsar_ctx* ctx, const int32_t* labels, int n_regi
         }
         if (lo < 0 || hi >= n_regions) return fail(ctx, TSAR_ERR_INVALID, "a label is outside [0, n_regions)");
     }
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->canny, labels, np * 4, in_kind(mem), ctx->stream));
-    TRY(dev_alloc(ctx, &ctx->region_text, (size_t)n_regions));
-    TRY(dev_alloc(ctx, &ctx->region_size, (size_t)n_regions));
-    TRY(dev_alloc(ctx, &ctx->region_n4, (size_t)n_regions));
-    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->region_text, region_text, (size_t)n_regions * 4, in_kind(mem), ctx->stream));
-    if (region_size) TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->region_size, region_size, (size_t)n_regions * 4, in_kind(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->canny, labels, np * 4, kind_to_dev(mem), ctx->stream));
+    TRY(install_regions(ctx, n_regions));
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->region_text, region_text, (size_t)n_regions * 4, kind_to_dev(mem), ctx->stream));
+    if (region_size) TSAR_HIP_TRY(ctx, hipMemcpyAsync(ctx->region_size, region_size, (size_t)n_regions * 4, kind_to_dev(mem), ctx->stream));
     else TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->region_size, 0, (size_t)n_regions * 4, ctx->stream));
-    TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->region_n4, 0, (size_t)n_regions * 16, ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->n_regions = n_regions;
     return TSAR_OK;
@@ -1163,7 +1088,7 @@ extern "C" int tsar_fake_depth(tsar_ctx* ctx, float* fakedepth_out, int mem) {
     NEED_VIEWS(ctx);
     NEED_REGIONS(ctx);
     TRY(launch_fake_depth(ctx));
-    if (fakedepth_out) TSAR_HIP_TRY(ctx, hipMemcpyAsync(fakedepth_out, ctx->fakedepth, (size_t)ctx->w * ctx->h * 4, out_kind(mem), ctx->stream));
+    if (fakedepth_out) TSAR_HIP_TRY(ctx, hipMemcpyAsync(fakedepth_out, ctx->fakedepth, (size_t)ctx->w * ctx->h * 4, kind_from_dev(mem), ctx->stream));
     TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSAR_OK;
 }
@@ -1258,34 +1183,20 @@ extern "C" int tsar_get_kernel_timing(tsar_ctx* ctx, tsar_kernel_timing* out, in
 extern "C" int tsar_selftest_divide(tsar_ctx* ctx, const float* X, const float* Y, const float* Z, size_t n, float* u_out, float* v_out, int ieee) {
     CHECK_CTX(ctx);
     if (!X || !Y || !Z || !u_out || !v_out || n == 0 || n > ((size_t)1 << 28)) return fail(ctx, TSAR_ERR_INVALID, "NULL argument or n out of range (1..2^28)");
-    ScratchScope scratch(ctx);
-    float* d[5];
-    for (auto& p : d)
-        if (!(p = (float*)scratch.alloc(n * sizeof(float)))) return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed");
-    const float* src[3] = {X, Y, Z};
-    int rc = TSAR_OK;
-    for (int k = 0; k < 3 && rc == TSAR_OK; k++)
-        if (hipMemcpyAsync(d[k], src[k], n * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (rc == TSAR_OK) rc = launch_selftest_divide(ctx, d[0], d[1], d[2], n, d[3], d[4], ieee);
-    if (rc == TSAR_OK && (hipMemcpyAsync(u_out, d[3], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                          hipMemcpyAsync(v_out, d[4], n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
-        rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    return rc;                             // (the scratch goes back on return: the stream is idle)
+    CallFrame f(ctx, __func__);
+    const float *x = f.in(X, n, TSAR_MEM_HOST), *y = f.in(Y, n, TSAR_MEM_HOST), *z = f.in(Z, n, TSAR_MEM_HOST);
+    float *u = f.out(u_out, n, TSAR_MEM_HOST), *v = f.out(v_out, n, TSAR_MEM_HOST);
+    if (f.ok()) f.take(launch_selftest_divide(ctx, x, y, z, n, u, v, ieee));
+    return f.finish();
 }
 // The counter self-tests: n zeroed 64-bit device counters from the scratch arena, launch(counters), the counters copied to out[n].
 template <typename Launch>
 static int run_counters(tsar_ctx* ctx, int n, uint64_t* out, Launch launch) {
-    ScratchScope scratch(ctx);             // (released on return, after the synchronise below)
-    const size_t bytes = (size_t)n * sizeof(unsigned long long);
-    unsigned long long* dc = (unsigned long long*)scratch.alloc(bytes);
-    if (!dc) return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed");
-    int rc = TSAR_OK;
-    if (hipMemsetAsync(dc, 0, bytes, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemsetAsync failed");
-    if (rc == TSAR_OK) rc = launch(dc);
-    if (rc == TSAR_OK && hipMemcpyAsync(out, dc, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, TSAR_ERR_HIP, "hipMemcpyAsync failed");
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) rc = fail(ctx, TSAR_ERR_HIP, "hipStreamSynchronize failed");
-    return rc;
+    CallFrame f(ctx, __func__);
+    unsigned long long* dc = f.out((unsigned long long*)out, (size_t)n, TSAR_MEM_HOST);
+    f.zero(dc, (size_t)n * sizeof(unsigned long long));
+    if (f.ok()) f.take(launch(dc));
+    return f.finish();
 }
 extern "C" int tsar_selftest_divide_random(tsar_ctx* ctx, int log2_triples, uint64_t seed, int mode, int guarded, uint64_t* mismatches_out,
                                            uint64_t* outside_guard_out) {

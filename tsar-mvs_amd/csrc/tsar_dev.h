@@ -3,8 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -99,9 +101,9 @@ struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
-// Device scratch of the operators that need temporaries (weak-texture detection, region RANSAC): one arena per context, grown to
-// the largest call seen and kept, so that a worker refining view after view (tsar_gipuma --all --mode=tsar) does not pay ~18
-// hipMalloc + hipFree per operator and view (26 of the 59 ms of a RANSAC call at 24 MP were these).
+// Device scratch of the calls that need temporaries or stage host buffers (CallFrame below; DESIGN.md lists them): one arena per
+// context, grown to the largest call seen and kept, so that a worker refining view after view (tsar_gipuma --all --mode=tsar) does
+// not pay ~18 hipMalloc + hipFree per operator and view (26 of the 59 ms of a RANSAC call at 24 MP were these).
 struct ScratchArena {
     char* base = nullptr;
     size_t cap = 0;
@@ -238,14 +240,16 @@ struct DevTmp {
     T* release() { T* q = p; p = nullptr; return q; }
 };
 
-// One operator call's view of the arena: alloc() hands out 256-byte-aligned pieces; what does not fit is a plain hipMalloc for
-// this call; the second time a call overflows, the arena is re-sized to the largest total seen, and calls of that size allocate
-// nothing from then on.
+// One call's view of the arena: alloc() hands out 256-byte-aligned pieces; what does not fit is a plain hipMalloc for this call;
+// the second time a call overflows, the arena is re-sized to the largest total seen, and calls of that size allocate nothing from
+// then on.  grow = false: a call that must not grow what the context keeps (diagnostics, the few bytes of a probe) uses the arena
+// space that is there and leaves `wanted` and the arena alone.
 struct ScratchScope {
     tsar_ctx* ctx;
+    bool grow;
     size_t used = 0, need = 0;
     std::vector<void*> extra;
-    explicit ScratchScope(tsar_ctx* c) : ctx(c) {}
+    explicit ScratchScope(tsar_ctx* c, bool grow_arena = true) : ctx(c), grow(grow_arena) {}
     void* alloc(size_t bytes) {
         bytes = ((bytes ? bytes : 4) + 255) & ~(size_t)255;
         need += bytes;
@@ -255,10 +259,10 @@ struct ScratchScope {
         extra.push_back(p);
         return p;
     }
-    void release() {                       // the stream is idle (callers synchronise first)
+    void release() {                       // the stream is idle (CallFrame synchronises first)
         for (void* p : extra) hipFree(p);
         extra.clear();
-        if (need > ctx->scratch.cap) {
+        if (grow && need > ctx->scratch.cap) {
             const bool again = ctx->scratch.wanted > ctx->scratch.cap;          // an earlier call overflowed this arena too
             if (need > ctx->scratch.wanted) ctx->scratch.wanted = need;
             if (again) {
@@ -274,6 +278,89 @@ struct ScratchScope {
     ~ScratchScope() { release(); }
 };
 
+// where a caller's buffer lies decides the kind of a copy to / from a context buffer
+static inline hipMemcpyKind copy_kind(int mem, hipMemcpyKind host_kind) { return mem == TSAR_MEM_DEVICE ? hipMemcpyDeviceToDevice : host_kind; }
+static inline hipMemcpyKind kind_to_dev(int mem) { return copy_kind(mem, hipMemcpyHostToDevice); }
+static inline hipMemcpyKind kind_from_dev(int mem) { return copy_kind(mem, hipMemcpyDeviceToHost); }
+
+// One ABI call's frame, created after the guards: its pieces of the arena, device views of the caller's buffers, a sticky status
+// and the way out.  The first failure is recorded with its message; every later operation on a failed frame does nothing, so a
+// function takes its pieces, queues its copies and looks at ok() once before it launches.  finish() (or the destructor, on an
+// early return) synchronises the stream and releases the pieces: every exit leaves an idle stream and a released scope.
+struct CallFrame {
+    tsar_ctx* ctx;
+    const char* entry;                     // names the call in allocation and HIP failure messages
+    const char* tag;                       // "[ransac]": trace() lines on stderr when TSAR_TRACE_HOST is set, else null
+    ScratchScope scratch;
+    int rc = TSAR_OK;
+    bool closed = false;
+    struct Back { void* dst; const void* src; size_t bytes; };
+    std::vector<Back> back;                // staged outputs that finish() copies to the caller's host buffers
+    std::chrono::steady_clock::time_point t0;
+    CallFrame(tsar_ctx* c, const char* entry_name, const char* trace_tag = nullptr, bool grow_arena = true)
+        : ctx(c), entry(entry_name), tag(c->trace_host ? trace_tag : nullptr), scratch(c, grow_arena), t0(std::chrono::steady_clock::now()) {}
+    CallFrame(const CallFrame&) = delete;
+    CallFrame& operator=(const CallFrame&) = delete;
+    ~CallFrame() { close(); }
+
+    bool ok() const { return rc == TSAR_OK; }
+    int fail(int code, const std::string& msg) { if (ok()) { rc = code; ctx->err = msg; } return rc; }
+    void take(int code) { if (ok()) rc = code; }                      // a launcher's status (which has left its message in ctx->err)
+    bool hip(hipError_t e, const char* what) {                          // as TSAR_HIP_TRY: TSAR_ERR_HIP with the name of the failing call
+        if (e != hipSuccess) fail(TSAR_ERR_HIP, std::string(entry) + ": " + what + ": " + hipGetErrorString(e));
+        return ok();
+    }
+    template <typename T>
+    T* tmp(size_t n) {                                                  // a piece of the arena for this call
+        if (!ok()) return nullptr;
+        T* p = (T*)scratch.alloc(n * sizeof(T));
+        if (!p) fail(TSAR_ERR_NOMEM, std::string(entry) + ": device allocation failed");
+        return p;
+    }
+    template <typename T>
+    const T* in(const T* src, size_t n, int mem) {                      // device view of a caller's input: host buffers are copied in
+        if (!src || mem == TSAR_MEM_DEVICE) return src;
+        T* d = tmp<T>(n);
+        copy(d, src, n * sizeof(T), hipMemcpyHostToDevice);
+        return d;
+    }
+    template <typename T>
+    T* out(T* dst, size_t n, int mem) {                                 // device view of a caller's output: finish() fills host buffers
+        if (!dst || mem == TSAR_MEM_DEVICE) return dst;
+        T* d = tmp<T>(n);
+        if (d) back.push_back({dst, d, n * sizeof(T)});
+        return d;
+    }
+    void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        if (ok() && bytes) hip(hipMemcpyAsync(dst, src, bytes, kind, ctx->stream), "hipMemcpyAsync");
+    }
+    void zero(void* p, size_t bytes) {
+        if (ok() && bytes) hip(hipMemsetAsync(p, 0, bytes, ctx->stream), "hipMemsetAsync");
+    }
+    bool launched() { return ok() && hip(hipGetLastError(), "kernel launch"); }
+    bool sync() { return ok() && hip(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"); }   // where the host reads a value mid-call
+    void trace(const char* what) {
+        if (!tag) return;
+        hipStreamSynchronize(ctx->stream);
+        const auto n = std::chrono::steady_clock::now();
+        fprintf(stderr, "%s %s %.3f ms\n", tag, what, std::chrono::duration<double, std::milli>(n - t0).count());
+        t0 = n;
+    }
+    int finish() {                                                      // copy-backs only if all went well; one synchronise
+        if (!closed)
+            for (const Back& b : back) copy(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost);
+        close();
+        return rc;
+    }
+    void close() {
+        if (closed) return;
+        closed = true;
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        hip(e, "hipStreamSynchronize");
+        scratch.release();
+    }
+};
+
 #define TSAR_HIP_TRY(ctx, expr)                                                                       \
     do {                                                                                              \
         hipError_t e_ = (expr);                                                                       \
@@ -282,6 +369,18 @@ struct ScratchScope {
             return TSAR_ERR_HIP;                                                                      \
         }                                                                                             \
     } while (0)
+
+// The region tables (text, size, planes; n entries each), installed by tsar_set_regions and tsar_detect_weak_texture.  n_regions is
+// 0 from before anything is freed until the caller, having filled the tables, sets it: a failure on the way leaves a context that
+// NEED_REGIONS refuses.
+static inline int install_regions(tsar_ctx* ctx, int n) {
+    ctx->n_regions = 0;
+    TRY(dev_alloc(ctx, &ctx->region_text, (size_t)n));
+    TRY(dev_alloc(ctx, &ctx->region_size, (size_t)n));
+    TRY(dev_alloc(ctx, &ctx->region_n4, (size_t)n));
+    TSAR_HIP_TRY(ctx, hipMemsetAsync(ctx->region_n4, 0, (size_t)n * 16, ctx->stream));
+    return TSAR_OK;
+}
 
 // RAII bracket that records a hipEvent pair around a launch when timing is enabled.
 struct ScopedKernelTimer {

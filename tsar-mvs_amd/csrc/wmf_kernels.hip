@@ -445,27 +445,28 @@ extern "C" int tsar_wmf(tsar_ctx* ctx, int iters, int final_pass) {
     if (iters < 1 || iters > (final_pass ? 6 : 4)) return fail(ctx, TSAR_ERR_INVALID, "tsar_wmf: iters must be 1..4 (detect) or 1..6 (final)");
     if (final_pass) NEED_REGIONS(ctx);
     const size_t np = (size_t)ctx->w * ctx->h;
-    ScratchScope scratch(ctx);             // the launch-start snapshots come out of the context's scratch arena
-    float* scale_snap = (float*)scratch.alloc(np * 4);
-    float* depth_snap = final_pass ? (float*)scratch.alloc(np * 4) : nullptr;
-    if (!scale_snap || (final_pass && !depth_snap)) return fail(ctx, TSAR_ERR_NOMEM, "device allocation failed");
+    CallFrame f(ctx, __func__);            // the launch-start snapshots come out of the context's scratch arena
+    float* scale_snap = f.tmp<float>(np);
+    float* depth_snap = final_pass ? f.tmp<float>(np) : nullptr;
+    if (!f.ok()) return f.finish();        // nothing was launched: the state stands
     const dim3 grid((unsigned)((np + WMF_PIX - 1) / WMF_PIX)), block(WMF_BLOCK);
-    int rc = TSAR_OK;
-    for (int it = 0; it < iters && rc == TSAR_OK; it++) {
-        hipMemcpyAsync(scale_snap, ctx->scale, np * 4, hipMemcpyDeviceToDevice, ctx->stream);
+    for (int it = 0; it < iters; it++) {
+        f.copy(scale_snap, ctx->scale, np * 4, hipMemcpyDeviceToDevice);
         if (final_pass) {
-            hipMemcpyAsync(depth_snap, ctx->depth, np * 4, hipMemcpyDeviceToDevice, ctx->stream);
-            hipMemcpyAsync(ctx->buf[1].n4, ctx->buf[0].n4, np * 16, hipMemcpyDeviceToDevice, ctx->stream);
+            f.copy(depth_snap, ctx->depth, np * 4, hipMemcpyDeviceToDevice);
+            f.copy(ctx->buf[1].n4, ctx->buf[0].n4, np * 16, hipMemcpyDeviceToDevice);
+            if (!f.ok()) break;
             ScopedKernelTimer tm(ctx, "wmf_fill");
             hipLaunchKernelGGL(wmf_fill_kernel, grid, block, 0, ctx->stream, ctx->dscene, ctx->canny, ctx->region_text, scale_snap, depth_snap,
                                ctx->buf[1].n4, ctx->scale, ctx->depth, ctx->buf[0].n4, it);
         } else {
+            if (!f.ok()) break;
             ScopedKernelTimer tm(ctx, "wmf_detect");
             hipLaunchKernelGGL(wmf_detect_kernel, grid, block, 0, ctx->stream, ctx->dscene, scale_snap, ctx->depth, ctx->buf[0].n4, ctx->scale, it);
         }
-        if (hipGetLastError() != hipSuccess) { ctx->err = "wmf launch failed"; rc = TSAR_ERR_HIP; }
+        if (!f.launched()) break;
     }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == TSAR_OK) { ctx->err = "wmf kernel failed"; rc = TSAR_ERR_HIP; }
+    const int rc = f.finish();
     ctx->result_voided();
     if (final_pass) ctx->costs_voided();   // the final pass rewrites planes
     return rc;
