@@ -352,6 +352,50 @@ typedef struct tsar_geom_check_params {
 void tsar_default_geom_check_params(tsar_geom_check_params* p);
 int tsar_geom_check(tsar_ctx* ctx, const float* depth, const tsar_geom_check_params* p, uint8_t* count_out, float* depth_out, int mem);
 
+/* The source views' depth maps rendered into the reference camera: what do the sources see at each pixel of the reference view, and how
+ * many of them agree on it?  The way OpenMVS and the learned pipelines start a view from its neighbours; the complement of tsar_geom_check,
+ * which can only say that the sources do not confirm a depth.  Needs views and an installed term, like tsar_geom_check: tsar_set_geom_depths
+ * supplies the maps and B (a weight of 0 installs maps for this call only).  depth_out [h][w] float32 and count_out [h][w] uint8 may each be
+ * NULL, not both; `mem` applies to both.  The call writes nothing in the context: lines->scale, planes, stored costs, the propagation
+ * memo, the sweep counter, the result planes and the term stay as they are.  Timed as "geom_reproject" (three launches).
+ * The arithmetic, the same in both arithmetic modes: float32, every operation one IEEE-754 operation rounded to nearest (no fused
+ * multiply-add).  For every view v = 1 .. n_views - 1 that has a map, in any order (the view subset does not matter), and every pixel
+ * (c, r) of it, with D_v = depth_v[r][c]:
+ *   candidate = D_v > 0 and D_v < inf (NaN fails both)
+ *   C = float(c), R = float(r);  cd = C * D_v, rd = R * D_v
+ *   B  = view v's back-projection as tsar_get_geom_matrices returns it;  p_k = ((B[k][0] * cd + B[k][1] * rd) + B[k][2] * D_v) + B[k][3], k = 0, 1, 2
+ *   x' = p_0 / p_2, y' = p_1 / p_2 (correctly rounded);  xi = floor(x' + 0.5), yi = floor(y' + 0.5) (the sum rounded first)
+ *   lands = candidate and p_2 > 0 and p_2 < inf and 0 <= xi <= w - 1 and 0 <= yi <= h - 1 (NaN fails every comparison): the pixel
+ *           lands on reference pixel (xi, yi) at depth p_2
+ * and then for every reference pixel:
+ *   Z     = the minimum of p_2 over all landings of all views there (the front-most surface); a pixel nothing lands on has no Z
+ *   dd    = depth_diff * Z;  view v supports the pixel when at least one of its landings there has |p_2 - Z| <= dd (the front-most
+ *           landing always supports itself);  count = the number of supporting views
+ *   count_out = count where something landed, else 0;  depth_out = Z where something landed and count >= min_views, else 0
+ * A minimum and a set of views do not depend on the order of arrival: the outputs are the same bits in every run.
+ * TSAR_ERR_STATE: no term installed.  TSAR_ERR_INVALID: p NULL; both outputs NULL; depth_diff not finite or <= 0; min_views outside
+ * [1, 63]; mem unknown. */
+typedef struct tsar_geom_reproject_params {
+    float depth_diff;         /* relative, default 0.01: a view supports a pixel's front-most depth Z when one of its landings there is within depth_diff * Z of Z */
+    int32_t min_views;        /* default 1, in [1, 63]: depth_out is Z only where at least this many views support it */
+} tsar_geom_reproject_params;
+void tsar_default_geom_reproject_params(tsar_geom_reproject_params* p);
+int tsar_geom_reproject(tsar_ctx* ctx, const tsar_geom_reproject_params* p, float* depth_out, uint8_t* count_out, int mem);
+
+/* Offers a depth map of the reference view (tsar_geom_reproject's, say) to the matcher: each pixel takes the plane with its own normal
+ * through the offered depth where that plane scores lower.  Needs views, sources and a plane state.  The result is this composition of
+ * existing entries, bit for bit:
+ *   1. the state is rescored exactly as tsar_pm_rescore does (invalid planes get tsar_pm_init's draw): planes P, costs C, best views, ratios;
+ *   2. the candidate of pixel (x, y), D = depth[y][x]: where D is finite and depth_min <= D <= depth_max, Q = (P's normal, d) with d the
+ *      offset of the plane with that normal through the pixel at depth D (getD_cu gipuma.cu:71-86, what tsar_load_planes computes);
+ *      elsewhere Q = P;
+ *   3. Q is scored as tsar_pm_cost_planes scores it (the context's arithmetic, window, best-N, subset and term);
+ *   4. where cost(Q) < C, strictly (the own plane wins ties), the pixel takes Q's plane, cost, best view and ratio.
+ * Afterwards every stored cost is its plane's score, the sweep counter is 0 and the result is void, as after tsar_pm_rescore.
+ * *n_taken_out (may be NULL): the number of pixels that took Q.  TSAR_ERR_INVALID: depth NULL, mem unknown; TSAR_ERR_STATE as
+ * tsar_pm_rescore.  Timed as "pm_rescore", tsar_pm_cost_planes's name for the scoring, and "pm_merge_depths" (two launches). */
+int tsar_pm_merge_depths(tsar_ctx* ctx, const float* depth, int mem, int64_t* n_taken_out);
+
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */
 int tsar_get_result(tsar_ctx* ctx, float* depth, float* normal_world, float* cost, float* confid,

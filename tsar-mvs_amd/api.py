@@ -58,6 +58,10 @@ class GeomCheckParams(C.Structure):
     _fields_ = [("reproj_error", C.c_float), ("depth_diff", C.c_float), ("min_consistent", C.c_int32)]
 
 
+class GeomReprojectParams(C.Structure):
+    _fields_ = [("depth_diff", C.c_float), ("min_views", C.c_int32)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -75,6 +79,7 @@ ABI_SYMBOLS = [
     "tsar_set_geom_depths", "tsar_clear_geom", "tsar_pm_rescore", "tsar_get_geom_matrices",
     "tsar_geom_pyramid", "tsar_pyramid_planes", "tsar_upsample_merge",
     "tsar_default_geom_check_params", "tsar_geom_check",
+    "tsar_default_geom_reproject_params", "tsar_geom_reproject", "tsar_pm_merge_depths",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -133,6 +138,10 @@ def load_library(path: str = LIB_PATH):
     L.tsar_default_geom_check_params.restype = None
     L.tsar_default_geom_check_params.argtypes = [C.POINTER(GeomCheckParams)]
     L.tsar_geom_check.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(GeomCheckParams), C.c_void_p, C.c_void_p, C.c_int]
+    L.tsar_default_geom_reproject_params.restype = None
+    L.tsar_default_geom_reproject_params.argtypes = [C.POINTER(GeomReprojectParams)]
+    L.tsar_geom_reproject.argtypes = [C.c_void_p, C.POINTER(GeomReprojectParams), C.c_void_p, C.c_void_p, C.c_int]
+    L.tsar_pm_merge_depths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -440,6 +449,44 @@ class Matcher:
         self._chk(self.L.tsar_geom_check(self._ctx, d, C.byref(p), _ptr(res.get("count"))[0], _ptr(res.get("depth"))[0], kind))
         return res
 
+    # ---- the sources' maps rendered into the reference camera, and offered to the matcher ----
+    def geom_reproject(self, depth_diff: float = 0.01, min_views: int = 1, want=("depth", "count"), device: bool = False):
+        """the installed source maps rendered into the reference camera (tsar_geom_reproject; set_geom_depths installs the maps, weight 0
+        for this only): per pixel the front-most depth Z that lands there and the number of views with a landing within depth_diff * Z of
+        it.  Returns a dict with "depth" ([h, w] float32: Z where count >= min_views, else 0) and / or "count" ([h, w] uint8), as `want`
+        names them: numpy arrays, or torch tensors on the context's device with device=True.  Nothing in the context changes."""
+        p = GeomReprojectParams(float(depth_diff), int(min_views))
+        res = {}
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if "depth" in want:
+                res["depth"] = torch.empty((self.h, self.w), dtype=torch.float32, device=dev)
+            if "count" in want:
+                res["count"] = torch.empty((self.h, self.w), dtype=torch.uint8, device=dev)
+        else:
+            if "depth" in want:
+                res["depth"] = np.empty((self.h, self.w), np.float32)
+            if "count" in want:
+                res["count"] = np.empty((self.h, self.w), np.uint8)
+        self._chk(self.L.tsar_geom_reproject(self._ctx, C.byref(p), _ptr(res.get("depth"))[0], _ptr(res.get("count"))[0], MEM_DEVICE if device else MEM_HOST))
+        return res
+
+    def merge_depths(self, depth) -> int:
+        """offer `depth` ([h, w] float32 in the reference camera, numpy or a torch device tensor; values outside [depth_min, depth_max] or
+        not finite offer nothing) to the matcher (tsar_pm_merge_depths): the state is rescored, and each pixel takes the plane with its
+        own normal through the offered depth where that scores strictly lower.  Returns the number of pixels that took it."""
+        on_device = _is_torch(depth) and depth.is_cuda
+        if not on_device:
+            depth = np.ascontiguousarray(depth.numpy() if _is_torch(depth) else depth, np.float32)
+        else:
+            assert str(depth.dtype) == "torch.float32"
+        assert tuple(depth.shape) == (self.h, self.w), "the depth map has shape %s, the views are %dx%d" % (tuple(depth.shape), self.w, self.h)
+        d, kind = _ptr(depth)
+        taken = C.c_int64(0)
+        self._chk(self.L.tsar_pm_merge_depths(self._ctx, d, kind, C.byref(taken)))
+        return int(taken.value)
+
     def get_result(self, want=("depth", "normal", "cost", "confid"), pinned=False, out=None):
         """pinned=True: the result arrays are page-locked (tsar_host_alloc), so the D2H copies run at PCIe rate.
         out: dict of caller-owned arrays to fill instead (e.g. page-locked ones allocated once and reused per view)."""
@@ -649,30 +696,55 @@ def run_multiscale(matcher: Matcher, levels: int, coarse_iters: int, fine_iters:
     return coarse
 
 
-def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, iters: int, weight: float = 0.2, clip: float = 3.0):
+def _check_cross_view(cross_view, cross_view_depth_diff):
+    if int(cross_view) != cross_view or not 0 <= cross_view <= MAX_VIEWS - 1:
+        raise ValueError("cross_view must be an integer in 0..63")
+    if cross_view and not (cross_view_depth_diff > 0 and np.isfinite(cross_view_depth_diff)):
+        raise ValueError("cross_view_depth_diff must be finite and > 0")
+
+
+def _cross_view_merge(matcher: Matcher, cross_view: int, cross_view_depth_diff: float) -> int:
+    """the sources' maps rendered into the reference camera (kept where `cross_view` views agree) and offered to the matcher, on the
+    device; the merge rescores first, so it stands in for rescore()"""
+    r = matcher.geom_reproject(cross_view_depth_diff, cross_view, want=("depth",), device=True)
+    return matcher.merge_depths(r["depth"])
+
+
+def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, iters: int, weight: float = 0.2, clip: float = 3.0,
+                  cross_view: int = 0, cross_view_depth_diff: float = 0.01):
     """The geometric-consistency pass of one reference view: start from its own photometric result (depth [h, w], world normals
     [h, w, 3]), install the source views' depth maps (src_depths[v] for view v of the matcher, [0] ignored, None = no term), rescore,
-    run `iters` iterations with the term, compute_disp.  The term stays installed (clear_geom removes it)."""
+    run `iters` iterations with the term, compute_disp.  The term stays installed (clear_geom removes it).
+    cross_view = K >= 1: in place of the rescore, the source maps are rendered into this view (geom_reproject with min_views = K and
+    depth_diff = cross_view_depth_diff) and offered to the matcher (merge_depths, which rescores first)."""
     if iters < 0:
         raise ValueError("iters must be >= 0")
+    _check_cross_view(cross_view, cross_view_depth_diff)
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
-    matcher.rescore()
+    if cross_view:
+        _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
+    else:
+        matcher.rescore()
     matcher.pm_iterate(iters)
     matcher.compute_disp()
 
 
 def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_depths, levels: int, coarse_iters: int, fine_iters: int,
-                             weight: float = 0.2, clip: float = 3.0, coarse=None):
+                             weight: float = 0.2, clip: float = 3.0, coarse=None, cross_view: int = 0, cross_view_depth_diff: float = 0.01):
     """The geometric-consistency pass coarse to fine (include/tsar.h tsar_geom_pyramid): `levels` pyramid levels below `matcher`; the
     view's own result and the term are carried down the chain, `coarse_iters` iterations run at the coarsest level, then every finer
     level (matcher's own included) merges the coarser planes into its own and runs `fine_iters` iterations; compute_disp.  levels = 0
     is run_geom_pass(matcher, ..., fine_iters).  coarse: the coarse contexts of an earlier call (finest first), reused; returns the
-    list used.  The terms stay installed (clear_geom removes them)."""
+    list used.  The terms stay installed (clear_geom removes them).
+    cross_view = K >= 1: as in run_geom_pass, on the full-resolution matcher right after its term is installed and before the chain is
+    carried down (the coarser levels then start from the merged planes)."""
     if levels < 0 or coarse_iters < 0 or fine_iters < 0:
         raise ValueError("levels and iteration counts must be >= 0")
+    _check_cross_view(cross_view, cross_view_depth_diff)
     if levels == 0:
-        run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip)
+        run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip, cross_view=cross_view,
+                      cross_view_depth_diff=cross_view_depth_diff)
         return list(coarse or [])
     coarse = list(coarse or [])
     while len(coarse) < levels:
@@ -684,6 +756,8 @@ def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_
         coarser.pyramid_from(finer)
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
+    if cross_view:
+        _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
     for finer, coarser in zip(chain[:-1], chain[1:]):
         coarser.geom_pyramid_from(finer)
         coarser.pyramid_planes_from(finer)

@@ -996,6 +996,64 @@ extern "C" int tsar_geom_check(tsar_ctx* ctx, const float* depth, const tsar_geo
     return f.finish();
 }
 
+// ---- the source views' maps rendered into the reference camera (geom_reproject_kernels.hip) ---------------------------------------
+extern "C" void tsar_default_geom_reproject_params(tsar_geom_reproject_params* p) {
+    if (!p) return;
+    p->depth_diff = 0.01f;                 // tsar_default_geom_check_params' value
+    p->min_views = 1;
+}
+
+// Reads the term's maps and matrices, writes the caller's outputs and two temporaries of the call: no transition of the plane state
+// (tsar_dev.h) is involved, and lines->scale is left alone
+extern "C" int tsar_geom_reproject(tsar_ctx* ctx, const tsar_geom_reproject_params* p, float* depth_out, uint8_t* count_out, int mem) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (!ctx->hscene.geom_on) return fail(ctx, TSAR_ERR_STATE, "tsar_geom_reproject: no geometric-consistency term installed (tsar_set_geom_depths supplies the source maps)");
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_reproject: params is NULL");
+    if (!depth_out && !count_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_reproject: depth_out and count_out are both NULL");
+    if (!(p->depth_diff > 0.0f) || !(p->depth_diff < __builtin_inff())) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_reproject: depth_diff must be finite and > 0");
+    if (p->min_views < 1 || p->min_views > TSAR_MAX_VIEWS - 1) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_reproject: min_views must be in 1..63");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_geom_reproject: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    const size_t np = (size_t)ctx->w * ctx->h;
+    CallFrame f(ctx, __func__);
+    float* dd = f.out(depth_out, np, mem);
+    uint8_t* dc = f.out(count_out, np, mem);
+    uint32_t* zbuf = f.tmp<uint32_t>(np);
+    unsigned long long* mask = f.tmp<unsigned long long>(np);
+    if (f.ok()) f.take(launch_geom_reproject(ctx, p, zbuf, mask, dd, dc));
+    return f.finish();
+}
+
+// ---- a depth map offered to the matcher -----------------------------------------------------------------------------------------------
+// The composition include/tsar.h states: rescore_state, the candidates, tsar_pm_cost_planes's launcher, the strict select
+extern "C" int tsar_pm_merge_depths(tsar_ctx* ctx, const float* depth, int mem, int64_t* n_taken_out) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    NEED_SOURCES(ctx);
+    NEED_STATE(ctx);
+    if (!depth) return fail(ctx, TSAR_ERR_INVALID, "tsar_pm_merge_depths: depth is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_pm_merge_depths: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    TRY(rescore_state(ctx));               // from here on the state is a scored one, whatever happens below
+    const size_t np = (size_t)ctx->w * ctx->h;
+    unsigned long long taken = 0;
+    CallFrame f(ctx, __func__);
+    const float* d = f.in(depth, np, mem);
+    float4* cand = f.tmp<float4>(np);
+    float* cand_c = f.tmp<float>(np);
+    int32_t* cand_bv = f.tmp<int32_t>(np);
+    float* cand_rt = f.tmp<float>(np);
+    unsigned long long* dtaken = f.tmp<unsigned long long>(1);
+    f.zero(dtaken, sizeof(unsigned long long));
+    if (f.ok()) f.take(launch_merge_candidates(ctx, d, cand));
+    if (f.ok()) f.take(launch_pm_cost_planes(ctx, cand, cand_c, cand_bv, cand_rt));
+    if (f.ok()) f.take(launch_merge_select(ctx, cand, cand_c, cand_bv, cand_rt, dtaken));
+    f.copy(&taken, dtaken, sizeof taken, hipMemcpyDeviceToHost);
+    TRY(f.finish());                       // (synchronises: `taken` is complete)
+    ctx->state_scored(true);               // every taken cost is the taken plane's score on the sweep window
+    if (n_taken_out) *n_taken_out = (int64_t)taken;
+    return TSAR_OK;
+}
+
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);

@@ -427,6 +427,11 @@ int launch_geom_pyramid(tsar_ctx* ctx, const float* src, int w, int h, float* ds
 int launch_pyramid_planes(tsar_ctx* ctx, const float4* src, int w, int h, float4* dst);        // tsar_pyramid.hip
 int launch_geom_check(tsar_ctx* ctx, const float* depth, int depth_stride, const tsar_geom_check_params* p, uint8_t* count_out,
                       float* depth_out);                                                       // geom_check_kernels.hip (writes ctx->scale)
+int launch_geom_reproject(tsar_ctx* ctx, const tsar_geom_reproject_params* p, uint32_t* zbuf, unsigned long long* mask, float* depth_out,
+                          uint8_t* count_out);                                                 // geom_reproject_kernels.hip
+int launch_merge_candidates(tsar_ctx* ctx, const float* depth, float4* cand);                  // geom_reproject_kernels.hip (reads buf[0].n4)
+int launch_merge_select(tsar_ctx* ctx, const float4* cand, const float* cand_c, const int32_t* cand_bv, const float* cand_rt,
+                        unsigned long long* n_taken);                                          // geom_reproject_kernels.hip (writes buf[0], beview, ratio)
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world);
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);

@@ -26,6 +26,10 @@
 //                      run at the coarsest, then each finer level merges the coarser planes into its own (tsar_upsample_merge) and runs
 //                      --geom_iterations iterations; each worker keeps its coarse contexts across views; TSAR_geom.txt gains a line
 //                      with the two settings when L >= 1.  L = 0: the single-scale pass above
+//     [--geom_cross_view[=K (2)] [--geom_cross_view_depth_diff=REL (0.01)]]   phase 2 also takes hypotheses from its sources: their maps
+//                      are rendered into the view (tsar_geom_reproject, kept where K sources agree within REL) and offered to the
+//                      matcher (tsar_pm_merge_depths, in device memory), in place of the rescore at L = 0 and right after the term is
+//                      installed at L >= 1; TSAR_geom.txt gains a line with the two settings only when the switch is on
 //   --all --consistency_filter[=K (2)] [--filter_reproj_error=PX (2)] [--filter_depth_diff=REL (0.01)]   a last phase after the matching
 //                      phases, before --fuse: each view's depth map of the phase that ran last (TSAR_geom_disp.dmb with
 //                      --geom_consistency, else TSAR_disp.dmb) is checked against its pair.txt sources' maps of the same phase
@@ -93,6 +97,9 @@ struct Options {
     int geom_multi_scale = 0, geom_coarse_iterations = -1;   // --geom_multi_scale / --geom_coarse_iterations (-1: --geom_iterations)
     bool geom_coarse_iterations_set = false;
     float geom_weight = 0.2f, geom_clip = 3.0f;      // ACMM's lambda and tau (include/tsar.h tsar_set_geom_depths)
+    bool geom_cross_view = false;                    // --geom_cross_view[=K]: phase 2 takes hypotheses from its sources' maps (tsar_geom_reproject + tsar_pm_merge_depths)
+    bool geom_cross_view_option_set = false;         // --geom_cross_view_depth_diff was given
+    tsar_geom_reproject_params cross{};              // --geom_cross_view_depth_diff, K
     bool filter = false;                             // --consistency_filter[=K]: the last phase of --all (run_filter_view)
     bool filter_option_set = false;                  // a --filter_* switch was given
     tsar_geom_check_params check{};                  // K, --filter_reproj_error, --filter_depth_diff (include/tsar.h tsar_geom_check)
@@ -192,7 +199,8 @@ static void usage() {
            "                   [--depth_min=D --depth_max=D] [--mode=patchmatch|load|tsar] [--all --gpus=N --workers=W] [--seed=S] [--strict] [--fix-quirks] [--texture-filter-8bit] [-color_processing] [--display_outputs] [--timing]\n"
            "                   [--multi_scale=L [--coarse_iterations=N] [--textureless_merge]]\n"
            "       tsar_gipuma --all [--gpus=N] [--force] [--fuse [--num_consistent=N --reproj_error=PX --depth_diff=REL --angle=DEG --used_list=0|1]]\n"
-           "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX] [--geom_multi_scale=L [--geom_coarse_iterations=N]]]\n"
+           "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX] [--geom_multi_scale=L [--geom_coarse_iterations=N]]\n"
+           "                    [--geom_cross_view[=K] [--geom_cross_view_depth_diff=REL]]]\n"
            "                   [--consistency_filter[=K] [--filter_reproj_error=PX] [--filter_depth_diff=REL]]\n"
            "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n"
            "       tsar_gipuma --check-mask=MASK.png | --encode-mask=DEPTH.dmb:MASK.png | --decode-image=IN[:OUT.pgm]     (no GPU)\n");
@@ -283,6 +291,15 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
         else if (starts("--geom_iterations=")) o.geom_iterations = atoi(a + 18);
         else if (starts("--geom_weight=")) o.geom_weight = (float)atof(a + 14);
         else if (starts("--geom_clip=")) o.geom_clip = (float)atof(a + 12);
+        else if (!strcmp(a, "--geom_cross_view")) { o.geom_cross_view = true; o.cross.min_views = 2; }
+        else if (starts("--geom_cross_view=")) {
+            char* end = nullptr;
+            const long k = strtol(a + 18, &end, 10);
+            if (!a[18] || *end || k < 1 || k > 63) { printf("Command-line parameter error: --geom_cross_view=K must be an integer in 1..63\n"); return -1; }
+            o.geom_cross_view = true;
+            o.cross.min_views = (int)k;
+        }
+        else if (starts("--geom_cross_view_depth_diff=")) { o.cross.depth_diff = (float)atof(a + 29); o.geom_cross_view_option_set = true; }
         else if (!strcmp(a, "--consistency_filter")) o.filter = true;
         else if (starts("--consistency_filter=")) {
             char* end = nullptr;
@@ -459,6 +476,10 @@ static std::string geom_record_of(const Options& o) {
              o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
              o.fix_quirks ? 1 : 0, o.tex8 ? 1 : 0, (double)o.cam_scale, (double)o.depth_min, (double)o.depth_max);
     std::string rec = b;
+    if (o.geom_cross_view) {          // (a record without the switch is byte for byte what it was before the switch existed)
+        snprintf(b, sizeof b, "geom_cross_view=%d geom_cross_view_depth_diff=%.9g\n", o.cross.min_views, (double)o.cross.depth_diff);
+        rec += b;
+    }
     if (o.geom_multi_scale > 0) {     // (an L = 0 record is the single-scale one, byte for byte)
         snprintf(b, sizeof b, "geom_multi_scale=%d geom_coarse_iterations=%d\n", o.geom_multi_scale, geom_coarse_iterations_of(o));
         rec += b;
@@ -887,8 +908,19 @@ static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vecto
     }
     if (tsar_load_planes(ctx, own_d.data(), own_n.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
     if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
+    if (o.geom_cross_view) {
+        // the sources' maps rendered into this view, kept where K of them agree, and offered to the matcher; the rendered map stays on the
+        // device.  The merge rescores first: at L = 0 it stands in for tsar_pm_rescore, at L >= 1 the chain is carried down from its planes
+        float* rendered = (float*)tsar_device_alloc(wk.device, (size_t)w * h * sizeof(float));
+        if (!rendered) return fail("tsar_device_alloc");
+        int rc = tsar_geom_reproject(ctx, &o.cross, rendered, nullptr, TSAR_MEM_DEVICE);
+        const char* what = "tsar_geom_reproject";
+        if (rc == TSAR_OK) { rc = tsar_pm_merge_depths(ctx, rendered, TSAR_MEM_DEVICE, nullptr); what = "tsar_pm_merge_depths"; }
+        tsar_device_free(wk.device, rendered);
+        if (rc != TSAR_OK) return fail(what);
+    }
     if (L == 0) {
-        if (tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
+        if (!o.geom_cross_view && tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
         if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
     } else {
         for (int k = 1; k <= L; k++) {
@@ -1212,6 +1244,15 @@ static bool options_valid(const Options& o) {
         if (o.mode == "tsar") { fprintf(stderr, "--geom_consistency does not work with --mode=tsar\n"); return false; }
         if (o.geom_iterations < 0 || !(o.geom_weight >= 0.f) || !(o.geom_clip > 0.f)) { fprintf(stderr, "--geom_iterations must be >= 0, --geom_weight >= 0, --geom_clip > 0\n"); return false; }
     }
+    if ((o.geom_cross_view || o.geom_cross_view_option_set) && !o.geom) {
+        fprintf(stderr, "--geom_cross_view / --geom_cross_view_depth_diff work with --geom_consistency only\n");
+        return false;
+    }
+    if (o.geom_cross_view_option_set && !o.geom_cross_view) { fprintf(stderr, "--geom_cross_view_depth_diff needs --geom_cross_view\n"); return false; }
+    if (o.geom_cross_view && (!(o.cross.depth_diff > 0.f) || !(o.cross.depth_diff < INFINITY))) {
+        fprintf(stderr, "--geom_cross_view_depth_diff must be finite and > 0\n");
+        return false;
+    }
     if (o.filter_option_set && !o.filter) { fprintf(stderr, "--filter_reproj_error / --filter_depth_diff work with --consistency_filter only\n"); return false; }
     if (o.filter) {
         if (!o.all) { fprintf(stderr, "--consistency_filter needs --all (the filter reads every view's depth map)\n"); return false; }
@@ -1230,6 +1271,7 @@ int main(int argc, char** argv) {
     Options o;
     tsar_default_fusion_params(&o.fusion);
     tsar_default_geom_check_params(&o.check);
+    tsar_default_geom_reproject_params(&o.cross);
     const int pr = parse_args(argc, argv, o);
     if (pr != 0) return pr < 0 ? 1 : 0;
     if (!options_valid(o)) return 1;
