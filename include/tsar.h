@@ -396,6 +396,52 @@ int tsar_geom_reproject(tsar_ctx* ctx, const tsar_geom_reproject_params* p, floa
  * tsar_pm_rescore.  Timed as "pm_rescore", tsar_pm_cost_planes's name for the scoring, and "pm_merge_depths" (two launches). */
 int tsar_pm_merge_depths(tsar_ctx* ctx, const float* depth, int mem, int64_t* n_taken_out);
 
+/* ---- plane prior ------------------------------------------------------------------------------ */
+/* A per-pixel prior plane and a truncated penalty on a hypothesis's deviation from it, added to the multi-view cost (ACMP's planar
+ * prior, used softly: the photometric and geometric costs arbitrate).  The prior may be a region plane, a coarser result, a filled map
+ * of the textureless refinement, anything external; the library builds none.
+ * The prior the context holds, per pixel (q_x, q_y, q_z, Dp): Dp is the caller's depth[y][x], unchanged; q is the caller's
+ * normal_world[y][x] taken to reference-camera coordinates exactly as tsar_load_planes takes it (the same device function, bit for bit).
+ * A pixel has a prior iff Dp > 0 and Dp < inf and the three normal components are finite; otherwise the held entry is (0, 0, 0, 0).
+ * Normals are used as given: the caller supplies unit normals.  tsar_get_plane_prior returns the held entries [h][w][4].
+ * The term, the same in both arithmetic modes: float32, every operation one IEEE-754 operation rounded to nearest, no fused
+ * multiply-add, quotients correctly rounded.  For a hypothesis n4 = (n_x, n_y, n_z, d) at (x, y):
+ *   c = its multi-view cost as without a prior: after best-N, with the geometric term inside it when one is installed
+ *   if no view was valid (c is TSAR_MAXCOST, best view -1) the result is c;  if the pixel has no prior the result is c;  otherwise
+ *   D   = the hypothesis's depth at (x, y) (getDepthFromPlane3_cu; the value the geometric term uses, once per hypothesis)
+ *   a   = |D - Dp|;  rel = a / Dp
+ *   r_d = rel / depth_clip if rel < depth_clip, else 1 (NaN fails the comparison: 1)
+ *   s   = 1 - ((n_x * q_x + n_y * q_y) + n_z * q_z);  s0 = 0 if s < 0, else s
+ *   r_n = s0 / normal_clip if s < normal_clip, else 1
+ *   t   = (weight_depth * r_d) + (weight_normal * r_n)
+ *   the result: c + t
+ * Best view and ratio are not touched.  The penalty is truncated on purpose: far from a wrong prior every hypothesis pays the same
+ * constant, so the data decide there.  As with the geometric term, a valid hypothesis's cost may now exceed TSAR_MAXCOST; only the
+ * invalid one equals it by construction.
+ *
+ * tsar_set_plane_prior: depth [h][w], normal_world [h][w][3] (what tsar_get_result returns), copied into memory the context owns.  Voids
+ * the stored costs and the propagation memo, like tsar_set_geom_depths; works with or without a geometric term; tsar_set_views removes
+ * the prior.  TSAR_ERR_INVALID: a NULL pointer; unknown mem; a weight negative or not finite; depth_clip not finite or <= 0; normal_clip
+ * outside (0, 2].  TSAR_ERR_STATE: no source views.
+ * With a prior installed every plane-scoring entry includes the term: tsar_pm_init, tsar_pm_iterate[_final], tsar_pm_sweep,
+ * tsar_pm_cost_planes, tsar_pm_rescore, tsar_pm_merge_depths, and tsar_upsample_merge on the fine context (the kernels are those of the
+ * geometric term, timed under its names: "pm_sweep_geom").  tsar_pyramid_views and tsar_upsample_planes return TSAR_ERR_STATE for a context
+ * with a prior, as with the geometric term.  A prior never moves to another context: tsar_pyramid_planes / tsar_geom_pyramid score the
+ * coarse context with the coarse context's own cost.  tsar_lrdiff, the check, the reprojection and the refinement operators do not score
+ * planes this way and are unchanged.
+ * tsar_clear_plane_prior: removes the prior (voids the stored costs).  tsar_get_plane_prior: TSAR_ERR_STATE without a prior.
+ * Timed as "plane_prior" (the conversion). */
+typedef struct tsar_plane_prior_params {
+    float weight_depth;   /* default 0.1  */
+    float weight_normal;  /* default 0.05 */
+    float depth_clip;     /* relative, default 0.02 */
+    float normal_clip;    /* 1 - cos(angle), default 1 - cos(30 deg) rounded once from float64 */
+} tsar_plane_prior_params;
+void tsar_default_plane_prior_params(tsar_plane_prior_params* p);
+int tsar_set_plane_prior(tsar_ctx* ctx, const float* depth, const float* normal_world, int mem, const tsar_plane_prior_params* p);
+int tsar_clear_plane_prior(tsar_ctx* ctx);
+int tsar_get_plane_prior(tsar_ctx* ctx, float* prior_out /* [h][w][4] as held */, int mem);
+
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */
 int tsar_get_result(tsar_ctx* ctx, float* depth, float* normal_world, float* cost, float* confid,

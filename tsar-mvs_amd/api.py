@@ -62,6 +62,10 @@ class GeomReprojectParams(C.Structure):
     _fields_ = [("depth_diff", C.c_float), ("min_views", C.c_int32)]
 
 
+class PlanePriorParams(C.Structure):
+    _fields_ = [("weight_depth", C.c_float), ("weight_normal", C.c_float), ("depth_clip", C.c_float), ("normal_clip", C.c_float)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -80,6 +84,7 @@ ABI_SYMBOLS = [
     "tsar_geom_pyramid", "tsar_pyramid_planes", "tsar_upsample_merge",
     "tsar_default_geom_check_params", "tsar_geom_check",
     "tsar_default_geom_reproject_params", "tsar_geom_reproject", "tsar_pm_merge_depths",
+    "tsar_default_plane_prior_params", "tsar_set_plane_prior", "tsar_clear_plane_prior", "tsar_get_plane_prior",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -142,6 +147,11 @@ def load_library(path: str = LIB_PATH):
     L.tsar_default_geom_reproject_params.argtypes = [C.POINTER(GeomReprojectParams)]
     L.tsar_geom_reproject.argtypes = [C.c_void_p, C.POINTER(GeomReprojectParams), C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_pm_merge_depths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+    L.tsar_default_plane_prior_params.restype = None
+    L.tsar_default_plane_prior_params.argtypes = [C.POINTER(PlanePriorParams)]
+    L.tsar_set_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PlanePriorParams)]
+    L.tsar_clear_plane_prior.argtypes = [C.c_void_p]
+    L.tsar_get_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -225,6 +235,7 @@ class Matcher:
         self.w = self.h = self.n_views = 0
         self.device = device
         self._keep = []
+        self.plane_prior_params = None     # the struct the last set_plane_prior passed, while that prior is installed
 
     def close(self):
         if self._ctx:
@@ -277,6 +288,7 @@ class Matcher:
         self._chk((self.L.tsar_set_views_u8 if u8 else self.L.tsar_set_views)(self._ctx, n, w, h, ptrs, kinds.pop(), cams))
         self._keep.clear()
         self.w, self.h, self.n_views = w, h, n
+        self.plane_prior_params = None     # tsar_set_views removes a prior
 
     def set_view_subset(self, idx):
         a = np.ascontiguousarray(idx, np.int32)
@@ -404,6 +416,34 @@ class Matcher:
         b = np.empty((3, 4), np.float32)
         self._chk(self.L.tsar_get_geom_matrices(self._ctx, view, _ptr(f)[0], _ptr(b)[0]))
         return f, b
+
+    # ---- plane prior ----
+    def set_plane_prior(self, depth, normal_world, weight_depth: float = 0.1, weight_normal: float = 0.05, depth_clip: float = 0.02,
+                        angle_clip_deg: float = 30.0):
+        """install a per-pixel prior plane (tsar_set_plane_prior): depth [h, w] and unit world normals [h, w, 3], numpy arrays or torch
+        device tensors; a pixel whose depth is not in (0, inf) or whose normal is not finite has no prior.  Every plane-scoring entry then
+        adds weight_depth * min(|D - Dp| / Dp / depth_clip, 1) + weight_normal * min((1 - n.q) / normal_clip, 1) to a valid hypothesis's
+        cost, normal_clip = 1 - cos(angle_clip_deg) rounded once from float64.  The struct passed is kept as plane_prior_params."""
+        depth_keep = depth if _is_torch(depth) else np.ascontiguousarray(depth, np.float32)
+        normal_keep = normal_world if _is_torch(normal_world) else np.ascontiguousarray(normal_world, np.float32)
+        assert tuple(depth_keep.shape) == (self.h, self.w) and tuple(normal_keep.shape) == (self.h, self.w, 3), "the prior must be [h, w] and [h, w, 3]"
+        d, kd = _ptr(depth_keep)
+        n, kn = _ptr(normal_keep)
+        assert kd == kn, "depth and normal_world must live in the same memory space"
+        p = PlanePriorParams(float(weight_depth), float(weight_normal), float(depth_clip), float(1.0 - np.cos(np.deg2rad(np.float64(angle_clip_deg)))))
+        self._chk(self.L.tsar_set_plane_prior(self._ctx, d, n, kd, C.byref(p)))
+        self.plane_prior_params = p
+
+    def clear_plane_prior(self):
+        """remove the plane prior (tsar_clear_plane_prior)"""
+        self._chk(self.L.tsar_clear_plane_prior(self._ctx))
+        self.plane_prior_params = None
+
+    def get_plane_prior(self):
+        """the prior as the context holds it: [h, w, 4] float32 (normal in reference-camera coordinates, depth), all zero where the pixel has none"""
+        out = np.empty((self.h, self.w, 4), np.float32)
+        self._chk(self.L.tsar_get_plane_prior(self._ctx, _ptr(out)[0], MEM_HOST))
+        return out
 
     # ---- the geometric-consistency pass coarse to fine ----
     def geom_pyramid_from(self, fine: "Matcher"):
@@ -710,18 +750,30 @@ def _cross_view_merge(matcher: Matcher, cross_view: int, cross_view_depth_diff: 
     return matcher.merge_depths(r["depth"])
 
 
+def _install_prior(matcher: Matcher, prior, prior_params):
+    """prior = (depth, normal_world); prior_params = None (the defaults) or a dict of set_plane_prior's keyword arguments"""
+    depth, normal_world = prior
+    matcher.set_plane_prior(depth, normal_world, **(prior_params or {}))
+
+
 def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, iters: int, weight: float = 0.2, clip: float = 3.0,
-                  cross_view: int = 0, cross_view_depth_diff: float = 0.01):
+                  cross_view: int = 0, cross_view_depth_diff: float = 0.01, prior=None, prior_params=None):
     """The geometric-consistency pass of one reference view: start from its own photometric result (depth [h, w], world normals
     [h, w, 3]), install the source views' depth maps (src_depths[v] for view v of the matcher, [0] ignored, None = no term), rescore,
     run `iters` iterations with the term, compute_disp.  The term stays installed (clear_geom removes it).
     cross_view = K >= 1: in place of the rescore, the source maps are rendered into this view (geom_reproject with min_views = K and
-    depth_diff = cross_view_depth_diff) and offered to the matcher (merge_depths, which rescores first)."""
+    depth_diff = cross_view_depth_diff) and offered to the matcher (merge_depths, which rescores first).
+    prior = (depth, normal_world): installed as the plane prior right after the maps (set_plane_prior; prior_params = its keyword
+    arguments as a dict, None = the defaults); it stays installed too (clear_plane_prior removes it)."""
     if iters < 0:
         raise ValueError("iters must be >= 0")
     _check_cross_view(cross_view, cross_view_depth_diff)
+    if prior is None and prior_params is not None:
+        raise ValueError("prior_params without a prior")
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
+    if prior is not None:
+        _install_prior(matcher, prior, prior_params)
     if cross_view:
         _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
     else:
@@ -731,20 +783,25 @@ def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, ite
 
 
 def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_depths, levels: int, coarse_iters: int, fine_iters: int,
-                             weight: float = 0.2, clip: float = 3.0, coarse=None, cross_view: int = 0, cross_view_depth_diff: float = 0.01):
+                             weight: float = 0.2, clip: float = 3.0, coarse=None, cross_view: int = 0, cross_view_depth_diff: float = 0.01,
+                             prior=None, prior_params=None):
     """The geometric-consistency pass coarse to fine (include/tsar.h tsar_geom_pyramid): `levels` pyramid levels below `matcher`; the
     view's own result and the term are carried down the chain, `coarse_iters` iterations run at the coarsest level, then every finer
     level (matcher's own included) merges the coarser planes into its own and runs `fine_iters` iterations; compute_disp.  levels = 0
     is run_geom_pass(matcher, ..., fine_iters).  coarse: the coarse contexts of an earlier call (finest first), reused; returns the
     list used.  The terms stay installed (clear_geom removes them).
     cross_view = K >= 1: as in run_geom_pass, on the full-resolution matcher right after its term is installed and before the chain is
-    carried down (the coarser levels then start from the merged planes)."""
+    carried down (the coarser levels then start from the merged planes).
+    prior, prior_params: as in run_geom_pass, on the full-resolution matcher only (a prior is not carried to coarser levels: they score
+    with their own cost); any prior the chain's contexts still hold is removed first, since tsar_pyramid_views refuses it."""
     if levels < 0 or coarse_iters < 0 or fine_iters < 0:
         raise ValueError("levels and iteration counts must be >= 0")
     _check_cross_view(cross_view, cross_view_depth_diff)
+    if prior is None and prior_params is not None:
+        raise ValueError("prior_params without a prior")
     if levels == 0:
         run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip, cross_view=cross_view,
-                      cross_view_depth_diff=cross_view_depth_diff)
+                      cross_view_depth_diff=cross_view_depth_diff, prior=prior, prior_params=prior_params)
         return list(coarse or [])
     coarse = list(coarse or [])
     while len(coarse) < levels:
@@ -752,10 +809,14 @@ def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_
     chain = [matcher] + coarse[:levels]
     for m in chain:                    # tsar_pyramid_views refuses contexts with a term
         m.clear_geom()
+        if prior is not None:
+            m.clear_plane_prior()
     for finer, coarser in zip(chain[:-1], chain[1:]):
         coarser.pyramid_from(finer)
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
+    if prior is not None:
+        _install_prior(matcher, prior, prior_params)
     if cross_view:
         _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
     for finer, coarser in zip(chain[:-1], chain[1:]):

@@ -115,6 +115,20 @@ __global__ __launch_bounds__(EW_BLOCK) void get_disp_kernel(const DevScene* __re
     c[p] = 1.0f;
 }
 
+// tsar_set_plane_prior: the prior as the context holds it, (q, Dp) per pixel: q is the caller's world normal taken to reference-camera
+// coordinates by get_disp_kernel's own mat3vec, Dp the caller's depth; (0, 0, 0, 0) where the pixel has no prior (include/tsar.h)
+__global__ __launch_bounds__(EW_BLOCK) void plane_prior_kernel(const DevScene* __restrict__ sc, const float* __restrict__ depth_in,
+                                                               const float* __restrict__ normal_world, float4* __restrict__ prior) {
+    PIXEL_LOOP_BEGIN
+    const float nw[3] = {normal_world[3 * (size_t)p], normal_world[3 * (size_t)p + 1], normal_world[3 * (size_t)p + 2]};
+    float n[3];
+    mat3vec(sc->ref.Rorig, nw, n);
+    const float Dp = depth_in[p];
+    const float inf = __builtin_inff();
+    const bool has = Dp > 0.0f && Dp < inf && fabsf(nw[0]) < inf && fabsf(nw[1]) < inf && fabsf(nw[2]) < inf;   // (NaN fails each)
+    prior[p] = has ? make_float4(n[0], n[1], n[2], Dp) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 // gipuma_compute_disp gipuma.cu:810-844: out4 = (R_orig^-1 n, depth or 0 where c == MAXCOST)
 __global__ __launch_bounds__(EW_BLOCK) void compute_disp_kernel(const DevScene* __restrict__ sc, const float* __restrict__ c,
                                                                 const float4* __restrict__ n4, float4* __restrict__ out4) {
@@ -244,6 +258,9 @@ __global__ __launch_bounds__(EW_BLOCK) void split_out4_kernel(const float4* __re
 
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world) {
     EW_LAUNCH(ctx, "get_disp", get_disp_kernel, ctx->dscene, depth_in, normal_world, ctx->buf[0].c, ctx->buf[0].n4, ctx->depth);
+}
+int launch_plane_prior(tsar_ctx* ctx, const float* depth_in, const float* normal_world, float4* prior) {
+    EW_LAUNCH(ctx, "plane_prior", plane_prior_kernel, ctx->dscene, depth_in, normal_world, prior);
 }
 int launch_compute_disp(tsar_ctx* ctx) { EW_LAUNCH(ctx, "compute_disp", compute_disp_kernel, ctx->dscene, ctx->buf[0].c, ctx->buf[0].n4, ctx->out4); }
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text) {

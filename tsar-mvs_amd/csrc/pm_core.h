@@ -195,10 +195,33 @@ DEVFN float geom_term(const DevScene* __restrict__ sc, const DevView& vw, int vi
     return sc->geom_weight * e;
 }
 
+// The plane-prior term t of the hypothesis n4 whose depth at (x, y) is D, added to its multi-view cost c (include/tsar.h states the
+// sequence; tests/test_plane_prior_cpu.py restates it in numpy float32).  Every operation is one IEEE fp32 operation and the three
+// quotients are the compiler's correctly rounded `/` (once per hypothesis, beside n_sel tap loops), so the value is the same in both
+// arithmetic modes.  (x, y) is the SCORED pixel: the packed sweep scores other lanes' pixels.  No prior installed is one scalar
+// branch (the pointer is wave-uniform); a pixel without a prior (held entry all zero) keeps c.
+DEVFN float add_prior_term(const DevScene* __restrict__ sc, int x, int y, const float4& n4, float D, float c) {
+    const float4* pp = sc->prior;
+    if (pp == nullptr) return c;
+    typedef float prior_entry __attribute__((ext_vector_type(4)));       // one 16-byte global load
+    const prior_entry q = ((const __attribute__((address_space(1))) prior_entry*)pp)[y * sc->w + x];
+    const float Dp = q.w;
+    const float a = fabsf(D - Dp);
+    const float rel = a / Dp;
+    const float dclip = sc->prior_depth_clip, nclip = sc->prior_normal_clip;
+    const float r_d = rel < dclip ? rel / dclip : 1.0f;                  // (NaN fails the comparison)
+    const float s = 1.0f - ((n4.x * q.x + n4.y * q.y) + n4.z * q.z);
+    const float s0 = s < 0.0f ? 0.0f : s;
+    const float r_n = s < nclip ? s0 / nclip : 1.0f;
+    const float t = (sc->prior_weight_depth * r_d) + (sc->prior_weight_normal * r_n);
+    return Dp > 0.0f ? c + t : c;
+}
+
 // pmCostMultiview_cu gipuma.cu:455-518: best-N combination over the selected views.  The NB
 // smallest costs are kept sorted in registers (sort_small :425-434 sorts all of them).
 // V & TSAR_V_GEOM: each view's cost becomes c_v + lambda e_v (geom_term) after the validity test, which stays on c_v; the depth of the
-// hypothesis at (x, y) is computed once, before the view loop.  The other bits of V name the tap loop.
+// hypothesis at (x, y) is computed once, before the view loop; after the best-N division the plane-prior term is added
+// (add_prior_term), which leaves best view and ratio alone.  The other bits of V name the tap loop.
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileOf<QUAD>::type* tile, int tw, int own, const float* wts, const PixelRef& pr,
                            int x, int y, const float4& n4, int& beview, float& ratio) {
@@ -265,6 +288,7 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
     cost = cost / (float)nb;
     ratio = num >= 2 ? best[0] / best[1] : 0.f;
     beview = bv;
+    if constexpr (GEOM) cost = add_prior_term(sc, x, y, n4, depth_h, cost);
     return cost;
 }
 

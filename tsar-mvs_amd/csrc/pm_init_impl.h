@@ -98,7 +98,7 @@ static int launch_full_t(tsar_ctx* ctx, const float4* planes, float* c, float4* 
     return TSAR_OK;
 }
 
-// The production launchers' entry, for a configuration of pm_dispatch.h: with a geometric-consistency term installed the same kernel
+// The production launchers' entry, for a configuration of pm_dispatch.h: with a geometric-consistency term or a plane prior installed the same kernel
 // with variant bit 24; REDRAW (tsar_pm_rescore) runs the initialising form with bit 25 as well (which always carries the term's code:
 // without maps every view's term is 0 and the scores are the photometric ones bit for bit).
 template <class Cfg, bool INIT, bool REDRAW = false>
@@ -107,6 +107,6 @@ static int launch_full_g(Cfg, tsar_ctx* ctx, const float4* planes, float* c, flo
     constexpr bool STRICT = Cfg::STRICT, QUAD = Cfg::QUAD;
     static_assert(INIT || !REDRAW, "only the initialising form redraws");
     if constexpr (REDRAW) return launch_full_t<NB, HR, STRICT, QUAD, true, V | TSAR_V_GEOM | TSAR_V_REDRAW>(ctx, planes, c, n, bv, rt);
-    else if (ctx->hscene.geom_on) return launch_full_t<NB, HR, STRICT, QUAD, INIT, V | TSAR_V_GEOM>(ctx, planes, c, n, bv, rt);
+    else if (scene_has_terms(ctx->hscene)) return launch_full_t<NB, HR, STRICT, QUAD, INIT, V | TSAR_V_GEOM>(ctx, planes, c, n, bv, rt);
     else return launch_full_t<NB, HR, STRICT, QUAD, INIT, V>(ctx, planes, c, n, bv, rt);
 }

@@ -82,7 +82,7 @@ int launch_pm_sweep(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const Pl
 #ifdef TSAR_EXPERIMENTS
     // measured-and-rejected / diagnostic forms (pm_sweep_experiments.hip: TSAR_VARIANT / TSAR_VARIANT_NOW); they have no form with the
     // geometric-consistency term, so while one is installed the production kernels run (with it) instead
-    if (!hs.geom_on) {
+    if (!scene_has_terms(hs)) {
         int launched = 0;
         const int rc = launch_pm_sweep_experiment(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine, &launched);
         if (rc != TSAR_OK || launched) return rc;

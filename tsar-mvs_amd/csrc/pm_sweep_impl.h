@@ -493,12 +493,12 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
     return TSAR_OK;
 }
 
-// The production launchers' entry: the same kernel with the geometric-consistency term (variant bit 24) while one is installed
-// (tsar_set_geom_depths).  The maps are fixed for the whole call, so a plane's score is still a function of the plane and the pixel:
+// The production launchers' entry: the same kernel with the geometric-consistency and plane-prior terms (variant bit 24) while either
+// is installed (tsar_set_geom_depths, tsar_set_plane_prior).  The maps and the prior are fixed for the whole call, so a plane's score is still a function of the plane and the pixel:
 // the memo and the packed form hold as they are.
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 static int launch_sweep_g(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
                           uint32_t stream_id, int do_prop, int do_refine) {
-    if (ctx->hscene.geom_on) return launch_sweep_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, BLK>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
+    if (scene_has_terms(ctx->hscene)) return launch_sweep_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, BLK>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
     return launch_sweep_t<NB, HR, STRICT, QUAD, V, BLK>(ctx, colour, same_in, other, same_out, stream_id, do_prop, do_refine);
 }

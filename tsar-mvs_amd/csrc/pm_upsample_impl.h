@@ -91,12 +91,12 @@ static int launch_up_t(tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
 }
 
 // The launchers' entry, for a configuration of pm_dispatch.h: the merge form carries the geometric-consistency term (variant bit 24)
-// while one is installed; the plain form never runs with one (tsar_upsample_planes refuses it).
+// while one, or a plane prior, is installed; the plain form never runs with either (tsar_upsample_planes refuses them).
 template <class Cfg, bool MERGE>
 static int launch_up_g(Cfg, tsar_ctx* ctx, const float4* coarse, int cw, int ch) {
     constexpr int NB = Cfg::NB, HR = Cfg::HR, V = Cfg::V;
     constexpr bool STRICT = Cfg::STRICT, QUAD = Cfg::QUAD;
     if constexpr (MERGE)
-        if (ctx->hscene.geom_on) return launch_up_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, true>(ctx, coarse, cw, ch);
+        if (scene_has_terms(ctx->hscene)) return launch_up_t<NB, HR, STRICT, QUAD, V | TSAR_V_GEOM, true>(ctx, coarse, cw, ch);
     return launch_up_t<NB, HR, STRICT, QUAD, V, MERGE>(ctx, coarse, cw, ch);
 }

@@ -262,6 +262,10 @@ static void free_geom(tsar_ctx* ctx) {
     for (auto& p : ctx->hscene.geom_depth) p = nullptr;
     ctx->hscene.geom_on = 0;
 }
+static void free_prior(tsar_ctx* ctx) {
+    dev_free(ctx->prior);
+    ctx->hscene.prior = nullptr;
+}
 static void free_planes(tsar_ctx* ctx) {
     for (int b = 0; b < 2; b++) { dev_free(ctx->buf[b].c); dev_free(ctx->buf[b].n4); }
     dev_free(ctx->ratio); dev_free(ctx->depth); dev_free(ctx->scale); dev_free(ctx->lrdiff); dev_free(ctx->confid);
@@ -279,6 +283,7 @@ extern "C" int tsar_destroy(tsar_ctx* ctx) {
     free_views(ctx);
     free_planes(ctx);
     free_geom(ctx);
+    free_prior(ctx);
     dev_free(ctx->dscene); dev_free(ctx->region_text); dev_free(ctx->region_size); dev_free(ctx->region_n4);
     if (ctx->scratch.base) hipFree(ctx->scratch.base);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
@@ -380,6 +385,7 @@ static int check_views_args(tsar_ctx* ctx, int n_views, int w, int h, const void
 // images, quad textures (and whether the imagery is 8-bit: use_quad), difference textures, derived cameras
 static int upload_views(tsar_ctx* ctx, int n_views, int w, int h, const void* const* gray, int elem, int mem, const tsar_camera* cams) {
     free_geom(ctx);                        // depth maps of the previous views' sources: not this scene's
+    free_prior(ctx);                       // nor is the prior
     // The image and quad-texture buffers of the previous views are kept when the size is the same (a worker matching view after
     // view of a scene): 2 x n_views hipMalloc + hipFree of ~100 MB each cost 55 ms per call at ETH3D size, more than the copies.
     // Buffers beyond n_views stay in the pool; a change of size releases everything.
@@ -748,6 +754,8 @@ extern "C" int tsar_pyramid_views(tsar_ctx* coarse, const tsar_ctx* fine_in) {
     if (!fine->have_views) return fail(coarse, TSAR_ERR_INVALID, "tsar_pyramid_views: the fine context has no views");
     if (fine->hscene.geom_on || coarse->hscene.geom_on)
         return fail(coarse, TSAR_ERR_STATE, "tsar_pyramid_views: coarse-to-fine with a geometric-consistency term is not supported (tsar_clear_geom first)");
+    if (fine->hscene.prior || coarse->hscene.prior)
+        return fail(coarse, TSAR_ERR_STATE, "tsar_pyramid_views: coarse-to-fine with a plane prior is not supported (tsar_clear_plane_prior first)");
     const tsar_params& fp = fine->params;
     const int cw = (fine->w + 1) / 2, ch = (fine->h + 1) / 2;
     if (cw < fp.box_hsize || ch < fp.box_vsize || cw < 8 || ch < 8)
@@ -781,6 +789,8 @@ extern "C" int tsar_upsample_planes(tsar_ctx* fine, const tsar_ctx* coarse_in) {
     NEED_SOURCES(fine);
     if (fine->hscene.geom_on || coarse->hscene.geom_on)
         return fail(fine, TSAR_ERR_STATE, "tsar_upsample_planes: coarse-to-fine with a geometric-consistency term is not supported (tsar_clear_geom first)");
+    if (fine->hscene.prior || coarse->hscene.prior)
+        return fail(fine, TSAR_ERR_STATE, "tsar_upsample_planes: coarse-to-fine with a plane prior is not supported (tsar_clear_plane_prior first)");
     if (!is_level_below(coarse, fine))
         return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context must hold views of ((w + 1) / 2, (h + 1) / 2) of the fine one on the same device (tsar_pyramid_views)");
     if (!coarse->have_state) return fail(fine, TSAR_ERR_INVALID, "tsar_upsample_planes: the coarse context has no plane state");
@@ -872,6 +882,69 @@ extern "C" int tsar_clear_geom(tsar_ctx* ctx) {
     free_geom(ctx);
     ctx->costs_voided();                   // scored with the term
     return ctx->dscene ? upload_scene(ctx) : TSAR_OK;
+}
+
+// ---- plane prior ---------------------------------------------------------------------------------
+extern "C" void tsar_default_plane_prior_params(tsar_plane_prior_params* p) {
+    if (!p) return;
+    p->weight_depth = 0.1f;
+    p->weight_normal = 0.05f;
+    p->depth_clip = 0.02f;
+    p->normal_clip = (float)(1.0 - 0.86602540378443864676);   // 1 - cos(30 deg), rounded once from float64
+}
+
+extern "C" int tsar_set_plane_prior(tsar_ctx* ctx, const float* depth, const float* normal_world, int mem, const tsar_plane_prior_params* p) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (ctx->n_views < 2 || ctx->hscene.n_sel < 1) return fail(ctx, TSAR_ERR_STATE, "tsar_set_plane_prior: the context has no source views");
+    if (!depth || !normal_world || !p) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_plane_prior: depth, normal_world or params is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_plane_prior: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    const float inf = __builtin_inff();
+    if (!(p->weight_depth >= 0.0f) || !(p->weight_depth < inf) || !(p->weight_normal >= 0.0f) || !(p->weight_normal < inf))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_set_plane_prior: the weights must be finite and >= 0");
+    if (!(p->depth_clip > 0.0f) || !(p->depth_clip < inf)) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_plane_prior: depth_clip must be finite and > 0");
+    if (!(p->normal_clip > 0.0f) || !(p->normal_clip <= 2.0f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_set_plane_prior: normal_clip must be in (0, 2]");
+    const size_t np = (size_t)ctx->w * ctx->h;
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // no kernel may still read the prior about to be replaced
+    if (!ctx->prior) {
+        const int rc = dev_alloc(ctx, &ctx->prior, np);
+        if (rc != TSAR_OK) { free_prior(ctx); upload_scene(ctx); return rc; }
+    }
+    {
+        CallFrame f(ctx, __func__);
+        const float *d = f.in(depth, np, mem), *n = f.in(normal_world, 3 * np, mem);
+        if (f.ok()) f.take(launch_plane_prior(ctx, d, n, ctx->prior));
+        const int rc = f.finish();
+        if (rc != TSAR_OK) { free_prior(ctx); upload_scene(ctx); return rc; }   // the device block must not keep a half-written prior
+    }
+    DevScene& sc = ctx->hscene;
+    sc.prior = ctx->prior;
+    sc.prior_weight_depth = p->weight_depth;
+    sc.prior_weight_normal = p->weight_normal;
+    sc.prior_depth_clip = p->depth_clip;
+    sc.prior_normal_clip = p->normal_clip;
+    ctx->costs_voided();                   // scored without this term, or with another prior
+    return upload_scene(ctx);
+}
+
+extern "C" int tsar_clear_plane_prior(tsar_ctx* ctx) {
+    CHECK_CTX(ctx);
+    if (!ctx->prior) return TSAR_OK;
+    if (ctx->stream) TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    free_prior(ctx);
+    ctx->costs_voided();                   // scored with the term
+    return ctx->dscene ? upload_scene(ctx) : TSAR_OK;
+}
+
+extern "C" int tsar_get_plane_prior(tsar_ctx* ctx, float* prior_out, int mem) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (!prior_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_get_plane_prior: prior_out is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_get_plane_prior: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (!ctx->hscene.prior) return fail(ctx, TSAR_ERR_STATE, "tsar_get_plane_prior: no plane prior installed (tsar_set_plane_prior)");
+    TSAR_HIP_TRY(ctx, hipMemcpyAsync(prior_out, ctx->prior, (size_t)ctx->w * ctx->h * sizeof(float4), kind_from_dev(mem), ctx->stream));
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSAR_OK;
 }
 
 // buf[0]'s planes scored with the context's cost (invalid ones redrawn as tsar_pm_init draws) into buf[1], which becomes the state:

@@ -78,14 +78,19 @@ struct DevScene {
     float geom_back[TSAR_MAX_VIEWS][12];           // [K_ref R^T K_v^-1 | -K_ref R^T t]: (c D_v, r D_v, D_v, 1) -> reference image (derive_cameras)
     float geom_weight, geom_clip, geom_clip_sq;    // lambda, tau, tau * tau
     int geom_on;                                   // a term is installed: the launchers pick the variant-bit-24 kernels
+    // Plane-prior term (include/tsar.h tsar_set_plane_prior; pm_core.h prior_term), carried by the same variant-bit-24 kernels.
+    const float4* prior;                           // [h][w] (q in reference-camera coordinates, Dp), all zero = no prior there (device, owned); null = no term
+    float prior_weight_depth, prior_weight_normal, prior_depth_clip, prior_normal_clip;
 };
+// the launchers pick the variant-bit-24 kernels: a geometric term, a plane prior or both (a prior alone runs them with every map null)
+static inline bool scene_has_terms(const DevScene& s) { return s.geom_on != 0 || s.prior != nullptr; }
 
 // Variant bits of the tap loops beside the box-11 loop's own numbers (114 / 122 / 250, pm_tap_r5.h)
 #define TSAR_V_LUT 1024           // bit 10: the general-window loop, weights from the shared table (pm_core_lut.h; chunk length in bits 11-13)
 #define TSAR_V_BUF 131072         // bit 17: gathers as structured buffer loads (pm_tap_r5.h BUF)
 #define TSAR_V_MIX 2097152        // bit 21, with TSAR_V_BUF: gathers from the half-float difference texture (pm_tap_r5.h MIX)
 // Variant bits of the geometric-consistency kernels (the remaining bits name the tap loop as before)
-#define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term)
+#define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term) and the plane-prior term to the result (add_prior_term)
 #define TSAR_V_REDRAW 33554432    // bit 25, with INIT: pm_full_kernel keeps the given plane where it is a valid hypothesis (tsar_pm_rescore)
 
 // State planes of one ping-pong buffer (linestate.h:12-13).
@@ -163,6 +168,8 @@ struct tsar_ctx {
     const float* final_text = nullptr;   // device lines->text while tsar_pm_iterate_final runs (the kernels' `final` mode), else null
     // geometric consistency (tsar_set_geom_depths): the source views' depth maps, owned; hscene.geom_depth points into them
     std::vector<float*> geom_maps;
+    // plane prior (tsar_set_plane_prior): owned; hscene.prior is this pointer while a prior is installed
+    float4* prior = nullptr;
     // timing
     int variant = 2;             // TSAR_VARIANT=n: code-generation variant of the fast-mode tap loop (pm_tap_r5.h view_cost_r5); tsar_create picks 250 (med3/fract + D16 window loads + clamp-free loop for in-image windows + wave priority + SGPR-pinned texture base and line-top weight loads + row-wise window walk in fast mode; strict mode runs it as 122, the oracle's column order) when the D16 probe passes, else 114
     bool mix_gather = true;      // TSAR_MIX_GATHER=0: keep the byte texture for the buffer-load launches too (pm_tap_r5.h MIX off)
@@ -433,6 +440,7 @@ int launch_merge_candidates(tsar_ctx* ctx, const float* depth, float4* cand);   
 int launch_merge_select(tsar_ctx* ctx, const float4* cand, const float* cand_c, const int32_t* cand_bv, const float* cand_rt,
                         unsigned long long* n_taken);                                          // geom_reproject_kernels.hip (writes buf[0], beview, ratio)
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world);
+int launch_plane_prior(tsar_ctx* ctx, const float* depth_in, const float* normal_world, float4* prior);   // plane_kernels.hip
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);
 int launch_depth_to_plane(tsar_ctx* ctx);

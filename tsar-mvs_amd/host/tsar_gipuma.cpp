@@ -30,6 +30,12 @@
 //                      are rendered into the view (tsar_geom_reproject, kept where K sources agree within REL) and offered to the
 //                      matcher (tsar_pm_merge_depths, in device memory), in place of the rescore at L = 0 and right after the term is
 //                      installed at L >= 1; TSAR_geom.txt gains a line with the two settings only when the switch is on
+//     [--geom_plane_prior=STEM [--geom_prior_weight_depth=W (0.1)] [--geom_prior_weight_normal=W (0.05)] [--geom_prior_depth_clip=REL (0.02)]
+//      [--geom_prior_angle_clip=DEG (30)]]   phase 2 of a view reads APD/<id>/STEM_disp.dmb + STEM_normals.dmb (a copy of a --mode=tsar
+//                      run's filled maps, say) as its plane prior (include/tsar.h tsar_set_plane_prior), installed on the full-resolution
+//                      context right after the term; a view lacking either file runs without a prior and is named on stdout;
+//                      TSAR_geom.txt gains a line with STEM and the four settings only when the switch is on, and a view whose prior
+//                      files are newer than its outputs is recomputed
 //   --all --consistency_filter[=K (2)] [--filter_reproj_error=PX (2)] [--filter_depth_diff=REL (0.01)]   a last phase after the matching
 //                      phases, before --fuse: each view's depth map of the phase that ran last (TSAR_geom_disp.dmb with
 //                      --geom_consistency, else TSAR_disp.dmb) is checked against its pair.txt sources' maps of the same phase
@@ -100,6 +106,10 @@ struct Options {
     bool geom_cross_view = false;                    // --geom_cross_view[=K]: phase 2 takes hypotheses from its sources' maps (tsar_geom_reproject + tsar_pm_merge_depths)
     bool geom_cross_view_option_set = false;         // --geom_cross_view_depth_diff was given
     tsar_geom_reproject_params cross{};              // --geom_cross_view_depth_diff, K
+    std::string geom_prior_stem;                     // --geom_plane_prior=STEM: phase 2 reads APD/<id>/STEM_disp.dmb + STEM_normals.dmb as its plane prior
+    bool geom_prior = false, geom_prior_option_set = false;   // the switch was given; one of its four settings was
+    tsar_plane_prior_params prior{};                 // --geom_prior_weight_depth / _weight_normal / _depth_clip; normal_clip from the angle
+    double geom_prior_angle = 30.0;                  // --geom_prior_angle_clip, degrees
     bool filter = false;                             // --consistency_filter[=K]: the last phase of --all (run_filter_view)
     bool filter_option_set = false;                  // a --filter_* switch was given
     tsar_geom_check_params check{};                  // K, --filter_reproj_error, --filter_depth_diff (include/tsar.h tsar_geom_check)
@@ -200,7 +210,9 @@ static void usage() {
            "                   [--multi_scale=L [--coarse_iterations=N] [--textureless_merge]]\n"
            "       tsar_gipuma --all [--gpus=N] [--force] [--fuse [--num_consistent=N --reproj_error=PX --depth_diff=REL --angle=DEG --used_list=0|1]]\n"
            "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX] [--geom_multi_scale=L [--geom_coarse_iterations=N]]\n"
-           "                    [--geom_cross_view[=K] [--geom_cross_view_depth_diff=REL]]]\n"
+           "                    [--geom_cross_view[=K] [--geom_cross_view_depth_diff=REL]]\n"
+           "                    [--geom_plane_prior=STEM [--geom_prior_weight_depth=W] [--geom_prior_weight_normal=W] [--geom_prior_depth_clip=REL]\n"
+           "                     [--geom_prior_angle_clip=DEG]]]\n"
            "                   [--consistency_filter[=K] [--filter_reproj_error=PX] [--filter_depth_diff=REL]]\n"
            "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n"
            "       tsar_gipuma --check-mask=MASK.png | --encode-mask=DEPTH.dmb:MASK.png | --decode-image=IN[:OUT.pgm]     (no GPU)\n");
@@ -300,6 +312,11 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
             o.cross.min_views = (int)k;
         }
         else if (starts("--geom_cross_view_depth_diff=")) { o.cross.depth_diff = (float)atof(a + 29); o.geom_cross_view_option_set = true; }
+        else if (starts("--geom_plane_prior=")) { o.geom_prior = true; o.geom_prior_stem = a + 19; }
+        else if (starts("--geom_prior_weight_depth=")) { o.prior.weight_depth = (float)atof(a + 26); o.geom_prior_option_set = true; }
+        else if (starts("--geom_prior_weight_normal=")) { o.prior.weight_normal = (float)atof(a + 27); o.geom_prior_option_set = true; }
+        else if (starts("--geom_prior_depth_clip=")) { o.prior.depth_clip = (float)atof(a + 24); o.geom_prior_option_set = true; }
+        else if (starts("--geom_prior_angle_clip=")) { o.geom_prior_angle = atof(a + 24); o.geom_prior_option_set = true; }
         else if (!strcmp(a, "--consistency_filter")) o.filter = true;
         else if (starts("--consistency_filter=")) {
             char* end = nullptr;
@@ -470,14 +487,20 @@ static std::string ms_record_of(const Options& o) {
     return b;
 }
 static int geom_coarse_iterations_of(const Options& o) { return o.geom_coarse_iterations_set ? o.geom_coarse_iterations : o.geom_iterations; }
+static std::string prior_file_of(const Options& o, int ref, const char* what) { return view_dir_of(o, ref) + o.geom_prior_stem + what; }
 static std::string geom_record_of(const Options& o) {
-    char b[400];
+    char b[640];
     snprintf(b, sizeof b, "geom_iterations=%d geom_weight=%.9g geom_clip=%.9g blocksize=%d n_best=%d cost_comb=%d seed=%llu strict=%d fix_quirks=%d texture_filter_8bit=%d cam_scale=%.9g depth_min=%.9g depth_max=%.9g\n",
              o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
              o.fix_quirks ? 1 : 0, o.tex8 ? 1 : 0, (double)o.cam_scale, (double)o.depth_min, (double)o.depth_max);
     std::string rec = b;
     if (o.geom_cross_view) {          // (a record without the switch is byte for byte what it was before the switch existed)
         snprintf(b, sizeof b, "geom_cross_view=%d geom_cross_view_depth_diff=%.9g\n", o.cross.min_views, (double)o.cross.depth_diff);
+        rec += b;
+    }
+    if (o.geom_prior) {
+        snprintf(b, sizeof b, "geom_plane_prior=%s geom_prior_weight_depth=%.9g geom_prior_weight_normal=%.9g geom_prior_depth_clip=%.9g geom_prior_angle_clip=%.9g\n",
+                 o.geom_prior_stem.c_str(), (double)o.prior.weight_depth, (double)o.prior.weight_normal, (double)o.prior.depth_clip, o.geom_prior_angle);
         rec += b;
     }
     if (o.geom_multi_scale > 0) {     // (an L = 0 record is the single-scale one, byte for byte)
@@ -552,6 +575,9 @@ static bool geom_outputs_current(const Options& o, int ref, const std::vector<in
     for (int s : srcs) inputs.push_back(view_dir_of(o, s) + PHASE1_FILES.depth);
     for (const std::string& in : inputs)
         if (!mtime_of(in, ti) || newer(ti, out)) return false;
+    if (o.geom_prior)                  // a prior file that is not there is no input (the view ran without a prior)
+        for (const char* what : {"_disp.dmb", "_normals.dmb"})
+            if (mtime_of(prior_file_of(o, ref, what), ti) && newer(ti, out)) return false;
     return true;
 }
 
@@ -908,6 +934,16 @@ static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vecto
     }
     if (tsar_load_planes(ctx, own_d.data(), own_n.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
     if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
+    if (o.geom_prior) {
+        // the view's plane prior, on the full-resolution context only; a view without the two files runs without one
+        std::vector<float> prior_d, prior_n;
+        int hh = 0, ww = 0, nn = 0;
+        const bool have = read_dmb(prior_file_of(o, ref, "_disp.dmb"), prior_d, hh, ww, nn) && hh == h && ww == w && nn == 1 &&
+                          read_dmb(prior_file_of(o, ref, "_normals.dmb"), prior_n, hh, ww, nn) && hh == h && ww == w && nn == 3;
+        if (!have) printf("view %08d (geom): no plane prior (%s / %s not readable at %d x %d): runs without one\n", ref,
+                          prior_file_of(o, ref, "_disp.dmb").c_str(), prior_file_of(o, ref, "_normals.dmb").c_str(), w, h);
+        else if (tsar_set_plane_prior(ctx, prior_d.data(), prior_n.data(), TSAR_MEM_HOST, &o.prior) != TSAR_OK) return fail("tsar_set_plane_prior");
+    }
     if (o.geom_cross_view) {
         // the sources' maps rendered into this view, kept where K of them agree, and offered to the matcher; the rendered map stays on the
         // device.  The merge rescores first: at L = 0 it stands in for tsar_pm_rescore, at L >= 1 the chain is carried down from its planes
@@ -940,6 +976,7 @@ static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vecto
     hr.normal.resize((size_t)3 * w * h);
     if (tsar_get_result(ctx, hr.depth.data(), hr.normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
     if (tsar_clear_geom(ctx) != TSAR_OK) return fail("tsar_clear_geom");
+    if (tsar_clear_plane_prior(ctx) != TSAR_OK) return fail("tsar_clear_plane_prior");
     const bool ok = write_maps(hr, GEOM_FILES, geom_record_of(o));
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return ok ? 0 : -1;
@@ -1253,6 +1290,28 @@ static bool options_valid(const Options& o) {
         fprintf(stderr, "--geom_cross_view_depth_diff must be finite and > 0\n");
         return false;
     }
+    if ((o.geom_prior || o.geom_prior_option_set) && !o.geom) {
+        fprintf(stderr, "--geom_plane_prior and its settings work with --geom_consistency only\n");
+        return false;
+    }
+    if (o.geom_prior_option_set && !o.geom_prior) {
+        fprintf(stderr, "--geom_prior_weight_depth / --geom_prior_weight_normal / --geom_prior_depth_clip / --geom_prior_angle_clip need --geom_plane_prior=STEM\n");
+        return false;
+    }
+    if (o.geom_prior) {
+        const std::string& st = o.geom_prior_stem;
+        if (st.empty() || st.find('/') != std::string::npos || st.find('\\') != std::string::npos) {
+            fprintf(stderr, "--geom_plane_prior=STEM: STEM must be a non-empty file-name stem without a path separator\n");
+            return false;
+        }
+        if (st == "TSAR" || st == "TSAR_geom") { fprintf(stderr, "--geom_plane_prior=STEM: TSAR and TSAR_geom name a phase's own outputs\n"); return false; }
+        const tsar_plane_prior_params& q = o.prior;
+        if (!(q.weight_depth >= 0.f) || !(q.weight_depth < INFINITY) || !(q.weight_normal >= 0.f) || !(q.weight_normal < INFINITY) || !(q.depth_clip > 0.f) ||
+            !(q.depth_clip < INFINITY) || !(o.geom_prior_angle > 0.0) || !(o.geom_prior_angle <= 180.0) || !(q.normal_clip > 0.f) || !(q.normal_clip <= 2.f)) {
+            fprintf(stderr, "--geom_prior_weight_depth / --geom_prior_weight_normal must be finite and >= 0, --geom_prior_depth_clip finite and > 0, --geom_prior_angle_clip in (0, 180] degrees\n");
+            return false;
+        }
+    }
     if (o.filter_option_set && !o.filter) { fprintf(stderr, "--filter_reproj_error / --filter_depth_diff work with --consistency_filter only\n"); return false; }
     if (o.filter) {
         if (!o.all) { fprintf(stderr, "--consistency_filter needs --all (the filter reads every view's depth map)\n"); return false; }
@@ -1272,8 +1331,10 @@ int main(int argc, char** argv) {
     tsar_default_fusion_params(&o.fusion);
     tsar_default_geom_check_params(&o.check);
     tsar_default_geom_reproject_params(&o.cross);
+    tsar_default_plane_prior_params(&o.prior);
     const int pr = parse_args(argc, argv, o);
     if (pr != 0) return pr < 0 ? 1 : 0;
+    o.prior.normal_clip = (float)(1.0 - cos(o.geom_prior_angle * (M_PI / 180.0)));   // 1 - cos(angle), rounded once from float64
     if (!options_valid(o)) return 1;
     if (o.mslp_folder.back() != '/') o.mslp_folder += '/';
     if (o.images_folder.back() != '/') o.images_folder += '/';
