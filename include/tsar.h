@@ -558,6 +558,11 @@ int tsar_selftest_sweep_census(tsar_ctx* ctx, int colour, uint64_t* out8);
  * [4] of those, pairs in which every alive lane repeats, [5] sum over waves of max-over-lanes alive arms, [6] ... of fresh ones,
  * [7] sum over waves of ceil(fresh pairs of the wave / 64) = the propagation trips of the packed form. */
 int tsar_selftest_sweep_repeat(tsar_ctx* ctx, int colour, void* memo_dev, uint64_t* out8);
+/* Census of the sweep's partial-window pruning (kernels with variant bit 26): on = 1 starts counting in every
+ * following sweep launch of this context, on = 0 stops and returns out32 = [refinement step 0..7][4]: (wave, hypothesis) pairs
+ * checked, (wave, view) pairs they had, (wave, view) pairs left early, hypotheses scored a second time in full because a lane
+ * accepted.  Launches that run no pruning kernel, or check no step, count nothing. */
+int tsar_selftest_prune_census(tsar_ctx* ctx, int on, uint32_t* out32);
 /* One stage of tsar_slic on caller-supplied HOST arrays, so that a test can hold every SLIC kernel to the outputs of the reference's
  * own per-pixel functions (gSLICr_seg_engine_shared.h:7-204, host-compiled from the reference where it lies: tests/golden/slic_ref.npz).
  * Centres are 32-byte records laid out like the reference's spixel_info (gSLICr_spixel_info.h:11-17: center 2 f32, color_info

@@ -89,7 +89,7 @@ ABI_SYMBOLS = [
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
     "tsar_host_alloc", "tsar_host_free", "tsar_device_alloc", "tsar_device_free", "tsar_device_write", "tsar_peer_copy", "tsar_enable_kernel_timing", "tsar_reset_kernel_timing", "tsar_get_kernel_timing",
-    "tsar_selftest_divide", "tsar_selftest_divide_random", "tsar_selftest_sqrt", "tsar_selftest_sweep_census", "tsar_selftest_sweep_repeat", "tsar_selftest_slic_stage",
+    "tsar_selftest_divide", "tsar_selftest_divide_random", "tsar_selftest_sqrt", "tsar_selftest_sweep_census", "tsar_selftest_prune_census", "tsar_selftest_sweep_repeat", "tsar_selftest_slic_stage",
 ]
 
 _lib = None
@@ -187,6 +187,8 @@ def load_library(path: str = LIB_PATH):
     L.tsar_get_kernel_timing.argtypes = [C.c_void_p, C.POINTER(KernelTiming), C.c_int, C.POINTER(C.c_int)]
     L.tsar_selftest_divide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_selftest_sweep_census.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+    if hasattr(L, "tsar_selftest_prune_census"):      # (a library built before the pruning kernels, loaded through TSAR_LIB for an A/B run)
+        L.tsar_selftest_prune_census.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
     L.tsar_selftest_sweep_repeat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
     L.tsar_selftest_sqrt.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tsar_selftest_divide_random.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -582,6 +584,15 @@ class Matcher:
         self._chk(self.L.tsar_selftest_sweep_census(self._ctx, colour, out))
         keys = ("waves", "arms_any_lane", "max_lane_survivors", "max_lane_survivors_nodup", "lane_survivors", "lane_survivors_nodup", "pixels", "arms_present")
         return dict(zip(keys, [int(v) for v in out]))
+
+    def selftest_prune_census(self, on: bool):
+        """on: start counting in the sweeps that follow; off: stop and return [step][checked, views, views_left, repeats] (8 x 4)"""
+        if on:
+            self._chk(self.L.tsar_selftest_prune_census(self._ctx, 1, None))
+            return None
+        out = (C.c_uint32 * 32)()
+        self._chk(self.L.tsar_selftest_prune_census(self._ctx, 0, out))
+        return np.array(out, np.int64).reshape(8, 4)
 
     def selftest_divide_random(self, log2_triples: int, seed: int, mode: int, guarded: bool = True):
         """(quotients differing from IEEE division, triples outside the operand guard) over 2^log2_triples device-generated triples."""

@@ -222,11 +222,16 @@ DEVFN float add_prior_term(const DevScene* __restrict__ sc, int x, int y, const 
 // V & TSAR_V_GEOM: each view's cost becomes c_v + lambda e_v (geom_term) after the validity test, which stays on c_v; the depth of the
 // hypothesis at (x, y) is computed once, before the view loop; after the best-N division the plane-prior term is added
 // (add_prior_term), which leaves best view and ratio alone.  The other bits of V name the tap loop.
+// V & TSAR_V_PRUNE (the sweep's best-view-only kernels, pruned_cost in pm_sweep_impl.h): while `prune` (wave-uniform), a view may be
+// left early when the partial-window bound proves its cost >= cost_now for every active lane; it then counts as invalid (MAXCOST) and
+// `skipped` is raised: the result is exact for a lane only if it is not below cost_now — pruned_cost repeats the hypothesis otherwise.
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileOf<QUAD>::type* tile, int tw, int own, const float* wts, const PixelRef& pr,
-                           int x, int y, const float4& n4, int& beview, float& ratio) {
+                           int x, int y, const float4& n4, int& beview, float& ratio, bool prune = false, float cost_now = 0.0f, int* skipped = nullptr) {
     constexpr bool GEOM = (V & TSAR_V_GEOM) != 0;
-    constexpr int VT = V & ~(TSAR_V_GEOM | TSAR_V_REDRAW);
+    constexpr bool PRUNE = (V & TSAR_V_PRUNE) != 0;
+    static_assert(!PRUNE || !GEOM, "the bound speaks of the photometric cost alone");
+    constexpr int VT = V & ~(TSAR_V_GEOM | TSAR_V_REDRAW | TSAR_V_PRUNE);
     float best[NB];
 #pragma unroll
     for (int k = 0; k < NB; k++) best[k] = __builtin_inff();
@@ -245,7 +250,14 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
         // V names the tap loop: bit 10 = the general-window loop (chunk length in bits 11-13), a production variant of the box-11
         // loop (pm_tap_r5.h), 0 = the generic one-tap loop; anything else exists in the experiments build only
         if constexpr ((VT & TSAR_V_LUT) != 0) c = view_cost_lut<STRICT, (VT >> 11) & 7, (VT & TSAR_V_BUF) != 0 && !STRICT, (VT & TSAR_V_MIX) != 0 && !STRICT>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
-        else if constexpr (QUAD && HR == 5 && r5_production_variant(VT))
+        else if constexpr (QUAD && HR == 5 && r5_production_variant(VT) && PRUNE) {
+            static_assert((VT & 250) == 250 && !STRICT, "pruning instantiations exist for the fast row-wise loop");
+            ViewPrune vp;
+            vp.on = prune; vp.skipped = false;
+            vp.cost_now = cmin < cost_now ? TSAR_MAXCOST : cost_now;          // (a lane that will accept needs exact values)
+            c = view_cost_r5<false, true, true, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK, 0, true>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4, &vp);
+            if (vp.skipped) *skipped += 1;
+        } else if constexpr (QUAD && HR == 5 && r5_production_variant(VT))
             c = view_cost_r5<STRICT, (VT & 128) != 0 && !STRICT, (VT & 8) != 0, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
 #ifdef TSAR_EXPERIMENTS
         else if constexpr (QUAD && HR == 5 && r5_diag_variant(VT))

@@ -54,7 +54,17 @@ static int launch_sweep_nh(tsar_ctx* ctx, int colour, const PlaneBuf& a, const P
 #define SWEEP_R5(S, V, B) (buf ? launch_sweep_g<NB, 5, S, true, (V) | TSAR_V_BUF, B>(ctx, colour, a, b, c, sid, dp, dr) : launch_sweep_g<NB, 5, S, true, V, B>(ctx, colour, a, b, c, sid, dp, dr))
         // fast mode, buffer-load launches: the half-float difference texture (pm_tap_r5.h MIX) when tsar_set_views built it
         const bool mix = buf && !strict && v == 250 && ctx->hscene.n_sel > 0 && ctx->hscene.view[ctx->hscene.sel[0]].dquad != nullptr;
-#define SWEEP_R5_FAST250(B) (mix ? launch_sweep_g<NB, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_MIX, B>(ctx, colour, a, b, c, sid, dp, dr) : SWEEP_R5(false, 250, B))
+#define SWEEP_R5_FAST250_ALL(B) (mix ? launch_sweep_g<NB, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_MIX, B>(ctx, colour, a, b, c, sid, dp, dr) : SWEEP_R5(false, 250, B))
+        // ... and, where a hypothesis's cost is its best view's alone (best-N combination, n_best 1, no geometric or prior term), the
+        // same three forms with the partial-window check of the wide refinement steps (TSAR_V_PRUNE; TSAR_PRUNE=0: never)
+        // Only in the launches that check (from launch TSAR_PRUNE_FROM of a call on): the pruning instantiation of the global-load
+        // form, which the first sweep of a view runs, is 5.8 ms slower than the plain one with its checks idle (profiles/prune).
+        const bool prune = NB == 2 && !strict && v == 250 && ctx->prune && ctx->prune_steps > 0 && dr && ctx->call_launch >= ctx->prune_from &&
+                           ctx->hscene.cost_comb == TSAR_COMB_BEST_N && ctx->hscene.n_best == 1 && !scene_has_terms(ctx->hscene);
+#define SWEEP_R5_PRUNE(B) (mix ? launch_sweep_t<2, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_MIX | TSAR_V_PRUNE, B>(ctx, colour, a, b, c, sid, dp, dr) \
+                           : buf ? launch_sweep_t<2, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_PRUNE, B>(ctx, colour, a, b, c, sid, dp, dr)              \
+                                 : launch_sweep_t<2, 5, false, true, 250 | TSAR_V_PRUNE, B>(ctx, colour, a, b, c, sid, dp, dr))
+#define SWEEP_R5_FAST250(B) (prune ? SWEEP_R5_PRUNE(B) : SWEEP_R5_FAST250_ALL(B))
         if constexpr (NB == 2) {
             // small images: 128-thread workgroups (see SWEEP_SMALL_IMAGE_TILES); TSAR_BLOCK=128|256 forces a shape (A/B runs)
             const int tiles256 = ((ctx->hscene.w + PM_RW - 1) / PM_RW) * ((ctx->hscene.h + 15) / 16);
@@ -69,6 +79,8 @@ static int launch_sweep_nh(tsar_ctx* ctx, int colour, const PlaneBuf& a, const P
         if (strict) return SWEEP_R5(true, 122, PM_BLOCK);
         return v == 250 ? SWEEP_R5_FAST250(PM_BLOCK) : launch_sweep_g<NB, 5, false, true, 122>(ctx, colour, a, b, c, sid, dp, dr);
 #undef SWEEP_R5_FAST250
+#undef SWEEP_R5_PRUNE
+#undef SWEEP_R5_FAST250_ALL
 #undef SWEEP_R5
     }
     constexpr int NBG = NB == 4 ? 32 : NB;      // the one-tap-at-a-time kernels exist for 2 and 32 best views

@@ -119,7 +119,41 @@ struct SweepMemo {
     uint32_t launch, valid_from;     // this launch's number; memos written before valid_from are void
     int mode;                        // 0 = off, 1 = kept and applied (a memo-skipped arm is an arm skipped)
     int slot_off;                    // CMP kernels: byte offset in dynamic LDS of the waves' hand-over slots (6 bytes per lane)
+    int prune_steps;                 // TSAR_V_PRUNE kernels: refinement steps below this are checked in this launch (0: none)
+    uint32_t* prune_counts;          // ... and, while a census runs (tsar_selftest_prune_census), [step][4] counters; else null
 };
+
+// A hypothesis's multi-view cost, as the loop bodies below call it.  The pruning kernels (variant bit TSAR_V_PRUNE: best view only,
+// no geometric or prior term) check refinement steps below memo.prune_steps (`step` is wave-uniform; -1 = a propagation arm): views
+// the partial-window bound proves >= cost_now for the whole wave are left early.  A rejected hypothesis needs no value.  If any lane
+// accepts while the wave left views, the hypothesis is scored again in full for the wave, so that an accepted hypothesis carries the
+// exact cost, second-best ratio and best view.  Counters per step: hypotheses checked, views checked, views left, repeats.
+template <int NB, int HR, bool STRICT, bool QUAD, int V, int BLK>
+DEVFN float pruned_cost(const DevScene* __restrict__ sc, const typename TileOf<QUAD>::type* tile, int tw, int own, const float* wts, const PixelRef& pr,
+                        int x, int y, const float4& n4, int& beview, float& ratio, int step, float cost_now, int prune_steps, uint32_t* prune_counts) {
+    if constexpr ((V & TSAR_V_PRUNE) == 0) {
+        return multiview_cost<NB, HR, STRICT, QUAD, V, BLK>(sc, tile, tw, own, wts, pr, x, y, n4, beview, ratio);
+    } else {
+        bool prune = step >= 0 && step < prune_steps;
+        float c;
+#pragma unroll 1
+        for (;;) {
+            int skipped = 0;
+            c = multiview_cost<NB, HR, STRICT, QUAD, V, BLK>(sc, tile, tw, own, wts, pr, x, y, n4, beview, ratio, prune, cost_now, &skipped);
+            const bool redo = skipped != 0 && __any(c < cost_now);
+            if (prune && prune_counts != nullptr) {
+                const uint64_t act = __ballot(1);
+                if ((threadIdx.x & 63) == __ffsll((long long)act) - 1) {
+                    uint32_t* k = prune_counts + 4 * step;
+                    atomicAdd(k + 0, 1u); atomicAdd(k + 1, (uint32_t)sc->n_sel); atomicAdd(k + 2, (uint32_t)skipped); atomicAdd(k + 3, redo ? 1u : 0u);
+                }
+            }
+            if (!redo) break;
+            prune = false;
+        }
+        return c;
+    }
+}
 
 // One hypothesis of the propagation / refinement loop scored for pixel (x, y): what the loop body shares between its forms.
 // CMP = false: the rolled loop over the eight arms and the refinement steps, each lane scoring its own pixel's hypotheses (a lane
@@ -277,7 +311,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
                     deltaZ = deltaZ / 10.0f;
                 }
                 int bv; float rt;
-                const float cost_t = multiview_cost<NB, HR, STRICT, QUAD, V, BLK>(sc, tile, tw, own, wts, pr, x, y, n_t, bv, rt);
+                const float cost_t = pruned_cost<NB, HR, STRICT, QUAD, V, BLK>(sc, tile, tw, own, wts, pr, x, y, n_t, bv, rt, h - 8, cost_now, memo.prune_steps, memo.prune_counts);
                 if (cost_t < cost_now) {
                     cost_now = cost_t; n_now = n_t; depth_now = depth_t;
                     ratio_w = rt; beview_w = bv; wrote = true;
@@ -413,7 +447,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
             const float* ewts = LUTW ? wts_base : wts_base + etid;
             int bv = -1;
             float rt = 0.f, cost_t = TSAR_MAXCOST;
-            if (go) cost_t = multiview_cost<NB, HR, STRICT, QUAD, V, BLK>(sc, tile, tw, eown, ewts, epr, ex, ey, n_t, bv, rt);
+            if (go) cost_t = pruned_cost<NB, HR, STRICT, QUAD, V, BLK>(sc, tile, tw, eown, ewts, epr, ex, ey, n_t, bv, rt, it - trips, cost_now, memo.prune_steps, memo.prune_counts);
             if (it < trips) {
                 // owners collect, arms in increasing order: the reference's eight calls one after the other
                 arms_of_trip(lo, [&](int a, int j, bool has) {
@@ -457,7 +491,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
 
 // the tap loops of 8-bit imagery — box 11's own and the general-window one — have a packed form (CMP) beside the rolled one
 template <int HR, bool QUAD, int V>
-constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~TSAR_V_GEOM)) || (V & TSAR_V_LUT) != 0); }
+constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~(TSAR_V_GEOM | TSAR_V_PRUNE))) || (V & TSAR_V_LUT) != 0); }
 
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
@@ -472,6 +506,8 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
     memo.cand = ctx->memo_cand; memo.seq = ctx->memo_seq; memo.changed = ctx->changed_seq;
     memo.launch = ctx->launch_seq; memo.valid_from = ctx->memo_valid_from;
     memo.mode = (ctx->memo_mode && ctx->memo_cand && ctx->cost_consistent && !ctx->final_text) ? 1 : 0;
+    memo.prune_steps = ((V & TSAR_V_PRUNE) != 0 && do_refine && ctx->call_launch >= ctx->prune_from) ? ctx->prune_steps : 0;
+    memo.prune_counts = (V & TSAR_V_PRUNE) != 0 ? ctx->prune_counts : nullptr;
     bool packed = false;
     if constexpr (sweep_has_packed_form<HR, QUAD, V>())
         packed = memo.mode && do_prop && ctx->compact_from >= 0 && ctx->call_launch >= ctx->compact_from;
@@ -485,6 +521,7 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
     {
         ScopedKernelTimer tm(ctx, (V & TSAR_V_GEOM) ? "pm_sweep_geom" : "pm_sweep");
         ScopedKernelTimer tm_packed(ctx, packed ? "pm_sweep_packed" : nullptr);      // (the packed launches a second time under their own name)
+        ScopedKernelTimer tm_prune(ctx, (V & TSAR_V_PRUNE) ? "pm_sweep_prune" : nullptr);   // (and the pruning kernels, checking or not)
         hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(BLK), g.lds, ctx->stream, ctx->dscene, colour, same_in.c, same_in.n4, other.c,
                            other.n4, same_out.c, same_out.n4, ctx->ratio, ctx->beview, stream_id, do_prop, do_refine, g.tiles_x, g.n_tiles,
                            ctx->cost_consistent ? 1 : 0, strip_width(ctx->strip_w, g.tiles_x), ctx->final_text, memo);

@@ -185,6 +185,41 @@ DEVFN PixelRef pixel_ref_from_sums(float sum_ref, float sum_ref_ref, float inv_w
     return pr;
 }
 
+// ---- the partial-window bound of the pruning kernels (variant bit TSAR_V_PRUNE; pm_tap_r5.h runs it, DESIGN.md section 4 argues it) ----
+// What multiview_cost hands a view's tap loop, and what comes back: `on` and `skipped` are wave-uniform.
+struct ViewPrune {
+    float cost_now;   // the lane's cost, or >= 1 for a lane that must not be proven (it has seen a view below its cost: it will accept)
+    bool on;          // this hypothesis is checked at all
+    bool skipped;     // out: every lane was proven and the view was left (its cost is >= cost_now, value unknown)
+};
+// e bounds the rounding of each W-normalised second moment the cost tail forms (var_ref, var_src, covar; 36 taps of 8-bit data summed
+// in fp32: <= 227 u 255^2 = 0.881, u = 2^-24); e_A the same for the W_A-scaled moments of the taps walked so far (<= 103 u 255^2 = 0.40).
+#define PM_PRUNE_E 0.9f
+#define PM_PRUNE_EA 0.45f
+#define PM_PRUNE_SLACK 1.0e-4f     // every other rounding: the tail's root, quotient and 1 - x (< 2e-6), this test's own operations
+// The test after the taps of A: aw, ar, arr = sum(w), sum(w r), sum(w r^2) over A, t = the view's running sums.  With a = W_A S_rr,A,
+// b = W_A S_ss,A, c = W_A S_rs,A (centred sums times W_A), Q_A = (a - c^2 / b) / W_A grows with a and b and falls with |c|, so
+// q <= Q_A is formed from a - E, b - E, |c| + E, E = e_A W_A^2.  Then, for the exact moments of the whole window,
+// ncc^2 <= 1 - Q_A / (W var_ref) <= n2 = 1 - q / (W (var_ref_k + e)), var_src >= S_ss,A / W >= vs, var_ref >= vr = var_ref_k - e, and
+// the tail's own value obeys ncc_k^2 <= (ncc^2 + 2 e / g + (e / g)^2) / ((1 - e / vr) (1 - e / vs)) with g = sqrt(vr vs).  Proven:
+// that is <= (1 - cost_now)^2 - slack.  Six reciprocal-class operations per check, three checks per view of ~7000 issue units.
+// Anything non-finite or out of range fails.
+DEVFN bool prune_proven(const TapSums& t, float aw, float ar, float arr, const PixelRef& pr, float cost_now) {
+    const float E = PM_PRUNE_EA * aw * aw;
+    const float a_lo = fma_(aw, arr, -(ar * ar)) - E;
+    const float b_lo = fma_(aw, t.src_src, -(t.src * t.src)) - E;
+    const float c_hi = fabsf(fma_(aw, t.ref_src, -(ar * t.src))) + E;
+    const float raw = __builtin_amdgcn_rcpf(aw);
+    const float q = fma_(-(c_hi * c_hi), __builtin_amdgcn_rcpf(b_lo), a_lo) * raw;
+    const float vs = (b_lo * raw) * pr.inv_wsum, vr = pr.var_ref - PM_PRUNE_E;
+    const float n2 = fma_(-q, pr.inv_wsum * __builtin_amdgcn_rcpf(pr.var_ref + PM_PRUNE_E), 1.0f);
+    const float eg = PM_PRUNE_E * __builtin_amdgcn_rsqf(vr * vs);
+    const float tt = 1.0f - cost_now;
+    const float lhs = fma_(eg, 2.0f + eg, n2);
+    const float rhs = (fma_(tt, tt, -PM_PRUNE_SLACK) * (1.0f - PM_PRUNE_E * __builtin_amdgcn_rcpf(vr))) * (1.0f - PM_PRUNE_E * __builtin_amdgcn_rcpf(vs));
+    return cost_now < 1.0f && vr >= 2.0f * PM_PRUNE_E && vs >= 2.0f * PM_PRUNE_E && lhs <= rhs;
+}
+
 // The cost of a view from its three sums, the tail of pmCost (gipuma.cu:229-298), on 8-bit imagery: MAXCOST below the variance
 // threshold, else 1 - NCC clamped to [0, MAXCOST].  Both variances are >= 1e-5 here and at most 255^2, so their product lies
 // inside sqrt_rsq_exact's range by construction and the correctly rounded root needs no guard (and none of the six v_cndmask of

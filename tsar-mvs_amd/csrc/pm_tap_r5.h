@@ -34,13 +34,23 @@
 // BLK: threads per workgroup = stride, in floats, between the weights of consecutive taps of one thread ([tap][thread]).
 #pragma once
 
+// the partial-window checks (PRUNE below) run after lines PM_PRUNE_FIRST_LINE .. PM_PRUNE_LAST_LINE of the six
+#define PM_PRUNE_FIRST_LINE 2
+#define PM_PRUNE_LAST_LINE 4
+
 // DIAG (experiments build only, WRONG RESULTS by construction; the ceilings of profiles/r04): 1 = the MIX body with every gather
 // removed (the tap's halfs are synthesised from its element index: the VALU floor of the shipping body), 2 = every gather replaced
 // by an 8-byte LDS read at a per-lane address (ds_read_b64: the instruction mix of source patches staged in LDS, before any staging).
-template <bool STRICT, bool ROW, bool D16, bool BUF, bool MIX, int BLK, int DIAG = 0>
+// PRUNE (variant bit TSAR_V_PRUNE; fast mode, ROW + D16 only): while vp.on, the view is left after its second, third or fourth line
+// when the partial-window bound (prune_proven, pm_tap_common.h) shows for EVERY active lane that this loop's own result would be
+// >= the lane's cost_now; vp.skipped then tells the caller that the returned MAXCOST stands for "not below cost_now".  The three
+// reference sums over the lines walked so far are formed from LDS at each check (no register lives across a line for them: the
+// kernels have none to spare).  The decision is wave-uniform, like the clamp-free one.
+template <bool STRICT, bool ROW, bool D16, bool BUF, bool MIX, int BLK, int DIAG = 0, bool PRUNE = false>
 DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, const unsigned short* tile, int tw, int own, const float* wts,
-                         const PixelRef& pr, int x, int y, const float4& n4) {
+                         const PixelRef& pr, int x, int y, const float4& n4, ViewPrune* vp = nullptr) {
     static_assert(!(STRICT && ROW), "the row-wise walk changes the summation order: fast mode only");
+    static_assert(!PRUNE || (ROW && D16 && !STRICT && DIAG == 0), "the partial-window bound is written for the fast row-wise loop");
     static_assert(!MIX || (BUF && !STRICT), "the half-float difference texture serves the fast arithmetic's blend through buffer loads");
     const int w = sc->w, h = sc->h, qp = sc->quad_pitch;
     const int qorg = quad_border_bytes(qp);
@@ -212,17 +222,38 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
             sum_src = t.src; sum_src_src = t.src_src; sum_ref_src = t.ref_src;
         }
     };
+    // after line `line` (0-based): true = every active lane is proven, leave the view
+    auto pruned = [&](int line) {
+        if constexpr (PRUNE) {
+            if (vp->on && line >= PM_PRUNE_FIRST_LINE - 1 && line < PM_PRUNE_LAST_LINE) {
+                float pa_w = 0.f, pa_r = 0.f, pa_rr = 0.f;
+#pragma unroll 1
+                for (int l = 0; l <= line; l++) {
+#pragma unroll
+                    for (int jj = 0; jj < 6; jj++) {
+                        const float wt = wts[(6 * jj + l) * BLK], r = tile_value(tile[own + (2 * l - 5) * tw + (2 * jj - 5)]);
+                        const float wr = wt * r;
+                        pa_w += wt;
+                        pa_r += wr;
+                        pa_rr = fma_(wr, r, pa_rr);
+                    }
+                }
+                if (__all(prune_proven(TapSums{sum_src, sum_src_src, sum_ref_src}, pa_w, pa_r, pa_rr, pr, vp->cost_now))) { vp->skipped = true; return true; }
+            }
+        }
+        return false;
+    };
     if (need_clamp) {
 #pragma unroll 1
-        for (int i = -5; i <= 5; i += 2) line6(i, std::true_type(), std::false_type());
-    } else if constexpr (MIX) {
+        for (int i = -5; i <= 5; i += 2) { line6(i, std::true_type(), std::false_type()); if (pruned((i + 5) >> 1)) return TSAR_MAXCOST; }
+    } else if (MIX && !(PRUNE && vp->on)) {      // (a checked hypothesis walks the rolled loop below: the checks sit between its trips)
         // the converged launches' hot path: the six lines unrolled (-6 VALU and the loop's scalar bookkeeping per line; +0.65 %
         // Mpix/s, profiles/r04/ab_unrolled_lines)
 #pragma unroll
-        for (int i = -5; i <= 5; i += 2) line6(i, std::false_type(), std::true_type());
+        for (int i = -5; i <= 5; i += 2) line6(i, std::false_type(), std::bool_constant<MIX>());
     } else {
 #pragma unroll 1
-        for (int i = -5; i <= 5; i += 2) line6(i, std::false_type(), std::false_type());
+        for (int i = -5; i <= 5; i += 2) { line6(i, std::false_type(), std::false_type()); if (pruned((i + 5) >> 1)) return TSAR_MAXCOST; }
     }
     return ncc_cost(pr, TapSums{sum_src, sum_src_src, sum_ref_src});
 }
@@ -231,4 +262,5 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
 // + TSAR_V_MIX (with 250 | TSAR_V_BUF): MIX
 // + 4194304 / + 8388608 (experiments build): DIAG 1 / 2 of the MIX body
 __host__ __device__ constexpr bool r5_diag_variant(int V) { return V == (250 | TSAR_V_BUF | TSAR_V_MIX | 4194304) || V == (250 | TSAR_V_BUF | TSAR_V_MIX | 8388608); }
+// + TSAR_V_PRUNE (with 250 and its BUF / MIX forms): PRUNE; masked off before this test, like TSAR_V_GEOM
 __host__ __device__ constexpr bool r5_production_variant(int V) { return V == 114 || V == 122 || V == 250 || V == (114 | TSAR_V_BUF) || V == (122 | TSAR_V_BUF) || V == (250 | TSAR_V_BUF) || V == (250 | TSAR_V_BUF | TSAR_V_MIX); }

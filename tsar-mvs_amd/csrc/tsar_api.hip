@@ -217,6 +217,9 @@ static void read_knobs(tsar_ctx* ctx) {
     ctx->force_block = num("TSAR_BLOCK", 0);
     ctx->memo_mode = num("TSAR_MEMO", 1);
     ctx->compact_from = num("TSAR_COMPACT_FROM", 6);
+    ctx->prune = num("TSAR_PRUNE", 1);
+    ctx->prune_steps = std::min(std::max(num("TSAR_PRUNE_STEPS", 2), 0), 8);      // (the census keeps eight steps' counters)
+    ctx->prune_from = num("TSAR_PRUNE_FROM", 1);
     ctx->lut_mode = num("TSAR_LUT", 1);
     ctx->ransac_wgs = num("TSAR_RANSAC_WGS", 8);
     ctx->ransac_chain = num("TSAR_RANSAC_CHAIN", 8);
@@ -271,6 +274,7 @@ static void free_planes(tsar_ctx* ctx) {
     dev_free(ctx->ratio); dev_free(ctx->depth); dev_free(ctx->scale); dev_free(ctx->lrdiff); dev_free(ctx->confid);
     dev_free(ctx->fakedepth); dev_free(ctx->beview); dev_free(ctx->canny); dev_free(ctx->out4);
     dev_free(ctx->memo_cand); dev_free(ctx->memo_seq); dev_free(ctx->changed_seq);
+    if (ctx->prune_counts) { (void)hipFree(ctx->prune_counts); ctx->prune_counts = nullptr; }
     dev_free(ctx->resize4);
     ctx->have_resize = false;
 }
@@ -1368,4 +1372,20 @@ extern "C" int tsar_selftest_sweep_census(tsar_ctx* ctx, int colour, uint64_t* o
     NEED_STATE(ctx);
     if (!out8) return fail(ctx, TSAR_ERR_INVALID, "out8 is NULL");
     return run_counters(ctx, 8, out8, [&](unsigned long long* dc) { return launch_sweep_census(ctx, colour & 1, dc); });
+}
+// Counters of the pruning kernels (pm_sweep_impl.h pruned_cost): on = 1 zeroes them and makes every following sweep launch of this
+// context count; on = 0 hands them back (out32 may be NULL) and stops the counting.
+extern "C" int tsar_selftest_prune_census(tsar_ctx* ctx, int on, uint32_t* out32) {
+    CHECK_CTX(ctx);
+    TSAR_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (on) {
+        if (!ctx->prune_counts) TSAR_HIP_TRY(ctx, hipMalloc((void**)&ctx->prune_counts, 32 * sizeof(uint32_t)));
+        TSAR_HIP_TRY(ctx, hipMemset(ctx->prune_counts, 0, 32 * sizeof(uint32_t)));
+        return TSAR_OK;
+    }
+    if (!ctx->prune_counts) return fail(ctx, TSAR_ERR_INVALID, "no prune census is running");
+    if (out32) TSAR_HIP_TRY(ctx, hipMemcpy(out32, ctx->prune_counts, 32 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    TSAR_HIP_TRY(ctx, hipFree(ctx->prune_counts));
+    ctx->prune_counts = nullptr;
+    return TSAR_OK;
 }

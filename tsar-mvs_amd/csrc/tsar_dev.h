@@ -91,6 +91,7 @@ static inline bool scene_has_terms(const DevScene& s) { return s.geom_on != 0 ||
 #define TSAR_V_MIX 2097152        // bit 21, with TSAR_V_BUF: gathers from the half-float difference texture (pm_tap_r5.h MIX)
 // Variant bits of the geometric-consistency kernels (the remaining bits name the tap loop as before)
 #define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term) and the plane-prior term to the result (add_prior_term)
+#define TSAR_V_PRUNE 67108864     // bit 26, with 250 and its BUF / MIX forms, sweep only: wide refinement steps leave a view the partial-window bound proves rejected (pm_tap_r5.h PRUNE)
 #define TSAR_V_REDRAW 33554432    // bit 25, with INIT: pm_full_kernel keeps the given plane where it is a valid hypothesis (tsar_pm_rescore)
 
 // State planes of one ping-pong buffer (linestate.h:12-13).
@@ -160,6 +161,11 @@ struct tsar_ctx {
     int call_launch = 0;              // launches since the current sweep call began
     int memo_mode = 1;                // TSAR_MEMO=0: off
     int compact_from = 6;             // TSAR_COMPACT_FROM=n (-1: never): from launch n of a call on, a wave packs its surviving hypotheses (pm_sweep_impl.h)
+    // Partial-window pruning of the wide refinement steps (pm_tap_r5.h PRUNE; fast mode, best view only, no geometric / prior term)
+    int prune = 1;                    // TSAR_PRUNE=0: off (the kernels without the check)
+    int prune_steps = 2;              // TSAR_PRUNE_STEPS=n: refinement steps 0 .. n - 1 are checked
+    int prune_from = 1;               // TSAR_PRUNE_FROM=n: from launch n of a call on
+    uint32_t* prune_counts = nullptr; // tsar_selftest_prune_census: device counters while a census runs, else null
     // coarse-to-fine mode (tsar_pyramid_views / tsar_upsample_planes)
     std::vector<tsar_camera> cams;    // the cameras tsar_set_views was given (before cam_scale), from which a coarser level derives its own
     bool views_u8 = false;            // the views came through tsar_set_views_u8 (a coarser level is then an 8-bit decode too)
