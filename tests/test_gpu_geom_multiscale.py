@@ -580,3 +580,48 @@ def test_cli_geom_multi_scale(tmp_path):
     back = _cli(CLI, *geom)
     assert back.stdout.count("(geom): ok") == n and back.stdout.count("outputs present, skipped") == n
     assert open(vd(0) + "TSAR_geom.txt").read() == rec0
+
+
+def test_cli_every_geom_switch_at_once(tmp_path):
+    """--geom_multi_scale, --geom_cross_view, --geom_plane_prior and --consistency_filter in one run: each view's geom maps are, bit for
+    bit, api.run_geom_pass_multiscale with the same switches on the files the tool read (the term, then the prior, then the merge, then the
+    chain down), and its filtered map is Matcher.geom_check on the geom maps"""
+    import shutil
+    from tsar_mvs_amd import io as tio
+    sc = synth.make_scene(96, 72, 2, seed=95)
+    root = str(tmp_path) + "/"
+    tio.export_scene(sc, root)
+    n = len(sc.images)
+    vd = lambda k: root + f"APD/{k:08d}/"
+    common = ["--all", "--gpus=1", "-mslp_folder", root, "-images_folder", root + "images/", "--iterations=2", "--blocksize=11", "--n_best=1", "--seed=7"]
+    _cli(CLI, *common)
+    for k in range(n):                                 # P: a copy of each view's phase-1 maps
+        shutil.copy(vd(k) + "TSAR_disp.dmb", vd(k) + "P_disp.dmb")
+        shutil.copy(vd(k) + "TSAR_normals.dmb", vd(k) + "P_normals.dmb")
+    out = _cli(CLI, *common, "--geom_consistency", "--geom_iterations=1", "--geom_multi_scale=1", "--geom_cross_view=1", "--geom_plane_prior=P",
+               "--consistency_filter=1")
+    assert out.stdout.count("(geom): ok") == n and out.stdout.count("(filter): ok") == n and "no plane prior" not in out.stdout
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    for k in range(n):
+        ids = [k] + [s for s in range(n) if s != k]
+        imgs = [tio.read_pgm(root + f"images/{i:08d}.pgm") for i in ids]
+        cams = [tio.read_cam(root + f"cams/{i:08d}_cam.txt") for i in ids]
+        m = api.Matcher()
+        m.set_params(api.default_params(box_hsize=11, box_vsize=11, n_best=1, depth_min=cams[0][3], depth_max=cams[0][4], flags=0, seed=7 + k))
+        m.set_views(imgs, np.stack([c[0] for c in cams]), np.stack([c[1] for c in cams]), np.stack([c[2] for c in cams]), u8=True)
+        src = [None] + [tio.read_dmb(vd(i) + "TSAR_disp.dmb") for i in ids[1:]]
+        coarse = api.run_geom_pass_multiscale(m, tio.read_dmb(vd(k) + "TSAR_disp.dmb"), tio.read_dmb(vd(k) + "TSAR_normals.dmb"), src, levels=1,
+                                              coarse_iters=1, fine_iters=1, cross_view=1,
+                                              prior=(tio.read_dmb(vd(k) + "P_disp.dmb"), tio.read_dmb(vd(k) + "P_normals.dmb")))
+        r = m.get_result(("depth", "normal"))
+        geom_depth = tio.read_dmb(vd(k) + "TSAR_geom_disp.dmb")
+        assert np.array_equal(bits(r["depth"]), bits(geom_depth)), k
+        assert np.array_equal(bits(r["normal"]), bits(tio.read_dmb(vd(k) + "TSAR_geom_normals.dmb"))), k
+        # the filter: the geom maps checked against the sources' geom maps, K = 1
+        m.clear_plane_prior()
+        m.set_geom_depths([None] + [tio.read_dmb(vd(i) + "TSAR_geom_disp.dmb") for i in ids[1:]], weight=0.0)
+        kept = m.geom_check(geom_depth, min_consistent=1, want=("depth",))["depth"]
+        m.close()
+        for c in coarse:
+            c.close()
+        assert np.array_equal(bits(kept), bits(tio.read_dmb(vd(k) + "TSAR_filtered_disp.dmb"))), k

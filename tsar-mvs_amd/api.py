@@ -338,7 +338,6 @@ class Matcher:
 
     # ---- plane <-> depth ----
     def load_planes(self, depth, normal_world):
-        d, kd = _ptr(depth if _is_torch(depth) else np.ascontiguousarray(depth, np.float32))
         depth_keep = depth if _is_torch(depth) else np.ascontiguousarray(depth, np.float32)
         normal_keep = normal_world if _is_torch(normal_world) else np.ascontiguousarray(normal_world, np.float32)
         d, kd = _ptr(depth_keep)
@@ -727,18 +726,29 @@ def matcher_from_scene(scene, box=11, n_best=1, cost_comb=COMB_BEST_N, flags=0, 
     return m
 
 
+def _pyramid_chain(matcher: Matcher, levels: int, coarse, prepare=None):
+    """`coarse` (the coarse contexts of an earlier call, finest first, or None) grown to `levels` contexts, and the chain [matcher] +
+    coarse[:levels] with matcher's views carried down it (pyramid_from); every context of the chain goes through `prepare` first
+    (tsar_pyramid_views refuses a context that holds a term or a prior).  Returns (coarse, chain)."""
+    coarse = list(coarse or [])
+    while len(coarse) < levels:
+        coarse.append(Matcher(matcher.device))
+    chain = [matcher] + coarse[:levels]
+    if prepare is not None:
+        for m in chain:
+            prepare(m)
+    for finer, coarser in zip(chain[:-1], chain[1:]):
+        coarser.pyramid_from(finer)
+    return coarse, chain
+
+
 def run_multiscale(matcher: Matcher, levels: int, coarse_iters: int, fine_iters: int, coarse=None):
     """Coarse-to-fine PatchMatch on `matcher`'s views: init + `coarse_iters` iterations at the coarsest of `levels` pyramid levels,
     then at every finer level (matcher's own included) upsample + `fine_iters` iterations.  levels = 0 is plain init + coarse_iters.
     coarse: the coarse contexts of an earlier call (finest first), reused; returns the list used, for the next call."""
     if levels < 0 or coarse_iters < 0 or fine_iters < 0:
         raise ValueError("levels and iteration counts must be >= 0")
-    coarse = list(coarse or [])
-    while len(coarse) < levels:
-        coarse.append(Matcher(matcher.device))
-    chain = [matcher] + coarse[:levels]
-    for finer, coarser in zip(chain[:-1], chain[1:]):
-        coarser.pyramid_from(finer)
+    coarse, chain = _pyramid_chain(matcher, levels, coarse)
     chain[-1].pm_init()
     chain[-1].pm_iterate(coarse_iters)
     for k in range(levels - 1, -1, -1):
@@ -814,16 +824,11 @@ def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_
         run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip, cross_view=cross_view,
                       cross_view_depth_diff=cross_view_depth_diff, prior=prior, prior_params=prior_params)
         return list(coarse or [])
-    coarse = list(coarse or [])
-    while len(coarse) < levels:
-        coarse.append(Matcher(matcher.device))
-    chain = [matcher] + coarse[:levels]
-    for m in chain:                    # tsar_pyramid_views refuses contexts with a term
+    def clear(m):
         m.clear_geom()
         if prior is not None:
             m.clear_plane_prior()
-    for finer, coarser in zip(chain[:-1], chain[1:]):
-        coarser.pyramid_from(finer)
+    coarse, chain = _pyramid_chain(matcher, levels, coarse, prepare=clear)
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
     if prior is not None:

@@ -160,6 +160,9 @@ struct PinnedAllocator {
 };
 typedef std::vector<float, PinnedAllocator<float>> PinnedFloats;
 
+typedef std::chrono::steady_clock Clock;
+static double seconds_since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
 static std::string stem8(const std::string& name) { return name.substr(0, 8); }   // main.cpp:1460
 static std::string pnm_name(const std::string& name, const char* want) {
     const size_t dot = name.find_last_of('.');
@@ -218,57 +221,66 @@ static void usage() {
            "       tsar_gipuma --check-mask=MASK.png | --encode-mask=DEPTH.dmb:MASK.png | --decode-image=IN[:OUT.pgm]     (no GPU)\n");
 }
 
+// the text after "--name=" when `a` is that option, else null
+static const char* value_of(const char* a, const char* name) {
+    const size_t n = strlen(name);
+    return strncmp(a, name, n) == 0 && a[n] == '=' ? a + n + 1 : nullptr;
+}
+// a whole decimal integer in lo..hi into `out`; false, and `out` as it was, for anything else (empty text included)
+static bool checked_int(const char* v, long lo, long hi, int& out) {
+    char* end = nullptr;
+    const long k = strtol(v, &end, 10);
+    if (!*v || *end || k < lo || k > hi) return false;
+    out = (int)k;
+    return true;
+}
 static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946: same spellings, unknown options only warn
     for (int i = 1; i < argc; i++) {
         const char* a = argv[i];
-        auto starts = [&](const char* p) { return strncmp(a, p, strlen(p)) == 0; };
+        const char* v = nullptr;                              // the value of the option `opt` matched last
+        auto opt = [&](const char* name) { return (v = value_of(a, name)) != nullptr; };
+        auto is = [&](const char* name) { return strcmp(a, name) == 0; };
         if (a[0] != '-') o.images.push_back(a);
-        else if (starts("--iterations=")) o.iterations = atoi(a + 13);
-        else if (starts("--blocksize=")) {
-            const int k = atoi(a + 12);
+        else if (opt("--iterations")) o.iterations = atoi(v);
+        else if (opt("--blocksize")) {
+            const int k = atoi(v);
             if (k < 1 || k % 2 != 1) { printf("Command-line parameter error: The block size (--blocksize=<...>) must be a positive odd number\n"); return -1; }
             o.blocksize = k;
-        } else if (starts("--n_best=")) o.n_best = atoi(a + 9);
-        else if (starts("--cost_comb=")) {
-            const char* v = a + 12;
+        } else if (opt("--n_best")) o.n_best = atoi(v);
+        else if (opt("--cost_comb")) {
             if (!strcmp(v, "all")) o.cost_comb = TSAR_COMB_ALL;
             else if (!strcmp(v, "best_n")) o.cost_comb = TSAR_COMB_BEST_N;
             else if (!strcmp(v, "angle")) o.cost_comb = TSAR_COMB_ANGLE;      // main.cpp:787-790; the kernels treat both as "all" (gipuma.cu:496-499)
             else if (!strcmp(v, "good")) o.cost_comb = TSAR_COMB_GOOD;
             else { printf("Command-line parameter error: Unknown cost combination method\n\n"); usage(); return -1; }
-        } else if (starts("--cam_scale=")) o.cam_scale = (float)atof(a + 12);
-        else if (starts("--depth_min=")) o.depth_min = (float)atof(a + 12);
-        else if (starts("--depth_max=")) o.depth_max = (float)atof(a + 12);
-        else if (starts("--gpus=")) o.gpus = atoi(a + 7);
-        else if (starts("--workers=")) o.workers = atoi(a + 10);
-        else if (starts("--seed=")) o.seed = strtoull(a + 7, nullptr, 10);
-        else if (starts("--mode=")) o.mode = a + 7;
-        else if (starts("--multi_scale=") || starts("--coarse_iterations=") || starts("--geom_multi_scale=") || starts("--geom_coarse_iterations=")) {
-            const bool geom = starts("--geom_"), ms = starts(geom ? "--geom_multi_scale=" : "--multi_scale=");
-            const char* v = strchr(a, '=') + 1;
-            char* end = nullptr;
-            const long k = strtol(v, &end, 10);
-            if (!*v || *end || k < 0 || k > (ms ? 8 : 1000000)) {
-                printf("Command-line parameter error: %s must be %s\n", a, ms ? "an integer in 0..8" : "a non-negative integer");
-                return -1;
-            }
-            if (ms) (geom ? o.geom_multi_scale : o.multi_scale) = (int)k;
-            else if (geom) { o.geom_coarse_iterations = (int)k; o.geom_coarse_iterations_set = true; }
-            else { o.coarse_iterations = (int)k; o.coarse_iterations_set = true; }
+        } else if (opt("--cam_scale")) o.cam_scale = (float)atof(v);
+        else if (opt("--depth_min")) o.depth_min = (float)atof(v);
+        else if (opt("--depth_max")) o.depth_max = (float)atof(v);
+        else if (opt("--gpus")) o.gpus = atoi(v);
+        else if (opt("--workers")) o.workers = atoi(v);
+        else if (opt("--seed")) o.seed = strtoull(v, nullptr, 10);
+        else if (opt("--mode")) o.mode = v;
+        else if (opt("--multi_scale") || opt("--geom_multi_scale")) {
+            if (!checked_int(v, 0, 8, value_of(a, "--multi_scale") ? o.multi_scale : o.geom_multi_scale)) { printf("Command-line parameter error: %s must be an integer in 0..8\n", a); return -1; }
         }
-        else if (!strcmp(a, "--textureless_merge")) o.textureless_merge = true;
-        else if (starts("--check-mask=")) {          // diagnostics, no GPU: decode a weak.png the way --mode=tsar does
+        else if (opt("--coarse_iterations") || opt("--geom_coarse_iterations")) {
+            const bool geom = !value_of(a, "--coarse_iterations");
+            if (!checked_int(v, 0, 1000000, geom ? o.geom_coarse_iterations : o.coarse_iterations)) { printf("Command-line parameter error: %s must be a non-negative integer\n", a); return -1; }
+            (geom ? o.geom_coarse_iterations_set : o.coarse_iterations_set) = true;
+        }
+        else if (is("--textureless_merge")) o.textureless_merge = true;
+        else if (opt("--check-mask")) {              // diagnostics, no GPU: decode a weak.png the way --mode=tsar does
             std::vector<float> scale;
             int mw = 0, mh = 0;
-            if (!read_reliable_mask(a + 13, scale, mw, mh)) { printf("cannot decode %s\n", a + 13); return -1; }
+            if (!read_reliable_mask(v, scale, mw, mh)) { printf("cannot decode %s\n", v); return -1; }
             size_t ones = 0, wsum = 0;
             for (size_t k = 0; k < scale.size(); k++)
                 if (scale[k] == 1.0f) { ones++; wsum += k % 9973; }
             printf("mask %d x %d reliable %zu checksum %zu\n", mw, mh, ones, wsum);
             return 1;
         }
-        else if (starts("--encode-mask=")) {         // diagnostics, no GPU: the mask of a filtered depth map (kept = depth > 0) the way --consistency_filter writes TSAR_consistent.png
-            std::string in = a + 14, out;
+        else if (opt("--encode-mask")) {             // diagnostics, no GPU: the mask of a filtered depth map (kept = depth > 0) the way --consistency_filter writes TSAR_consistent.png
+            std::string in = v, out;
             const size_t colon = in.rfind(':');
             if (colon != std::string::npos) { out = in.substr(colon + 1); in = in.substr(0, colon); }
             std::vector<float> depth;
@@ -280,8 +292,8 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
             printf("mask %d x %d reliable %zu -> %s\n", dw, dh, ones, out.c_str());
             return 1;
         }
-        else if (starts("--decode-image=")) {        // no GPU: decode an image the way a run would, --decode-image=IN[:OUT.pgm] [-color_processing first]
-            std::string in = a + 15, out;
+        else if (opt("--decode-image")) {            // no GPU: decode an image the way a run would, --decode-image=IN[:OUT.pgm] [-color_processing first]
+            std::string in = v, out;
             const size_t colon = in.rfind(':');
             if (colon != std::string::npos) { out = in.substr(colon + 1); in = in.substr(0, colon); }
             std::vector<uint8_t> px;
@@ -289,7 +301,7 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
             std::string why;
             if (!read_view_image(in, o.color, px, iw, ih, &why)) { printf("cannot decode %s: %s\n", in.c_str(), why.c_str()); return -1; }
             uint64_t sum = 0, mix = 1469598103934665603ull;
-            for (uint8_t v : px) { sum += v; mix = (mix ^ v) * 1099511628211ull; }
+            for (uint8_t b : px) { sum += b; mix = (mix ^ b) * 1099511628211ull; }
             printf("image %d x %d sum %llu fnv1a %016llx\n", iw, ih, (unsigned long long)sum, (unsigned long long)mix);
             if (!out.empty()) {
                 FILE* f = fopen(out.c_str(), "wb");
@@ -298,56 +310,50 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
             }
             return 1;
         }
-        else if (!strcmp(a, "--all")) o.all = true;
-        else if (!strcmp(a, "--geom_consistency")) o.geom = true;
-        else if (starts("--geom_iterations=")) o.geom_iterations = atoi(a + 18);
-        else if (starts("--geom_weight=")) o.geom_weight = (float)atof(a + 14);
-        else if (starts("--geom_clip=")) o.geom_clip = (float)atof(a + 12);
-        else if (!strcmp(a, "--geom_cross_view")) { o.geom_cross_view = true; o.cross.min_views = 2; }
-        else if (starts("--geom_cross_view=")) {
-            char* end = nullptr;
-            const long k = strtol(a + 18, &end, 10);
-            if (!a[18] || *end || k < 1 || k > 63) { printf("Command-line parameter error: --geom_cross_view=K must be an integer in 1..63\n"); return -1; }
+        else if (is("--all")) o.all = true;
+        else if (is("--geom_consistency")) o.geom = true;
+        else if (opt("--geom_iterations")) o.geom_iterations = atoi(v);
+        else if (opt("--geom_weight")) o.geom_weight = (float)atof(v);
+        else if (opt("--geom_clip")) o.geom_clip = (float)atof(v);
+        else if (is("--geom_cross_view")) { o.geom_cross_view = true; o.cross.min_views = 2; }
+        else if (opt("--geom_cross_view")) {
+            if (!checked_int(v, 1, 63, o.cross.min_views)) { printf("Command-line parameter error: --geom_cross_view=K must be an integer in 1..63\n"); return -1; }
             o.geom_cross_view = true;
-            o.cross.min_views = (int)k;
         }
-        else if (starts("--geom_cross_view_depth_diff=")) { o.cross.depth_diff = (float)atof(a + 29); o.geom_cross_view_option_set = true; }
-        else if (starts("--geom_plane_prior=")) { o.geom_prior = true; o.geom_prior_stem = a + 19; }
-        else if (starts("--geom_prior_weight_depth=")) { o.prior.weight_depth = (float)atof(a + 26); o.geom_prior_option_set = true; }
-        else if (starts("--geom_prior_weight_normal=")) { o.prior.weight_normal = (float)atof(a + 27); o.geom_prior_option_set = true; }
-        else if (starts("--geom_prior_depth_clip=")) { o.prior.depth_clip = (float)atof(a + 24); o.geom_prior_option_set = true; }
-        else if (starts("--geom_prior_angle_clip=")) { o.geom_prior_angle = atof(a + 24); o.geom_prior_option_set = true; }
-        else if (!strcmp(a, "--consistency_filter")) o.filter = true;
-        else if (starts("--consistency_filter=")) {
-            char* end = nullptr;
-            const long k = strtol(a + 21, &end, 10);
-            if (!a[21] || *end || k < 1 || k > 31) { printf("Command-line parameter error: --consistency_filter=K must be an integer in 1..31\n"); return -1; }
+        else if (opt("--geom_cross_view_depth_diff")) { o.cross.depth_diff = (float)atof(v); o.geom_cross_view_option_set = true; }
+        else if (opt("--geom_plane_prior")) { o.geom_prior = true; o.geom_prior_stem = v; }
+        else if (opt("--geom_prior_weight_depth")) { o.prior.weight_depth = (float)atof(v); o.geom_prior_option_set = true; }
+        else if (opt("--geom_prior_weight_normal")) { o.prior.weight_normal = (float)atof(v); o.geom_prior_option_set = true; }
+        else if (opt("--geom_prior_depth_clip")) { o.prior.depth_clip = (float)atof(v); o.geom_prior_option_set = true; }
+        else if (opt("--geom_prior_angle_clip")) { o.geom_prior_angle = atof(v); o.geom_prior_option_set = true; }
+        else if (is("--consistency_filter")) o.filter = true;
+        else if (opt("--consistency_filter")) {
+            if (!checked_int(v, 1, 31, o.check.min_consistent)) { printf("Command-line parameter error: --consistency_filter=K must be an integer in 1..31\n"); return -1; }
             o.filter = true;
-            o.check.min_consistent = (int)k;
         }
-        else if (starts("--filter_reproj_error=")) { o.check.reproj_error = (float)atof(a + 22); o.filter_option_set = true; }
-        else if (starts("--filter_depth_diff=")) { o.check.depth_diff = (float)atof(a + 20); o.filter_option_set = true; }
-        else if (!strcmp(a, "--fuse")) o.fuse = true;
-        else if (!strcmp(a, "--force")) o.force = true;                        // --all: recompute views whose outputs are already there
-        else if (starts("--num_consistent=")) o.fusion.num_consistent = atoi(a + 17);
-        else if (starts("--reproj_error=")) o.fusion.reproj_error = (float)atof(a + 15);
-        else if (starts("--depth_diff=")) o.fusion.depth_diff = (float)atof(a + 13);
-        else if (starts("--angle=")) o.fusion.angle_deg = (float)atof(a + 8);
-        else if (starts("--used_list=")) o.fusion.used_list = atoi(a + 12);
-        else if (!strcmp(a, "--strict")) o.strict = true;
-        else if (!strcmp(a, "--fix-quirks")) o.fix_quirks = true;
-        else if (!strcmp(a, "--texture-filter-8bit")) o.tex8 = true;      // bilinear weights with 8 fractional bits, like the CUDA texture unit
-        else if (!strcmp(a, "-images_folder") && i + 1 < argc) o.images_folder = argv[++i];
-        else if (!strcmp(a, "-mslp_folder") && i + 1 < argc) o.mslp_folder = argv[++i];
-        else if (!strcmp(a, "-krt_file") && i + 1 < argc) o.krt_file = argv[++i];
-        else if (!strcmp(a, "-output_folder") && i + 1 < argc) o.output_folder = argv[++i];
-        else if (!strcmp(a, "-color_processing")) o.color = true;      // main.cpp:727,909
-        else if (!strcmp(a, "--timing")) o.timing = true;                     // wall time of each host-side step of a view, on stdout
-        else if (!strcmp(a, "--display_outputs")) o.display_outputs = true;   // TSAR_normals.png + TSAR_model.ply (main.cpp:1800-1838)
-        else if (!strcmp(a, "-no_display") || starts("--cost_gamma=") || starts("--min_angle=") || starts("--max_angle=") || starts("--cost_tau_color=") ||
-                 starts("--cost_tau_gradient=") || starts("--cost_alpha=") || starts("--max_views=") || starts("--num_img_processed=")) {
+        else if (opt("--filter_reproj_error")) { o.check.reproj_error = (float)atof(v); o.filter_option_set = true; }
+        else if (opt("--filter_depth_diff")) { o.check.depth_diff = (float)atof(v); o.filter_option_set = true; }
+        else if (is("--fuse")) o.fuse = true;
+        else if (is("--force")) o.force = true;                                // --all: recompute views whose outputs are already there
+        else if (opt("--num_consistent")) o.fusion.num_consistent = atoi(v);
+        else if (opt("--reproj_error")) o.fusion.reproj_error = (float)atof(v);
+        else if (opt("--depth_diff")) o.fusion.depth_diff = (float)atof(v);
+        else if (opt("--angle")) o.fusion.angle_deg = (float)atof(v);
+        else if (opt("--used_list")) o.fusion.used_list = atoi(v);
+        else if (is("--strict")) o.strict = true;
+        else if (is("--fix-quirks")) o.fix_quirks = true;
+        else if (is("--texture-filter-8bit")) o.tex8 = true;              // bilinear weights with 8 fractional bits, like the CUDA texture unit
+        else if (is("-images_folder") && i + 1 < argc) o.images_folder = argv[++i];
+        else if (is("-mslp_folder") && i + 1 < argc) o.mslp_folder = argv[++i];
+        else if (is("-krt_file") && i + 1 < argc) o.krt_file = argv[++i];
+        else if (is("-output_folder") && i + 1 < argc) o.output_folder = argv[++i];
+        else if (is("-color_processing")) o.color = true;              // main.cpp:727,909
+        else if (is("--timing")) o.timing = true;                             // wall time of each host-side step of a view, on stdout
+        else if (is("--display_outputs")) o.display_outputs = true;           // TSAR_normals.png + TSAR_model.ply (main.cpp:1800-1838)
+        else if (is("-no_display") || opt("--cost_gamma") || opt("--min_angle") || opt("--max_angle") || opt("--cost_tau_color") ||
+                 opt("--cost_tau_gradient") || opt("--cost_alpha") || opt("--max_views") || opt("--num_img_processed")) {
             // accepted for script compatibility; these feed cost functions / view selection the GPU path does not use
-        } else if (!strcmp(a, "-h") || !strcmp(a, "--help")) { usage(); return 1; }
+        } else if (is("-h") || is("--help")) { usage(); return 1; }
         else printf("Command-line parameter warning: unknown option %s\n", a);
     }
     return 0;
@@ -430,13 +436,11 @@ void ExternalInputs::start(const std::string& view_dir, bool want_mask, const st
     started = true;
     depth_ok = normal_ok = mask_ok = false;
     maps = std::async(std::launch::async, [this, ref_image_path]() {
-        if (pinned) {
-            depth_ok = read_dmb(dir + "depths_geom.dmb", pdepth, dh, dw, dnb);
-            normal_ok = read_dmb(dir + "normals.dmb", pnormal, nh, nw, nnb);
-        } else {
-            depth_ok = read_dmb(dir + "depths_geom.dmb", vdepth, dh, dw, dnb);
-            normal_ok = read_dmb(dir + "normals.dmb", vnormal, nh, nw, nnb);
-        }
+        auto read_maps = [this](auto& depth, auto& normal) {
+            depth_ok = read_dmb(dir + "depths_geom.dmb", depth, dh, dw, dnb);
+            normal_ok = read_dmb(dir + "normals.dmb", normal, nh, nw, nnb);
+        };
+        if (pinned) read_maps(pdepth, pnormal); else read_maps(vdepth, vnormal);
         if (!ref_image_path.empty()) g_images.get(ref_image_path);      // a prefetch: decoded into the cache for the view's own start
     });
     if (want_mask) mask = std::async(std::launch::async, [this]() { mask_ok = read_reliable_mask(dir + "weak.png", scale, mw, mh); });
@@ -475,9 +479,18 @@ static std::vector<std::string> names_of(int ref, const std::vector<int>& srcs) 
 }
 
 // ---- settings records: what each phase leaves in APD/<id>/ and when --all takes it as done ------------------------------------
-struct MapFiles { const char *depth, *normal, *record; };
-static const MapFiles PHASE1_FILES = {"TSAR_disp.dmb", "TSAR_normals.dmb", "TSAR_multiscale.txt"};
-static const MapFiles GEOM_FILES = {"TSAR_geom_disp.dmb", "TSAR_geom_normals.dmb", "TSAR_geom.txt"};
+// A phase's two output files, with the channel count of each that is a .dmb map (0: not a map, only its presence counts), and the
+// record of the settings they were made with.  For a matching phase the two are its depth and normal maps.
+struct PhaseFiles {
+    const char* out[2];
+    int channels[2];
+    const char* record;
+    const char* depth() const { return out[0]; }
+    const char* normal() const { return out[1]; }
+};
+static const PhaseFiles PHASE1_FILES = {{"TSAR_disp.dmb", "TSAR_normals.dmb"}, {1, 3}, "TSAR_multiscale.txt"};
+static const PhaseFiles GEOM_FILES = {{"TSAR_geom_disp.dmb", "TSAR_geom_normals.dmb"}, {1, 3}, "TSAR_geom.txt"};
+static const PhaseFiles FILTER_FILES = {{"TSAR_filtered_disp.dmb", "TSAR_consistent.png"}, {1, 0}, "TSAR_filter.txt"};
 // what a multi-scale view records beside its maps (empty for a single-scale run, which leaves no record)
 static std::string ms_record_of(const Options& o) {
     if (o.multi_scale == 0) return "";
@@ -488,7 +501,7 @@ static std::string ms_record_of(const Options& o) {
 }
 static int geom_coarse_iterations_of(const Options& o) { return o.geom_coarse_iterations_set ? o.geom_coarse_iterations : o.geom_iterations; }
 static std::string prior_file_of(const Options& o, int ref, const char* what) { return view_dir_of(o, ref) + o.geom_prior_stem + what; }
-static std::string geom_record_of(const Options& o) {
+static std::string geom_record_of(const Options& o, const std::vector<int>&) {
     char b[640];
     snprintf(b, sizeof b, "geom_iterations=%d geom_weight=%.9g geom_clip=%.9g blocksize=%d n_best=%d cost_comb=%d seed=%llu strict=%d fix_quirks=%d texture_filter_8bit=%d cam_scale=%.9g depth_min=%.9g depth_max=%.9g\n",
              o.geom_iterations, (double)o.geom_weight, (double)o.geom_clip, o.blocksize, o.n_best, o.cost_comb, (unsigned long long)o.seed, o.strict ? 1 : 0,
@@ -510,52 +523,50 @@ static std::string geom_record_of(const Options& o) {
     return rec;
 }
 // the filter phase: the maps it checks are those of the matching phase that ran last
-static const char* const FILTER_DEPTH = "TSAR_filtered_disp.dmb";
-static const char* const FILTER_MASK = "TSAR_consistent.png";
-static const char* const FILTER_RECORD = "TSAR_filter.txt";
-static const MapFiles& filter_input_files(const Options& o) { return o.geom ? GEOM_FILES : PHASE1_FILES; }
+static const PhaseFiles& filter_input_files(const Options& o) { return o.geom ? GEOM_FILES : PHASE1_FILES; }
 static std::string filter_record_of(const Options& o, const std::vector<int>& srcs) {
     char b[256];
     snprintf(b, sizeof b, "min_consistent=%d reproj_error=%.9g depth_diff=%.9g cam_scale=%.9g checked=%s sources=", o.check.min_consistent,
-             (double)o.check.reproj_error, (double)o.check.depth_diff, (double)o.cam_scale, filter_input_files(o).depth);
+             (double)o.check.reproj_error, (double)o.check.depth_diff, (double)o.cam_scale, filter_input_files(o).depth());
     std::string rec = b;
     for (size_t i = 0; i < srcs.size(); i++) rec += (i ? "," : "") + id8(srcs[i]);
     return rec + "\n";
 }
 static std::string read_text_file(const std::string& path) {          // (no file reads as empty)
-    std::string txt;
-    if (FILE* fp = fopen(path.c_str(), "r")) {
-        char b[512];
-        size_t k;
-        while ((k = fread(b, 1, sizeof b, fp)) > 0) txt.append(b, k);
-        fclose(fp);
-    }
-    return txt;
+    std::stringstream txt;
+    txt << std::ifstream(path).rdbuf();
+    return txt.str();
 }
-// both maps complete for the size of the view's reference image, and a record that reads exactly `record` (no file reads as empty)
-static bool maps_current(const Options& o, int ref, const MapFiles& f, const std::string& record) {
+// a phase's maps complete for the size of the view's reference image, and a record that reads exactly `record` (no file reads as
+// empty): the done marker of a phase-1 view, whose record is this run's multi-scale settings
+static bool outputs_recorded(const Options& o, int ref, const PhaseFiles& f, const std::string& record) {
     int w = 0, h = 0;
     if (!view_image_size(view_image_of(o, ref), w, h)) return false;
     const std::string d = view_dir_of(o, ref);
-    if (!dmb_complete(d + f.depth, h, w, 1) || !dmb_complete(d + f.normal, h, w, 3)) return false;
+    for (int i = 0; i < 2; i++)
+        if (f.channels[i] && !dmb_complete(d + f.out[i], h, w, f.channels[i])) return false;
     return read_text_file(d + f.record) == record;
 }
-// the two maps side by side (a write is a copy into the page cache), under their record: the record goes first and comes back
-// last, so maps that are being replaced never carry the record of other settings.  An empty record: none is written.
-static bool write_maps(const HostResult& r, const MapFiles& f, const std::string& record) {
-    unlink((r.out_dir + f.record).c_str());
-    auto normals = std::async(std::launch::async, [&r, &f]() { return write_dmb(r.out_dir + f.normal, r.normal.data(), r.h, r.w, 3); });
-    const bool depth_ok = write_dmb(r.out_dir + f.depth, r.depth.data(), r.h, r.w, 1);
-    bool ok = normals.get() && depth_ok;
+// Outputs under their record: the record goes first and comes back last, so outputs that are being replaced never carry the record
+// of other settings.  `write_outputs` writes the files; an empty record: none is written.
+static bool write_under_record(const std::string& dir, const PhaseFiles& f, const std::string& record, const std::function<bool()>& write_outputs) {
+    unlink((dir + f.record).c_str());
+    bool ok = write_outputs();
     if (ok && !record.empty()) {
-        FILE* fp = fopen((r.out_dir + f.record).c_str(), "w");
+        FILE* fp = fopen((dir + f.record).c_str(), "w");
         ok = fp && fputs(record.c_str(), fp) >= 0;
         if (fp && fclose(fp) != 0) ok = false;
     }
     return ok;
 }
-// the done marker of a phase-1 view: its maps, made with this run's multi-scale settings
-static bool outputs_complete(const Options& o, int ref) { return maps_current(o, ref, PHASE1_FILES, ms_record_of(o)); }
+// a matching phase's two maps, side by side (a write is a copy into the page cache)
+static bool write_maps(const HostResult& r, const PhaseFiles& f, const std::string& record) {
+    return write_under_record(r.out_dir, f, record, [&r, &f]() {
+        auto normals = std::async(std::launch::async, [&r, &f]() { return write_dmb(r.out_dir + f.normal(), r.normal.data(), r.h, r.w, 3); });
+        const bool depth_ok = write_dmb(r.out_dir + f.depth(), r.depth.data(), r.h, r.w, 1);
+        return normals.get() && depth_ok;
+    });
+}
 static bool mtime_of(const std::string& path, struct timespec& t) {
     struct stat st;
     if (stat(path.c_str(), &st) != 0) return false;
@@ -563,40 +574,6 @@ static bool mtime_of(const std::string& path, struct timespec& t) {
     return true;
 }
 static bool newer(const struct timespec& a, const struct timespec& b) { return a.tv_sec != b.tv_sec ? a.tv_sec > b.tv_sec : a.tv_nsec > b.tv_nsec; }
-// resume of phase 2: the geom maps with the record of this run's settings, and no input (the view's own phase-1 maps, its sources'
-// depth maps) newer than the older of the two outputs
-static bool geom_outputs_current(const Options& o, int ref, const std::vector<int>& srcs) {
-    if (!maps_current(o, ref, GEOM_FILES, geom_record_of(o))) return false;
-    const std::string d = view_dir_of(o, ref);
-    struct timespec t1, t2, ti;
-    if (!mtime_of(d + GEOM_FILES.depth, t1) || !mtime_of(d + GEOM_FILES.normal, t2)) return false;
-    const struct timespec out = newer(t1, t2) ? t2 : t1;
-    std::vector<std::string> inputs = {d + PHASE1_FILES.depth, d + PHASE1_FILES.normal};
-    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + PHASE1_FILES.depth);
-    for (const std::string& in : inputs)
-        if (!mtime_of(in, ti) || newer(ti, out)) return false;
-    if (o.geom_prior)                  // a prior file that is not there is no input (the view ran without a prior)
-        for (const char* what : {"_disp.dmb", "_normals.dmb"})
-            if (mtime_of(prior_file_of(o, ref, what), ti) && newer(ti, out)) return false;
-    return true;
-}
-
-// resume of the filter phase: the filtered map complete, the mask there, the record of this run's settings and maps, and no input map
-// (the view's own, its sources') newer than the older of the two outputs
-static bool filter_outputs_current(const Options& o, int ref, const std::vector<int>& srcs) {
-    int w = 0, h = 0;
-    if (!view_image_size(view_image_of(o, ref), w, h)) return false;
-    const std::string d = view_dir_of(o, ref);
-    if (!dmb_complete(d + FILTER_DEPTH, h, w, 1) || read_text_file(d + FILTER_RECORD) != filter_record_of(o, srcs)) return false;
-    struct timespec t1, t2, ti;
-    if (!mtime_of(d + FILTER_DEPTH, t1) || !mtime_of(d + FILTER_MASK, t2)) return false;
-    const struct timespec out = newer(t1, t2) ? t2 : t1;
-    std::vector<std::string> inputs = {d + filter_input_files(o).depth};
-    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + filter_input_files(o).depth);
-    for (const std::string& in : inputs)
-        if (!mtime_of(in, ti) || newer(ti, out)) return false;
-    return true;
-}
 
 // The GPU state of one pool thread of --all (or of a one-view process), kept across its views: its context and, coarse to fine, the
 // contexts of the coarser levels (device planes are allocated once); two page-locked result sets its views alternate between (the
@@ -642,6 +619,26 @@ struct Worker {
     }
 };
 
+// The pyramid ladder over a worker's chain of contexts, for phase 1's --multi_scale and phase 2's --geom_multi_scale: they differ in the
+// call made per level, named in the failure message.  Down: level by level from the full resolution, each of `calls` as fn(level k,
+// level k - 1).  0, or non-zero after the message.
+struct LevelCall { int (*fn)(tsar_ctx* to, const tsar_ctx* from); const char* name; };
+static int descend(const Worker& wk, int ref, int L, std::initializer_list<LevelCall> calls) {
+    for (int k = 1; k <= L; k++)
+        for (const LevelCall& c : calls)
+            if (c.fn(wk.level(k), wk.level(k - 1)) != TSAR_OK) return wk.fail(ref, c.name, wk.level(k));
+    return 0;
+}
+// up: coarse_iters iterations at the coarsest level, then per finer level up.fn(level k, level k + 1) and iters iterations
+static int climb(const Worker& wk, int ref, int L, int coarse_iters, int iters, LevelCall up) {
+    if (tsar_pm_iterate(wk.level(L), coarse_iters) != TSAR_OK) return wk.fail(ref, "tsar_pm_iterate (coarsest level)", wk.level(L));
+    for (int k = L - 1; k >= 0; k--) {
+        if (up.fn(wk.level(k), wk.level(k + 1)) != TSAR_OK) return wk.fail(ref, up.name, wk.level(k));
+        if (tsar_pm_iterate(wk.level(k), iters) != TSAR_OK) return wk.fail(ref, "tsar_pm_iterate", wk.level(k));
+    }
+    return 0;
+}
+
 // A view's images and cameras as tsar_set_views_u8 takes them (the reference first), and the depth range it is matched in
 struct ViewSet {
     std::vector<std::shared_ptr<ImageCache::Entry>> gray;
@@ -657,19 +654,19 @@ struct ViewSet {
 // and the depth range taken from the reference camera (fileIoUtils.h:150-153) unless the command line gave it.  0, or non-zero after
 // a message.
 static int load_views(const Options& o, Worker& wk, const std::vector<std::string>& names, ViewSet& v) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     std::future<int> creating;
     if (!wk.ctx) creating = std::async(std::launch::async, [&wk, &v]() {
-        const auto c0 = std::chrono::steady_clock::now();
+        const auto c0 = Clock::now();
         const int rc = tsar_create(wk.device, &wk.ctx);
-        v.ms_create = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+        v.ms_create = 1e3 * seconds_since(c0);
         return rc;
     });
     std::vector<std::future<std::shared_ptr<ImageCache::Entry>>> decoding;
     for (const std::string& name : names)
         decoding.push_back(std::async(std::launch::async, [&o, &name]() { return g_images.get(image_path(o, name)); }));
     for (auto& d : decoding) v.gray.push_back(d.get());
-    v.ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    v.ms_decode = 1e3 * seconds_since(t0);
     const int create_rc = creating.valid() ? creating.get() : TSAR_OK;
     if (create_rc != TSAR_OK) return wk.create_failed(create_rc);
     std::vector<const uint8_t*> host, dev;
@@ -728,16 +725,15 @@ static tsar_params params_of(const Options& o, int ref_id, float dmin, float dma
 // maps land in hr and, unless the caller defers that (--all writes them while the next view is matched), in their files.
 static int run_view(const Options& o, Worker& wk, const std::vector<std::string>& names, const std::vector<int>& subset_slots, int ref_id, double* seconds,
                     HostResult& hr, DeviceResult* keep = nullptr, bool defer_write = false, ExternalInputs* preloaded = nullptr) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     auto t_last = t0;
     std::string steps;                                            // --timing: "step ms | step ms | ..."
     auto stamp = [&](const char* what) {
         if (!o.timing) return;
-        const auto now = std::chrono::steady_clock::now();
         char buf[96];
-        snprintf(buf, sizeof buf, "%s%s %.1f", steps.empty() ? "" : " | ", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+        snprintf(buf, sizeof buf, "%s%s %.1f", steps.empty() ? "" : " | ", what, 1e3 * seconds_since(t_last));
         steps += buf;
-        t_last = now;
+        t_last = Clock::now();
     };
     // The refinement modes never read a source image (load_planes, weak-texture detection, region RANSAC and fill work on the
     // reference view and the plane maps): only the reference image is decoded and handed to the library there.
@@ -796,15 +792,10 @@ static int run_view(const Options& o, Worker& wk, const std::vector<std::string>
         // iterations at each finer one
         const int L = o.multi_scale;
         if (wk.ensure(L) != TSAR_OK) return -1;
-        for (int k = 1; k <= L; k++)
-            if (tsar_pyramid_views(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_pyramid_views", wk.level(k));
+        if (descend(wk, ref_id, L, {{tsar_pyramid_views, "tsar_pyramid_views"}})) return -1;
         stamp("pyramid_views");
         if (tsar_pm_init(wk.level(L)) != TSAR_OK) return fail("tsar_pm_init (coarsest level)", wk.level(L));
-        if (tsar_pm_iterate(wk.level(L), o.coarse_iterations_set ? o.coarse_iterations : o.iterations) != TSAR_OK) return fail("tsar_pm_iterate (coarsest level)", wk.level(L));
-        for (int k = L - 1; k >= 0; k--) {
-            if (tsar_upsample_planes(wk.level(k), wk.level(k + 1)) != TSAR_OK) return fail("tsar_upsample_planes", wk.level(k));
-            if (tsar_pm_iterate(wk.level(k), o.iterations) != TSAR_OK) return fail("tsar_pm_iterate", wk.level(k));
-        }
+        if (climb(wk, ref_id, L, o.coarse_iterations_set ? o.coarse_iterations : o.iterations, o.iterations, {tsar_upsample_planes, "tsar_upsample_planes"})) return -1;
         stamp("coarse-to-fine pm_init + pm_iterate");
     } else {
         if (tsar_pm_init(ctx) != TSAR_OK) return fail("tsar_pm_init");
@@ -843,8 +834,7 @@ static int run_view(const Options& o, Worker& wk, const std::vector<std::string>
         stamp("detect_weak_texture + compute_disp_final_upsampled");
     } else if (tsar_compute_disp(ctx) != TSAR_OK) return fail("tsar_compute_disp");
     if (sizing.valid()) sizing.get();
-    PinnedFloats &depth = hr.depth, &normal = hr.normal;
-    if (tsar_get_result(ctx, depth.data(), normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
+    if (tsar_get_result(ctx, hr.depth.data(), hr.normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
     stamp("get_result");
     if (keep) {   // the same maps stay on this GPU for the gather to the fusing device
         keep->device = wk.device; keep->w = w; keep->h = h;
@@ -867,7 +857,7 @@ static int run_view(const Options& o, Worker& wk, const std::vector<std::string>
         }
     }
     if (o.display_outputs && !write_display_outputs(hr, v.gray[0]->gray, v.cams[0])) return -1;
-    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const double sec = seconds_since(t0);
     if (seconds) *seconds = sec;
     FILE* rf = fopen((out_dir + "TSAR_results.txt").c_str(), "a");   // main.cpp:1854-1860
     if (rf) { fprintf(rf, "Total runtime: %g sec ( %g min)\n", sec, sec / 60.0); fclose(rf); }
@@ -895,53 +885,104 @@ static double ms_since_exec() {
     return (up - (double)start_ticks / (double)sysconf(_SC_CLK_TCK)) * 1e3;
 }
 
+// ---- the phases of --all after phase 1 (--geom_consistency, --consistency_filter): one view at a time on one worker per GPU, from map
+// files to map files ---------------------------------------------------------------------------------------------------------------
+struct LaterPhase {
+    const char* name;                                                             // in its messages: "geom", "filter"
+    const PhaseFiles& files;                                                      // what it writes; the resume line names the two outputs
+    std::string (*record_of)(const Options&, const std::vector<int>& srcs);       // its record for a view
+    const PhaseFiles& (*reads)(const Options&);                                   // the phase whose maps are its inputs: the sources' depth maps, the view's own depth map
+    bool reads_normal;                                                            // ... and the view's own normal map
+    std::vector<std::string> (*optional_inputs)(const Options&, int ref);         // files a view may lack (it then runs without them); may be null
+    int (*view)(const Options&, Worker&, const LaterPhase&, int ref, const std::vector<int>& srcs, double* seconds);
+};
+static const PhaseFiles& phase1_files(const Options&) { return PHASE1_FILES; }
+static std::vector<std::string> prior_files_of(const Options& o, int ref) {
+    if (!o.geom_prior) return {};
+    return {prior_file_of(o, ref, "_disp.dmb"), prior_file_of(o, ref, "_normals.dmb")};
+}
+// the map files a view of the phase reads, its own first
+static std::vector<std::string> inputs_of(const Options& o, const LaterPhase& ph, int ref, const std::vector<int>& srcs) {
+    const PhaseFiles& in = ph.reads(o);
+    std::vector<std::string> inputs = {view_dir_of(o, ref) + in.depth()};
+    if (ph.reads_normal) inputs.push_back(view_dir_of(o, ref) + in.normal());
+    for (int s : srcs) inputs.push_back(view_dir_of(o, s) + in.depth());
+    return inputs;
+}
+// resume of a later phase: its outputs complete, under the record of this run's settings, and no input newer than the older of the two
+// outputs (an optional input that is not there is no input)
+static bool outputs_current(const Options& o, const LaterPhase& ph, int ref, const std::vector<int>& srcs) {
+    if (!outputs_recorded(o, ref, ph.files, ph.record_of(o, srcs))) return false;
+    const std::string d = view_dir_of(o, ref);
+    struct timespec t1, t2, ti;
+    if (!mtime_of(d + ph.files.out[0], t1) || !mtime_of(d + ph.files.out[1], t2)) return false;
+    const struct timespec out = newer(t1, t2) ? t2 : t1;
+    for (const std::string& in : inputs_of(o, ph, ref, srcs))
+        if (!mtime_of(in, ti) || newer(ti, out)) return false;
+    if (ph.optional_inputs)
+        for (const std::string& in : ph.optional_inputs(o, ref))
+            if (mtime_of(in, ti) && newer(ti, out)) return false;
+    return true;
+}
+
+static bool read_map(const std::string& path, int h, int w, int nb, std::vector<float>& out) {   // a .dmb map of exactly h x w x nb
+    int hh = 0, ww = 0, nn = 0;
+    return read_dmb(path, out, hh, ww, nn) && hh == h && ww == w && nn == nb;
+}
+// What a view of a later phase starts from: its images and cameras on the worker's context (parameters and views set), its own map(s)
+// of the phase it reads and, per view slot, its pair.txt sources' depth maps of that phase (slot 0: none), each of the image size
+struct LaterView : ViewSet {
+    std::vector<float> own_depth, own_normal;
+    std::vector<std::vector<float>> src_depth;
+    std::vector<const float*> maps;    // as tsar_set_geom_depths takes them
+};
+static int load_later_view(const Options& o, Worker& wk, const LaterPhase& ph, int ref, const std::vector<int>& srcs, LaterView& lv) {
+    ViewSet& v = lv;
+    if (const int rc = load_views(o, wk, names_of(ref, srcs), v)) return rc;
+    const int n = (int)v.cams.size();
+    const std::vector<std::string> inputs = inputs_of(o, ph, ref, srcs);
+    size_t next = 0;
+    auto read_next = [&](int nb, std::vector<float>& out) {          // the inputs in their order
+        const std::string& path = inputs[next++];
+        if (read_map(path, v.h, v.w, nb, out)) return true;
+        fprintf(stderr, "cannot read %s\n", path.c_str());
+        return false;
+    };
+    if (!read_next(1, lv.own_depth) || (ph.reads_normal && !read_next(3, lv.own_normal))) return -1;
+    lv.src_depth.resize(n);
+    lv.maps.assign(n, nullptr);
+    for (int i = 1; i < n; i++) {
+        if (!read_next(1, lv.src_depth[i])) return -1;
+        lv.maps[i] = lv.src_depth[i].data();
+    }
+    const tsar_params p = params_of(o, ref, v.dmin, v.dmax);
+    if (tsar_set_params(wk.ctx, &p) != TSAR_OK) return wk.fail(ref, "tsar_set_params");
+    if (tsar_set_views_u8(wk.ctx, n, v.w, v.h, v.px.data(), v.mem, v.cams.data()) != TSAR_OK) return wk.fail(ref, "tsar_set_views_u8");
+    return 0;
+}
+
 // Phase 2 of one view (--geom_consistency): it starts from its own phase-1 maps (TSAR_disp.dmb + TSAR_normals.dmb), installs its
 // pair.txt sources' TSAR_disp.dmb as the geometric-consistency term, rescores, runs --geom_iterations iterations at full resolution
 // and writes TSAR_geom_disp.dmb + TSAR_geom_normals.dmb (the layout of the phase-1 maps) under TSAR_geom.txt, the settings they were
 // made with.  --geom_multi_scale=L >= 1 runs the pass coarse to fine instead (api.run_geom_pass_multiscale's chain).
-static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vector<int>& srcs, double* seconds) {
-    const auto t0 = std::chrono::steady_clock::now();
-    ViewSet v;
-    if (const int rc = load_views(o, wk, names_of(ref, srcs), v)) return rc;
-    const int n = (int)v.cams.size(), w = v.w, h = v.h;
-    // the maps: the view's own phase-1 result and its sources' depths, each of the image size
-    const std::string d = view_dir_of(o, ref);
-    auto read_map = [&](const std::string& path, int nb, std::vector<float>& out) {
-        int hh = 0, ww = 0, nn = 0;
-        if (read_dmb(path, out, hh, ww, nn) && hh == h && ww == w && nn == nb) return true;
-        fprintf(stderr, "cannot read %s\n", path.c_str());
-        return false;
-    };
-    std::vector<float> own_d, own_n;
-    std::vector<std::vector<float>> src_d(n);
-    if (!read_map(d + PHASE1_FILES.depth, 1, own_d) || !read_map(d + PHASE1_FILES.normal, 3, own_n)) return -1;
-    std::vector<const float*> maps(n, nullptr);
-    for (int i = 1; i < n; i++) {
-        if (!read_map(view_dir_of(o, srcs[i - 1]) + PHASE1_FILES.depth, 1, src_d[i])) return -1;
-        maps[i] = src_d[i].data();
-    }
+static int run_geom_view(const Options& o, Worker& wk, const LaterPhase& ph, int ref, const std::vector<int>& srcs, double* seconds) {
+    const auto t0 = Clock::now();
+    LaterView lv;
+    if (const int rc = load_later_view(o, wk, ph, ref, srcs, lv)) return rc;
+    const int n = (int)lv.maps.size(), w = lv.w, h = lv.h;
     tsar_ctx* const ctx = wk.ctx;
-    auto fail = [&](const char* what, tsar_ctx* c = nullptr) { return wk.fail(ref, what, c); };
-    const tsar_params p = params_of(o, ref, v.dmin, v.dmax);
-    if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
-    if (tsar_set_views_u8(ctx, n, w, h, v.px.data(), v.mem, v.cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
+    auto fail = [&](const char* what) { return wk.fail(ref, what); };
     // coarse to fine: every level's views first, while no term is installed (the coarse contexts still hold the previous view's)
     const int L = o.geom_multi_scale;
     if (wk.ensure(L) != TSAR_OK) return -1;
-    for (int k = 1; k <= L; k++) {
-        if (tsar_clear_geom(wk.level(k)) != TSAR_OK) return fail("tsar_clear_geom", wk.level(k));
-        if (tsar_pyramid_views(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_pyramid_views", wk.level(k));
-    }
-    if (tsar_load_planes(ctx, own_d.data(), own_n.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
-    if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
+    if (descend(wk, ref, L, {{[](tsar_ctx* c, const tsar_ctx*) { return tsar_clear_geom(c); }, "tsar_clear_geom"}, {tsar_pyramid_views, "tsar_pyramid_views"}})) return -1;
+    if (tsar_load_planes(ctx, lv.own_depth.data(), lv.own_normal.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_load_planes");
+    if (tsar_set_geom_depths(ctx, n, lv.maps.data(), TSAR_MEM_HOST, o.geom_weight, o.geom_clip) != TSAR_OK) return fail("tsar_set_geom_depths");
     if (o.geom_prior) {
         // the view's plane prior, on the full-resolution context only; a view without the two files runs without one
+        const std::vector<std::string> files = prior_files_of(o, ref);
         std::vector<float> prior_d, prior_n;
-        int hh = 0, ww = 0, nn = 0;
-        const bool have = read_dmb(prior_file_of(o, ref, "_disp.dmb"), prior_d, hh, ww, nn) && hh == h && ww == w && nn == 1 &&
-                          read_dmb(prior_file_of(o, ref, "_normals.dmb"), prior_n, hh, ww, nn) && hh == h && ww == w && nn == 3;
-        if (!have) printf("view %08d (geom): no plane prior (%s / %s not readable at %d x %d): runs without one\n", ref,
-                          prior_file_of(o, ref, "_disp.dmb").c_str(), prior_file_of(o, ref, "_normals.dmb").c_str(), w, h);
+        if (!read_map(files[0], h, w, 1, prior_d) || !read_map(files[1], h, w, 3, prior_n)) printf("view %08d (geom): no plane prior (%s / %s not readable at %d x %d): runs without one\n", ref, files[0].c_str(), files[1].c_str(), w, h);
         else if (tsar_set_plane_prior(ctx, prior_d.data(), prior_n.data(), TSAR_MEM_HOST, &o.prior) != TSAR_OK) return fail("tsar_set_plane_prior");
     }
     if (o.geom_cross_view) {
@@ -959,75 +1000,45 @@ static int run_geom_view(const Options& o, Worker& wk, int ref, const std::vecto
         if (!o.geom_cross_view && tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
         if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
     } else {
-        for (int k = 1; k <= L; k++) {
-            if (tsar_geom_pyramid(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_geom_pyramid", wk.level(k));
-            if (tsar_pyramid_planes(wk.level(k), wk.level(k - 1)) != TSAR_OK) return fail("tsar_pyramid_planes", wk.level(k));
-        }
-        if (tsar_pm_iterate(wk.level(L), geom_coarse_iterations_of(o)) != TSAR_OK) return fail("tsar_pm_iterate (coarsest level)", wk.level(L));
-        for (int k = L - 1; k >= 0; k--) {
-            if (tsar_upsample_merge(wk.level(k), wk.level(k + 1)) != TSAR_OK) return fail("tsar_upsample_merge", wk.level(k));
-            if (tsar_pm_iterate(wk.level(k), o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate", wk.level(k));
-        }
+        if (descend(wk, ref, L, {{tsar_geom_pyramid, "tsar_geom_pyramid"}, {tsar_pyramid_planes, "tsar_pyramid_planes"}})) return -1;
+        if (climb(wk, ref, L, geom_coarse_iterations_of(o), o.geom_iterations, {tsar_upsample_merge, "tsar_upsample_merge"})) return -1;
     }
     if (tsar_compute_disp(ctx) != TSAR_OK) return fail("tsar_compute_disp");
     HostResult& hr = wk.result[0];
-    hr.out_dir = d; hr.w = w; hr.h = h;
+    hr.out_dir = view_dir_of(o, ref); hr.w = w; hr.h = h;
     hr.depth.resize((size_t)w * h);
     hr.normal.resize((size_t)3 * w * h);
     if (tsar_get_result(ctx, hr.depth.data(), hr.normal.data(), nullptr, nullptr, TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_result");
     if (tsar_clear_geom(ctx) != TSAR_OK) return fail("tsar_clear_geom");
     if (tsar_clear_plane_prior(ctx) != TSAR_OK) return fail("tsar_clear_plane_prior");
-    const bool ok = write_maps(hr, GEOM_FILES, geom_record_of(o));
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const bool ok = write_maps(hr, ph.files, ph.record_of(o, srcs));
+    if (seconds) *seconds = seconds_since(t0);
     return ok ? 0 : -1;
 }
 
 // The filter phase of one view (--consistency_filter): its depth map of the matching phase that ran last is checked against its
 // pair.txt sources' maps of that phase (tsar_geom_check; the maps are installed as a term of weight 0, which only the check reads), and
 // TSAR_filtered_disp.dmb + TSAR_consistent.png are written under TSAR_filter.txt, the settings and maps they were made with.
-static int run_filter_view(const Options& o, Worker& wk, int ref, const std::vector<int>& srcs, double* seconds) {
-    const auto t0 = std::chrono::steady_clock::now();
-    ViewSet v;
-    if (const int rc = load_views(o, wk, names_of(ref, srcs), v)) return rc;
-    const int n = (int)v.cams.size(), w = v.w, h = v.h;
-    const MapFiles& in = filter_input_files(o);
-    const std::string d = view_dir_of(o, ref);
-    auto read_map = [&](const std::string& path, std::vector<float>& out) {
-        int hh = 0, ww = 0, nn = 0;
-        if (read_dmb(path, out, hh, ww, nn) && hh == h && ww == w && nn == 1) return true;
-        fprintf(stderr, "cannot read %s\n", path.c_str());
-        return false;
-    };
-    std::vector<float> own_d;
-    std::vector<std::vector<float>> src_d(n);
-    if (!read_map(d + in.depth, own_d)) return -1;
-    std::vector<const float*> maps(n, nullptr);
-    for (int i = 1; i < n; i++) {
-        if (!read_map(view_dir_of(o, srcs[i - 1]) + in.depth, src_d[i])) return -1;
-        maps[i] = src_d[i].data();
-    }
+static int run_filter_view(const Options& o, Worker& wk, const LaterPhase& ph, int ref, const std::vector<int>& srcs, double* seconds) {
+    const auto t0 = Clock::now();
+    LaterView lv;
+    if (const int rc = load_later_view(o, wk, ph, ref, srcs, lv)) return rc;
+    const int n = (int)lv.maps.size(), w = lv.w, h = lv.h;
     tsar_ctx* const ctx = wk.ctx;
     auto fail = [&](const char* what) { return wk.fail(ref, what); };
-    const tsar_params p = params_of(o, ref, v.dmin, v.dmax);
-    if (tsar_set_params(ctx, &p) != TSAR_OK) return fail("tsar_set_params");
-    if (tsar_set_views_u8(ctx, n, w, h, v.px.data(), v.mem, v.cams.data()) != TSAR_OK) return fail("tsar_set_views_u8");
-    if (tsar_set_geom_depths(ctx, n, maps.data(), TSAR_MEM_HOST, 0.0f, 3.0f) != TSAR_OK) return fail("tsar_set_geom_depths");
+    if (tsar_set_geom_depths(ctx, n, lv.maps.data(), TSAR_MEM_HOST, 0.0f, 3.0f) != TSAR_OK) return fail("tsar_set_geom_depths");
     std::vector<float> filtered((size_t)w * h), mask((size_t)w * h);
-    if (tsar_geom_check(ctx, own_d.data(), &o.check, nullptr, filtered.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_geom_check");
+    if (tsar_geom_check(ctx, lv.own_depth.data(), &o.check, nullptr, filtered.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_geom_check");
     if (tsar_get_reliable_mask(ctx, mask.data(), TSAR_MEM_HOST) != TSAR_OK) return fail("tsar_get_reliable_mask");
     if (tsar_clear_geom(ctx) != TSAR_OK) return fail("tsar_clear_geom");
-    // the record goes first and comes back last, so outputs that are being replaced never carry the record of other settings
-    unlink((d + FILTER_RECORD).c_str());
-    bool ok = write_dmb(d + FILTER_DEPTH, filtered.data(), h, w, 1) && write_mask_png(d + FILTER_MASK, mask.data(), w, h);
-    if (ok) {
-        FILE* fp = fopen((d + FILTER_RECORD).c_str(), "w");
-        ok = fp && fputs(filter_record_of(o, srcs).c_str(), fp) >= 0;
-        if (fp && fclose(fp) != 0) ok = false;
-    }
+    const std::string d = view_dir_of(o, ref);
+    const bool ok = write_under_record(d, ph.files, ph.record_of(o, srcs), [&]() {
+        return write_dmb(d + ph.files.out[0], filtered.data(), h, w, 1) && write_mask_png(d + ph.files.out[1], mask.data(), w, h);
+    });
     size_t kept = 0;
     for (float m : mask) kept += m == 1.0f;
-    if (ok) printf("view %08d (filter): %zu of %zu pixels of %s kept\n", ref, kept, mask.size(), in.depth);
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (ok) printf("view %08d (filter): %zu of %zu pixels of %s kept\n", ref, kept, mask.size(), ph.reads(o).depth());
+    if (seconds) *seconds = seconds_since(t0);
     return ok ? 0 : -1;
 }
 
@@ -1077,11 +1088,11 @@ static std::vector<int> run_pool(const Options& o, const char* phase, const std:
 }
 
 // --fuse: a view's maps read back from its files onto device g (a resumed view's phase-1 maps, or every view's geom maps)
-static bool load_kept(const Options& o, int ref, int g, const MapFiles& f, DeviceResult& r) {
+static bool load_kept(const Options& o, int ref, int g, const PhaseFiles& f, DeviceResult& r) {
     std::vector<float> d, nr;
     int h = 0, w = 0, nb = 0, h2 = 0, w2 = 0, nb2 = 0;
     const std::string dir = view_dir_of(o, ref);
-    if (!read_dmb(dir + f.depth, d, h, w, nb) || !read_dmb(dir + f.normal, nr, h2, w2, nb2) || h != h2 || w != w2 || nb != 1 || nb2 != 3) return false;
+    if (!read_dmb(dir + f.depth(), d, h, w, nb) || !read_dmb(dir + f.normal(), nr, h2, w2, nb2) || h != h2 || w != w2 || nb != 1 || nb2 != 3) return false;
     r.device = g; r.w = w; r.h = h;
     r.depth = (float*)tsar_device_alloc(g, d.size() * 4);
     r.normal = (float*)tsar_device_alloc(g, nr.size() * 4);
@@ -1094,12 +1105,12 @@ static bool load_kept(const Options& o, int ref, int g, const MapFiles& f, Devic
 static bool run_phase1(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs, std::vector<DeviceResult>& kept) {
     const int nthr = std::max(1, o.gpus) * std::max(1, o.workers);
     // resume: the views whose output files are complete are not matched again (decided up front, so that nothing is read ahead for them)
+    const std::string record = ms_record_of(o);
     std::vector<char> skip(refs.size(), 0);
     size_t n_skip = 0;
     if (!o.force)
-        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = outputs_complete(o, refs[k]) ? 1 : 0);
+        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = outputs_recorded(o, refs[k], PHASE1_FILES, record) ? 1 : 0);
     if (n_skip) printf("resuming: %zu of %zu views already have complete TSAR_disp.dmb / TSAR_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
-    const std::string record = ms_record_of(o);
     const bool tsar_mode = o.mode == "tsar", external = o.mode == "load" || tsar_mode;
     // refinement modes: a ring of (page-locked) input buffers per worker; the maps, weak.png and reference image of its next seven
     // views are read while view k is on the GPU (one weak.png inflates in ~0.3 s, a view's kernels take ~0.1 s).  (About sixteen
@@ -1142,44 +1153,31 @@ static bool run_phase1(const Options& o, const std::vector<int>& refs, const std
     const std::vector<int> rc = run_pool(o, nullptr, refs, skip, nthr, view, skipped);
     int missing = 0;
     for (size_t k = 0; k < refs.size(); k++)
-        if (rc[k] != 0 || !outputs_complete(o, refs[k])) { fprintf(stderr, "view %08d: outputs missing or incomplete\n", refs[k]); missing++; }
+        if (rc[k] != 0 || !outputs_recorded(o, refs[k], PHASE1_FILES, record)) { fprintf(stderr, "view %08d: outputs missing or incomplete\n", refs[k]); missing++; }
     return missing == 0 && write_failures == 0;       // (a file of an otherwise matched view that could not be written)
 }
 
-// --all --geom_consistency: phase 2 over every view, one worker per GPU.  False when a view has no current geom outputs.
-static bool run_geom_phase(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs) {
+static const LaterPhase GEOM_PHASE = {"geom", GEOM_FILES, geom_record_of, phase1_files, true, prior_files_of, run_geom_view};
+static const LaterPhase FILTER_PHASE = {"filter", FILTER_FILES, filter_record_of, filter_input_files, false, nullptr, run_filter_view};
+// A later phase of --all over every view, one worker per GPU.  False when a view has no current outputs of the phase.
+static bool run_later_phase(const Options& o, const LaterPhase& ph, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs) {
     std::vector<char> skip(refs.size(), 0);
     size_t n_skip = 0;
     if (!o.force)
-        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = geom_outputs_current(o, refs[k], pairs.at(refs[k])) ? 1 : 0);
-    if (n_skip) printf("geom: resuming: %zu of %zu views have current TSAR_geom_disp.dmb / TSAR_geom_normals.dmb and are skipped (--force recomputes them)\n", n_skip, refs.size());
-    const std::vector<int> rc = run_pool(o, "geom", refs, skip, std::max(1, o.gpus),
-                                         [&](Worker& wk, size_t k, int, double* sec) { return run_geom_view(o, wk, refs[k], pairs.at(refs[k]), sec); });
+        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = outputs_current(o, ph, refs[k], pairs.at(refs[k])) ? 1 : 0);
+    if (n_skip) printf("%s: resuming: %zu of %zu views have current %s / %s and are skipped (--force recomputes them)\n", ph.name, n_skip, refs.size(), ph.files.out[0], ph.files.out[1]);
+    const std::vector<int> rc = run_pool(o, ph.name, refs, skip, std::max(1, o.gpus),
+                                         [&](Worker& wk, size_t k, int, double* sec) { return ph.view(o, wk, ph, refs[k], pairs.at(refs[k]), sec); });
     int missing = 0;
     for (size_t k = 0; k < refs.size(); k++)
-        if (rc[k] != 0) { fprintf(stderr, "view %08d: geom outputs missing\n", refs[k]); missing++; }
-    return missing == 0;
-}
-
-// --all --consistency_filter: the filter phase over every view, one worker per GPU.  False when a view has no current filter outputs.
-static bool run_filter_phase(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs) {
-    std::vector<char> skip(refs.size(), 0);
-    size_t n_skip = 0;
-    if (!o.force)
-        for (size_t k = 0; k < refs.size(); k++) n_skip += (skip[k] = filter_outputs_current(o, refs[k], pairs.at(refs[k])) ? 1 : 0);
-    if (n_skip) printf("filter: resuming: %zu of %zu views have current TSAR_filtered_disp.dmb / TSAR_consistent.png and are skipped (--force recomputes them)\n", n_skip, refs.size());
-    const std::vector<int> rc = run_pool(o, "filter", refs, skip, std::max(1, o.gpus),
-                                         [&](Worker& wk, size_t k, int, double* sec) { return run_filter_view(o, wk, refs[k], pairs.at(refs[k]), sec); });
-    int missing = 0;
-    for (size_t k = 0; k < refs.size(); k++)
-        if (rc[k] != 0) { fprintf(stderr, "view %08d: filter outputs missing\n", refs[k]); missing++; }
+        if (rc[k] != 0) { fprintf(stderr, "view %08d: %s outputs missing\n", refs[k], ph.name); missing++; }
     return missing == 0;
 }
 
 // --fuse: every view's maps gathered to GPU 0 (peer copies over xGMI; views matched on GPU 0 are already there), fused there, and the
 // cloud written to APD/APD_TSAR.ply
 static int fuse_views(const Options& o, const std::vector<int>& refs, const std::map<int, std::vector<int>>& pairs, std::vector<DeviceResult>& kept) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     if (refs.empty() || kept.empty()) { fprintf(stderr, "--fuse: no view was matched\n"); return 1; }
     const int n = (int)refs.size(), fw = kept[0].w, fh = kept[0].h;
     const size_t np = (size_t)fw * fh;
@@ -1220,7 +1218,7 @@ static int fuse_views(const Options& o, const std::vector<int>& refs, const std:
         if (!read_cam(cam_path(o, id8(refs[k])), cf)) { fprintf(stderr, "--fuse: camera of view %08d\n", refs[k]); release_owned(); return 1; }
         cams[k] = cf.cam;
     }
-    const double t_gather = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const double t_gather = seconds_since(t0);
     std::vector<int32_t> off(n + 1, 0), idx;
     for (int k = 0; k < n; k++) {
         for (int sv : pairs.at(refs[k]))
@@ -1237,7 +1235,7 @@ static int fuse_views(const Options& o, const std::vector<int>& refs, const std:
     if (cnt > cap) cnt = cap;
     const std::string out = o.mslp_folder + "APD/APD_TSAR.ply";
     if (!write_cloud_ply(out, pts.get(), cnt)) { fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
-    const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const double t_all = seconds_since(t0);
     printf("fused %d views on gpu 0: %lld points -> %s (gather of %.1f MB from other gpus + uploads %.3f s, total %.3f s)\n", n, (long long)cnt, out.c_str(),
            moved / 1e6, t_gather, t_all);
     return 0;
@@ -1251,8 +1249,8 @@ static int run_all(const Options& o, const std::map<int, std::vector<int>>& pair
     for (auto& kv : pairs) refs.push_back(kv.first);
     std::vector<DeviceResult> kept(o.fuse ? refs.size() : 0);
     bool ok = run_phase1(o, refs, pairs, kept);
-    if (ok && o.geom) ok = run_geom_phase(o, refs, pairs);
-    if (ok && o.filter) ok = run_filter_phase(o, refs, pairs);
+    if (ok && o.geom) ok = run_later_phase(o, GEOM_PHASE, refs, pairs);
+    if (ok && o.filter) ok = run_later_phase(o, FILTER_PHASE, refs, pairs);
     g_device_images.release();
     if (!ok) return 1;
     if (o.geom && o.fuse)        // --fuse fuses the geom maps: they replace the phase-1 maps kept on each view's device
