@@ -92,6 +92,7 @@ static int launch_full_t(tsar_ctx* ctx, const float4* planes, float* c, float4* 
     if (const int rc = tap_grid(ctx, kern, FULL_RH, PM_BLOCK, QUAD, V, 0, g)) return rc;
     {
         ScopedKernelTimer tm(ctx, (INIT && (V & TSAR_V_REDRAW)) ? "pm_rescore" : INIT ? "pm_init" : "pm_cost_planes");
+        ScopedKernelTimer tm_pair(ctx, (V & TSAR_V_PAIR) ? "pm_init_pair" : nullptr);       // (the paired-gather kernel a second time under its own name)
         hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(PM_BLOCK), g.lds, ctx->stream, ctx->dscene, planes, c, n, bv, rt, g.tiles_x, g.n_tiles, strip_width(ctx->strip_w, g.tiles_x));
     }
     TSAR_HIP_TRY(ctx, hipGetLastError());

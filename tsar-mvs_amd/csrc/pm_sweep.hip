@@ -64,7 +64,10 @@ static int launch_sweep_nh(tsar_ctx* ctx, int colour, const PlaneBuf& a, const P
 #define SWEEP_R5_PRUNE(B) (mix ? launch_sweep_t<2, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_MIX | TSAR_V_PRUNE, B>(ctx, colour, a, b, c, sid, dp, dr) \
                            : buf ? launch_sweep_t<2, 5, false, true, 250 | TSAR_V_BUF | TSAR_V_PRUNE, B>(ctx, colour, a, b, c, sid, dp, dr)              \
                                  : launch_sweep_t<2, 5, false, true, 250 | TSAR_V_PRUNE, B>(ctx, colour, a, b, c, sid, dp, dr))
-#define SWEEP_R5_FAST250(B) (prune ? SWEEP_R5_PRUNE(B) : SWEEP_R5_FAST250_ALL(B))
+        // ... and where the choice is the plain global-load kernel <2, 5, false, true, 250, B> (the first sweep of a run: random planes,
+        // every lane on its own cache line), the paired-gather kernel of pm_pair.hip (TSAR_PAIR bit 1)
+        const bool pair = NB == 2 && !strict && v == 250 && !buf && !prune && (ctx->pair & 2) && !scene_has_terms(ctx->hscene);
+#define SWEEP_R5_FAST250(B) (prune ? SWEEP_R5_PRUNE(B) : pair ? launch_pm_sweep_pair(ctx, B, colour, a, b, c, sid, dp, dr) : SWEEP_R5_FAST250_ALL(B))
         if constexpr (NB == 2) {
             // small images: 128-thread workgroups (see SWEEP_SMALL_IMAGE_TILES); TSAR_BLOCK=128|256 forces a shape (A/B runs)
             const int tiles256 = ((ctx->hscene.w + PM_RW - 1) / PM_RW) * ((ctx->hscene.h + 15) / 16);

@@ -1,7 +1,9 @@
 // pm_sweep_experiments.hip — dispatch of the diagnostic tap-loop variants (pm_tap_r5.h DIAG: the ceilings of profiles/r04) and of the
 // production variants forced into every launch.  Built only into libtsar_hip_exp.so (`make TSAR_EXPERIMENTS=1`); selected with
 // TSAR_VARIANT / TSAR_VARIANT_NOW.  (The measured-and-rejected tap loops of rounds 1-3 — lane maps, paired gathers, pipelined lines,
-// the LDS-patch sweep — were removed in round 4; their numbers are in profiles/r01-r03 and DESIGN.md section 4.)
+// the LDS-patch sweep — were removed in round 4; their numbers are in profiles/r01-r03 and DESIGN.md section 4.  The paired gathers
+// priced there served the converged difference-texture loop, where the gather path is a tenth of a launch; the paired loop DIAG 3
+// belongs to (pm_tap_r5.h PAIR, pm_pair.hip) ships for the random-plane launches on the byte texture, which are bound by L1 look-ups.)
 #include "pm_sweep_impl.h"
 
 int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& a, const PlaneBuf& b, const PlaneBuf& c, uint32_t sid, int dp, int dr, int* launched) {
@@ -25,6 +27,7 @@ int launch_pm_sweep_experiment(tsar_ctx* ctx, int colour, const PlaneBuf& a, con
         EXP(false, 2228474);   // the production difference-texture loop (pm_tap_r5.h MIX) in EVERY launch (needs the context's dquad textures)
         EXP(false, 6422778);   // WRONG RESULTS: the difference-texture loop without gathers: what the shipping body costs without its gather path (pm_tap_r5.h DIAG 1)
         EXP(false, 10617082);  // WRONG RESULTS: the difference-texture loop with every gather replaced by an 8-byte LDS read (DIAG 2): the ceiling of LDS-staged source patches
+        EXP(false, 138412282); // WRONG RESULTS: the paired loop (pm_tap_r5.h PAIR) without the uncovered lanes' gathers (DIAG 3), in EVERY launch: its ceiling on the first sweep
         default: return TSAR_OK;
     }
 #undef EXP

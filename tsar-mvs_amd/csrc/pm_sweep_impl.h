@@ -522,6 +522,7 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
         ScopedKernelTimer tm(ctx, (V & TSAR_V_GEOM) ? "pm_sweep_geom" : "pm_sweep");
         ScopedKernelTimer tm_packed(ctx, packed ? "pm_sweep_packed" : nullptr);      // (the packed launches a second time under their own name)
         ScopedKernelTimer tm_prune(ctx, (V & TSAR_V_PRUNE) ? "pm_sweep_prune" : nullptr);   // (and the pruning kernels, checking or not)
+        ScopedKernelTimer tm_pair(ctx, (V & TSAR_V_PAIR) ? "pm_sweep_pair" : nullptr);      // (and the paired-gather kernels)
         hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(BLK), g.lds, ctx->stream, ctx->dscene, colour, same_in.c, same_in.n4, other.c,
                            other.n4, same_out.c, same_out.n4, ctx->ratio, ctx->beview, stream_id, do_prop, do_refine, g.tiles_x, g.n_tiles,
                            ctx->cost_consistent ? 1 : 0, strip_width(ctx->strip_w, g.tiles_x), ctx->final_text, memo);

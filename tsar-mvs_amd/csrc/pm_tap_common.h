@@ -49,6 +49,7 @@ DEVFN void tap_divide(float X, float Y, float Z, float& u, float& v) {
 // From a tap's homogeneous position to its bilinear fractions and the element index of its quad entry, for the loops that address
 // the quad texture from entry (1, 1) with an unsigned offset.  CLAMP = false: the caller has shown that the tap lies inside the
 // image (pm_tap_r5.h: strict mode's corner test, the fast loops' centre-and-extent test) — strict mode then also drops the divide's operand guard.
+// (pm_tap_r5.h PAIR reads 16 bytes at the entry and relies on iu <= w - 1, iv <= h - 1 below: a wider range here moves its bound.)
 // Clamp range.  The oracle clamps to [-1, w] (tex2D at u + .5 with clamp addressing).  The offset is unsigned from entry (1, 1), so
 // floor(u) must be >= 0: clamp to [0, w - 1] = [0, uhi] instead.  The sample is the same bit for bit: for u in [-1, 0) both texels
 // of the pair are T(0) (edge replication), so the blend returns T(0) whatever the fraction — exactly what u = 0 returns (fraction
@@ -117,6 +118,20 @@ DEVFN std::conditional_t<MIX, uint64_t, uint32_t> buffer_gather(int lin, u32x4s 
     if constexpr (MIX) asm volatile("buffer_load_dwordx2 %0, %1, %2, 0 idxen" : "=v"(q) : "v"(lin), "s"(rsrc));
     else asm volatile("buffer_load_dword %0, %1, %2, 0 idxen" : "=v"(q) : "v"(lin), "s"(rsrc));
     return q;
+}
+// A 16-byte gather from a 4-byte-aligned address (one global_load_dwordx4), and dword k (0..3) of its result per lane: two levels
+// of v_perm_b32, whose selector 0x03020100 takes the second operand and 0x07060504 the first.  What the compiler emits for it
+// (tools/isa.sh on pm_pair.hip): the three v_perm_b32, and each selector as v_and / v_cmp / v_cndmask between the two constants
+// held in registers, not the mask arithmetic written here: 9 VALU, 11 per pair with the index difference and the range test.  Left
+// so: the kernels that run it are bound by L1 look-ups and have the issue slots (profiles/pair_gather).  Any k gives some dword of
+// the four.
+typedef u32x4s u32x4s_a4 __attribute__((aligned(4)));
+typedef const u32x4s_a4 __attribute__((address_space(1)))* global_u32x4_a4_ptr;
+DEVFN uint32_t pick_dword(u32x4s a, uint32_t k) {
+    const uint32_t b0 = (uint32_t)((int32_t)(k << 31) >> 31), b1 = (uint32_t)((int32_t)(k << 30) >> 31);      // all ones where the bit is set
+    const uint32_t s0 = (b0 & 0x04040404u) | 0x03020100u, s1 = (b1 & 0x04040404u) | 0x03020100u;
+    const uint32_t lo = __builtin_amdgcn_perm(a.y, a.x, s0), hi = __builtin_amdgcn_perm(a.w, a.z, s0);
+    return __builtin_amdgcn_perm(hi, lo, s1);
 }
 // ---- how they are blended --------------------------------------------------------------------------------------------------------
 // FAST = false: the reference's blend, two horizontal interpolations and one vertical (tex2D, linear filter).  FAST (the fast

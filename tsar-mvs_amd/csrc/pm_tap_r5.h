@@ -46,12 +46,22 @@
 // >= the lane's cost_now; vp.skipped then tells the caller that the returned MAXCOST stands for "not below cost_now".  The three
 // reference sums over the lines walked so far are formed from LDS at each check (no register lives across a line for them: the
 // kernels have none to spare).  The decision is wave-uniform, like the clamp-free one.
-template <bool STRICT, bool ROW, bool D16, bool BUF, bool MIX, int BLK, int DIAG = 0, bool PRUNE = false>
+// PAIR (variant bit TSAR_V_PAIR; the plain fast form only: ROW + D16, global loads on the byte texture, no pruning): a row's six taps
+// are 2 px apart in the reference and land ~2 entries apart in the source texture, so the 16 bytes from tap j's entry on hold tap
+// j + 1's entry for ~87 % of lanes on random planes (tools/pair_gather_census.py).  Taps 0, 2, 4 are gathered as 16 bytes
+// (global_load_dwordx4, 4-byte aligned); a lane whose k = lin[j + 1] - lin[j] is in 0..3 takes dword k of them for tap j + 1, the
+// others gather tap j + 1 as before, after the three wide loads.  The test is on the element indices alone and every tap's entry
+// reaches blend_quad unchanged and in the same order: the same bits, with ~38 % fewer L1 look-ups where every lane is on its own
+// line (init, the first sweep of a view).
+// DIAG 3 (experiments build only, WRONG RESULTS): PAIR with the uncovered lanes' gathers left out: the ceiling of the paired loop.
+template <bool STRICT, bool ROW, bool D16, bool BUF, bool MIX, int BLK, int DIAG = 0, bool PRUNE = false, bool PAIR = false>
 DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, const unsigned short* tile, int tw, int own, const float* wts,
                          const PixelRef& pr, int x, int y, const float4& n4, ViewPrune* vp = nullptr) {
     static_assert(!(STRICT && ROW), "the row-wise walk changes the summation order: fast mode only");
     static_assert(!PRUNE || (ROW && D16 && !STRICT && DIAG == 0), "the partial-window bound is written for the fast row-wise loop");
     static_assert(!MIX || (BUF && !STRICT), "the half-float difference texture serves the fast arithmetic's blend through buffer loads");
+    static_assert(!PAIR || (ROW && D16 && !STRICT && !BUF && !MIX && !PRUNE), "the paired gathers are written for the plain fast row-wise loop on the byte texture");
+    static_assert(DIAG != 3 || PAIR, "DIAG 3 is a form of the paired loop");
     const int w = sc->w, h = sc->h, qp = sc->quad_pitch;
     const int qorg = quad_border_bytes(qp);
     float H[9];
@@ -152,6 +162,8 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
         float ax[6], ay[6];
         uint32_t q[6];
         uint64_t q2[6];                              // MIX: the tap's four halfs
+        int linv[6];                                 // PAIR: the taps' element indices
+        u32x4s wide[3];                              // PAIR: the 16 bytes from taps 0, 2, 4 on
         __builtin_amdgcn_s_setprio(3);               // a wave computing tap positions / issuing gathers goes ahead of waves that are blending
 #pragma unroll
         for (int jj = 0; jj < 6; jj++) {                        // phase 1: tap positions -> element index; phase 2: gathers
@@ -171,10 +183,25 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
                 q2[jj] = buffer_gather<true>(lin, rsrc);
             } else if (BUF) {
                 q[jj] = buffer_gather<false>(lin, rsrc);
+            } else if constexpr (PAIR) {
+                // Reading past the last entry: the base is entry (1, 1) of a texture of (h + 2) rows of qp = w + 2 entries
+                // (tsar_api.hip: dev_alloc of (w + 2) (h + 2) dwords), and lin <= (h - 1) qp + (w - 1) (tap_position: iu <= w - 1,
+                // iv <= h - 1), i.e. entry h qp + w of the allocation at most.  The 16 bytes end with entry h qp + w + 3 =
+                // (h + 1) qp + 1, inside the border row below the image: no padding is needed.  (The bound on lin is tap_position's
+                // clamp range [0, w - 1] x [0, h - 1], pm_tap_common.h "Clamp range", and the clamp-free loop's inside test above.)
+                linv[jj] = lin;
+                if ((jj & 1) == 0) wide[jj >> 1] = *(global_u32x4_a4_ptr)((const char __attribute__((address_space(1)))*)(uintptr_t)(((uint64_t)qb_hi << 32) | qb_lo) + ((uint32_t)lin << 2));
             } else {                                            // base already holds the border offset: the byte offset is a plain shift
                 const uint32_t off2 = (uint32_t)lin << 2;
                 q[jj] = *(global_u32_ptr)((const char __attribute__((address_space(1)))*)(uintptr_t)(((uint64_t)qb_hi << 32) | qb_lo) + off2);
             }
+        }
+        if constexpr (PAIR && DIAG != 3) {
+            // the lanes whose odd tap is not among the anchor's four entries: today's gather, behind the three wide ones
+#pragma unroll
+            for (int jj = 1; jj < 6; jj += 2)
+                if ((uint32_t)(linv[jj] - linv[jj - 1]) > 3u)
+                    q[jj] = *(global_u32_ptr)((const char __attribute__((address_space(1)))*)(uintptr_t)(((uint64_t)qb_hi << 32) | qb_lo) + ((uint32_t)linv[jj] << 2));
         }
         __builtin_amdgcn_sched_barrier(0);           // nothing of phase 3 may move above the last gather
         __builtin_amdgcn_s_setprio(0);
@@ -203,6 +230,14 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
                 if (jj == 3) asm("s_waitcnt vmcnt(2)" : "+v"(q[3]), "+v"(sum_src_src) : "v"(q[5]));
                 if (jj == 4) asm("s_waitcnt vmcnt(1)" : "+v"(q[4]), "+v"(sum_src_src) : "v"(q[5]));
                 if (jj == 5) asm("s_waitcnt vmcnt(0)" : "+v"(q[5]), "+v"(sum_src_src));
+            }
+            if constexpr (PAIR) {
+                // selected as each pair returns: the anchor's four dwords die with its odd tap
+                if ((jj & 1) == 0) q[jj] = wide[jj >> 1].x;
+                else {
+                    const uint32_t k = (uint32_t)(linv[jj] - linv[jj - 1]);
+                    if (DIAG == 3 || k <= 3u) q[jj] = pick_dword(wide[jj >> 1], k);
+                }
             }
             float s;
             if (MIX) s = blend_dquad(q2[jj], ax[jj], ay[jj]);
@@ -263,4 +298,5 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
 // + 4194304 / + 8388608 (experiments build): DIAG 1 / 2 of the MIX body
 __host__ __device__ constexpr bool r5_diag_variant(int V) { return V == (250 | TSAR_V_BUF | TSAR_V_MIX | 4194304) || V == (250 | TSAR_V_BUF | TSAR_V_MIX | 8388608); }
 // + TSAR_V_PRUNE (with 250 and its BUF / MIX forms): PRUNE; masked off before this test, like TSAR_V_GEOM
+// + TSAR_V_PAIR (with 250 alone): PAIR; masked off likewise (+ 4194304, experiments build: DIAG 3)
 __host__ __device__ constexpr bool r5_production_variant(int V) { return V == 114 || V == 122 || V == 250 || V == (114 | TSAR_V_BUF) || V == (122 | TSAR_V_BUF) || V == (250 | TSAR_V_BUF) || V == (250 | TSAR_V_BUF | TSAR_V_MIX); }

@@ -92,6 +92,7 @@ static inline bool scene_has_terms(const DevScene& s) { return s.geom_on != 0 ||
 // Variant bits of the geometric-consistency kernels (the remaining bits name the tap loop as before)
 #define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term) and the plane-prior term to the result (add_prior_term)
 #define TSAR_V_PRUNE 67108864     // bit 26, with 250 and its BUF / MIX forms, sweep only: wide refinement steps leave a view the partial-window bound proves rejected (pm_tap_r5.h PRUNE)
+#define TSAR_V_PAIR 134217728     // bit 27, with 250 alone (pm_pair.hip): one 16-byte gather per pair of row taps (pm_tap_r5.h PAIR)
 #define TSAR_V_REDRAW 33554432    // bit 25, with INIT: pm_full_kernel keeps the given plane where it is a valid hypothesis (tsar_pm_rescore)
 
 // State planes of one ping-pong buffer (linestate.h:12-13).
@@ -165,6 +166,9 @@ struct tsar_ctx {
     int prune = 1;                    // TSAR_PRUNE=0: off (the kernels without the check)
     int prune_steps = 2;              // TSAR_PRUNE_STEPS=n: refinement steps 0 .. n - 1 are checked
     int prune_from = 1;               // TSAR_PRUNE_FROM=n: from launch n of a call on
+    // Paired gathers in the random-plane launches (pm_pair.hip, pm_tap_r5.h PAIR): TSAR_PAIR=0 neither, 1 the initialisation, 2 the
+    // first sweep of a run (the plain global-load launches), 3 both
+    int pair = 3;
     uint32_t* prune_counts = nullptr; // tsar_selftest_prune_census: device counters while a census runs, else null
     // coarse-to-fine mode (tsar_pyramid_views / tsar_upsample_planes)
     std::vector<tsar_camera> cams;    // the cameras tsar_set_views was given (before cam_scale), from which a coarser level derives its own
@@ -409,6 +413,9 @@ int launch_build_quad(tsar_ctx* ctx, const float* img, uint32_t* quad, int w, in
 int launch_expand_u8(tsar_ctx* ctx, const uint8_t* in, float* out, size_t n);   // plane_kernels.hip
 int launch_build_dquad(tsar_ctx* ctx, const uint32_t* quad, uint2* dquad, int w, int h);
 int launch_pm_init(tsar_ctx* ctx);
+int launch_pm_init_pair(tsar_ctx* ctx);    // pm_pair.hip: the plain fast box-11 configuration with paired gathers
+int launch_pm_sweep_pair(tsar_ctx* ctx, int block, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
+                         uint32_t stream_id, int do_prop, int do_refine);   // pm_pair.hip
 bool probe_d16_hi_zeroes(tsar_ctx* ctx);   // pm_sweep.hip
 int launch_pm_sweep(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
                     uint32_t stream_id, int do_prop, int do_refine);
