@@ -399,7 +399,7 @@ int tsar_pm_merge_depths(tsar_ctx* ctx, const float* depth, int mem, int64_t* n_
 /* ---- plane prior ------------------------------------------------------------------------------ */
 /* A per-pixel prior plane and a truncated penalty on a hypothesis's deviation from it, added to the multi-view cost (ACMP's planar
  * prior, used softly: the photometric and geometric costs arbitrate).  The prior may be a region plane, a coarser result, a filled map
- * of the textureless refinement, anything external; the library builds none.
+ * of the textureless refinement, anything external, or what tsar_build_plane_prior below builds from a checked depth map.
  * The prior the context holds, per pixel (q_x, q_y, q_z, Dp): Dp is the caller's depth[y][x], unchanged; q is the caller's
  * normal_world[y][x] taken to reference-camera coordinates exactly as tsar_load_planes takes it (the same device function, bit for bit).
  * A pixel has a prior iff Dp > 0 and Dp < inf and the three normal components are finite; otherwise the held entry is (0, 0, 0, 0).
@@ -441,6 +441,56 @@ void tsar_default_plane_prior_params(tsar_plane_prior_params* p);
 int tsar_set_plane_prior(tsar_ctx* ctx, const float* depth, const float* normal_world, int mem, const tsar_plane_prior_params* p);
 int tsar_clear_plane_prior(tsar_ctx* ctx);
 int tsar_get_plane_prior(tsar_ctx* ctx, float* prior_out /* [h][w][4] as held */, int mem);
+
+/* A plane prior built from the pixels of a depth map that a check confirmed (ACMP builds its prior from a triangulation of such pixels):
+ * a hierarchical lattice triangulation, exact integer geometry up to the choice of a triangle, then one float64 solve per pixel.  No
+ * sort, no floating-point atomics, no data-dependent loop bound: every output bit is the same in every run and in both arithmetic modes.
+ * depth [h][w] float32: the filtered map, 0 where a pixel was dropped (tsar_geom_check's depth_out).  score [h][w] float32 or NULL: lower
+ * is better (a stored cost; ACMP's "most credible point").  Needs views: the reference camera, and w, h <= 65535.
+ *   candidate: depth > 0 and depth < inf (NaN and -0.0 fail), and, with a score, score >= 0 and score < inf (NaN fails; a score of -0.0
+ *     is a candidate and counts as +0.0)
+ *   levels: level l has cells of edge s_l = cell << l on a grid of ceil(w / s_l) x ceil(h / s_l) cells (the last column and row may be
+ *     partial); it exists while both grid dimensions are >= 2, l < max_levels (max_levels = 0: all that fit) and l < 16
+ *   support point of a cell: its candidate with the smallest (score, raster index), lexicographic, scores compared as their bit
+ *     patterns (the order of non-negative floats); without a score the smallest raster index.  A cell without a candidate is empty.
+ *     (A coarser cell's support point is the minimum over its four children: a minimum, so no order of arrival can matter.)
+ *   quads: cells (a, b), (a+1, b), (a, b+1), (a+1, b+1) of one level form a quad when all four exist and none is empty; their support
+ *     points are P00, P10, P01, P11.  orient(A, B, C) = (Bx - Ax)(Cy - Ay) - (By - Ay)(Cx - Ax), in integers.  The quad is split along
+ *     P00-P11 when orient(P00, P11, P10) and orient(P00, P11, P01) have strictly opposite signs: triangles (P00, P10, P11), (P00, P11, P01);
+ *     otherwise along P10-P01: triangles (P00, P10, P01), (P10, P11, P01).  A triangle (A, B, C) with area2 = orient(A, B, C) = 0 is skipped;
+ *     a pixel P is inside when orient(A, B, P), orient(B, C, P), orient(C, A, P) are each zero or of area2's sign (edges and vertices inside).
+ *   the triangle of pixel (x, y): levels from 0 upwards; at level l, with the pixel in cell (i, j) = (x / s_l, y / s_l), the quads with
+ *     origin (i-1, j-1), (i, j-1), (i-1, j), (i, j) in that order, each quad's two triangles in the order above; the first triangle that
+ *     contains the pixel is taken, l is its level.  At most 8 triangles per level are tried.  A pixel no level covers has no prior.
+ *   the plane of (A, B, C), float64, every operation one IEEE-754 operation rounded to nearest (no fused multiply-add), quotients and the
+ *     square root correctly rounded; integers and float32 values enter exactly:
+ *       wA = 1 / depth[A], wB, wC likewise;  dB = wB - wA;  dC = wC - wA          (the inverse depth of a plane is affine in the pixel)
+ *       gx = (dB * (Cy - Ay) - dC * (By - Ay)) / area2;   gy = (dC * (Bx - Ax) - dB * (Cx - Ax)) / area2
+ *       wp = (wA + gx * (x - Ax)) + gy * (y - Ay);   no prior unless wp > 0 (it is, whenever the three depths are of comparable size)
+ *       c0 = (wA - gx * Ax) - gy * Ay;   m_k = (K[0][k] * gx + K[1][k] * gy) + K[2][k] * c0, k = 0, 1, 2   (K: the reference camera's, as
+ *            the kernels hold it: float32 after cam_scale)
+ *       len = sqrt((m_0 * m_0 + m_1 * m_1) + m_2 * m_2);   q_k = -m_k / len        (the unit normal in reference-camera coordinates, facing
+ *            the camera)
+ *       normal_world_k = float32((R[0][k] * q_0 + R[1][k] * q_1) + R[2][k] * q_2)   (R: the reference camera's world->camera rotation; the
+ *            convention of tsar_get_result's normal_world, so the map can go straight into tsar_set_plane_prior)
+ *       depth = float32(1 / wp)
+ * Outputs, each may be NULL, not all three: depth_out [h][w] float32 and normal_world_out [h][w][3] float32, 0 where there is no prior;
+ * level_out [h][w] uint8, the level used, 255 where there is no prior.  `mem` applies to every pointer; with device pointers nothing
+ * touches the host.  The call changes nothing in the context: planes, stored costs, the propagation memo, the sweep counter, lines->scale,
+ * the result planes, the term and any prior the context holds stay as they are.  The grids are temporaries of the call.  Timed as
+ * "plane_prior_build" (the per-pixel look-up and solve), "plane_prior_build_supports" (level 0) and "plane_prior_build_levels" (the
+ * coarser levels, one timed bracket around their launches).
+ * TSAR_ERR_STATE: no views.  TSAR_ERR_INVALID: depth or p NULL; all three outputs NULL; mem unknown; cell outside [2, 256]; max_levels
+ * outside [0, 16]; an image too small for one level (w <= cell or h <= cell) or larger than 65535 in either direction. */
+#define TSAR_PLANE_PRIOR_MAX_LEVELS 16
+typedef struct tsar_plane_prior_build_params {
+    int32_t cell;         /* level-0 cell edge in pixels, in [2, 256]; default 4: ACMP's spacing is 5, and on the 160 x 120 simulated scene of
+                             DESIGN.md section 8 a cell of 4 did better than 8.  Untuned on real scenes. */
+    int32_t max_levels;   /* default 0 = every level that fits; in [0, 16] */
+} tsar_plane_prior_build_params;
+void tsar_default_plane_prior_build_params(tsar_plane_prior_build_params* p);
+int tsar_build_plane_prior(tsar_ctx* ctx, const float* depth, const float* score /* may be NULL */, int mem,
+                           const tsar_plane_prior_build_params* p, float* depth_out, float* normal_world_out, uint8_t* level_out);
 
 /* After tsar_compute_disp: depth [h][w] (0 where cost == MAXCOST), normal_world [h][w][3],
  * cost [h][w], confid [h][w]; any may be NULL. */

@@ -66,6 +66,10 @@ class PlanePriorParams(C.Structure):
     _fields_ = [("weight_depth", C.c_float), ("weight_normal", C.c_float), ("depth_clip", C.c_float), ("normal_clip", C.c_float)]
 
 
+class PlanePriorBuildParams(C.Structure):
+    _fields_ = [("cell", C.c_int32), ("max_levels", C.c_int32)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -85,6 +89,7 @@ ABI_SYMBOLS = [
     "tsar_default_geom_check_params", "tsar_geom_check",
     "tsar_default_geom_reproject_params", "tsar_geom_reproject", "tsar_pm_merge_depths",
     "tsar_default_plane_prior_params", "tsar_set_plane_prior", "tsar_clear_plane_prior", "tsar_get_plane_prior",
+    "tsar_default_plane_prior_build_params", "tsar_build_plane_prior",
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
@@ -152,6 +157,10 @@ def load_library(path: str = LIB_PATH):
     L.tsar_set_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PlanePriorParams)]
     L.tsar_clear_plane_prior.argtypes = [C.c_void_p]
     L.tsar_get_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, "tsar_build_plane_prior"):          # (a library built before the builder, loaded through TSAR_LIB for an A/B run)
+        L.tsar_default_plane_prior_build_params.restype = None
+        L.tsar_default_plane_prior_build_params.argtypes = [C.POINTER(PlanePriorBuildParams)]
+        L.tsar_build_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PlanePriorBuildParams), C.c_void_p, C.c_void_p, C.c_void_p]
     L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -445,6 +454,48 @@ class Matcher:
         out = np.empty((self.h, self.w, 4), np.float32)
         self._chk(self.L.tsar_get_plane_prior(self._ctx, _ptr(out)[0], MEM_HOST))
         return out
+
+    def build_plane_prior(self, depth, score=None, cell: int = 4, max_levels: int = 0, want=("depth", "normal", "level"), device: bool = False):
+        """a plane prior built from a checked depth map (tsar_build_plane_prior): depth [h, w] float32 is the filtered map, 0 where a
+        pixel was dropped (geom_check's "depth"); score [h, w] float32 or None, lower is better (a stored cost).  A lattice of cells of
+        edge cell << level keeps each cell's best candidate, neighbouring candidates span triangles, and every pixel gets the plane of
+        the first triangle that contains it, finest level first (max_levels = 0: every level that fits).  Inputs are numpy arrays or
+        torch device tensors (both the same).  Returns a dict with "depth" ([h, w] float32), "normal" ([h, w, 3] float32 world normals:
+        what set_plane_prior takes) and / or "level" ([h, w] uint8, 255 = no prior; depth and normal are 0 there), as `want` names
+        them: torch tensors on the device when the inputs are, or with device=True; numpy arrays otherwise.  Nothing in the context
+        changes."""
+        on_device = _is_torch(depth) and depth.is_cuda
+        if score is not None:
+            assert (_is_torch(score) and score.is_cuda) == on_device, "depth and score must live in the same memory space"
+        if on_device:
+            assert str(depth.dtype) == "torch.float32" and (score is None or str(score.dtype) == "torch.float32")
+        else:
+            depth = np.ascontiguousarray(depth.numpy() if _is_torch(depth) else depth, np.float32)
+            if score is not None:
+                score = np.ascontiguousarray(score.numpy() if _is_torch(score) else score, np.float32)
+        assert tuple(depth.shape) == (self.h, self.w), "the depth map has shape %s, the views are %dx%d" % (tuple(depth.shape), self.w, self.h)
+        assert score is None or tuple(score.shape) == (self.h, self.w), "the score must be [h, w]"
+        if device and not on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            depth = torch.from_numpy(depth).to(dev)
+            score = torch.from_numpy(score).to(dev) if score is not None else None
+            on_device = True
+        shapes = {"depth": ((self.h, self.w), "float32"), "normal": ((self.h, self.w, 3), "float32"), "level": ((self.h, self.w), "uint8")}
+        res = {}
+        for k, (shape, dt) in shapes.items():
+            if k not in want:
+                continue
+            if on_device:
+                import torch
+                res[k] = torch.empty(shape, dtype=getattr(torch, dt), device=depth.device)
+            else:
+                res[k] = np.empty(shape, dt)
+        p = PlanePriorBuildParams(int(cell), int(max_levels))
+        d, kind = _ptr(depth)
+        self._chk(self.L.tsar_build_plane_prior(self._ctx, d, _ptr(score)[0], kind, C.byref(p), _ptr(res.get("depth"))[0],
+                                                _ptr(res.get("normal"))[0], _ptr(res.get("level"))[0]))
+        return res
 
     # ---- the geometric-consistency pass coarse to fine ----
     def geom_pyramid_from(self, fine: "Matcher"):
@@ -777,27 +828,60 @@ def _install_prior(matcher: Matcher, prior, prior_params):
     matcher.set_plane_prior(depth, normal_world, **(prior_params or {}))
 
 
+_BUILD_PRIOR_KEYS = {"cell": "cell", "max_levels": "max_levels", "reproj_error": "check", "depth_diff": "check", "min_consistent": "check"}
+
+
+def _check_prior_arguments(prior, prior_params, build_prior):
+    if prior is not None and build_prior is not None:
+        raise ValueError("prior and build_prior are mutually exclusive")
+    if prior is None and build_prior is None and prior_params is not None:
+        raise ValueError("prior_params without a prior")
+    if build_prior is not None and set(build_prior) - set(_BUILD_PRIOR_KEYS):
+        raise ValueError("build_prior: unknown settings %s" % sorted(set(build_prior) - set(_BUILD_PRIOR_KEYS)))
+
+
+def _build_prior(matcher: Matcher, own_depth, build_prior, prior_params):
+    """the prior built from the view's own depth, after the maps are installed: rescore; the stored cost is the score; geom_check(own
+    depth) keeps the confirmed depths; build_plane_prior; set_plane_prior; rescore again (installing a prior voids the costs).  The
+    built maps stay on the device."""
+    check = {k: v for k, v in build_prior.items() if _BUILD_PRIOR_KEYS[k] == "check"}
+    build = {k: v for k, v in build_prior.items() if _BUILD_PRIOR_KEYS[k] != "check"}
+    matcher.rescore()
+    score = matcher.get_plane()[1]
+    kept = matcher.geom_check(own_depth, want=("depth",), **check)["depth"]
+    if _is_torch(kept) and kept.is_cuda:
+        import torch
+        score = torch.from_numpy(score).to(kept.device)
+    built = matcher.build_plane_prior(kept, score, want=("depth", "normal"), device=True, **build)
+    matcher.set_plane_prior(built["depth"], built["normal"], **(prior_params or {}))
+    matcher.rescore()
+
+
 def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, iters: int, weight: float = 0.2, clip: float = 3.0,
-                  cross_view: int = 0, cross_view_depth_diff: float = 0.01, prior=None, prior_params=None):
+                  cross_view: int = 0, cross_view_depth_diff: float = 0.01, prior=None, prior_params=None, build_prior=None):
     """The geometric-consistency pass of one reference view: start from its own photometric result (depth [h, w], world normals
     [h, w, 3]), install the source views' depth maps (src_depths[v] for view v of the matcher, [0] ignored, None = no term), rescore,
     run `iters` iterations with the term, compute_disp.  The term stays installed (clear_geom removes it).
     cross_view = K >= 1: in place of the rescore, the source maps are rendered into this view (geom_reproject with min_views = K and
     depth_diff = cross_view_depth_diff) and offered to the matcher (merge_depths, which rescores first).
     prior = (depth, normal_world): installed as the plane prior right after the maps (set_plane_prior; prior_params = its keyword
-    arguments as a dict, None = the defaults); it stays installed too (clear_plane_prior removes it)."""
+    arguments as a dict, None = the defaults); it stays installed too (clear_plane_prior removes it).
+    build_prior = a dict (in place of prior): the prior is built from the view's own depth (_build_prior says how; the dict holds
+    build_plane_prior's "cell" and "max_levels" and geom_check's "reproj_error", "depth_diff" and "min_consistent", each optional) and
+    installed with prior_params."""
     if iters < 0:
         raise ValueError("iters must be >= 0")
     _check_cross_view(cross_view, cross_view_depth_diff)
-    if prior is None and prior_params is not None:
-        raise ValueError("prior_params without a prior")
+    _check_prior_arguments(prior, prior_params, build_prior)
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
     if prior is not None:
         _install_prior(matcher, prior, prior_params)
+    if build_prior is not None:
+        _build_prior(matcher, own_depth, build_prior, prior_params)
     if cross_view:
         _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
-    else:
+    elif build_prior is None:              # (_build_prior ends with this rescore)
         matcher.rescore()
     matcher.pm_iterate(iters)
     matcher.compute_disp()
@@ -805,7 +889,7 @@ def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, ite
 
 def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_depths, levels: int, coarse_iters: int, fine_iters: int,
                              weight: float = 0.2, clip: float = 3.0, coarse=None, cross_view: int = 0, cross_view_depth_diff: float = 0.01,
-                             prior=None, prior_params=None):
+                             prior=None, prior_params=None, build_prior=None):
     """The geometric-consistency pass coarse to fine (include/tsar.h tsar_geom_pyramid): `levels` pyramid levels below `matcher`; the
     view's own result and the term are carried down the chain, `coarse_iters` iterations run at the coarsest level, then every finer
     level (matcher's own included) merges the coarser planes into its own and runs `fine_iters` iterations; compute_disp.  levels = 0
@@ -814,25 +898,27 @@ def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_
     cross_view = K >= 1: as in run_geom_pass, on the full-resolution matcher right after its term is installed and before the chain is
     carried down (the coarser levels then start from the merged planes).
     prior, prior_params: as in run_geom_pass, on the full-resolution matcher only (a prior is not carried to coarser levels: they score
-    with their own cost); any prior the chain's contexts still hold is removed first, since tsar_pyramid_views refuses it."""
+    with their own cost); any prior the chain's contexts still hold is removed first, since tsar_pyramid_views refuses it.
+    build_prior: as in run_geom_pass, on the full-resolution matcher only, right after its term is installed."""
     if levels < 0 or coarse_iters < 0 or fine_iters < 0:
         raise ValueError("levels and iteration counts must be >= 0")
     _check_cross_view(cross_view, cross_view_depth_diff)
-    if prior is None and prior_params is not None:
-        raise ValueError("prior_params without a prior")
+    _check_prior_arguments(prior, prior_params, build_prior)
     if levels == 0:
         run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip, cross_view=cross_view,
-                      cross_view_depth_diff=cross_view_depth_diff, prior=prior, prior_params=prior_params)
+                      cross_view_depth_diff=cross_view_depth_diff, prior=prior, prior_params=prior_params, build_prior=build_prior)
         return list(coarse or [])
     def clear(m):
         m.clear_geom()
-        if prior is not None:
+        if prior is not None or build_prior is not None:
             m.clear_plane_prior()
     coarse, chain = _pyramid_chain(matcher, levels, coarse, prepare=clear)
     matcher.load_planes(own_depth, own_normal_world)
     matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
     if prior is not None:
         _install_prior(matcher, prior, prior_params)
+    if build_prior is not None:
+        _build_prior(matcher, own_depth, build_prior, prior_params)
     if cross_view:
         _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
     for finer, coarser in zip(chain[:-1], chain[1:]):

@@ -952,6 +952,37 @@ extern "C" int tsar_get_plane_prior(tsar_ctx* ctx, float* prior_out, int mem) {
     return TSAR_OK;
 }
 
+// ---- a prior built from a checked depth map (plane_prior_build_kernels.hip) -------------------------------------------------------
+extern "C" void tsar_default_plane_prior_build_params(tsar_plane_prior_build_params* p) {
+    if (!p) return;
+    p->cell = 4;                           // include/tsar.h says why, and that it is untuned
+    p->max_levels = 0;
+}
+
+// Reads the map, the score and the reference camera, writes the caller's outputs and one temporary of the call: no transition of the
+// plane state (tsar_dev.h) is involved, and nothing the context owns is written
+extern "C" int tsar_build_plane_prior(tsar_ctx* ctx, const float* depth, const float* score, int mem, const tsar_plane_prior_build_params* p,
+                                      float* depth_out, float* normal_world_out, uint8_t* level_out) {
+    CHECK_CTX(ctx);
+    NEED_VIEWS(ctx);
+    if (!depth || !p) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: depth or params is NULL");
+    if (!depth_out && !normal_world_out && !level_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: every output is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (p->cell < 2 || p->cell > 256) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: cell must be in 2..256");
+    if (p->max_levels < 0 || p->max_levels > TSAR_PLANE_PRIOR_MAX_LEVELS) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: max_levels must be in 0..16");
+    if (ctx->w > 65535 || ctx->h > 65535) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: the image is larger than 65535 pixels in a direction");
+    const size_t keys = plane_prior_build_grid_keys(ctx->w, ctx->h, p->cell, p->max_levels);
+    if (keys == 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_build_plane_prior: the image is too small for one level (both sides must exceed cell)");
+    const size_t np = (size_t)ctx->w * ctx->h;
+    CallFrame f(ctx, __func__);
+    const float *d = f.in(depth, np, mem), *s = f.in(score, np, mem);
+    unsigned long long* grid = f.tmp<unsigned long long>(keys);
+    float *od = f.out(depth_out, np, mem), *on = f.out(normal_world_out, 3 * np, mem);
+    uint8_t* ol = f.out(level_out, np, mem);
+    if (f.ok()) f.take(launch_plane_prior_build(ctx, d, s, p->cell, p->max_levels, grid, od, on, ol));
+    return f.finish();
+}
+
 // buf[0]'s planes scored with the context's cost (invalid ones redrawn as tsar_pm_init draws) into buf[1], which becomes the state:
 // the kernel's plane pointers are restrict-qualified, so it cannot run in place
 static int rescore_state(tsar_ctx* ctx) {

@@ -454,6 +454,9 @@ int launch_merge_select(tsar_ctx* ctx, const float4* cand, const float* cand_c, 
                         unsigned long long* n_taken);                                          // geom_reproject_kernels.hip (writes buf[0], beview, ratio)
 int launch_get_disp(tsar_ctx* ctx, const float* depth_in, const float* normal_world);
 int launch_plane_prior(tsar_ctx* ctx, const float* depth_in, const float* normal_world, float4* prior);   // plane_kernels.hip
+size_t plane_prior_build_grid_keys(int w, int h, int cell, int max_levels);                      // plane_prior_build_kernels.hip (0: no level fits)
+int launch_plane_prior_build(tsar_ctx* ctx, const float* depth, const float* score, int cell, int max_levels, unsigned long long* grid,
+                             float* depth_out, float* normal_out, uint8_t* level_out);          // plane_prior_build_kernels.hip
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);
 int launch_depth_to_plane(tsar_ctx* ctx);

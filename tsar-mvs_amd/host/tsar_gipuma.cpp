@@ -36,6 +36,11 @@
 //                      context right after the term; a view lacking either file runs without a prior and is named on stdout;
 //                      TSAR_geom.txt gains a line with STEM and the four settings only when the switch is on, and a view whose prior
 //                      files are newer than its outputs is recomputed
+//     [--geom_build_prior[=CELL (4)] [--geom_build_prior_levels=N (0: all)]]   phase 2 builds the view's plane prior itself, on the device,
+//                      right after the term is installed: rescore, the stored cost as the score, the view's own depth checked against
+//                      its sources' maps (tsar_geom_check at its defaults), tsar_build_plane_prior on the kept depths with level-0
+//                      cells of CELL pixels, tsar_set_plane_prior with the four --geom_prior_* settings, rescore; TSAR_geom.txt gains
+//                      a line with the settings only when the switch is on.  Not together with --geom_plane_prior=STEM
 //   --all --consistency_filter[=K (2)] [--filter_reproj_error=PX (2)] [--filter_depth_diff=REL (0.01)]   a last phase after the matching
 //                      phases, before --fuse: each view's depth map of the phase that ran last (TSAR_geom_disp.dmb with
 //                      --geom_consistency, else TSAR_disp.dmb) is checked against its pair.txt sources' maps of the same phase
@@ -86,6 +91,15 @@
 
 #include "../../include/tsar.h"
 
+// Entries that only --geom_build_prior calls are referred to weakly: the tool still links against, and runs with, a library that
+// lacks them (the recording stand-in of tests/test_cli_phases_cpu.py), and refuses the switch there.
+extern "C" {
+void tsar_default_plane_prior_build_params(tsar_plane_prior_build_params* p) __attribute__((weak));
+int tsar_build_plane_prior(tsar_ctx* ctx, const float* depth, const float* score, int mem, const tsar_plane_prior_build_params* p, float* depth_out,
+                           float* normal_world_out, uint8_t* level_out) __attribute__((weak));
+int tsar_get_plane(tsar_ctx* ctx, float* planes, float* cost, int32_t* beview, float* ratio, int mem) __attribute__((weak));
+}
+
 struct Options {
     std::vector<std::string> images;
     std::string images_folder, mslp_folder, krt_file, output_folder;
@@ -110,6 +124,11 @@ struct Options {
     bool geom_prior = false, geom_prior_option_set = false;   // the switch was given; one of its four settings was
     tsar_plane_prior_params prior{};                 // --geom_prior_weight_depth / _weight_normal / _depth_clip; normal_clip from the angle
     double geom_prior_angle = 30.0;                  // --geom_prior_angle_clip, degrees
+    bool geom_build = false;                         // --geom_build_prior[=CELL]: phase 2 builds its plane prior (tsar_build_plane_prior)
+    int geom_build_cell = 0, geom_build_levels = 0;  // CELL (0: the library's default), --geom_build_prior_levels
+    bool geom_build_levels_set = false;
+    tsar_plane_prior_build_params build{};           // what the builder is called with
+    tsar_geom_check_params build_check{};            // the check that chooses the builder's candidates: the library's defaults
     bool filter = false;                             // --consistency_filter[=K]: the last phase of --all (run_filter_view)
     bool filter_option_set = false;                  // a --filter_* switch was given
     tsar_geom_check_params check{};                  // K, --filter_reproj_error, --filter_depth_diff (include/tsar.h tsar_geom_check)
@@ -215,7 +234,8 @@ static void usage() {
            "                   [--geom_consistency [--geom_iterations=N] [--geom_weight=W] [--geom_clip=PX] [--geom_multi_scale=L [--geom_coarse_iterations=N]]\n"
            "                    [--geom_cross_view[=K] [--geom_cross_view_depth_diff=REL]]\n"
            "                    [--geom_plane_prior=STEM [--geom_prior_weight_depth=W] [--geom_prior_weight_normal=W] [--geom_prior_depth_clip=REL]\n"
-           "                     [--geom_prior_angle_clip=DEG]]]\n"
+           "                     [--geom_prior_angle_clip=DEG]]\n"
+           "                    [--geom_build_prior[=CELL] [--geom_build_prior_levels=N] [the four --geom_prior_* settings]]]\n"
            "                   [--consistency_filter[=K] [--filter_reproj_error=PX] [--filter_depth_diff=REL]]\n"
            "                   -images_folder DIR/ -mslp_folder DIR/ [options]\n"
            "       tsar_gipuma --check-mask=MASK.png | --encode-mask=DEPTH.dmb:MASK.png | --decode-image=IN[:OUT.pgm]     (no GPU)\n");
@@ -326,6 +346,15 @@ static int parse_args(int argc, char** argv, Options& o) {   // main.cpp:708-946
         else if (opt("--geom_prior_weight_normal")) { o.prior.weight_normal = (float)atof(v); o.geom_prior_option_set = true; }
         else if (opt("--geom_prior_depth_clip")) { o.prior.depth_clip = (float)atof(v); o.geom_prior_option_set = true; }
         else if (opt("--geom_prior_angle_clip")) { o.geom_prior_angle = atof(v); o.geom_prior_option_set = true; }
+        else if (is("--geom_build_prior")) o.geom_build = true;
+        else if (opt("--geom_build_prior")) {
+            if (!checked_int(v, 2, 256, o.geom_build_cell)) { printf("Command-line parameter error: --geom_build_prior=CELL must be an integer in 2..256\n"); return -1; }
+            o.geom_build = true;
+        }
+        else if (opt("--geom_build_prior_levels")) {
+            if (!checked_int(v, 0, TSAR_PLANE_PRIOR_MAX_LEVELS, o.geom_build_levels)) { printf("Command-line parameter error: --geom_build_prior_levels=N must be an integer in 0..16\n"); return -1; }
+            o.geom_build_levels_set = true;
+        }
         else if (is("--consistency_filter")) o.filter = true;
         else if (opt("--consistency_filter")) {
             if (!checked_int(v, 1, 31, o.check.min_consistent)) { printf("Command-line parameter error: --consistency_filter=K must be an integer in 1..31\n"); return -1; }
@@ -514,6 +543,13 @@ static std::string geom_record_of(const Options& o, const std::vector<int>&) {
     if (o.geom_prior) {
         snprintf(b, sizeof b, "geom_plane_prior=%s geom_prior_weight_depth=%.9g geom_prior_weight_normal=%.9g geom_prior_depth_clip=%.9g geom_prior_angle_clip=%.9g\n",
                  o.geom_prior_stem.c_str(), (double)o.prior.weight_depth, (double)o.prior.weight_normal, (double)o.prior.depth_clip, o.geom_prior_angle);
+        rec += b;
+    }
+    if (o.geom_build) {
+        snprintf(b, sizeof b, "geom_build_prior=%d geom_build_prior_levels=%d geom_build_min_consistent=%d geom_build_reproj_error=%.9g geom_build_depth_diff=%.9g "
+                 "geom_prior_weight_depth=%.9g geom_prior_weight_normal=%.9g geom_prior_depth_clip=%.9g geom_prior_angle_clip=%.9g\n",
+                 o.build.cell, o.build.max_levels, o.build_check.min_consistent, (double)o.build_check.reproj_error, (double)o.build_check.depth_diff,
+                 (double)o.prior.weight_depth, (double)o.prior.weight_normal, (double)o.prior.depth_clip, o.geom_prior_angle);
         rec += b;
     }
     if (o.geom_multi_scale > 0) {     // (an L = 0 record is the single-scale one, byte for byte)
@@ -985,6 +1021,30 @@ static int run_geom_view(const Options& o, Worker& wk, const LaterPhase& ph, int
         if (!read_map(files[0], h, w, 1, prior_d) || !read_map(files[1], h, w, 3, prior_n)) printf("view %08d (geom): no plane prior (%s / %s not readable at %d x %d): runs without one\n", ref, files[0].c_str(), files[1].c_str(), w, h);
         else if (tsar_set_plane_prior(ctx, prior_d.data(), prior_n.data(), TSAR_MEM_HOST, &o.prior) != TSAR_OK) return fail("tsar_set_plane_prior");
     }
+    if (o.geom_build) {
+        // the view's plane prior built from its own depth where its sources confirm it (api.run_geom_pass's build_prior), in device memory:
+        // one buffer holds the stored cost, then the prior's depth; one the own depth, filtered in place; one the prior's normals
+        const size_t np = (size_t)w * h;
+        float* score = (float*)tsar_device_alloc(wk.device, np * sizeof(float));
+        float* kept = (float*)tsar_device_alloc(wk.device, np * sizeof(float));
+        float* built = (float*)tsar_device_alloc(wk.device, 4 * np * sizeof(float));
+        const char* what = "tsar_device_alloc";
+        int rc = score && kept && built ? TSAR_OK : TSAR_ERR_NOMEM;
+        auto step = [&](const char* name, int status) { if (rc == TSAR_OK) { rc = status; what = name; } };
+        if (rc == TSAR_OK) {
+            step("tsar_pm_rescore", tsar_pm_rescore(ctx));
+            if (rc == TSAR_OK) step("tsar_get_plane", tsar_get_plane(ctx, nullptr, score, nullptr, nullptr, TSAR_MEM_DEVICE));
+            if (rc == TSAR_OK) step("tsar_device_write", tsar_device_write(wk.device, kept, lv.own_depth.data(), np * sizeof(float)));
+            if (rc == TSAR_OK) step("tsar_geom_check", tsar_geom_check(ctx, kept, &o.build_check, nullptr, kept, TSAR_MEM_DEVICE));
+            if (rc == TSAR_OK) step("tsar_build_plane_prior", tsar_build_plane_prior(ctx, kept, score, TSAR_MEM_DEVICE, &o.build, built, built + np, nullptr));
+            if (rc == TSAR_OK) step("tsar_set_plane_prior", tsar_set_plane_prior(ctx, built, built + np, TSAR_MEM_DEVICE, &o.prior));
+            if (rc == TSAR_OK) step("tsar_pm_rescore", tsar_pm_rescore(ctx));
+        }
+        if (score) tsar_device_free(wk.device, score);
+        if (kept) tsar_device_free(wk.device, kept);
+        if (built) tsar_device_free(wk.device, built);
+        if (rc != TSAR_OK) return fail(what);
+    }
     if (o.geom_cross_view) {
         // the sources' maps rendered into this view, kept where K of them agree, and offered to the matcher; the rendered map stays on the
         // device.  The merge rescores first: at L = 0 it stands in for tsar_pm_rescore, at L >= 1 the chain is carried down from its planes
@@ -997,7 +1057,7 @@ static int run_geom_view(const Options& o, Worker& wk, const LaterPhase& ph, int
         if (rc != TSAR_OK) return fail(what);
     }
     if (L == 0) {
-        if (!o.geom_cross_view && tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
+        if (!o.geom_cross_view && !o.geom_build /* (which ends with the rescore) */ && tsar_pm_rescore(ctx) != TSAR_OK) return fail("tsar_pm_rescore");
         if (tsar_pm_iterate(ctx, o.geom_iterations) != TSAR_OK) return fail("tsar_pm_iterate");
     } else {
         if (descend(wk, ref, L, {{tsar_geom_pyramid, "tsar_geom_pyramid"}, {tsar_pyramid_planes, "tsar_pyramid_planes"}})) return -1;
@@ -1288,12 +1348,22 @@ static bool options_valid(const Options& o) {
         fprintf(stderr, "--geom_cross_view_depth_diff must be finite and > 0\n");
         return false;
     }
+    if ((o.geom_build || o.geom_build_levels_set) && !o.geom) {
+        fprintf(stderr, "--geom_build_prior and --geom_build_prior_levels work with --geom_consistency only\n");
+        return false;
+    }
+    if (o.geom_build_levels_set && !o.geom_build) { fprintf(stderr, "--geom_build_prior_levels needs --geom_build_prior\n"); return false; }
+    if (o.geom_build && o.geom_prior) { fprintf(stderr, "--geom_build_prior and --geom_plane_prior=STEM are mutually exclusive\n"); return false; }
+    if (o.geom_build && (!tsar_build_plane_prior || !tsar_default_plane_prior_build_params || !tsar_get_plane)) {
+        fprintf(stderr, "--geom_build_prior: this libtsar_hip.so has no tsar_build_plane_prior\n");
+        return false;
+    }
     if ((o.geom_prior || o.geom_prior_option_set) && !o.geom) {
         fprintf(stderr, "--geom_plane_prior and its settings work with --geom_consistency only\n");
         return false;
     }
-    if (o.geom_prior_option_set && !o.geom_prior) {
-        fprintf(stderr, "--geom_prior_weight_depth / --geom_prior_weight_normal / --geom_prior_depth_clip / --geom_prior_angle_clip need --geom_plane_prior=STEM\n");
+    if (o.geom_prior_option_set && !o.geom_prior && !o.geom_build) {
+        fprintf(stderr, "--geom_prior_weight_depth / --geom_prior_weight_normal / --geom_prior_depth_clip / --geom_prior_angle_clip need --geom_plane_prior=STEM or --geom_build_prior\n");
         return false;
     }
     if (o.geom_prior) {
@@ -1303,6 +1373,8 @@ static bool options_valid(const Options& o) {
             return false;
         }
         if (st == "TSAR" || st == "TSAR_geom") { fprintf(stderr, "--geom_plane_prior=STEM: TSAR and TSAR_geom name a phase's own outputs\n"); return false; }
+    }
+    if (o.geom_prior || o.geom_build) {
         const tsar_plane_prior_params& q = o.prior;
         if (!(q.weight_depth >= 0.f) || !(q.weight_depth < INFINITY) || !(q.weight_normal >= 0.f) || !(q.weight_normal < INFINITY) || !(q.depth_clip > 0.f) ||
             !(q.depth_clip < INFINITY) || !(o.geom_prior_angle > 0.0) || !(o.geom_prior_angle <= 180.0) || !(q.normal_clip > 0.f) || !(q.normal_clip <= 2.f)) {
@@ -1334,6 +1406,12 @@ int main(int argc, char** argv) {
     if (pr != 0) return pr < 0 ? 1 : 0;
     o.prior.normal_clip = (float)(1.0 - cos(o.geom_prior_angle * (M_PI / 180.0)));   // 1 - cos(angle), rounded once from float64
     if (!options_valid(o)) return 1;
+    if (o.geom_build) {                                  // (the entries are there: options_valid looked)
+        tsar_default_plane_prior_build_params(&o.build);
+        tsar_default_geom_check_params(&o.build_check);
+        if (o.geom_build_cell) o.build.cell = o.geom_build_cell;
+        if (o.geom_build_levels_set) o.build.max_levels = o.geom_build_levels;
+    }
     if (o.mslp_folder.back() != '/') o.mslp_folder += '/';
     if (o.images_folder.back() != '/') o.images_folder += '/';
     std::map<int, std::vector<int>> pairs;
