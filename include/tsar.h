@@ -41,6 +41,7 @@
  *   copy-out of norm4 (main.cpp:1785-1795)               tsar_get_result / tsar_get_plane
  *   gSLICr core_engine::Process_Frame + Get_Seg_Res      tsar_slic
  *   Fusion.exe (binary only; flags x/1.sh:20-30)         tsar_fuse
+ *   (none: the reference ships no evaluation)            tsar_cloud_distance
  *
  * Conventions
  *   - every function returns an int status (TSAR_OK = 0, negative = error) and never exits the
@@ -554,6 +555,49 @@ int tsar_fuse(int device, int n_views, int w, int h, const tsar_camera* cams, co
               const float* const* normal_world, const float* const* gray, int mem, const int32_t* src_off,
               const int32_t* src_idx, const tsar_fusion_params* params, float* points_out, int64_t cap,
               int64_t* n_points_out);
+
+/* ---- cloud-to-cloud distances (what an accuracy / completeness evaluation of a fused cloud against a scan is made of) ----------- */
+/* For every query point the squared distance to its nearest target point within a radius R, and that target's index.  Records are
+ * `stride` float32 each (>= 3), x y z first, so tsar_fuse's 9-float records go in as they are.  `mem` names where query, target,
+ * dist2_out and index_out lie; tol, within_out, n_valid_query_out and pairs_out are host memory.  query and target may be one cloud.
+ * The arithmetic, the same in both arithmetic modes: float32, every operation one IEEE-754 operation rounded to nearest, no fused
+ * multiply-add.
+ *   candidate: a record whose x, y and z are all finite
+ *   for a candidate query i and a candidate target j:  dx = qx - tx, dy = qy - ty, dz = qz - tz;  d2(i, j) = (dx * dx + dy * dy) + dz * dz
+ *   R2 = fl(R * R), one float32 product
+ *   dist2[i] = the minimum of d2(i, j) over all candidate j, if that minimum is <= R2;  index[i] = the smallest j that attains it
+ *   otherwise dist2[i] = +inf and index[i] = -1: also for a query that is no candidate, and when no target is a candidate (n_target == 0)
+ *   within[k] = the number of i with dist2[i] <= fl(tol[k] * tol[k])
+ *   n_valid_query = the number of candidate queries
+ *   pairs = the number of (i, j) the call evaluated (below)
+ * This is the brute-force definition; a minimum and a count do not depend on an order of arrival, so the outputs are the same bits in
+ * every run.  How the pairs are found changes none of them: a uniform grid over the candidate targets, with
+ *   origin o = the per-axis minimum over the candidate targets (exact in any order);  cell edge e = (double)R * (1 + 2^-10);
+ *   cell coordinate of a point, per axis: floor(((double)p - (double)o) / e), in float64, the quotient correctly rounded.
+ * Two points whose float32 d2 is <= R2 are less than R (1 + 2^-10) apart on every axis (d2's rounding errors are a few 2^-24 of it), so
+ * their cell coordinates differ by at most 1: the 27 cells around the query's hold every such target, and the minimum over them is the
+ * minimum over all whenever that is <= R2.  pairs counts, over the candidate queries, the candidate targets in those 27 cells.
+ * TSAR_ERR_INVALID, with the reason in tsar_last_error: p NULL; mem unknown; a stride below 3; a count negative or above 2^31 - 1; max_dist
+ * not finite, or fl(R * R) not finite or not > 0; a tolerance not finite, not > 0 or above max_dist; a grid of 2^20 cells or more on an
+ * axis (max_dist is too small for the targets' extent); more than max_pairs pairs — then *pairs_out is still filled and nothing else is
+ * written: an R as large as the scene is a brute-force n_query x n_target launch, which is refused, not run.
+ * tsar_cloud_distance_ctx needs no views and no state, runs on the context's stream and changes nothing in the context; its temporaries
+ * (sort buffers of both clouds) are pieces of the call's frame that never grow the context's scratch arena: what the arena does not hold
+ * is allocated for the call and freed on exit.  tsar_cloud_distance is the context-free form, like tsar_fuse.
+ * Timed as "cloud_bounds", "cloud_keys", "cloud_sort" (both sorts), "cloud_gather", "cloud_pairs" and "cloud_distance" (the search). */
+typedef struct tsar_cloud_distance_params {
+    float max_dist;       /* R: the search radius; finite, fl(R * R) finite and > 0.  No default (0): the caller's scale */
+    int64_t max_pairs;    /* a call that would evaluate more (query, target) pairs than this is refused; default 1 << 40 */
+} tsar_cloud_distance_params;
+void tsar_default_cloud_distance_params(tsar_cloud_distance_params* p);
+int tsar_cloud_distance_ctx(tsar_ctx* ctx, const float* query, int64_t n_query, int query_stride, const float* target, int64_t n_target,
+                            int target_stride, const tsar_cloud_distance_params* p, int n_tol, const float* tol /* host, may be NULL with n_tol 0 */,
+                            float* dist2_out /* [n_query] or NULL */, int32_t* index_out /* [n_query] or NULL */,
+                            int64_t* within_out /* host [n_tol] or NULL */, int64_t* n_valid_query_out, int64_t* pairs_out /* host, may be NULL */,
+                            int mem);
+int tsar_cloud_distance(int device, const float* query, int64_t n_query, int query_stride, const float* target, int64_t n_target,
+                        int target_stride, const tsar_cloud_distance_params* p, int n_tol, const float* tol, float* dist2_out, int32_t* index_out,
+                        int64_t* within_out, int64_t* n_valid_query_out, int64_t* pairs_out, int mem);
 
 /* ---- page-locked host buffers --------------------------------------------------------------- */
 /* NULL on failure.  Replaces the reference's cudaMallocManaged host-visible planes (managed.h:7-15) on the host side of the

@@ -70,6 +70,10 @@ class PlanePriorBuildParams(C.Structure):
     _fields_ = [("cell", C.c_int32), ("max_levels", C.c_int32)]
 
 
+class CloudDistanceParams(C.Structure):
+    _fields_ = [("max_dist", C.c_float), ("max_pairs", C.c_int64)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -93,6 +97,7 @@ ABI_SYMBOLS = [
     "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
+    "tsar_default_cloud_distance_params", "tsar_cloud_distance_ctx", "tsar_cloud_distance",
     "tsar_host_alloc", "tsar_host_free", "tsar_device_alloc", "tsar_device_free", "tsar_device_write", "tsar_peer_copy", "tsar_enable_kernel_timing", "tsar_reset_kernel_timing", "tsar_get_kernel_timing",
     "tsar_selftest_divide", "tsar_selftest_divide_random", "tsar_selftest_sqrt", "tsar_selftest_sweep_census", "tsar_selftest_prune_census", "tsar_selftest_sweep_repeat", "tsar_selftest_slic_stage",
 ]
@@ -189,6 +194,12 @@ def load_library(path: str = LIB_PATH):
     L.tsar_fuse.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Camera), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
                             C.c_void_p, C.c_void_p, C.POINTER(FusionParams), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.tsar_fuse_ctx.argtypes = [C.c_void_p] + list(L.tsar_fuse.argtypes[1:])
+    if hasattr(L, "tsar_cloud_distance_ctx"):         # (a library built before the operator, loaded through TSAR_LIB for an A/B run)
+        L.tsar_default_cloud_distance_params.restype = None
+        L.tsar_default_cloud_distance_params.argtypes = [C.POINTER(CloudDistanceParams)]
+        L.tsar_cloud_distance.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(CloudDistanceParams), C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+        L.tsar_cloud_distance_ctx.argtypes = [C.c_void_p] + list(L.tsar_cloud_distance.argtypes[1:])
     L.tsar_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.tsar_synchronize.argtypes = [C.c_void_p]
     L.tsar_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -994,6 +1005,102 @@ def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = N
     pts = out[: min(cnt.value, cap)]
     pts = pts.clone() if mem == MEM_DEVICE else pts.copy()
     return (pts, int(cnt.value)) if return_count else pts
+
+
+def _cloud(a, name):
+    """an [n, k >= 3] float32 cloud as the library takes it: a contiguous numpy array, or a contiguous torch device tensor"""
+    if _is_torch(a) and a.is_cuda:
+        assert str(a.dtype) == "torch.float32" and a.dim() == 2 and a.shape[1] >= 3 and a.is_contiguous(), name + " must be a contiguous [n, k >= 3] float32 tensor"
+        return a, True
+    a = np.ascontiguousarray(a.numpy() if _is_torch(a) else a, np.float32)
+    assert a.ndim == 2 and a.shape[1] >= 3, name + " must be [n, k >= 3]"
+    return a, False
+
+
+def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "index"), max_pairs=None, matcher=None, device=0):
+    """For every point of `query` the squared float32 distance to its nearest point of `target` within max_dist, and that point's index
+    (tsar_cloud_distance_ctx; include/tsar.h states the arithmetic).  query, target: [n, k >= 3] float32, x y z first, both numpy arrays
+    or both torch device tensors (a fused cloud as api.fuse returns it goes in as it is: the stride is k).  Records with a non-finite
+    coordinate take no part.  tolerances: a sequence of distances, each in (0, max_dist].  max_pairs: the call is refused (TsarError,
+    TSAR_ERR_INVALID) when it would evaluate more (query, target) pairs; None = the library's default.  matcher: run on that context
+    (its device and stream; nothing in it changes); without one a context is created on `device` for the call.
+    Returns a dict: "dist2" ([n_query] float32, +inf where nothing lies within max_dist) and / or "index" ([n_query] int32, -1 there), as
+    `want` names them (numpy arrays, or torch tensors on the inputs' device); "within" (int64 numpy array: per tolerance the number of
+    queries with dist2 <= fl(tol * tol)); "n_valid_query" (queries with finite coordinates); "pairs" (pairs evaluated)."""
+    L = load_library()
+    q, q_dev = _cloud(query, "query")
+    t, t_dev = _cloud(target, "target")
+    assert q_dev == t_dev, "query and target must live in the same memory space"
+    if q_dev:
+        assert q.device == t.device, "query and target must live on one device"
+    p = CloudDistanceParams()
+    L.tsar_default_cloud_distance_params(C.byref(p))
+    p.max_dist = float(max_dist)
+    if max_pairs is not None:
+        p.max_pairs = int(max_pairs)
+    tol = np.ascontiguousarray([] if tolerances is None else tolerances, np.float32).reshape(-1)
+    within = np.zeros(len(tol), np.int64)
+    nq = int(q.shape[0])
+    res = {}
+    for k, dt in (("dist2", "float32"), ("index", "int32")):
+        if k in want:
+            if q_dev:
+                import torch
+                res[k] = torch.empty((nq,), dtype=getattr(torch, dt), device=q.device)
+            else:
+                res[k] = np.empty(nq, dt)
+    n_valid, pairs = C.c_int64(0), C.c_int64(-1)
+    own = matcher is None
+    m = Matcher(q.device.index if q_dev and q.device.index is not None else device) if own else matcher
+    try:
+        rc = L.tsar_cloud_distance_ctx(m._ctx, _ptr(q)[0] if nq else None, nq, int(q.shape[1]), _ptr(t)[0] if t.shape[0] else None, int(t.shape[0]), int(t.shape[1]),
+                                       C.byref(p), len(tol), tol.ctypes.data_as(C.c_void_p), _ptr(res.get("dist2"))[0], _ptr(res.get("index"))[0],
+                                       within.ctypes.data_as(C.c_void_p), C.byref(n_valid), C.byref(pairs), MEM_DEVICE if q_dev else MEM_HOST)
+        if rc != TSAR_OK:
+            err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
+            err.pairs = int(pairs.value) if pairs.value >= 0 else None      # filled when max_pairs refused the call
+            raise err
+    finally:
+        if own:
+            m.close()
+    res["within"] = within
+    res["n_valid_query"] = int(n_valid.value)
+    res["pairs"] = int(pairs.value)
+    return res
+
+
+def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0):
+    """Accuracy and completeness of the cloud `recon` against the cloud `gt` at each of `tolerances`: the point-wise precision / recall /
+    F-score.  Two cloud_distance calls with max_dist = max(tolerances):
+      accuracy[k]     = the share of recon's candidate points (finite coordinates) with a gt point within tolerances[k];
+      completeness[k] = the share of gt's candidate points with a recon point within tolerances[k];
+      f1[k]           = their harmonic mean (0 where both are 0).
+    This is NOT the evaluation program of a benchmark: ETH3D's averages over voxels of the scan so that dense areas do not dominate, DTU's
+    applies observation masks, and both align and crop first.  Nothing is down-sampled, cropped, masked or registered here: every point
+    counts once, and the clouds are compared where they lie.
+    Returns {"tolerances", "accuracy", "completeness", "f1"} as float64 numpy arrays (ratios formed on the host from the integer
+    counts; 0 where a denominator is 0), {"n_accurate", "n_complete"} as int64 arrays, and the integers "n_recon_valid", "n_gt_valid",
+    "pairs_accuracy", "pairs_completeness"."""
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    if tol.size == 0:
+        raise ValueError("evaluate_cloud needs at least one tolerance")
+    r = float(tol.max())
+    own = matcher is None
+    if own:                                # one context for both directions
+        matcher = Matcher(recon.device.index if _is_torch(recon) and recon.is_cuda and recon.device.index is not None else device)
+    try:
+        a = cloud_distance(recon, gt, r, tol, want=(), matcher=matcher)
+        c = cloud_distance(gt, recon, r, tol, want=(), matcher=matcher)
+    finally:
+        if own:
+            matcher.close()
+    na, nc = a["within"].astype(np.int64), c["within"].astype(np.int64)
+    acc = na / np.float64(a["n_valid_query"]) if a["n_valid_query"] else np.zeros(tol.size, np.float64)
+    com = nc / np.float64(c["n_valid_query"]) if c["n_valid_query"] else np.zeros(tol.size, np.float64)
+    s = acc + com
+    f1 = np.where(s > 0, 2.0 * acc * com / np.where(s > 0, s, 1.0), 0.0)
+    return {"tolerances": tol.copy(), "accuracy": acc, "completeness": com, "f1": f1, "n_accurate": na, "n_complete": nc,
+            "n_recon_valid": a["n_valid_query"], "n_gt_valid": c["n_valid_query"], "pairs_accuracy": a["pairs"], "pairs_completeness": c["pairs"]}
 
 
 def pinned_empty(shape, dtype=np.float32):

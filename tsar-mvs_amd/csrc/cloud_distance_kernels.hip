@@ -1,0 +1,323 @@
+// cloud_distance_kernels.hip — truncated nearest-neighbour distances between two point clouds (include/tsar.h tsar_cloud_distance).
+// The result is the brute-force definition written there (a minimum of float32 d2 over every candidate target); the uniform grid below
+// only decides which pairs are looked at, and every pair with d2 <= fl(R * R) lies in the 27 cells around the query's
+// (include/tsar.h says why), so no bit of the result depends on it.
+//
+// Per call:  bounds of the candidate targets (integer atomics on order-preserving float codes: a minimum, exact in any order)
+//            -> 60-bit z-major cell keys of the targets, radix-sorted with their indices (stable: equal keys keep index order)
+//            -> the targets copied into key order as 16-byte records (x, y, z, index)
+//            -> 63-bit cell keys of the queries, radix-sorted, so that a wave's lanes walk the same cells
+//            -> the pair count: per query the sizes of its 9 key ranges (cells x-1 .. x+1 of one (y, z) are one contiguous range)
+//            -> the query kernel: one lane per query in key order, a running minimum of the 64-bit (d2 bits, index) code.
+// No floating-point atomics and no order of arrival anywhere: the outputs are the same bits in every run.
+#include <float.h>
+#include <math.h>
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "tsar_dev.h"
+
+#define CD_BLOCK 256
+#define CD_T_NONE (1ull << 60)            // key of a target that is no candidate: above every cell key (3 x 20 bits)
+#define CD_Q_NONE (1ull << 63)            // key of a query that is no candidate: above every query key (3 x 21 bits)
+#define CD_MAX_EXTENT (1 << 20)           // cells per axis: refused from here on
+
+struct CdGrid {
+    double ox, oy, oz;                    // per-axis minimum of the candidate targets
+    double e;                             // cell edge (double)R * (1 + 2^-10)
+    int ex, ey, ez;                       // cells per axis: the targets' cells are 0 .. ex - 1
+};
+struct __align__(16) CdRec { float x, y, z; uint32_t j; };
+
+__device__ __forceinline__ bool cd_candidate(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }   // NaN fails
+// unsigned codes in the order of the floats they stand for (-0.0 below +0.0: the same double either way)
+__device__ __forceinline__ uint32_t cd_code(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+static inline float cd_decode(uint32_t c) { const uint32_t u = (c & 0x80000000u) ? (c & 0x7fffffffu) : ~c; float f; memcpy(&f, &u, 4); return f; }
+// the cell coordinate of include/tsar.h, as a double: floor(((double)p - (double)o) / e), the quotient correctly rounded
+__device__ __forceinline__ double cd_cell(float p, double o, double e) { return floor(((double)p - o) / e); }
+static inline double cd_cell_host(float p, double o, double e) { return floor(((double)p - o) / e); }
+
+__device__ __forceinline__ uint32_t cd_wave_min(uint32_t v) { for (int s = 32; s > 0; s >>= 1) { const uint32_t o = __shfl_xor(v, s, 64); v = o < v ? o : v; } return v; }
+__device__ __forceinline__ uint32_t cd_wave_max(uint32_t v) { for (int s = 32; s > 0; s >>= 1) { const uint32_t o = __shfl_xor(v, s, 64); v = o > v ? o : v; } return v; }
+__device__ __forceinline__ unsigned long long cd_wave_sum(unsigned long long v) { for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64); return v; }
+
+// bounds[0..2] = codes of the per-axis minima, bounds[3..5] = of the maxima, *count = the candidates
+__global__ __launch_bounds__(CD_BLOCK) void cd_bounds_kernel(const float* __restrict__ pts, long long n, int stride, uint32_t* __restrict__ bounds,
+                                                             unsigned long long* __restrict__ count) {
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    unsigned long long cnt = 0;
+    for (long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * CD_BLOCK) {
+        const float* p = pts + (size_t)i * stride;
+        const float x = p[0], y = p[1], z = p[2];
+        if (!cd_candidate(x, y, z)) continue;
+        const uint32_t c[3] = {cd_code(x), cd_code(y), cd_code(z)};
+        for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
+        cnt++;
+    }
+    for (int a = 0; a < 3; a++) { lo[a] = cd_wave_min(lo[a]); hi[a] = cd_wave_max(hi[a]); }
+    cnt = cd_wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) {
+        for (int a = 0; a < 3; a++) { atomicMin(&bounds[a], lo[a]); atomicMax(&bounds[3 + a], hi[a]); }
+        atomicAdd(count, cnt);
+    }
+}
+
+__device__ __forceinline__ int cd_clampi(double c, int lo, int hi) { return c < (double)lo ? lo : (c > (double)hi ? hi : (int)c); }
+
+__global__ __launch_bounds__(CD_BLOCK) void cd_target_keys_kernel(const float* __restrict__ pts, long long n, int stride, CdGrid g,
+                                                                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float* p = pts + (size_t)i * stride;
+    const float x = p[0], y = p[1], z = p[2];
+    unsigned long long key = CD_T_NONE;
+    if (cd_candidate(x, y, z)) {
+        // (the origin is the minimum and the extent comes from the maximum through the same monotone function: the clamps never bind)
+        const unsigned long long cx = (unsigned)cd_clampi(cd_cell(x, g.ox, g.e), 0, g.ex - 1), cy = (unsigned)cd_clampi(cd_cell(y, g.oy, g.e), 0, g.ey - 1),
+                                 cz = (unsigned)cd_clampi(cd_cell(z, g.oz, g.e), 0, g.ez - 1);
+        key = (cz << 40) | (cy << 20) | cx;
+    }
+    keys[i] = key;
+    vals[i] = (uint32_t)i;
+}
+
+// a query's cell may lie outside the targets' grid: kept exactly from -2 (no cell of the grid is its neighbour) to extent + 1, plus 2
+__global__ __launch_bounds__(CD_BLOCK) void cd_query_keys_kernel(const float* __restrict__ pts, long long n, int stride, CdGrid g,
+                                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                                 unsigned long long* __restrict__ n_valid) {
+    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    bool cand = false;
+    if (i < n) {
+        const float* p = pts + (size_t)i * stride;
+        const float x = p[0], y = p[1], z = p[2];
+        unsigned long long key = CD_Q_NONE;
+        cand = cd_candidate(x, y, z);
+        if (cand) {
+            const unsigned long long cx = (unsigned)(cd_clampi(cd_cell(x, g.ox, g.e), -2, g.ex + 1) + 2), cy = (unsigned)(cd_clampi(cd_cell(y, g.oy, g.e), -2, g.ey + 1) + 2),
+                                     cz = (unsigned)(cd_clampi(cd_cell(z, g.oz, g.e), -2, g.ez + 1) + 2);
+            key = (cz << 42) | (cy << 21) | cx;
+        }
+        keys[i] = key;
+        vals[i] = (uint32_t)i;
+    }
+    const unsigned long long m = __ballot(cand);
+    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(n_valid, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(CD_BLOCK) void cd_gather_kernel(const float* __restrict__ pts, int stride, const uint32_t* __restrict__ vals, uint32_t n_cand,
+                                                             CdRec* __restrict__ rec) {
+    const uint32_t k = blockIdx.x * CD_BLOCK + threadIdx.x;
+    if (k >= n_cand) return;
+    const uint32_t j = vals[k];
+    const float* p = pts + (size_t)j * stride;
+    CdRec r;
+    r.x = p[0]; r.y = p[1]; r.z = p[2]; r.j = j;
+    rec[k] = r;
+}
+
+// [b, e) = the sorted keys in [klo, khi]: a binary search for the start, then a gallop for the end (a range is short next to n)
+__device__ __forceinline__ void cd_range(const unsigned long long* __restrict__ keys, uint32_t n, unsigned long long klo, unsigned long long khi, uint32_t& b, uint32_t& e) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (keys[mid] < klo) lo = mid + 1; else hi = mid; }
+    b = lo;
+    uint32_t l = lo, h = lo, step = 1;
+    while (h < n && keys[h] <= khi) { l = h + 1; h = (n - h > step) ? h + step : n; step <<= 1; }
+    while (l < h) { const uint32_t mid = l + ((h - l) >> 1); if (keys[mid] <= khi) l = mid + 1; else h = mid; }
+    e = l;
+}
+
+// the query's r-th range, r = 3 (dz + 1) + (dy + 1): false when that row of cells lies outside the grid
+__device__ __forceinline__ bool cd_query_range(unsigned long long qkey, int r, const CdGrid& g, const unsigned long long* __restrict__ tkeys, uint32_t n_cand,
+                                               uint32_t& b, uint32_t& e) {
+    const int cx = (int)(qkey & 0x1fffffu) - 2, cy = (int)((qkey >> 21) & 0x1fffffu) - 2, cz = (int)((qkey >> 42) & 0x1fffffu) - 2;
+    const int ty = cy + (r % 3) - 1, tz = cz + (r / 3) - 1;
+    const int xlo = cx - 1 < 0 ? 0 : cx - 1, xhi = cx + 1 > g.ex - 1 ? g.ex - 1 : cx + 1;
+    if (ty < 0 || ty >= g.ey || tz < 0 || tz >= g.ez || xlo > xhi) return false;
+    const unsigned long long row = ((unsigned long long)tz << 40) | ((unsigned long long)ty << 20);
+    cd_range(tkeys, n_cand, row | (unsigned)xlo, row | (unsigned)xhi, b, e);
+    return true;
+}
+
+// *pairs += the number of targets in the 27 cells around every candidate query: what the query kernel would evaluate
+__global__ __launch_bounds__(CD_BLOCK) void cd_pairs_kernel(const unsigned long long* __restrict__ qkeys, long long n_query, CdGrid g,
+                                                            const unsigned long long* __restrict__ tkeys, uint32_t n_cand, unsigned long long* __restrict__ pairs) {
+    const long long k = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    unsigned long long cnt = 0;
+    if (k < n_query) {
+        const unsigned long long qkey = qkeys[k];
+        if (qkey != CD_Q_NONE)
+            for (int r = 0; r < 9; r++) {
+                uint32_t b, e;
+                if (cd_query_range(qkey, r, g, tkeys, n_cand, b, e)) cnt += e - b;
+            }
+    }
+    cnt = cd_wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(pairs, cnt);
+}
+
+// one lane per query, in key order: the minimum over its 27 cells of the 64-bit code (d2 bits, index) — d2 >= +0, so the codes order
+// like the distances and, among equal distances, like the indices
+__global__ __launch_bounds__(CD_BLOCK) void cd_query_kernel(const float* __restrict__ query, int stride, const unsigned long long* __restrict__ qkeys,
+                                                            const uint32_t* __restrict__ qvals, long long n_query, CdGrid g,
+                                                            const unsigned long long* __restrict__ tkeys, const CdRec* __restrict__ rec, uint32_t n_cand, float r2,
+                                                            int n_tol, const float* __restrict__ tol2, float* __restrict__ dist2_out, int32_t* __restrict__ index_out,
+                                                            unsigned long long* __restrict__ within) {
+    const long long k = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    float d2min = INFINITY;
+    if (k < n_query) {
+        const unsigned long long qkey = qkeys[k];
+        const uint32_t i = qvals[k];
+        unsigned long long best = ~0ull;
+        if (qkey != CD_Q_NONE) {
+            const float* p = query + (size_t)i * stride;
+            const float qx = p[0], qy = p[1], qz = p[2];
+            for (int r = 0; r < 9; r++) {
+                uint32_t b, e;
+                if (!cd_query_range(qkey, r, g, tkeys, n_cand, b, e)) continue;
+#pragma unroll 4
+                for (uint32_t t = b; t < e; t++) {   // (unrolled: four record loads in flight per lane; the launch waits on this load, profiles/cloud_distance)
+                    const CdRec c = rec[t];
+                    const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;          // no fused operation: the library is built with -ffp-contract=off
+                    const unsigned long long code = ((unsigned long long)__float_as_uint(d2) << 32) | c.j;
+                    best = code < best ? code : best;
+                }
+            }
+        }
+        const float d2 = __uint_as_float((uint32_t)(best >> 32));             // (the initial code reads as a NaN: fails the comparison)
+        const bool hit = d2 <= r2;
+        d2min = hit ? d2 : INFINITY;
+        if (dist2_out) dist2_out[i] = d2min;
+        if (index_out) index_out[i] = hit ? (int32_t)(uint32_t)best : -1;
+    }
+    for (int t = 0; t < n_tol; t++) {
+        const unsigned long long m = __ballot(d2min <= tol2[t]);
+        if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(&within[t], (unsigned long long)__popcll(m));
+    }
+}
+
+// no candidate target: every query gets +inf and -1; the candidate queries are still counted
+__global__ __launch_bounds__(CD_BLOCK) void cd_fill_kernel(const float* __restrict__ query, long long n_query, int stride, float* __restrict__ dist2_out,
+                                                           int32_t* __restrict__ index_out, unsigned long long* __restrict__ n_valid) {
+    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    bool cand = false;
+    if (i < n_query) {
+        const float* p = query + (size_t)i * stride;
+        cand = cd_candidate(p[0], p[1], p[2]);
+        if (dist2_out) dist2_out[i] = INFINITY;
+        if (index_out) index_out[i] = -1;
+    }
+    const unsigned long long m = __ballot(cand);
+    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(n_valid, (unsigned long long)__popcll(m));
+}
+
+static inline unsigned cd_blocks(long long n) { return (unsigned)((n + CD_BLOCK - 1) / CD_BLOCK); }
+
+// keys_in / vals_in sorted into keys_out / vals_out (bits [0, end_bit)); the sort's scratch is a piece of the frame
+template <typename F>
+static bool cd_sort(F& f, const char* name, unsigned long long* keys_in, unsigned long long* keys_out, uint32_t* vals_in, uint32_t* vals_out, long long n, int end_bit) {
+    size_t bytes = 0;
+    if (!f.ok() || !f.hip(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, end_bit, f.ctx->stream), "rocprim::radix_sort_pairs sizing")) return false;
+    void* tmp = f.template tmp<char>(bytes);
+    if (!f.ok()) return false;
+    ScopedKernelTimer tm(f.ctx, name);
+    return f.hip(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, end_bit, f.ctx->stream), "rocprim::radix_sort_pairs");
+}
+
+// query / target and the two per-query outputs are device pointers (the frame's views of the caller's buffers); tol2, within_out,
+// n_valid_out and pairs_out are the caller's host arrays.  The arguments have been checked (tsar_api.hip); 0 <= n < 2^31 on both sides.
+int run_cloud_distance(CallFrame& f, const float* query, long long n_query, int query_stride, const float* target, long long n_target, int target_stride, float r2,
+                       double edge, long long max_pairs, int n_tol, const float* tol2, float* dist2_out, int32_t* index_out, int64_t* within_out,
+                       int64_t* n_valid_out, int64_t* pairs_out) {
+    tsar_ctx* ctx = f.ctx;
+    hipStream_t st = ctx->stream;
+    // counters: [0..5] the bounds' codes, then (8-byte aligned) the candidate targets, the candidate queries, the pairs, within[n_tol]
+    struct Head { uint32_t bounds[6]; uint32_t pad[2]; unsigned long long n_cand, n_valid, pairs; } head;
+    for (int a = 0; a < 3; a++) { head.bounds[a] = 0xffffffffu; head.bounds[3 + a] = 0u; }
+    head.pad[0] = head.pad[1] = 0;
+    head.n_cand = head.n_valid = head.pairs = 0;
+    char* d_head = f.tmp<char>(sizeof(Head) + 8 * (size_t)(n_tol > 0 ? n_tol : 1));
+    float* d_tol2 = f.tmp<float>(n_tol > 0 ? n_tol : 1);
+    if (!f.ok()) return f.finish();
+    Head* dh = (Head*)d_head;
+    unsigned long long* d_within = (unsigned long long*)(d_head + sizeof(Head));
+    f.copy(d_head, &head, sizeof(Head), hipMemcpyHostToDevice);
+    f.zero(d_within, 8 * (size_t)(n_tol > 0 ? n_tol : 1));
+    if (n_tol > 0) f.copy(d_tol2, tol2, 4 * (size_t)n_tol, hipMemcpyHostToDevice);
+    if (n_target > 0 && f.ok()) {
+        ScopedKernelTimer tm(ctx, "cloud_bounds");
+        const unsigned blocks = cd_blocks(n_target) < 2048u ? cd_blocks(n_target) : 2048u;
+        hipLaunchKernelGGL(cd_bounds_kernel, dim3(blocks), dim3(CD_BLOCK), 0, st, target, n_target, target_stride, dh->bounds, &dh->n_cand);
+    }
+    f.launched();
+    f.copy(&head, d_head, sizeof(Head), hipMemcpyDeviceToHost);
+    if (!f.sync()) return f.finish();
+    const long long n_cand = (long long)head.n_cand;
+    std::vector<unsigned long long> h_within(n_tol > 0 ? n_tol : 1, 0ull);
+    if (n_cand == 0 || n_query == 0) {               // nothing to search: +inf and -1 throughout
+        if (n_query > 0) {
+            ScopedKernelTimer tm(ctx, "cloud_distance");
+            hipLaunchKernelGGL(cd_fill_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, n_query, query_stride, dist2_out, index_out, &dh->n_valid);
+        }
+        f.launched();
+        f.copy(&head, d_head, sizeof(Head), hipMemcpyDeviceToHost);
+        if (!f.sync()) return f.finish();
+        if (pairs_out) *pairs_out = 0;
+        if (n_valid_out) *n_valid_out = (int64_t)head.n_valid;
+        for (int t = 0; t < n_tol && within_out; t++) within_out[t] = 0;
+        return f.finish();
+    }
+    CdGrid g;
+    g.ox = (double)cd_decode(head.bounds[0]); g.oy = (double)cd_decode(head.bounds[1]); g.oz = (double)cd_decode(head.bounds[2]);
+    g.e = edge;
+    const double ext[3] = {cd_cell_host(cd_decode(head.bounds[3]), g.ox, edge) + 1.0, cd_cell_host(cd_decode(head.bounds[4]), g.oy, edge) + 1.0,
+                           cd_cell_host(cd_decode(head.bounds[5]), g.oz, edge) + 1.0};
+    for (int a = 0; a < 3; a++)
+        if (!(ext[a] >= 1.0 && ext[a] < (double)CD_MAX_EXTENT))
+            return f.fail(TSAR_ERR_INVALID, "tsar_cloud_distance: the targets span 2^20 cells or more of edge max_dist on an axis: max_dist is too small for this cloud's extent");
+    g.ex = (int)ext[0]; g.ey = (int)ext[1]; g.ez = (int)ext[2];
+
+    unsigned long long *tk0 = f.tmp<unsigned long long>((size_t)n_target), *tk1 = f.tmp<unsigned long long>((size_t)n_target);
+    uint32_t *tv0 = f.tmp<uint32_t>((size_t)n_target), *tv1 = f.tmp<uint32_t>((size_t)n_target);
+    CdRec* rec = f.tmp<CdRec>((size_t)n_cand);
+    unsigned long long *qk0 = f.tmp<unsigned long long>((size_t)n_query), *qk1 = f.tmp<unsigned long long>((size_t)n_query);
+    uint32_t *qv0 = f.tmp<uint32_t>((size_t)n_query), *qv1 = f.tmp<uint32_t>((size_t)n_query);
+    if (!f.ok()) return f.finish();
+    {
+        ScopedKernelTimer tm(ctx, "cloud_keys");
+        hipLaunchKernelGGL(cd_target_keys_kernel, dim3(cd_blocks(n_target)), dim3(CD_BLOCK), 0, st, target, n_target, target_stride, g, tk0, tv0);
+        hipLaunchKernelGGL(cd_query_keys_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, n_query, query_stride, g, qk0, qv0, &dh->n_valid);
+    }
+    f.launched();
+    if (!cd_sort(f, "cloud_sort", tk0, tk1, tv0, tv1, n_target, 61)) return f.finish();
+    if (!cd_sort(f, "cloud_sort", qk0, qk1, qv0, qv1, n_query, 64)) return f.finish();
+    {
+        ScopedKernelTimer tm(ctx, "cloud_gather");
+        hipLaunchKernelGGL(cd_gather_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, target, target_stride, tv1, (uint32_t)n_cand, rec);
+    }
+    f.launched();
+    {
+        ScopedKernelTimer tm(ctx, "cloud_pairs");
+        hipLaunchKernelGGL(cd_pairs_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, qk1, n_query, g, tk1, (uint32_t)n_cand, &dh->pairs);
+    }
+    f.launched();
+    f.copy(&head, d_head, sizeof(Head), hipMemcpyDeviceToHost);
+    if (!f.sync()) return f.finish();
+    if (pairs_out) *pairs_out = (int64_t)head.pairs;
+    if (head.pairs > (unsigned long long)max_pairs) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "tsar_cloud_distance: the call would evaluate %llu pairs, more than max_pairs = %lld: lower max_dist or raise max_pairs",
+                 head.pairs, max_pairs);
+        return f.fail(TSAR_ERR_INVALID, msg);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "cloud_distance");
+        hipLaunchKernelGGL(cd_query_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, query_stride, qk1, qv1, n_query, g, tk1, rec, (uint32_t)n_cand, r2,
+                           n_tol, d_tol2, dist2_out, index_out, d_within);
+    }
+    f.launched();
+    if (n_tol > 0) f.copy(h_within.data(), d_within, 8 * (size_t)n_tol, hipMemcpyDeviceToHost);
+    if (!f.sync()) return f.finish();
+    if (n_valid_out) *n_valid_out = (int64_t)head.n_valid;
+    for (int t = 0; t < n_tol && within_out; t++) within_out[t] = (int64_t)h_within[t];
+    return f.finish();
+}

@@ -1,4 +1,5 @@
 // tsar_api.hip — the C ABI of include/tsar.h: context, device memory, camera algebra, call order.
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1161,6 +1162,61 @@ extern "C" int tsar_pm_merge_depths(tsar_ctx* ctx, const float* depth, int mem, 
     ctx->state_scored(true);               // every taken cost is the taken plane's score on the sweep window
     if (n_taken_out) *n_taken_out = (int64_t)taken;
     return TSAR_OK;
+}
+
+// ---- cloud-to-cloud distances (cloud_distance_kernels.hip) ----------------------------------------------------------------------------
+extern "C" void tsar_default_cloud_distance_params(tsar_cloud_distance_params* p) {
+    if (!p) return;
+    p->max_dist = 0.0f;                    // no default: the caller's scale
+    p->max_pairs = (int64_t)1 << 40;
+}
+
+// Needs no views and no state, and writes nothing the context owns.  The frame does not grow the arena (tsar_dev.h ScratchScope, grow =
+// false): the sort buffers of two large clouds are no size a matching context should keep; what does not fit is freed on exit.
+extern "C" int tsar_cloud_distance_ctx(tsar_ctx* ctx, const float* query, int64_t n_query, int query_stride, const float* target, int64_t n_target,
+                                       int target_stride, const tsar_cloud_distance_params* p, int n_tol, const float* tol, float* dist2_out, int32_t* index_out,
+                                       int64_t* within_out, int64_t* n_valid_query_out, int64_t* pairs_out, int mem) {
+    CHECK_CTX(ctx);
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: params is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (n_query < 0 || n_target < 0 || n_query > INT32_MAX || n_target > INT32_MAX)
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: n_query and n_target must be in 0..2^31-1");
+    if (query_stride < 3 || target_stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: a stride must be at least 3 floats (x y z first)");
+    if ((n_query > 0 && !query) || (n_target > 0 && !target)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: query or target is NULL");
+    const float R = p->max_dist;
+    const volatile float r2v = R * R;      // fl(R * R), one float32 product
+    const float r2 = r2v;
+    if (!(fabsf(R) <= FLT_MAX) || !(r2 > 0.0f && r2 <= FLT_MAX) || !(R > 0.0f))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: max_dist must be finite and > 0, with max_dist * max_dist finite and > 0 in float32");
+    if (p->max_pairs < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: max_pairs must be >= 0");
+    if (n_tol < 0 || (n_tol > 0 && !tol)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: n_tol < 0, or tol is NULL");
+    std::vector<float> tol2((size_t)n_tol);
+    for (int k = 0; k < n_tol; k++) {
+        if (!(tol[k] > 0.0f && tol[k] <= R)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: every tolerance must be finite, > 0 and <= max_dist");
+        const volatile float t2 = tol[k] * tol[k];
+        tol2[k] = t2;
+    }
+    CallFrame f(ctx, "tsar_cloud_distance", nullptr, /*grow_arena=*/false);
+    const float* q = f.in(query, (size_t)n_query * query_stride, mem);
+    const float* t = (target == query && n_target == n_query && target_stride == query_stride) ? q : f.in(target, (size_t)n_target * target_stride, mem);
+    float* d2 = f.out(dist2_out, (size_t)n_query, mem);
+    int32_t* idx = f.out(index_out, (size_t)n_query, mem);
+    if (!f.ok()) return f.finish();
+    return run_cloud_distance(f, q, n_query, query_stride, t, n_target, target_stride, r2, (double)R * (1.0 + 1.0 / 1024.0), p->max_pairs, n_tol, tol2.data(), d2, idx,
+                              within_out, n_valid_query_out, pairs_out);
+}
+
+// Context-free form (the evaluation tool's two calls per pair of clouds): a context of its own for the duration of the call.
+extern "C" int tsar_cloud_distance(int device, const float* query, int64_t n_query, int query_stride, const float* target, int64_t n_target, int target_stride,
+                                   const tsar_cloud_distance_params* p, int n_tol, const float* tol, float* dist2_out, int32_t* index_out, int64_t* within_out,
+                                   int64_t* n_valid_query_out, int64_t* pairs_out, int mem) {
+    tsar_ctx* ctx = nullptr;
+    const int rc0 = tsar_create(device, &ctx);
+    if (rc0 != TSAR_OK) return rc0;
+    const int rc = tsar_cloud_distance_ctx(ctx, query, n_query, query_stride, target, n_target, target_stride, p, n_tol, tol, dist2_out, index_out, within_out,
+                                           n_valid_query_out, pairs_out, mem);
+    tsar_destroy(ctx);
+    return rc;
 }
 
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {

@@ -457,6 +457,9 @@ int launch_plane_prior(tsar_ctx* ctx, const float* depth_in, const float* normal
 size_t plane_prior_build_grid_keys(int w, int h, int cell, int max_levels);                      // plane_prior_build_kernels.hip (0: no level fits)
 int launch_plane_prior_build(tsar_ctx* ctx, const float* depth, const float* score, int cell, int max_levels, unsigned long long* grid,
                              float* depth_out, float* normal_out, uint8_t* level_out);          // plane_prior_build_kernels.hip
+int run_cloud_distance(CallFrame& f, const float* query, long long n_query, int query_stride, const float* target, long long n_target, int target_stride,
+                       float r2, double edge, long long max_pairs, int n_tol, const float* tol2, float* dist2_out, int32_t* index_out, int64_t* within_out,
+                       int64_t* n_valid_out, int64_t* pairs_out);                                  // cloud_distance_kernels.hip (device pointers; finishes the frame)
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);
 int launch_depth_to_plane(tsar_ctx* ctx);

@@ -363,6 +363,108 @@ static inline bool write_mask_png(const std::string& path, const float* scale, i
     return fclose(f) == 0;
 }
 
+// The x, y, z of a PLY's vertex element as n records of 3 floats: `ascii 1.0` or `binary_little_endian 1.0`; the vertex element may
+// have any scalar properties in any order; x, y, z float or double (a double is rounded once to float32); elements after the vertices
+// are ignored.  So it reads APD_TSAR.ply and TSAR_model.ply below, and a scan's PLY.  false with a one-line reason in `why`: a file that
+// is no PLY, a big-endian one, a list property inside the vertex element, a missing coordinate, a vertex count the file does not hold.
+static inline bool read_cloud_ply(const std::string& path, std::vector<float>& xyz, int64_t& n, std::string& why) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) { why = "cannot open " + path; return false; }
+    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+    auto bad = [&](const std::string& m) { why = path + ": " + m; return false; };
+    char line[1024];
+    auto next_line = [&]() -> bool {               // one header line without its line end
+        if (!fgets(line, sizeof line, f)) return false;
+        size_t len = strlen(line);
+        while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = '\0';
+        return true;
+    };
+    if (!next_line() || strcmp(line, "ply") != 0) return bad("not a PLY file");
+    struct Prop { std::string name; int size; int kind; };   // kind 0 integer (skipped), 1 float, 2 double
+    std::vector<Prop> props;
+    std::string format;
+    long long count = -1;
+    bool in_vertex = false, seen_vertex = false, ended = false;
+    while (next_line()) {
+        char a[64] = "", b[64] = "", c[64] = "", d[64] = "";
+        const int nw = sscanf(line, "%63s %63s %63s %63s", a, b, c, d);
+        if (nw < 1 || !strcmp(a, "comment") || !strcmp(a, "obj_info")) continue;
+        if (!strcmp(a, "end_header")) { ended = true; break; }
+        if (!strcmp(a, "format")) format = b;
+        else if (!strcmp(a, "element")) {
+            if (nw != 3) return bad("malformed element line");
+            in_vertex = !strcmp(b, "vertex");
+            if (in_vertex) {
+                char* end = nullptr;
+                count = strtoll(c, &end, 10);
+                if (*end != '\0' || count < 0) return bad("malformed vertex count");
+                seen_vertex = true;
+            } else if (!seen_vertex) return bad("an element comes before the vertices");
+        } else if (!strcmp(a, "property") && in_vertex) {
+            if (!strcmp(b, "list")) return bad("a list property inside the vertex element");
+            if (nw != 3) return bad("malformed property line");
+            static const struct { const char* name; int size; int kind; } types[] = {
+                {"char", 1, 0}, {"int8", 1, 0}, {"uchar", 1, 0}, {"uint8", 1, 0}, {"short", 2, 0}, {"int16", 2, 0}, {"ushort", 2, 0}, {"uint16", 2, 0},
+                {"int", 4, 0}, {"int32", 4, 0}, {"uint", 4, 0}, {"uint32", 4, 0}, {"float", 4, 1}, {"float32", 4, 1}, {"double", 8, 2}, {"float64", 8, 2}};
+            int found = -1;
+            for (int k = 0; k < 16; k++)
+                if (!strcmp(b, types[k].name)) found = k;
+            if (found < 0) return bad(std::string("unknown property type ") + b);
+            props.push_back({c, types[found].size, types[found].kind});
+        }
+    }
+    if (!ended) return bad("the header does not end");
+    const bool ascii = format == "ascii";
+    if (!ascii && format != "binary_little_endian") return bad("format " + format + " is not supported (ascii and binary_little_endian are)");
+    if (count < 0) return bad("no vertex element");
+    int col[3] = {-1, -1, -1}, off[3] = {0, 0, 0}, rec_bytes = 0;
+    for (size_t k = 0; k < props.size(); k++) {
+        for (int axis = 0; axis < 3; axis++)
+            if (props[k].name == std::string(1, "xyz"[axis])) {
+                if (col[axis] >= 0) return bad("property " + props[k].name + " appears twice");
+                if (props[k].kind == 0) return bad("property " + props[k].name + " is neither float nor double");
+                col[axis] = (int)k; off[axis] = rec_bytes;
+            }
+        rec_bytes += props[k].size;
+    }
+    for (int axis = 0; axis < 3; axis++)
+        if (col[axis] < 0) return bad(std::string("the vertex element has no property ") + "xyz"[axis]);
+    char msg[96];
+    snprintf(msg, sizeof msg, "the file holds fewer than %lld vertices", count);
+    // (a count beyond what the file can hold is refused before anything of that size is allocated)
+    const long body_at = ftell(f);
+    if (fseek(f, 0, SEEK_END) != 0) return bad("cannot seek");
+    const long long body_bytes = (long long)ftell(f) - body_at;
+    if (fseek(f, body_at, SEEK_SET) != 0) return bad("cannot seek");
+    const long long least = ascii ? 2 * (long long)props.size() - 1 : (long long)rec_bytes;     // an ASCII value is a character and a separator at least
+    if (count > 0 && (least <= 0 || count > body_bytes / least + 1)) return bad(msg);
+    n = count;
+    xyz.resize((size_t)count * 3);
+    if (ascii) {
+        for (long long i = 0; i < count; i++)
+            for (size_t k = 0; k < props.size(); k++) {
+                double v;
+                if (fscanf(f, "%lf", &v) != 1) return bad(msg);
+                for (int axis = 0; axis < 3; axis++)
+                    if (col[axis] == (int)k) xyz[(size_t)i * 3 + axis] = (float)v;
+            }
+        return true;
+    }
+    const long long chunk = 1 << 16;
+    std::vector<unsigned char> buf((size_t)chunk * rec_bytes);
+    for (long long i0 = 0; i0 < count; i0 += chunk) {
+        const long long m = count - i0 < chunk ? count - i0 : chunk;
+        if (fread(buf.data(), (size_t)rec_bytes, (size_t)m, f) != (size_t)m) return bad(msg);
+        for (long long i = 0; i < m; i++)
+            for (int axis = 0; axis < 3; axis++) {
+                const unsigned char* s = buf.data() + (size_t)i * rec_bytes + off[axis];
+                if (props[col[axis]].kind == 1) { float v; memcpy(&v, s, 4); xyz[(size_t)(i0 + i) * 3 + axis] = v; }
+                else { double v; memcpy(&v, s, 8); xyz[(size_t)(i0 + i) * 3 + axis] = (float)v; }
+            }
+    }
+    return true;
+}
+
 // fused cloud, binary little-endian: x y z nx ny nz red green blue per point (records of 9 floats from tsar_fuse)
 static bool write_cloud_ply(const std::string& path, const float* pts, int64_t n) {
     FILE* f = fopen(path.c_str(), "wb");

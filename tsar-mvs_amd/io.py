@@ -207,6 +207,81 @@ def convert_image(src: str, dst: str) -> None:
     write_pgm(dst, np.asarray(im.convert("L"), np.float32))
 
 
+# ---- point clouds (PLY) -------------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def write_ply(path: str, xyz, binary: bool = True) -> None:
+    """x y z of an [n, k >= 3] cloud as a PLY of float vertices (binary little-endian, or ASCII with nine significant digits:
+    enough to read every float32 back exactly)"""
+    a = np.ascontiguousarray(np.asarray(xyz, np.float32)[:, :3], "<f4")
+    with open(path, "wb") as f:
+        f.write(("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\nend_header\n"
+                 % ("binary_little_endian" if binary else "ascii", a.shape[0])).encode())
+        if binary:
+            f.write(a.tobytes())
+        else:
+            f.write("".join("%.9g %.9g %.9g\n" % tuple(r) for r in a.tolist()).encode())
+
+
+def read_ply(path: str) -> np.ndarray:
+    """[n, 3] float32: the x, y, z of a PLY's vertex element (`ascii 1.0` or `binary_little_endian 1.0`; any scalar properties in any
+    order; float or double coordinates, a double rounded once to float32; elements after the vertices are ignored).  What
+    host/tsar_io.h read_cloud_ply reads, with its refusals as ValueError."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, n, props, in_vertex, seen_vertex = None, None, [], False, False
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: the header does not end")
+            w = line.decode("ascii", "replace").split()
+            if not w or w[0] in ("comment", "obj_info"):
+                continue
+            if w[0] == "end_header":
+                break
+            if w[0] == "format":
+                fmt = w[1] if len(w) > 1 else ""
+            elif w[0] == "element":
+                if len(w) != 3:
+                    raise ValueError(f"{path}: malformed element line")
+                in_vertex = w[1] == "vertex"
+                if in_vertex:
+                    n, seen_vertex = int(w[2]), True
+                elif not seen_vertex:
+                    raise ValueError(f"{path}: an element comes before the vertices")
+            elif w[0] == "property" and in_vertex:
+                if len(w) > 1 and w[1] == "list":
+                    raise ValueError(f"{path}: a list property inside the vertex element")
+                if len(w) != 3 or w[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: malformed property line")
+                props.append((w[2], _PLY_TYPES[w[1]]))
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError(f"{path}: format {fmt} is not supported (ascii and binary_little_endian are)")
+        if n is None or n < 0:
+            raise ValueError(f"{path}: no vertex element")
+        names = [p[0] for p in props]
+        for c in "xyz":
+            if names.count(c) != 1:
+                raise ValueError(f"{path}: the vertex element has no property {c}")
+            if dict(props)[c] not in ("f4", "f8"):
+                raise ValueError(f"{path}: property {c} is neither float nor double")
+        if fmt == "ascii":
+            tok = f.read().split()
+            if len(tok) < n * len(props):
+                raise ValueError(f"{path}: the file holds fewer than {n} vertices")
+            rows = np.array(tok[: n * len(props)], dtype=object).reshape(n, len(props))
+            return np.stack([np.array(rows[:, names.index(c)], dtype=np.float64) for c in "xyz"], axis=1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+        dt = np.dtype([(nm, "<" + ty) for nm, ty in props])
+        body = f.read(n * dt.itemsize)
+        if len(body) != n * dt.itemsize:
+            raise ValueError(f"{path}: the file holds fewer than {n} vertices")
+        rec = np.frombuffer(body, dt)
+        return np.stack([rec[c].astype(np.float32) for c in "xyz"], axis=1) if n else np.zeros((0, 3), np.float32)
+
+
 # ---- a whole synthetic scene on disk, laid out like data/TRAIN/<scene>/ ---------------------------------
 def export_scene(scene, root: str, ref_ids=None) -> None:
     """Write `scene` (tsar_mvs_amd.synth.Scene; view k gets image id k) as images/%08d.pgm,
