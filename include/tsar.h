@@ -42,6 +42,7 @@
  *   gSLICr core_engine::Process_Frame + Get_Seg_Res      tsar_slic
  *   Fusion.exe (binary only; flags x/1.sh:20-30)         tsar_fuse
  *   (none: the reference ships no evaluation)            tsar_cloud_distance
+ *   (none: the reference's fuser thins nothing)          tsar_cloud_voxels
  *
  * Conventions
  *   - every function returns an int status (TSAR_OK = 0, negative = error) and never exits the
@@ -598,6 +599,48 @@ int tsar_cloud_distance_ctx(tsar_ctx* ctx, const float* query, int64_t n_query, 
 int tsar_cloud_distance(int device, const float* query, int64_t n_query, int query_stride, const float* target, int64_t n_target,
                         int target_stride, const tsar_cloud_distance_params* p, int n_tol, const float* tol, float* dist2_out, int32_t* index_out,
                         int64_t* within_out, int64_t* n_valid_query_out, int64_t* pairs_out, int mem);
+
+/* ---- a voxel grid over a cloud (thinning a fused cloud; the voxel-averaged accuracy / completeness of an evaluation) -------------- */
+/* Per occupied voxel of edge V: the number of its points, one representative point and, per tolerance, how many of its points have a
+ * dist2 (tsar_cloud_distance's output for the same cloud) within it; per point the number of its voxel.  Records are `stride` float32
+ * each (>= 3), x y z first.  `mem` names where cloud, dist2, rank_out, rep_out, count_out and within_out lie; tol, n_voxels_out and
+ * n_valid_out are host memory.  The arithmetic, the same in both arithmetic modes: every operation one IEEE-754 operation rounded to
+ * nearest, no fused multiply-add.
+ *   candidate: a record whose x, y and z are all finite (tsar_cloud_distance's rule)
+ *   origin o = the per-axis float32 minimum over the candidates (exact in any order)
+ *   cell of a point, per axis: floor(((double)p - (double)o) / (double)V), in float64, the quotient correctly rounded (the cell function
+ *     of tsar_cloud_distance with e = V); a cloud of 2^21 cells or more on an axis is refused
+ *   voxel key = z << 42 | y << 21 | x;  the occupied voxels are numbered 0 .. n_voxels - 1 in ascending key order
+ *   rank[i]  = the number of point i's voxel, -1 for a record that is no candidate
+ *   count[v] = the number of candidates in voxel v
+ *   rep[v]   = the index of the candidate of v nearest the cell's centre: per axis c = (double)o + ((double)cell + 0.5) * (double)V (one
+ *     product, then one sum), d = (double)p - c;  d2 = (dx * dx + dy * dy) + dz * dz in float64;  d2f = (float)d2;  the winner has the
+ *     minimal 64-bit code bits(d2f) << 32 | i: the smallest d2f, then the smallest index.  A real input point: row rep[v] of the cloud
+ *     keeps its whole record (normal, colour)
+ *   within[v][k] = the number of candidates i of v with dist2[i] <= fl(tol[k] * tol[k]) (one float32 product; NaN and +inf never pass)
+ *   n_valid  = the number of candidates
+ * The per-voxel outputs hold `cap` voxels: *n_voxels_out is the number found and may exceed cap; then the first cap voxels are written
+ * and the call still succeeds (like tsar_fuse).  Entries from min(n_voxels, cap) on are not written.  Minima and integer counts of
+ * bit-defined quantities: no output depends on an order of arrival, and every run gives the same bits.  n == 0 or no candidate: zero
+ * voxels, every rank -1, success.
+ * TSAR_ERR_INVALID, with the reason in tsar_last_error: p NULL; mem unknown; a stride below 3; n negative or above 2^31 - 1; voxel not
+ * finite or not > 0; 2^21 cells or more on an axis; n_tol > 0 with dist2 or tol NULL, or with a tolerance not finite or not > 0;
+ * within_out given with n_tol == 0; cap < 0.
+ * tsar_cloud_voxels_ctx needs no views and no state, runs on the context's stream and changes nothing in the context; its temporaries
+ * never grow the context's scratch arena.  tsar_cloud_voxels is the context-free form.  Timed as "cloud_bounds", "voxel_keys",
+ * "cloud_sort", "voxel_heads", "voxel_scan", "voxel_reduce" and "voxel_finish". */
+typedef struct tsar_cloud_voxels_params {
+    float voxel;          /* V: the voxel edge; finite and > 0.  No default (0): the caller's scale */
+} tsar_cloud_voxels_params;
+void tsar_default_cloud_voxels_params(tsar_cloud_voxels_params* p);
+int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p,
+                          const float* dist2 /* [n] or NULL */, int n_tol, const float* tol /* host; NULL with n_tol 0 */,
+                          int32_t* rank_out /* [n] or NULL */, int64_t cap, int32_t* rep_out /* [cap] or NULL */,
+                          int32_t* count_out /* [cap] or NULL */, int32_t* within_out /* [cap][n_tol] or NULL */,
+                          int64_t* n_voxels_out, int64_t* n_valid_out /* host, may be NULL */, int mem);
+int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2,
+                      int n_tol, const float* tol, int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out,
+                      int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out, int mem);
 
 /* ---- page-locked host buffers --------------------------------------------------------------- */
 /* NULL on failure.  Replaces the reference's cudaMallocManaged host-visible planes (managed.h:7-15) on the host side of the

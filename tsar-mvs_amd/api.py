@@ -74,6 +74,10 @@ class CloudDistanceParams(C.Structure):
     _fields_ = [("max_dist", C.c_float), ("max_pairs", C.c_int64)]
 
 
+class CloudVoxelsParams(C.Structure):
+    _fields_ = [("voxel", C.c_float)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -98,6 +102,7 @@ ABI_SYMBOLS = [
     "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
     "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
     "tsar_default_cloud_distance_params", "tsar_cloud_distance_ctx", "tsar_cloud_distance",
+    "tsar_default_cloud_voxels_params", "tsar_cloud_voxels_ctx", "tsar_cloud_voxels",
     "tsar_host_alloc", "tsar_host_free", "tsar_device_alloc", "tsar_device_free", "tsar_device_write", "tsar_peer_copy", "tsar_enable_kernel_timing", "tsar_reset_kernel_timing", "tsar_get_kernel_timing",
     "tsar_selftest_divide", "tsar_selftest_divide_random", "tsar_selftest_sqrt", "tsar_selftest_sweep_census", "tsar_selftest_prune_census", "tsar_selftest_sweep_repeat", "tsar_selftest_slic_stage",
 ]
@@ -200,6 +205,12 @@ def load_library(path: str = LIB_PATH):
         L.tsar_cloud_distance.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(CloudDistanceParams), C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
         L.tsar_cloud_distance_ctx.argtypes = [C.c_void_p] + list(L.tsar_cloud_distance.argtypes[1:])
+    if hasattr(L, "tsar_cloud_voxels_ctx"):           # (a library built before the operator, loaded through TSAR_LIB for an A/B run)
+        L.tsar_default_cloud_voxels_params.restype = None
+        L.tsar_default_cloud_voxels_params.argtypes = [C.POINTER(CloudVoxelsParams)]
+        L.tsar_cloud_voxels.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(CloudVoxelsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+        L.tsar_cloud_voxels_ctx.argtypes = [C.c_void_p] + list(L.tsar_cloud_voxels.argtypes[1:])
     L.tsar_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.tsar_synchronize.argtypes = [C.c_void_p]
     L.tsar_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int]
@@ -1069,28 +1080,150 @@ def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "ind
     return res
 
 
-def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0):
+def cloud_voxels(cloud, voxel, dist2=None, tolerances=None, want=("rank", "rep", "count"), matcher=None, device=0):
+    """A voxel grid of edge `voxel` over `cloud` (tsar_cloud_voxels_ctx; include/tsar.h states the arithmetic).  cloud: [n, k >= 3] float32, x y z
+    first, a numpy array or a torch device tensor; records with a non-finite coordinate take no part.  The occupied voxels are numbered in
+    ascending order of their key z << 42 | y << 21 | x.  dist2 ([n] float32, in the cloud's memory space: cloud_distance's output for this
+    cloud) and tolerances go together: with them the dict holds "within".  matcher / device: as cloud_distance.
+    Returns a dict: "rank" ([n] int32: the voxel of every point, -1 for a non-candidate), "rep" ([n_voxels] int32: the index of the point
+    nearest the voxel's centre, the smallest index among equals), "count" ([n_voxels] int32), as `want` names them; "within" ([n_voxels,
+    n_tol] int32: per voxel and tolerance the points with dist2 <= fl(tol * tol)) when tolerances are given; the integers "n_voxels" and
+    "n_valid".  Arrays are numpy arrays, or torch tensors on the cloud's device."""
+    L = load_library()
+    c, dev = _cloud(cloud, "cloud")
+    n = int(c.shape[0])
+    tol = np.ascontiguousarray([] if tolerances is None else tolerances, np.float32).reshape(-1)
+    assert (dist2 is None) == (tolerances is None), "dist2 and tolerances go together"
+    d2 = None
+    if dist2 is not None:
+        if dev:
+            assert _is_torch(dist2) and dist2.is_cuda and dist2.device == c.device and str(dist2.dtype) == "torch.float32" and dist2.is_contiguous(), \
+                "dist2 must be a contiguous float32 tensor on the cloud's device"
+            d2 = dist2
+        else:
+            d2 = np.ascontiguousarray(dist2.cpu().numpy() if _is_torch(dist2) else dist2, np.float32)
+        assert tuple(d2.shape) == (n,), "dist2 must be [n]"
+    p = CloudVoxelsParams()
+    L.tsar_default_cloud_voxels_params(C.byref(p))
+    p.voxel = float(voxel)
+
+    def empty(shape):
+        if dev:
+            import torch
+            return torch.empty(shape, dtype=torch.int32, device=c.device)
+        return np.empty(shape, np.int32)
+    out = {k: empty((n,)) for k in ("rank", "rep", "count") if k in want}      # at most n voxels: the per-voxel arrays are trimmed below
+    if tolerances is not None:
+        out["within"] = empty((n, len(tol)))
+    n_voxels, n_valid = C.c_int64(0), C.c_int64(0)
+    own = matcher is None
+    m = Matcher(c.device.index if dev and c.device.index is not None else device) if own else matcher
+    try:
+        rc = L.tsar_cloud_voxels_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), C.byref(p), _ptr(d2)[0], len(tol),
+                                     tol.ctypes.data_as(C.c_void_p) if tolerances is not None else None, _ptr(out.get("rank"))[0], n, _ptr(out.get("rep"))[0],
+                                     _ptr(out.get("count"))[0], _ptr(out.get("within"))[0] if len(tol) else None, C.byref(n_voxels), C.byref(n_valid),
+                                     MEM_DEVICE if dev else MEM_HOST)
+        if rc != TSAR_OK:
+            raise TsarError(rc, L.tsar_last_error(m._ctx).decode())
+    finally:
+        if own:
+            m.close()
+    nv = int(n_voxels.value)
+    for k in ("rep", "count", "within"):
+        if k in out:
+            out[k] = out[k][:nv].clone() if dev else out[k][:nv].copy()
+    out["n_voxels"] = nv
+    out["n_valid"] = int(n_valid.value)
+    return out
+
+
+def voxel_downsample(cloud, voxel, matcher=None, device=0):
+    """`cloud` thinned to one point per occupied voxel of edge `voxel`: the rows sorted(rep) of cloud_voxels — every voxel's point nearest its
+    centre, whole records (normals, colours), in the cloud's own order.  Returns an array or tensor like `cloud`."""
+    c, dev = _cloud(cloud, "cloud")
+    rep = cloud_voxels(c, voxel, want=("rep",), matcher=matcher, device=device)["rep"]
+    if dev:
+        return c[rep.sort().values.long()].clone()
+    return c[np.sort(rep)].copy()
+
+
+def _crop_cloud(cloud, crop):
+    """-> (a copy of `cloud` with x y z of every record outside the closed box replaced by NaN, the number of candidate records so removed)"""
+    c, dev = _cloud(cloud, "cloud")
+    lo, hi = np.asarray(crop[:3], np.float32), np.asarray(crop[3:], np.float32)
+    if dev:
+        import torch
+        xyz = c[:, :3]
+        cand = torch.isfinite(xyz).all(dim=1)
+        inside = ((xyz >= torch.from_numpy(lo).to(c.device)) & (xyz <= torch.from_numpy(hi).to(c.device))).all(dim=1)
+        out = c.clone()
+        out[:, :3] = torch.where((cand & inside)[:, None], xyz, torch.full_like(xyz, float("nan")))
+        return out, int((cand & ~inside).sum().item())
+    xyz = c[:, :3]
+    cand = np.isfinite(xyz).all(axis=1) if len(c) else np.zeros(0, bool)
+    with np.errstate(invalid="ignore"):
+        inside = ((xyz >= lo) & (xyz <= hi)).all(axis=1) if len(c) else np.zeros(0, bool)
+    out = c.copy()
+    out[~(cand & inside), :3] = np.nan
+    return out, int(np.count_nonzero(cand & ~inside))
+
+
+def _voxel_share(within, count):
+    """per tolerance (sum over the voxels, in ascending order, of within / count) / n_voxels: each term one float64 division, the terms added one
+    after another in float64 (np.cumsum adds sequentially; np.sum adds pairwise), 0 without voxels"""
+    within = (within.cpu().numpy() if _is_torch(within) else within).astype(np.float64)
+    count = (count.cpu().numpy() if _is_torch(count) else count).astype(np.float64)
+    if len(count) == 0:
+        return np.zeros(within.shape[1], np.float64)
+    return np.cumsum(within / count[:, None], axis=0)[-1] / np.float64(len(count))
+
+
+def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, crop=None):
     """Accuracy and completeness of the cloud `recon` against the cloud `gt` at each of `tolerances`: the point-wise precision / recall /
     F-score.  Two cloud_distance calls with max_dist = max(tolerances):
       accuracy[k]     = the share of recon's candidate points (finite coordinates) with a gt point within tolerances[k];
       completeness[k] = the share of gt's candidate points with a recon point within tolerances[k];
       f1[k]           = their harmonic mean (0 where both are 0).
-    This is NOT the evaluation program of a benchmark: ETH3D's averages over voxels of the scan so that dense areas do not dominate, DTU's
-    applies observation masks, and both align and crop first.  Nothing is down-sampled, cropped, masked or registered here: every point
-    counts once, and the clouds are compared where they lie.
+    voxel=V adds the voxel-averaged figures, so that dense areas do not dominate: a grid of edge V over each cloud (cloud_voxels), and
+      accuracy_voxel[k]     = the mean over recon's occupied voxels of the share of the voxel's points with a gt point within tolerances[k];
+      completeness_voxel[k] = the same over gt's voxels;  f1_voxel[k] = their harmonic mean.
+    (Each share is one float64 division of two integer counts; the shares are added in ascending voxel order, one after another.)
+    crop=(x0, y0, z0, x1, y1, z1) first makes every record of either cloud outside the closed box a non-candidate (on a copy: its
+    coordinates become NaN), before anything else is computed.
+    This is NOT the evaluation program of a benchmark.  With voxel and crop it averages over voxels and crops to a box in the manner of
+    the benchmarks, but ETH3D's program defines its voxels and its observed volume from the scanner's positions, DTU's applies observation
+    masks, and both align the clouds first: nothing is registered here, there are no occlusion or observation masks, and the clouds are
+    compared where they lie.  Without voxel and crop nothing is down-sampled or cropped either: every point counts once.
     Returns {"tolerances", "accuracy", "completeness", "f1"} as float64 numpy arrays (ratios formed on the host from the integer
     counts; 0 where a denominator is 0), {"n_accurate", "n_complete"} as int64 arrays, and the integers "n_recon_valid", "n_gt_valid",
-    "pairs_accuracy", "pairs_completeness"."""
+    "pairs_accuracy", "pairs_completeness"; with voxel also "accuracy_voxel", "completeness_voxel", "f1_voxel" (float64 arrays),
+    "n_recon_voxels" and "n_gt_voxels"; with crop also "n_recon_cropped" and "n_gt_cropped" (the candidate records outside the box)."""
     tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
     if tol.size == 0:
         raise ValueError("evaluate_cloud needs at least one tolerance")
     r = float(tol.max())
+    cropped = None
+    if crop is not None:
+        crop = tuple(float(v) for v in crop)
+        if len(crop) != 6 or not all(np.isfinite(crop)) or any(crop[a] > crop[3 + a] for a in range(3)):
+            raise ValueError("crop must be six finite numbers (x0, y0, z0, x1, y1, z1) with x0 <= x1, y0 <= y1, z0 <= z1")
+        (recon, n_rc), (gt, n_gc) = _crop_cloud(recon, crop), _crop_cloud(gt, crop)
+        cropped = {"n_recon_cropped": n_rc, "n_gt_cropped": n_gc}
     own = matcher is None
-    if own:                                # one context for both directions
+    if own:                                # one context for every call
         matcher = Matcher(recon.device.index if _is_torch(recon) and recon.is_cuda and recon.device.index is not None else device)
+    vox = None
     try:
-        a = cloud_distance(recon, gt, r, tol, want=(), matcher=matcher)
-        c = cloud_distance(gt, recon, r, tol, want=(), matcher=matcher)
+        want = () if voxel is None else ("dist2",)
+        a = cloud_distance(recon, gt, r, tol, want=want, matcher=matcher)
+        c = cloud_distance(gt, recon, r, tol, want=want, matcher=matcher)
+        if voxel is not None:
+            va = cloud_voxels(recon, voxel, a["dist2"], tol, want=("count",), matcher=matcher)
+            vc = cloud_voxels(gt, voxel, c["dist2"], tol, want=("count",), matcher=matcher)
+            acc_v, com_v = _voxel_share(va["within"], va["count"]), _voxel_share(vc["within"], vc["count"])
+            sv = acc_v + com_v
+            vox = {"accuracy_voxel": acc_v, "completeness_voxel": com_v, "f1_voxel": np.where(sv > 0, 2.0 * acc_v * com_v / np.where(sv > 0, sv, 1.0), 0.0),
+                   "n_recon_voxels": va["n_voxels"], "n_gt_voxels": vc["n_voxels"]}
     finally:
         if own:
             matcher.close()
@@ -1099,8 +1232,13 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0):
     com = nc / np.float64(c["n_valid_query"]) if c["n_valid_query"] else np.zeros(tol.size, np.float64)
     s = acc + com
     f1 = np.where(s > 0, 2.0 * acc * com / np.where(s > 0, s, 1.0), 0.0)
-    return {"tolerances": tol.copy(), "accuracy": acc, "completeness": com, "f1": f1, "n_accurate": na, "n_complete": nc,
-            "n_recon_valid": a["n_valid_query"], "n_gt_valid": c["n_valid_query"], "pairs_accuracy": a["pairs"], "pairs_completeness": c["pairs"]}
+    res = {"tolerances": tol.copy(), "accuracy": acc, "completeness": com, "f1": f1, "n_accurate": na, "n_complete": nc,
+           "n_recon_valid": a["n_valid_query"], "n_gt_valid": c["n_valid_query"], "pairs_accuracy": a["pairs"], "pairs_completeness": c["pairs"]}
+    if vox is not None:
+        res.update(vox)
+    if cropped is not None:
+        res.update(cropped)
+    return res
 
 
 def pinned_empty(shape, dtype=np.float32):

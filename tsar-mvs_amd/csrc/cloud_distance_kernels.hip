@@ -10,13 +10,9 @@
 //            -> the pair count: per query the sizes of its 9 key ranges (cells x-1 .. x+1 of one (y, z) are one contiguous range)
 //            -> the query kernel: one lane per query in key order, a running minimum of the 64-bit (d2 bits, index) code.
 // No floating-point atomics and no order of arrival anywhere: the outputs are the same bits in every run.
-#include <float.h>
-#include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
+// (The candidate rule, the float codes, the cell function, the bounds pass and the sort live in cloud_grid.h, shared with cloud_voxel_kernels.hip.)
+#include "cloud_grid.h"
 
-#include "tsar_dev.h"
-
-#define CD_BLOCK 256
 #define CD_T_NONE (1ull << 60)            // key of a target that is no candidate: above every cell key (3 x 20 bits)
 #define CD_Q_NONE (1ull << 63)            // key of a query that is no candidate: above every query key (3 x 21 bits)
 #define CD_MAX_EXTENT (1 << 20)           // cells per axis: refused from here on
@@ -27,39 +23,6 @@ struct CdGrid {
     int ex, ey, ez;                       // cells per axis: the targets' cells are 0 .. ex - 1
 };
 struct __align__(16) CdRec { float x, y, z; uint32_t j; };
-
-__device__ __forceinline__ bool cd_candidate(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }   // NaN fails
-// unsigned codes in the order of the floats they stand for (-0.0 below +0.0: the same double either way)
-__device__ __forceinline__ uint32_t cd_code(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-static inline float cd_decode(uint32_t c) { const uint32_t u = (c & 0x80000000u) ? (c & 0x7fffffffu) : ~c; float f; memcpy(&f, &u, 4); return f; }
-// the cell coordinate of include/tsar.h, as a double: floor(((double)p - (double)o) / e), the quotient correctly rounded
-__device__ __forceinline__ double cd_cell(float p, double o, double e) { return floor(((double)p - o) / e); }
-static inline double cd_cell_host(float p, double o, double e) { return floor(((double)p - o) / e); }
-
-__device__ __forceinline__ uint32_t cd_wave_min(uint32_t v) { for (int s = 32; s > 0; s >>= 1) { const uint32_t o = __shfl_xor(v, s, 64); v = o < v ? o : v; } return v; }
-__device__ __forceinline__ uint32_t cd_wave_max(uint32_t v) { for (int s = 32; s > 0; s >>= 1) { const uint32_t o = __shfl_xor(v, s, 64); v = o > v ? o : v; } return v; }
-__device__ __forceinline__ unsigned long long cd_wave_sum(unsigned long long v) { for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64); return v; }
-
-// bounds[0..2] = codes of the per-axis minima, bounds[3..5] = of the maxima, *count = the candidates
-__global__ __launch_bounds__(CD_BLOCK) void cd_bounds_kernel(const float* __restrict__ pts, long long n, int stride, uint32_t* __restrict__ bounds,
-                                                             unsigned long long* __restrict__ count) {
-    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    unsigned long long cnt = 0;
-    for (long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * CD_BLOCK) {
-        const float* p = pts + (size_t)i * stride;
-        const float x = p[0], y = p[1], z = p[2];
-        if (!cd_candidate(x, y, z)) continue;
-        const uint32_t c[3] = {cd_code(x), cd_code(y), cd_code(z)};
-        for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
-        cnt++;
-    }
-    for (int a = 0; a < 3; a++) { lo[a] = cd_wave_min(lo[a]); hi[a] = cd_wave_max(hi[a]); }
-    cnt = cd_wave_sum(cnt);
-    if ((threadIdx.x & 63) == 0 && cnt) {
-        for (int a = 0; a < 3; a++) { atomicMin(&bounds[a], lo[a]); atomicMax(&bounds[3 + a], hi[a]); }
-        atomicAdd(count, cnt);
-    }
-}
 
 __device__ __forceinline__ int cd_clampi(double c, int lo, int hi) { return c < (double)lo ? lo : (c > (double)hi ? hi : (int)c); }
 
@@ -208,19 +171,6 @@ __global__ __launch_bounds__(CD_BLOCK) void cd_fill_kernel(const float* __restri
     }
     const unsigned long long m = __ballot(cand);
     if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(n_valid, (unsigned long long)__popcll(m));
-}
-
-static inline unsigned cd_blocks(long long n) { return (unsigned)((n + CD_BLOCK - 1) / CD_BLOCK); }
-
-// keys_in / vals_in sorted into keys_out / vals_out (bits [0, end_bit)); the sort's scratch is a piece of the frame
-template <typename F>
-static bool cd_sort(F& f, const char* name, unsigned long long* keys_in, unsigned long long* keys_out, uint32_t* vals_in, uint32_t* vals_out, long long n, int end_bit) {
-    size_t bytes = 0;
-    if (!f.ok() || !f.hip(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, end_bit, f.ctx->stream), "rocprim::radix_sort_pairs sizing")) return false;
-    void* tmp = f.template tmp<char>(bytes);
-    if (!f.ok()) return false;
-    ScopedKernelTimer tm(f.ctx, name);
-    return f.hip(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, end_bit, f.ctx->stream), "rocprim::radix_sort_pairs");
 }
 
 // query / target and the two per-query outputs are device pointers (the frame's views of the caller's buffers); tol2, within_out,

@@ -1219,6 +1219,52 @@ extern "C" int tsar_cloud_distance(int device, const float* query, int64_t n_que
     return rc;
 }
 
+// ---- a voxel grid over a cloud (cloud_voxel_kernels.hip) -------------------------------------------------------------------------------
+extern "C" void tsar_default_cloud_voxels_params(tsar_cloud_voxels_params* p) {
+    if (!p) return;
+    p->voxel = 0.0f;                       // no default: the caller's scale
+}
+
+// Like tsar_cloud_distance_ctx: no views, no state, nothing of the context written, and a frame that does not grow the arena.
+extern "C" int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2, int n_tol,
+                                     const float* tol, int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out,
+                                     int64_t* n_valid_out, int mem) {
+    CHECK_CTX(ctx);
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: params is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: n must be in 0..2^31-1");
+    if (stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: the stride must be at least 3 floats (x y z first)");
+    if (n > 0 && !cloud) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: cloud is NULL");
+    const float V = p->voxel;
+    if (!(fabsf(V) <= FLT_MAX) || !(V > 0.0f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: voxel must be finite and > 0");
+    if (cap < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: cap must be >= 0");
+    if (n_tol < 0 || (n_tol > 0 && (!tol || (!dist2 && n > 0)))) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: n_tol < 0, or tolerances without tol or without dist2");
+    if (n_tol == 0 && within_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: within_out needs tolerances (n_tol is 0)");
+    std::vector<float> tol2((size_t)n_tol);
+    for (int k = 0; k < n_tol; k++) {
+        if (!(tol[k] > 0.0f && tol[k] <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: every tolerance must be finite and > 0");
+        const volatile float t2 = tol[k] * tol[k];      // fl(tol * tol), one float32 product
+        tol2[k] = t2;
+    }
+    CallFrame f(ctx, "tsar_cloud_voxels", nullptr, /*grow_arena=*/false);
+    const float* c = f.in(cloud, (size_t)n * stride, mem);
+    const float* d2 = n_tol > 0 ? f.in(dist2, (size_t)n, mem) : nullptr;
+    if (!f.ok()) return f.finish();
+    return run_cloud_voxels(f, c, n, stride, (double)V, d2, n_tol, tol2.data(), rank_out, cap, rep_out, count_out, within_out, n_voxels_out, n_valid_out, mem);
+}
+
+// Context-free form (the fuser's thinning step): a context of its own for the duration of the call.
+extern "C" int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2, int n_tol, const float* tol,
+                                 int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
+                                 int mem) {
+    tsar_ctx* ctx = nullptr;
+    const int rc0 = tsar_create(device, &ctx);
+    if (rc0 != TSAR_OK) return rc0;
+    const int rc = tsar_cloud_voxels_ctx(ctx, cloud, n, stride, p, dist2, n_tol, tol, rank_out, cap, rep_out, count_out, within_out, n_voxels_out, n_valid_out, mem);
+    tsar_destroy(ctx);
+    return rc;
+}
+
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);

@@ -460,6 +460,9 @@ int launch_plane_prior_build(tsar_ctx* ctx, const float* depth, const float* sco
 int run_cloud_distance(CallFrame& f, const float* query, long long n_query, int query_stride, const float* target, long long n_target, int target_stride,
                        float r2, double edge, long long max_pairs, int n_tol, const float* tol2, float* dist2_out, int32_t* index_out, int64_t* within_out,
                        int64_t* n_valid_out, int64_t* pairs_out);                                  // cloud_distance_kernels.hip (device pointers; finishes the frame)
+int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, double voxel, const float* dist2, int n_tol, const float* tol2, int32_t* rank_out,
+                     long long cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
+                     int mem);                                                                  // cloud_voxel_kernels.hip (cloud, dist2: device; outputs in `mem`; finishes the frame)
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);
 int launch_depth_to_plane(tsar_ctx* ctx);

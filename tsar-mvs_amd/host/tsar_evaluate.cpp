@@ -1,14 +1,27 @@
 // tsar_evaluate — accuracy and completeness of a reconstructed cloud against a ground-truth cloud, on the GPU:
-//   tsar_evaluate RECON.ply GT.ply --tolerances=0.01,0.02,0.05 [--max_pairs=N] [--device=D] [--json=FILE]
+//   tsar_evaluate RECON.ply GT.ply --tolerances=0.01,0.02,0.05 [--max_pairs=N] [--device=D] [--json=FILE] [--voxel=V] [--crop=x0,y0,z0,x1,y1,z1]
 // accuracy(tau) = the share of RECON's points with a GT point within tau; completeness(tau) = the share of GT's points with a RECON point
 // within tau; f1 = their harmonic mean: the point-wise precision / recall / F-score.  Not ETH3D's or DTU's evaluation program: nothing is
-// down-sampled, masked, cropped or aligned.  Two tsar_cloud_distance_ctx calls with max_dist = the largest tolerance (include/tsar.h);
+// masked or aligned, and without the two switches below nothing is down-sampled or cropped.  Two tsar_cloud_distance_ctx calls with max_dist = the largest tolerance (include/tsar.h);
 // points with a non-finite coordinate take no part.  Prints one table and one JSON line; --json=FILE gets the same line.
+// --voxel=V adds the voxel-averaged figures (a grid of edge V over each cloud, tsar_cloud_voxels_ctx: per occupied voxel the share of its
+// points within tau, averaged over the voxels in ascending voxel order, one float64 term after another), --crop= first makes every point
+// outside the closed box a non-candidate.  In the manner of the benchmarks, still not their programs: no alignment, no observation masks.
+#include <math.h>
 #include <stdlib.h>
 
 #include <chrono>
 
 #include "tsar_io.h"
+
+// The entries that only --voxel calls are referred to weakly: the tool still links against, and runs with, a library that lacks them, and
+// refuses the switch there.
+extern "C" {
+void tsar_default_cloud_voxels_params(tsar_cloud_voxels_params* p) __attribute__((weak));
+int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2, int n_tol, const float* tol,
+                          int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
+                          int mem) __attribute__((weak));
+}
 
 static int refuse(const std::string& msg) {
     fprintf(stderr, "%s\n", msg.c_str());
@@ -34,9 +47,11 @@ static std::string json_list(const std::vector<T>& v, Fmt fmt) {
 
 int main(int argc, char** argv) {
     (void)write_cloud_ply;                         // (tsar_io.h's writer, unused here)
-    const char* usage = "usage: tsar_evaluate RECON.ply GT.ply --tolerances=T1[,T2...] [--max_pairs=N] [--device=D] [--json=FILE]\n"
-                        "       point-wise accuracy / completeness / F-score of RECON against GT at each tolerance (not ETH3D's or DTU's program:\n"
-                        "       no voxel averaging, masks, cropping or alignment)\n";
+    const char* usage = "usage: tsar_evaluate RECON.ply GT.ply --tolerances=T1[,T2...] [--max_pairs=N] [--device=D] [--json=FILE] [--voxel=V]\n"
+                        "                     [--crop=x0,y0,z0,x1,y1,z1]\n"
+                        "       point-wise accuracy / completeness / F-score of RECON against GT at each tolerance; --voxel=V adds the figures averaged\n"
+                        "       over the occupied voxels of edge V, --crop= drops the points outside the closed box first (not ETH3D's or DTU's\n"
+                        "       program: no masks, no alignment)\n";
     if (argc >= 2 && (!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help"))) { printf("%s", usage); return 0; }
     std::vector<std::string> paths;
     std::vector<float> tol;
@@ -44,6 +59,9 @@ int main(int argc, char** argv) {
     long long max_pairs = -1;
     int device = 0;
     std::string json_path;
+    bool have_voxel = false, have_crop = false;
+    float voxel = 0.0f;
+    float crop[6] = {0, 0, 0, 0, 0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&](const char* opt) -> const char* { const size_t n = strlen(opt); return a.compare(0, n, opt) == 0 ? argv[i] + n : nullptr; };
@@ -68,6 +86,25 @@ int main(int argc, char** argv) {
             char* end = nullptr;
             device = (int)strtol(v, &end, 10);
             if (end == v || *end != '\0' || device < 0) return refuse("--device=D must be an integer >= 0");
+        } else if ((v = value("--voxel="))) {
+            char* end = nullptr;
+            const double t = strtod(v, &end);
+            if (end == v || *end != '\0' || !(t > 0.0) || !((float)t <= FLT_MAX) || !((float)t > 0.0f)) return refuse("--voxel=V must be a finite number > 0");
+            voxel = (float)t;
+            have_voxel = true;
+        } else if ((v = value("--crop="))) {
+            const char* msg = "--crop=x0,y0,z0,x1,y1,z1 must be six finite numbers with x0 <= x1, y0 <= y1 and z0 <= z1";
+            const char* s = v;
+            for (int k = 0; k < 6; k++) {
+                char* end = nullptr;
+                const double t = strtod(s, &end);
+                if (end == s || !(fabs(t) <= FLT_MAX) || *end != (k < 5 ? ',' : '\0')) return refuse(msg);
+                crop[k] = (float)t;
+                s = end + 1;
+            }
+            for (int a = 0; a < 3; a++)
+                if (!(crop[a] <= crop[3 + a])) return refuse(msg);
+            have_crop = true;
         } else if ((v = value("--json="))) {
             json_path = v;
         } else if (a.compare(0, 2, "--") == 0) {
@@ -78,6 +115,7 @@ int main(int argc, char** argv) {
     }
     if (paths.size() != 2) { fprintf(stderr, "%s", usage); return 1; }
     if (!have_tol || tol.empty()) return refuse("--tolerances=T1[,T2...] is required");
+    if (have_voxel && (!tsar_cloud_voxels_ctx || !tsar_default_cloud_voxels_params)) return refuse("--voxel: this libtsar_hip.so has no tsar_cloud_voxels");
     std::vector<float> cloud[2];
     int64_t n[2] = {0, 0};
     for (int k = 0; k < 2; k++) {
@@ -85,6 +123,15 @@ int main(int argc, char** argv) {
         if (!read_cloud_ply(paths[k], cloud[k], n[k], why)) return refuse(why);
         if (n[k] > INT32_MAX) return refuse(paths[k] + ": more than 2^31 - 1 points");
     }
+    int64_t cropped[2] = {0, 0};
+    for (int k = 0; k < 2 && have_crop; k++)        // a point outside the closed box becomes a non-candidate
+        for (int64_t i = 0; i < n[k]; i++) {
+            float* p = cloud[k].data() + 3 * i;
+            if (!(fabsf(p[0]) <= FLT_MAX && fabsf(p[1]) <= FLT_MAX && fabsf(p[2]) <= FLT_MAX)) continue;
+            if (p[0] >= crop[0] && p[0] <= crop[3] && p[1] >= crop[1] && p[1] <= crop[4] && p[2] >= crop[2] && p[2] <= crop[5]) continue;
+            p[0] = p[1] = p[2] = NAN;
+            cropped[k]++;
+        }
     tsar_cloud_distance_params prm;
     tsar_default_cloud_distance_params(&prm);
     for (const float t : tol) prm.max_dist = t > prm.max_dist ? t : prm.max_dist;
@@ -95,10 +142,23 @@ int main(int argc, char** argv) {
     std::vector<int64_t> within[2] = {std::vector<int64_t>(tol.size(), 0), std::vector<int64_t>(tol.size(), 0)};
     int64_t valid[2] = {0, 0}, pairs[2] = {0, 0};
     double ms[2] = {0, 0};
+    std::vector<float> dist2[2];
+    std::vector<int32_t> vcount[2], vwithin[2];
+    int64_t voxels[2] = {0, 0};
     for (int k = 0; k < 2; k++) {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = tsar_cloud_distance_ctx(ctx, cloud[k].data(), n[k], 3, cloud[1 - k].data(), n[1 - k], 3, &prm, (int)tol.size(), tol.data(), nullptr, nullptr,
-                                               within[k].data(), &valid[k], &pairs[k], TSAR_MEM_HOST);
+        if (have_voxel) dist2[k].resize((size_t)n[k] + 1);
+        int rc = tsar_cloud_distance_ctx(ctx, cloud[k].data(), n[k], 3, cloud[1 - k].data(), n[1 - k], 3, &prm, (int)tol.size(), tol.data(),
+                                         have_voxel ? dist2[k].data() : nullptr, nullptr, within[k].data(), &valid[k], &pairs[k], TSAR_MEM_HOST);
+        if (rc == TSAR_OK && have_voxel) {          // the cloud's voxels: per voxel its points and how many of them lie within each tolerance
+            tsar_cloud_voxels_params vp;
+            tsar_default_cloud_voxels_params(&vp);
+            vp.voxel = voxel;
+            vcount[k].resize((size_t)n[k] + 1);
+            vwithin[k].resize((size_t)n[k] * tol.size() + 1);
+            rc = tsar_cloud_voxels_ctx(ctx, cloud[k].data(), n[k], 3, &vp, dist2[k].data(), (int)tol.size(), tol.data(), nullptr, n[k], nullptr, vcount[k].data(),
+                                       vwithin[k].data(), &voxels[k], nullptr, TSAR_MEM_HOST);
+        }
         ms[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (rc != TSAR_OK) {
             fprintf(stderr, "%s\n", tsar_last_error(ctx));
@@ -113,9 +173,23 @@ int main(int argc, char** argv) {
         com[k] = valid[1] ? (double)within[1][k] / (double)valid[1] : 0.0;
         f1[k] = acc[k] + com[k] > 0.0 ? 2.0 * acc[k] * com[k] / (acc[k] + com[k]) : 0.0;
     }
-    printf("%12s %12s %12s %12s %14s %14s\n", "tolerance", "accuracy", "completeness", "f1", "n_accurate", "n_complete");
-    for (size_t k = 0; k < tol.size(); k++)
-        printf("%12.9g %12.6f %12.6f %12.6f %14lld %14lld\n", (double)tol[k], acc[k], com[k], f1[k], (long long)within[0][k], (long long)within[1][k]);
+    // the voxel-averaged shares: per voxel one float64 division, the terms added one after another in ascending voxel order
+    std::vector<double> vshare[2] = {std::vector<double>(tol.size(), 0.0), std::vector<double>(tol.size(), 0.0)}, vf1(tol.size(), 0.0);
+    for (int d = 0; d < 2 && have_voxel; d++)
+        for (size_t k = 0; k < tol.size(); k++) {
+            double sum = 0.0;
+            for (int64_t v = 0; v < voxels[d]; v++) sum += (double)vwithin[d][(size_t)v * tol.size() + k] / (double)vcount[d][(size_t)v];
+            vshare[d][k] = voxels[d] ? sum / (double)voxels[d] : 0.0;
+        }
+    for (size_t k = 0; k < tol.size(); k++) vf1[k] = vshare[0][k] + vshare[1][k] > 0.0 ? 2.0 * vshare[0][k] * vshare[1][k] / (vshare[0][k] + vshare[1][k]) : 0.0;
+    printf("%12s %12s %12s %12s %14s %14s", "tolerance", "accuracy", "completeness", "f1", "n_accurate", "n_complete");
+    if (have_voxel) printf(" %14s %18s %12s", "accuracy_voxel", "completeness_voxel", "f1_voxel");
+    printf("\n");
+    for (size_t k = 0; k < tol.size(); k++) {
+        printf("%12.9g %12.6f %12.6f %12.6f %14lld %14lld", (double)tol[k], acc[k], com[k], f1[k], (long long)within[0][k], (long long)within[1][k]);
+        if (have_voxel) printf(" %14.6f %18.6f %12.6f", vshare[0][k], vshare[1][k], vf1[k]);
+        printf("\n");
+    }
     auto f9 = [](float v) { char b[32]; snprintf(b, sizeof b, "%.9g", (double)v); return std::string(b); };
     auto f17 = [](double v) { char b[40]; snprintf(b, sizeof b, "%.17g", v); return std::string(b); };
     auto i64 = [](int64_t v) { return std::to_string((long long)v); };
@@ -125,9 +199,15 @@ int main(int argc, char** argv) {
     char tail[256];
     snprintf(tail, sizeof tail, "\"pairs_accuracy\": %lld, \"pairs_completeness\": %lld, \"ms_accuracy\": %.3f, \"ms_completeness\": %.3f", (long long)pairs[0],
              (long long)pairs[1], ms[0], ms[1]);
+    std::string more;
+    if (have_voxel)
+        more += ", \"voxel\": " + f9(voxel) + ", \"n_recon_voxels\": " + i64(voxels[0]) + ", \"n_gt_voxels\": " + i64(voxels[1]) + ", \"accuracy_voxel\": " +
+                json_list(vshare[0], f17) + ", \"completeness_voxel\": " + json_list(vshare[1], f17) + ", \"f1_voxel\": " + json_list(vf1, f17);
+    if (have_crop)
+        more += ", \"crop\": " + json_list(std::vector<float>(crop, crop + 6), f9) + ", \"n_recon_cropped\": " + i64(cropped[0]) + ", \"n_gt_cropped\": " + i64(cropped[1]);
     const std::string rec = "{\"recon\": " + json_string(paths[0]) + ", \"gt\": " + json_string(paths[1]) + ", " + head + "\"tolerances\": " + json_list(tol, f9) +
                             ", \"n_accurate\": " + json_list(within[0], i64) + ", \"n_complete\": " + json_list(within[1], i64) + ", \"accuracy\": " + json_list(acc, f17) +
-                            ", \"completeness\": " + json_list(com, f17) + ", \"f1\": " + json_list(f1, f17) + ", " + tail + "}";
+                            ", \"completeness\": " + json_list(com, f17) + ", \"f1\": " + json_list(f1, f17) + ", " + tail + more + "}";
     printf("%s\n", rec.c_str());
     if (!json_path.empty()) {
         FILE* f = fopen(json_path.c_str(), "w");

@@ -4,18 +4,32 @@
 // Reads <dir>/pair.txt, <dir>/cams/%08d_cam.txt, <dir>/images/%08d.pgm (else the .jpg of that name) and, per view,
 // <dir>/APD/%08d/TSAR_disp.dmb + TSAR_normals.dmb (what tsar_gipuma / the reference write), fuses them on
 // the GPU (tsar_fuse) and writes <dir>/APD/APD_TSAR.ply (binary little-endian: x y z nx ny nz red green blue).
+// --voxel=V thins the fused cloud before it is written: a grid of edge V over it (tsar_cloud_voxels), and per occupied voxel the record of
+// the point nearest the voxel's centre, whole, in the cloud's own order.
+#include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <future>
 #include <memory>
 
 #include "tsar_io.h"
 #include "tsar_jpeg.h"
 
+// The entries that only --voxel calls are referred to weakly: the tool still links against, and runs with, a library that lacks them, and
+// refuses the switch there.
+extern "C" {
+void tsar_default_cloud_voxels_params(tsar_cloud_voxels_params* p) __attribute__((weak));
+int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2, int n_tol, const float* tol,
+                          int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
+                          int mem) __attribute__((weak));
+}
+
 int main(int argc, char** argv) {
     if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
-        printf("usage: tsar_fusion <mslp_dir> [--num_consistent= N] [--reproj_error= PX] [--depth_diff= REL] [--angle= DEG] [--used_list= 0|1] [--gpu=K] [--geom]\n"
-               "       --geom: fuse APD/%%08d/TSAR_geom_disp.dmb + TSAR_geom_normals.dmb instead of TSAR_disp.dmb + TSAR_normals.dmb\n");
+        printf("usage: tsar_fusion <mslp_dir> [--num_consistent= N] [--reproj_error= PX] [--depth_diff= REL] [--angle= DEG] [--used_list= 0|1] [--gpu=K] [--geom] [--voxel=V]\n"
+               "       --geom: fuse APD/%%08d/TSAR_geom_disp.dmb + TSAR_geom_normals.dmb instead of TSAR_disp.dmb + TSAR_normals.dmb\n"
+               "       --voxel=V: write one point per occupied voxel of edge V (the one nearest the voxel's centre, its whole record)\n");
         return argc < 2 ? 1 : 0;
     }
     std::string dir = argv[1];
@@ -23,6 +37,7 @@ int main(int argc, char** argv) {
     tsar_fusion_params prm;
     tsar_default_fusion_params(&prm);
     int gpu = 0;
+    float voxel = 0.0f;         // --voxel=V: thin the fused cloud (0: off)
     bool geom = false;          // --geom: the geometric-consistency pass's maps (tsar_gipuma --all --geom_consistency)
     for (int i = 2; i < argc; i++) {
         const char* a = argv[i];
@@ -40,6 +55,13 @@ int main(int argc, char** argv) {
         else if ((v = value("--used_list="))) prm.used_list = atoi(v);
         else if ((v = value("--gpu="))) gpu = atoi(v);
         else if (!strcmp(a, "--geom")) geom = true;
+        else if ((v = value("--voxel="))) {
+            char* end = nullptr;
+            const double t = strtod(v, &end);
+            if (end == v || *end != '\0' || !(t > 0.0) || !((float)t <= FLT_MAX) || !((float)t > 0.0f)) { fprintf(stderr, "--voxel=V must be a finite number > 0\n"); return 1; }
+            voxel = (float)t;
+            if (!tsar_cloud_voxels_ctx || !tsar_default_cloud_voxels_params) { fprintf(stderr, "--voxel: this libtsar_hip.so has no tsar_cloud_voxels\n"); return 1; }
+        }
         else printf("Command-line parameter warning: unknown option %s\n", a);
     }
     printf("num_consistent: %d\nreproj_error: %g\ndepth_diff: %g\nangle: %g\nused_list: %d\n", prm.num_consistent, prm.reproj_error, prm.depth_diff, prm.angle_deg, prm.used_list);
@@ -105,6 +127,26 @@ int main(int argc, char** argv) {
     const int rc = tsar_fuse(gpu, n, w, h, cams.data(), pd.data(), pn.data(), pg.data(), TSAR_MEM_HOST, off.data(), idx.data(), &prm, pts.get(), cap, &cnt);
     if (rc != TSAR_OK) { fprintf(stderr, "tsar_fuse failed: %d\n", rc); return 1; }
     if (cnt > cap) cnt = cap;
+    if (voxel > 0.0f) {
+        if (cnt > INT32_MAX) { fprintf(stderr, "--voxel: more than 2^31 - 1 fused points\n"); return 1; }
+        tsar_cloud_voxels_params vp;
+        tsar_default_cloud_voxels_params(&vp);
+        vp.voxel = voxel;
+        std::vector<int32_t> rep((size_t)cnt + 1);
+        int64_t n_voxels = 0;
+        tsar_ctx* ctx = nullptr;
+        if (tsar_create(gpu, &ctx) != TSAR_OK) { fprintf(stderr, "tsar_create failed\n"); return 1; }
+        const int vrc = tsar_cloud_voxels_ctx(ctx, pts.get(), cnt, 9, &vp, nullptr, 0, nullptr, nullptr, cnt, rep.data(), nullptr, nullptr, &n_voxels, nullptr, TSAR_MEM_HOST);
+        if (vrc != TSAR_OK) fprintf(stderr, "%s\n", tsar_last_error(ctx));
+        tsar_destroy(ctx);
+        if (vrc != TSAR_OK) return 1;
+        // the representatives in the cloud's own order: ascending indices, so the records move towards the front in place
+        std::sort(rep.begin(), rep.begin() + n_voxels);
+        for (int64_t v = 0; v < n_voxels; v++)
+            if ((int64_t)rep[(size_t)v] != v) memmove(pts.get() + 9 * (size_t)v, pts.get() + 9 * (size_t)rep[(size_t)v], 9 * sizeof(float));
+        printf("--voxel=%g: %lld points -> %lld voxels\n", (double)voxel, (long long)cnt, (long long)n_voxels);
+        cnt = n_voxels;
+    }
     const std::string out = dir + "APD/APD_TSAR.ply";
     if (!write_cloud_ply(out, pts.get(), cnt)) { fprintf(stderr, "cannot write %s\n", out.c_str()); return 1; }
     printf("%lld points -> %s\n", (long long)cnt, out.c_str());
