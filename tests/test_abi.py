@@ -20,6 +20,34 @@ def test_header_and_binding_agree():
     assert _declared() == sorted(api.ABI_SYMBOLS)
 
 
+def _signatures():
+    """{name: (return type, argument count)} of every `type name(args);` in the header, comments stripped; the count is the number of
+    top-level commas plus one (no declaration nests parentheses), 0 for `void` or nothing"""
+    txt = open(os.path.join(ROOT, "include", "tsar.h")).read()
+    txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    sigs = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[ *]+)(tsar_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        assert name not in sigs, name
+        sigs[name] = (ret.replace(" ", ""), 0 if args.strip() in ("", "void") else args.count(",") + 1)
+    return sigs
+
+
+def test_binding_signatures_follow_the_header():
+    """every declaration has an _ABI entry, in the header's order, with the header's argument count and return type; load_library
+    sets both fields of every function"""
+    sigs = _signatures()
+    assert sorted(sigs) == _declared()                     # the parse misses no declaration (84 today)
+    assert list(api._ABI) == list(sigs) == api.ABI_SYMBOLS
+    restypes = {"int": ctypes.c_int, "void": None, "constchar*": ctypes.c_char_p, "void*": ctypes.c_void_p}
+    L = api.load_library()
+    for name, (ret, n_args) in sigs.items():
+        restype, argtypes = api._ABI[name]
+        assert len(argtypes) == n_args, (name, len(argtypes), n_args)
+        assert restype is restypes[ret], (name, restype, ret)
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
 def test_library_exports_every_declared_symbol():
     import __graft_entry__ as ge
     if not os.path.exists(api.LIB_PATH):

@@ -7,6 +7,7 @@ Buffers may be numpy arrays (host) or torch CUDA tensors (device, zero-copy via 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -85,27 +86,107 @@ class KernelTiming(C.Structure):
 # the reference's spixel_info (gSLICr_spixel_info.h:11-17), the record of tsar_selftest_slic_stage's centre arrays
 SPIXEL_DTYPE = np.dtype([("center", np.float32, 2), ("color", np.float32, 4), ("id", np.int32), ("n", np.int32)])
 
-# every symbol include/tsar.h declares (tests check that the library exports exactly these)
-ABI_SYMBOLS = [
-    "tsar_create", "tsar_destroy", "tsar_last_error", "tsar_version", "tsar_get_stream", "tsar_synchronize",
-    "tsar_default_params", "tsar_set_params", "tsar_set_views", "tsar_set_views_u8", "tsar_set_view_subset",
-    "tsar_pm_init", "tsar_pm_iterate", "tsar_pm_iterate_final", "tsar_pm_sweep", "tsar_set_sweep_counter", "tsar_pm_cost_planes", "tsar_set_plane", "tsar_get_plane",
-    "tsar_load_planes", "tsar_compute_disp", "tsar_compute_disp_final", "tsar_depth_to_plane", "tsar_get_result",
-    "tsar_pyramid_views", "tsar_upsample_planes", "tsar_compute_disp_final_upsampled", "tsar_get_view_image",
-    "tsar_set_geom_depths", "tsar_clear_geom", "tsar_pm_rescore", "tsar_get_geom_matrices",
-    "tsar_geom_pyramid", "tsar_pyramid_planes", "tsar_upsample_merge",
-    "tsar_default_geom_check_params", "tsar_geom_check",
-    "tsar_default_geom_reproject_params", "tsar_geom_reproject", "tsar_pm_merge_depths",
-    "tsar_default_plane_prior_params", "tsar_set_plane_prior", "tsar_clear_plane_prior", "tsar_get_plane_prior",
-    "tsar_default_plane_prior_build_params", "tsar_build_plane_prior",
-    "tsar_set_reliable_mask", "tsar_get_reliable_mask", "tsar_lrdiff", "tsar_getview", "tsar_wmf", "tsar_set_regions", "tsar_detect_weak_texture", "tsar_ransac_regions",
-    "tsar_set_region_planes", "tsar_fake_depth", "tsar_fill_textureless",
-    "tsar_default_slic_settings", "tsar_slic", "tsar_default_fusion_params", "tsar_fuse", "tsar_fuse_ctx",
-    "tsar_default_cloud_distance_params", "tsar_cloud_distance_ctx", "tsar_cloud_distance",
-    "tsar_default_cloud_voxels_params", "tsar_cloud_voxels_ctx", "tsar_cloud_voxels",
-    "tsar_host_alloc", "tsar_host_free", "tsar_device_alloc", "tsar_device_free", "tsar_device_write", "tsar_peer_copy", "tsar_enable_kernel_timing", "tsar_reset_kernel_timing", "tsar_get_kernel_timing",
-    "tsar_selftest_divide", "tsar_selftest_divide_random", "tsar_selftest_sqrt", "tsar_selftest_sweep_census", "tsar_selftest_prune_census", "tsar_selftest_sweep_repeat", "tsar_selftest_slic_stage",
-]
+# every function include/tsar.h declares, in the header's order: name -> (restype, argtypes).  tests/test_abi.py holds the names, the
+# argument counts and the return types to the header; __graft_entry__.build() holds the built library to the names.
+_P, _I, _F, _Z, _L, _U64, _p = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_uint64, C.POINTER
+_SET_VIEWS = (_I, [_P, _I, _I, _I, _p(_P), _I, _p(Camera)])
+_FUSE = (_I, [_I, _I, _I, _I, _p(Camera), _p(_P), _p(_P), _p(_P), _I, _P, _P, _p(FusionParams), _P, _L, _p(_L)])
+_CLOUD_DISTANCE = (_I, [_I, _P, _L, _I, _P, _L, _I, _p(CloudDistanceParams), _I, _P, _P, _P, _P, _p(_L), _p(_L), _I])
+_CLOUD_VOXELS = (_I, [_I, _P, _L, _I, _p(CloudVoxelsParams), _P, _I, _P, _P, _L, _P, _P, _P, _p(_L), _p(_L), _I])
+
+
+def _on_ctx(sig):
+    """the signature of a context-free entry's _ctx twin: the context in place of the device index"""
+    return sig[0], [_P] + sig[1][1:]
+
+
+_ABI = {
+    "tsar_create": (_I, [_I, _p(_P)]),
+    "tsar_destroy": (_I, [_P]),
+    "tsar_last_error": (C.c_char_p, [_P]),
+    "tsar_version": (C.c_char_p, []),
+    "tsar_get_stream": (_I, [_P, _p(_P)]),
+    "tsar_synchronize": (_I, [_P]),
+    "tsar_default_params": (None, [_p(Params)]),
+    "tsar_set_params": (_I, [_P, _p(Params)]),
+    "tsar_set_views": _SET_VIEWS,
+    "tsar_set_views_u8": _SET_VIEWS,
+    "tsar_set_view_subset": (_I, [_P, _I, _P]),
+    "tsar_pm_init": (_I, [_P]),
+    "tsar_pm_iterate": (_I, [_P, _I]),
+    "tsar_pm_iterate_final": (_I, [_P, _I, _P, _I]),
+    "tsar_pm_cost_planes": (_I, [_P, _P, _I, _P, _P, _P]),
+    "tsar_set_plane": (_I, [_P, _P, _P, _I]),
+    "tsar_pm_sweep": (_I, [_P, _I, _I, _I]),
+    "tsar_set_sweep_counter": (_I, [_P, _I]),
+    "tsar_get_plane": (_I, [_P, _P, _P, _P, _P, _I]),
+    "tsar_load_planes": (_I, [_P, _P, _P, _I]),
+    "tsar_compute_disp": (_I, [_P]),
+    "tsar_compute_disp_final": (_I, [_P, _P, _P, _I]),
+    "tsar_depth_to_plane": (_I, [_P]),
+    "tsar_pyramid_views": (_I, [_P, _P]),
+    "tsar_upsample_planes": (_I, [_P, _P]),
+    "tsar_compute_disp_final_upsampled": (_I, [_P, _P, _I]),
+    "tsar_get_view_image": (_I, [_P, _I, _P, _I]),
+    "tsar_set_geom_depths": (_I, [_P, _I, _p(_P), _I, _F, _F]),
+    "tsar_clear_geom": (_I, [_P]),
+    "tsar_pm_rescore": (_I, [_P]),
+    "tsar_get_geom_matrices": (_I, [_P, _I, _P, _P]),
+    "tsar_geom_pyramid": (_I, [_P, _P]),
+    "tsar_pyramid_planes": (_I, [_P, _P]),
+    "tsar_upsample_merge": (_I, [_P, _P]),
+    "tsar_default_geom_check_params": (None, [_p(GeomCheckParams)]),
+    "tsar_geom_check": (_I, [_P, _P, _p(GeomCheckParams), _P, _P, _I]),
+    "tsar_default_geom_reproject_params": (None, [_p(GeomReprojectParams)]),
+    "tsar_geom_reproject": (_I, [_P, _p(GeomReprojectParams), _P, _P, _I]),
+    "tsar_pm_merge_depths": (_I, [_P, _P, _I, _p(_L)]),
+    "tsar_default_plane_prior_params": (None, [_p(PlanePriorParams)]),
+    "tsar_set_plane_prior": (_I, [_P, _P, _P, _I, _p(PlanePriorParams)]),
+    "tsar_clear_plane_prior": (_I, [_P]),
+    "tsar_get_plane_prior": (_I, [_P, _P, _I]),
+    "tsar_default_plane_prior_build_params": (None, [_p(PlanePriorBuildParams)]),
+    "tsar_build_plane_prior": (_I, [_P, _P, _P, _I, _p(PlanePriorBuildParams), _P, _P, _P]),
+    "tsar_get_result": (_I, [_P, _P, _P, _P, _P, _I]),
+    "tsar_set_reliable_mask": (_I, [_P, _P, _I]),
+    "tsar_get_reliable_mask": (_I, [_P, _P, _I]),
+    "tsar_lrdiff": (_I, [_P]),
+    "tsar_getview": (_I, [_P]),
+    "tsar_wmf": (_I, [_P, _I, _I]),
+    "tsar_set_regions": (_I, [_P, _P, _I, _P, _P, _I]),
+    "tsar_detect_weak_texture": (_I, [_P, _P, _I, _p(_I), _P, _P, _I]),
+    "tsar_ransac_regions": (_I, [_P, _P, _P]),
+    "tsar_set_region_planes": (_I, [_P, _P]),
+    "tsar_fake_depth": (_I, [_P, _P, _I]),
+    "tsar_fill_textureless": (_I, [_P]),
+    "tsar_default_slic_settings": (None, [_p(SlicSettings)]),
+    "tsar_slic": (_I, [_P, _P, _I, _I, _p(SlicSettings), _P, _I]),
+    "tsar_default_fusion_params": (None, [_p(FusionParams)]),
+    "tsar_fuse_ctx": _on_ctx(_FUSE),
+    "tsar_fuse": _FUSE,
+    "tsar_default_cloud_distance_params": (None, [_p(CloudDistanceParams)]),
+    "tsar_cloud_distance_ctx": _on_ctx(_CLOUD_DISTANCE),
+    "tsar_cloud_distance": _CLOUD_DISTANCE,
+    "tsar_default_cloud_voxels_params": (None, [_p(CloudVoxelsParams)]),
+    "tsar_cloud_voxels_ctx": _on_ctx(_CLOUD_VOXELS),
+    "tsar_cloud_voxels": _CLOUD_VOXELS,
+    "tsar_host_alloc": (_P, [_Z]),
+    "tsar_host_free": (None, [_P]),
+    "tsar_device_alloc": (_P, [_I, _Z]),
+    "tsar_device_free": (None, [_I, _P]),
+    "tsar_device_write": (_I, [_I, _P, _P, _Z]),
+    "tsar_peer_copy": (_I, [_I, _P, _I, _P, _Z]),
+    "tsar_enable_kernel_timing": (_I, [_P, _I]),
+    "tsar_reset_kernel_timing": (_I, [_P]),
+    "tsar_get_kernel_timing": (_I, [_P, _p(KernelTiming), _I, _p(_I)]),
+    "tsar_selftest_sqrt": (_I, [_P, _I, _U64, _p(_U64)]),
+    "tsar_selftest_divide": (_I, [_P, _P, _P, _P, _Z, _P, _P, _I]),
+    "tsar_selftest_divide_random": (_I, [_P, _I, _U64, _I, _I, _p(_U64), _p(_U64)]),
+    "tsar_selftest_sweep_census": (_I, [_P, _I, _p(_U64)]),
+    "tsar_selftest_sweep_repeat": (_I, [_P, _I, _P, _p(_U64)]),
+    "tsar_selftest_prune_census": (_I, [_P, _I, _p(C.c_uint32)]),
+    "tsar_selftest_slic_stage": (_I, [_P, _I, _I, _I, _I, _I, _p(SlicSettings), _P, _P, _P]),
+}
+ABI_SYMBOLS = list(_ABI)      # (tests check that the library exports exactly these)
 
 _lib = None
 
@@ -119,111 +200,10 @@ def load_library(path: str = LIB_PATH):
         raise ImportError(f"{path} not found: build it with `make -C tsar-mvs_amd/csrc` "
                           "(or __graft_entry__.build()); there is no CPU fallback")
     L = C.CDLL(path)
-    L.tsar_last_error.restype = C.c_char_p
-    L.tsar_last_error.argtypes = [C.c_void_p]
-    L.tsar_version.restype = C.c_char_p
-    L.tsar_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.tsar_destroy.argtypes = [C.c_void_p]
-    L.tsar_default_params.restype = None
-    L.tsar_default_params.argtypes = [C.POINTER(Params)]
-    L.tsar_default_slic_settings.restype = None
-    L.tsar_default_slic_settings.argtypes = [C.POINTER(SlicSettings)]
-    L.tsar_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
-    L.tsar_set_views.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(Camera)]
-    L.tsar_set_views_u8.argtypes = L.tsar_set_views.argtypes
-    L.tsar_set_view_subset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.tsar_pm_init.argtypes = [C.c_void_p]
-    L.tsar_pm_iterate.argtypes = [C.c_void_p, C.c_int]
-    L.tsar_pm_iterate_final.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.tsar_pm_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.tsar_set_sweep_counter.argtypes = [C.c_void_p, C.c_int]
-    L.tsar_pm_cost_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tsar_set_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_get_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_load_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_compute_disp.argtypes = [C.c_void_p]
-    L.tsar_compute_disp_final.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_depth_to_plane.argtypes = [C.c_void_p]
-    L.tsar_pyramid_views.argtypes = [C.c_void_p, C.c_void_p]
-    L.tsar_upsample_planes.argtypes = [C.c_void_p, C.c_void_p]
-    L.tsar_compute_disp_final_upsampled.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_get_view_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.tsar_set_geom_depths.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_float, C.c_float]
-    L.tsar_clear_geom.argtypes = [C.c_void_p]
-    L.tsar_pm_rescore.argtypes = [C.c_void_p]
-    L.tsar_get_geom_matrices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.tsar_geom_pyramid.argtypes = [C.c_void_p, C.c_void_p]
-    L.tsar_pyramid_planes.argtypes = [C.c_void_p, C.c_void_p]
-    L.tsar_upsample_merge.argtypes = [C.c_void_p, C.c_void_p]
-    L.tsar_default_geom_check_params.restype = None
-    L.tsar_default_geom_check_params.argtypes = [C.POINTER(GeomCheckParams)]
-    L.tsar_geom_check.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(GeomCheckParams), C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_default_geom_reproject_params.restype = None
-    L.tsar_default_geom_reproject_params.argtypes = [C.POINTER(GeomReprojectParams)]
-    L.tsar_geom_reproject.argtypes = [C.c_void_p, C.POINTER(GeomReprojectParams), C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_pm_merge_depths.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-    L.tsar_default_plane_prior_params.restype = None
-    L.tsar_default_plane_prior_params.argtypes = [C.POINTER(PlanePriorParams)]
-    L.tsar_set_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PlanePriorParams)]
-    L.tsar_clear_plane_prior.argtypes = [C.c_void_p]
-    L.tsar_get_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    if hasattr(L, "tsar_build_plane_prior"):          # (a library built before the builder, loaded through TSAR_LIB for an A/B run)
-        L.tsar_default_plane_prior_build_params.restype = None
-        L.tsar_default_plane_prior_build_params.argtypes = [C.POINTER(PlanePriorBuildParams)]
-        L.tsar_build_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PlanePriorBuildParams), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tsar_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_set_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_get_reliable_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_host_alloc.restype = C.c_void_p
-    L.tsar_host_alloc.argtypes = [C.c_size_t]
-    L.tsar_host_free.restype = None
-    L.tsar_host_free.argtypes = [C.c_void_p]
-    L.tsar_device_alloc.restype = C.c_void_p
-    L.tsar_device_alloc.argtypes = [C.c_int, C.c_size_t]
-    L.tsar_device_free.restype = None
-    L.tsar_device_free.argtypes = [C.c_int, C.c_void_p]
-    L.tsar_device_write.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.tsar_peer_copy.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.tsar_lrdiff.argtypes = [C.c_void_p]
-    L.tsar_getview.argtypes = [C.c_void_p]
-    L.tsar_wmf.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.tsar_set_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_detect_weak_texture.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_ransac_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tsar_set_region_planes.argtypes = [C.c_void_p, C.c_void_p]
-    L.tsar_fake_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_fill_textureless.argtypes = [C.c_void_p]
-    L.tsar_slic.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(SlicSettings), C.c_void_p, C.c_int]
-    L.tsar_default_fusion_params.restype = None
-    L.tsar_default_fusion_params.argtypes = [C.POINTER(FusionParams)]
-    L.tsar_fuse.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Camera), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
-                            C.c_void_p, C.c_void_p, C.POINTER(FusionParams), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-    L.tsar_fuse_ctx.argtypes = [C.c_void_p] + list(L.tsar_fuse.argtypes[1:])
-    if hasattr(L, "tsar_cloud_distance_ctx"):         # (a library built before the operator, loaded through TSAR_LIB for an A/B run)
-        L.tsar_default_cloud_distance_params.restype = None
-        L.tsar_default_cloud_distance_params.argtypes = [C.POINTER(CloudDistanceParams)]
-        L.tsar_cloud_distance.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(CloudDistanceParams), C.c_int,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
-        L.tsar_cloud_distance_ctx.argtypes = [C.c_void_p] + list(L.tsar_cloud_distance.argtypes[1:])
-    if hasattr(L, "tsar_cloud_voxels_ctx"):           # (a library built before the operator, loaded through TSAR_LIB for an A/B run)
-        L.tsar_default_cloud_voxels_params.restype = None
-        L.tsar_default_cloud_voxels_params.argtypes = [C.POINTER(CloudVoxelsParams)]
-        L.tsar_cloud_voxels.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.POINTER(CloudVoxelsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
-        L.tsar_cloud_voxels_ctx.argtypes = [C.c_void_p] + list(L.tsar_cloud_voxels.argtypes[1:])
-    L.tsar_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.tsar_synchronize.argtypes = [C.c_void_p]
-    L.tsar_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int]
-    L.tsar_reset_kernel_timing.argtypes = [C.c_void_p]
-    L.tsar_get_kernel_timing.argtypes = [C.c_void_p, C.POINTER(KernelTiming), C.c_int, C.POINTER(C.c_int)]
-    L.tsar_selftest_divide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
-    L.tsar_selftest_sweep_census.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
-    if hasattr(L, "tsar_selftest_prune_census"):      # (a library built before the pruning kernels, loaded through TSAR_LIB for an A/B run)
-        L.tsar_selftest_prune_census.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
-    L.tsar_selftest_sweep_repeat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
-    L.tsar_selftest_sqrt.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
-    L.tsar_selftest_divide_random.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    L.tsar_selftest_slic_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SlicSettings), C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(L, name, None)       # None: a library built before the entry, loaded through TSAR_LIB for an A/B run; a call raises AttributeError
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -256,6 +236,55 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p), MEM_HOST
 
 
+def _coerce(a, dtype, shape=None, name="the array", tensors=None, typed=True):
+    """a caller's array (or None) as the library takes it.  tensors says which torch tensors stay as they are: None = none, "device" =
+    device tensors, "any" = CPU tensors too; a tensor that stays must be of `dtype` if `typed`.  Everything else goes through numpy and
+    comes back C-contiguous and of `dtype`, copied only where it is not that already.  shape: the exact shape to insist on."""
+    if a is None:
+        return None
+    if _is_torch(a) and (tensors == "any" or (tensors == "device" and a.is_cuda)):
+        assert not typed or str(a.dtype) == "torch." + np.dtype(dtype).name, "%s must be a %s tensor" % (name, np.dtype(dtype).name)
+    else:
+        a = np.ascontiguousarray(a.numpy() if tensors and _is_torch(a) else a, dtype)
+    assert shape is None or tuple(a.shape) == tuple(shape), "%s has shape %s, not %s" % (name, tuple(a.shape), tuple(shape))
+    return a
+
+
+def _buf(a, dtype, shape=None, name="the array", tensors=None, typed=True):
+    """_coerce's array, which the caller keeps alive over the call, with _ptr's pointer and memory kind: (array, pointer, kind)"""
+    a = _coerce(a, dtype, shape, name, tensors, typed)
+    return (a,) + _ptr(a)
+
+
+def _ptr_array(bufs, n):
+    """the n pointers of the _buf triples (NULL past the last) as a void* array"""
+    return (C.c_void_p * n)(*(p for _, p, _ in bufs))
+
+
+def _one_kind(bufs, what):
+    """the memory kind that the _buf triples share (None arrays aside; MEM_HOST if nothing is left); device tensors lie on one device"""
+    kinds = {kind for a, _, kind in bufs if a is not None}
+    assert len(kinds) <= 1, what + " must live in the same memory space"
+    assert len({a.device for a, _, kind in bufs if kind == MEM_DEVICE}) <= 1, what + " must live on one device"
+    return kinds.pop() if kinds else MEM_HOST
+
+
+def _outputs(spec, want, target=None, empty=np.empty):
+    """uninitialised outputs for the keys of spec = {key: (shape, dtype)} that `want` names: torch tensors on the torch.device `target`,
+    or (target None) host arrays from `empty`"""
+    spec = {k: v for k, v in spec.items() if k in want}
+    if target is None:
+        return {k: empty(shape, dt) for k, (shape, dt) in spec.items()}
+    import torch
+    return {k: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=target) for k, (shape, dt) in spec.items()}
+
+
+def _cameras(K, R, t, n):
+    """the Camera array of n views from their K [n, 3, 3], R [n, 3, 3] and t [n, 3]"""
+    rec = np.concatenate([np.asarray(a, np.float32).reshape(n, k) for a, k in ((K, 9), (R, 9), (t, 3))], axis=1)
+    return (Camera * n).from_buffer_copy(rec)
+
+
 class Matcher:
     """One context = one GPU.  Mirrors the order in which runGipuma drives the GPU operators."""
 
@@ -267,7 +296,6 @@ class Matcher:
             raise TsarError(rc, "tsar_create failed (is a HIP device visible?)")
         self.w = self.h = self.n_views = 0
         self.device = device
-        self._keep = []
         self.plane_prior_params = None     # the struct the last set_plane_prior passed, while that prior is installed
 
     def close(self):
@@ -297,29 +325,9 @@ class Matcher:
         n = len(images)
         first = images[0]
         h, w = int(first.shape[0]), int(first.shape[1])
-        ptrs = (C.c_void_p * n)()
-        kinds = set()
-        for i, im in enumerate(images):
-            assert tuple(im.shape) == (h, w)
-            if not _is_torch(im):
-                im = np.ascontiguousarray(im, dtype=np.uint8 if u8 else np.float32)
-                self._keep.append(im)
-            elif u8:
-                assert str(im.dtype) == "torch.uint8" and im.is_contiguous()
-            p, kind = _ptr(im)
-            ptrs[i] = p
-            kinds.add(kind)
-        assert len(kinds) == 1, "all images must live in the same memory space"
-        cams = (Camera * n)()
-        K = np.asarray(K, np.float32).reshape(n, 9)
-        R = np.asarray(R, np.float32).reshape(n, 9)
-        t = np.asarray(t, np.float32).reshape(n, 3)
-        for i in range(n):
-            cams[i].K[:] = K[i].tolist()
-            cams[i].R[:] = R[i].tolist()
-            cams[i].t[:] = t[i].tolist()
-        self._chk((self.L.tsar_set_views_u8 if u8 else self.L.tsar_set_views)(self._ctx, n, w, h, ptrs, kinds.pop(), cams))
-        self._keep.clear()
+        bufs = [_buf(im, np.uint8 if u8 else np.float32, (h, w), "image %d" % i, tensors="any", typed=u8) for i, im in enumerate(images)]
+        self._chk((self.L.tsar_set_views_u8 if u8 else self.L.tsar_set_views)(self._ctx, n, w, h, _ptr_array(bufs, n), _one_kind(bufs, "all images"),
+                                                                              _cameras(K, R, t, n)))
         self.w, self.h, self.n_views = w, h, n
         self.plane_prior_params = None     # tsar_set_views removes a prior
 
@@ -336,8 +344,7 @@ class Matcher:
 
     def pm_iterate_final(self, iters: int, text):
         """the kernels' `final == true` mode; text [h, w] = lines->text (-1: pixel is left untouched)"""
-        t = text if _is_torch(text) else np.ascontiguousarray(text, np.float32)
-        p, kind = _ptr(t)
+        text, p, kind = _buf(text, np.float32, tensors="any", typed=False)
         self._chk(self.L.tsar_pm_iterate_final(self._ctx, iters, p, kind))
 
     def pm_sweep(self, colour: int, do_prop: bool = True, do_refine: bool = True):
@@ -369,12 +376,9 @@ class Matcher:
 
     # ---- plane <-> depth ----
     def load_planes(self, depth, normal_world):
-        depth_keep = depth if _is_torch(depth) else np.ascontiguousarray(depth, np.float32)
-        normal_keep = normal_world if _is_torch(normal_world) else np.ascontiguousarray(normal_world, np.float32)
-        d, kd = _ptr(depth_keep)
-        n, kn = _ptr(normal_keep)
-        assert kd == kn
-        self._chk(self.L.tsar_load_planes(self._ctx, d, n, kd))
+        d = _buf(depth, np.float32, tensors="any", typed=False)
+        n = _buf(normal_world, np.float32, tensors="any", typed=False)
+        self._chk(self.L.tsar_load_planes(self._ctx, d[1], n[1], _one_kind((d, n), "depth and normal_world")))
 
     def compute_disp(self):
         self._chk(self.L.tsar_compute_disp(self._ctx))
@@ -408,8 +412,7 @@ class Matcher:
     def compute_disp_final_upsampled(self, text):
         """compute_disp_final with the planes the last upsample_planes kept; text [h, w] = lines->text (-1 textureless, 1 otherwise),
         a numpy array or a torch device tensor"""
-        t = text if _is_torch(text) else np.ascontiguousarray(text, np.float32)
-        p, kind = _ptr(t)
+        text, p, kind = _buf(text, np.float32, tensors="any", typed=False)
         self._chk(self.L.tsar_compute_disp_final_upsampled(self._ctx, p, kind))
 
     # ---- geometric consistency ----
@@ -417,21 +420,9 @@ class Matcher:
         """install the source views' depth maps for the geometric-consistency term (tsar_set_geom_depths): depths[v] is view v's
         [h, w] depth in its own camera (numpy or torch; <= 0 = no estimate) or None (no term for v); depths[0] is ignored.
         weight = lambda, clip = tau in pixels (ACMM's defaults)."""
-        n = len(depths)
-        ptrs = (C.c_void_p * n)()
-        keep, kinds = [], set()
-        for v, d in enumerate(depths):
-            if v == 0 or d is None:
-                continue
-            if not _is_torch(d):
-                d = np.ascontiguousarray(d, np.float32)
-            assert tuple(d.shape) == (self.h, self.w), "depth map %d has shape %s, the views are %dx%d" % (v, tuple(d.shape), self.w, self.h)
-            keep.append(d)
-            p, kind = _ptr(d)
-            ptrs[v] = p
-            kinds.add(kind)
-        assert len(kinds) <= 1, "all depth maps must live in the same memory space"
-        self._chk(self.L.tsar_set_geom_depths(self._ctx, n, ptrs, kinds.pop() if kinds else MEM_HOST, float(weight), float(clip)))
+        bufs = [_buf(d if v else None, np.float32, (self.h, self.w), "depth map %d" % v, tensors="any", typed=False) for v, d in enumerate(depths)]
+        n = len(bufs)
+        self._chk(self.L.tsar_set_geom_depths(self._ctx, n, _ptr_array(bufs, n), _one_kind(bufs, "all depth maps"), float(weight), float(clip)))
 
     def clear_geom(self):
         """remove the geometric-consistency term (tsar_clear_geom)"""
@@ -456,14 +447,10 @@ class Matcher:
         device tensors; a pixel whose depth is not in (0, inf) or whose normal is not finite has no prior.  Every plane-scoring entry then
         adds weight_depth * min(|D - Dp| / Dp / depth_clip, 1) + weight_normal * min((1 - n.q) / normal_clip, 1) to a valid hypothesis's
         cost, normal_clip = 1 - cos(angle_clip_deg) rounded once from float64.  The struct passed is kept as plane_prior_params."""
-        depth_keep = depth if _is_torch(depth) else np.ascontiguousarray(depth, np.float32)
-        normal_keep = normal_world if _is_torch(normal_world) else np.ascontiguousarray(normal_world, np.float32)
-        assert tuple(depth_keep.shape) == (self.h, self.w) and tuple(normal_keep.shape) == (self.h, self.w, 3), "the prior must be [h, w] and [h, w, 3]"
-        d, kd = _ptr(depth_keep)
-        n, kn = _ptr(normal_keep)
-        assert kd == kn, "depth and normal_world must live in the same memory space"
+        d = _buf(depth, np.float32, (self.h, self.w), "the prior's depth", tensors="any", typed=False)
+        n = _buf(normal_world, np.float32, (self.h, self.w, 3), "the prior's normal_world", tensors="any", typed=False)
         p = PlanePriorParams(float(weight_depth), float(weight_normal), float(depth_clip), float(1.0 - np.cos(np.deg2rad(np.float64(angle_clip_deg)))))
-        self._chk(self.L.tsar_set_plane_prior(self._ctx, d, n, kd, C.byref(p)))
+        self._chk(self.L.tsar_set_plane_prior(self._ctx, d[1], n[1], _one_kind((d, n), "depth and normal_world"), C.byref(p)))
         self.plane_prior_params = p
 
     def clear_plane_prior(self):
@@ -486,36 +473,18 @@ class Matcher:
         what set_plane_prior takes) and / or "level" ([h, w] uint8, 255 = no prior; depth and normal are 0 there), as `want` names
         them: torch tensors on the device when the inputs are, or with device=True; numpy arrays otherwise.  Nothing in the context
         changes."""
-        on_device = _is_torch(depth) and depth.is_cuda
-        if score is not None:
-            assert (_is_torch(score) and score.is_cuda) == on_device, "depth and score must live in the same memory space"
-        if on_device:
-            assert str(depth.dtype) == "torch.float32" and (score is None or str(score.dtype) == "torch.float32")
-        else:
-            depth = np.ascontiguousarray(depth.numpy() if _is_torch(depth) else depth, np.float32)
-            if score is not None:
-                score = np.ascontiguousarray(score.numpy() if _is_torch(score) else score, np.float32)
-        assert tuple(depth.shape) == (self.h, self.w), "the depth map has shape %s, the views are %dx%d" % (tuple(depth.shape), self.w, self.h)
-        assert score is None or tuple(score.shape) == (self.h, self.w), "the score must be [h, w]"
-        if device and not on_device:
+        bufs = [_buf(a, np.float32, (self.h, self.w), name, tensors="device") for a, name in ((depth, "the depth map"), (score, "the score"))]
+        kind = _one_kind(bufs, "depth and score")
+        if device and kind == MEM_HOST:
             import torch
             dev = torch.device("cuda", self.device)
-            depth = torch.from_numpy(depth).to(dev)
-            score = torch.from_numpy(score).to(dev) if score is not None else None
-            on_device = True
-        shapes = {"depth": ((self.h, self.w), "float32"), "normal": ((self.h, self.w, 3), "float32"), "level": ((self.h, self.w), "uint8")}
-        res = {}
-        for k, (shape, dt) in shapes.items():
-            if k not in want:
-                continue
-            if on_device:
-                import torch
-                res[k] = torch.empty(shape, dtype=getattr(torch, dt), device=depth.device)
-            else:
-                res[k] = np.empty(shape, dt)
+            bufs = [_buf(None if a is None else torch.from_numpy(a).to(dev), np.float32, tensors="device") for a, _, _ in bufs]
+            kind = _one_kind(bufs, "depth and score")
+        (depth, d, _), (score, s, _) = bufs
+        res = _outputs({"depth": ((self.h, self.w), np.float32), "normal": ((self.h, self.w, 3), np.float32), "level": ((self.h, self.w), np.uint8)},
+                       want, depth.device if kind == MEM_DEVICE else None)
         p = PlanePriorBuildParams(int(cell), int(max_levels))
-        d, kind = _ptr(depth)
-        self._chk(self.L.tsar_build_plane_prior(self._ctx, d, _ptr(score)[0], kind, C.byref(p), _ptr(res.get("depth"))[0],
+        self._chk(self.L.tsar_build_plane_prior(self._ctx, d, s, kind, C.byref(p), _ptr(res.get("depth"))[0],
                                                 _ptr(res.get("normal"))[0], _ptr(res.get("level"))[0]))
         return res
 
@@ -541,25 +510,8 @@ class Matcher:
         as `want` names them: numpy arrays, or torch tensors on depth's device when depth is a torch device tensor.  The mask itself
         is left in the context (get_reliable_mask)."""
         p = GeomCheckParams(float(reproj_error), float(depth_diff), int(min_consistent))
-        on_device = depth is not None and _is_torch(depth) and depth.is_cuda
-        if depth is not None and not on_device:
-            depth = np.ascontiguousarray(depth.numpy() if _is_torch(depth) else depth, np.float32)
-        if depth is not None:
-            assert tuple(depth.shape) == (self.h, self.w), "the depth map has shape %s, the views are %dx%d" % (tuple(depth.shape), self.w, self.h)
-        res = {}
-        if on_device:
-            import torch
-            assert depth.dtype == torch.float32
-            if "count" in want:
-                res["count"] = torch.empty((self.h, self.w), dtype=torch.uint8, device=depth.device)
-            if "depth" in want:
-                res["depth"] = torch.empty((self.h, self.w), dtype=torch.float32, device=depth.device)
-        else:
-            if "count" in want:
-                res["count"] = np.empty((self.h, self.w), np.uint8)
-            if "depth" in want:
-                res["depth"] = np.empty((self.h, self.w), np.float32)
-        d, kind = _ptr(depth)
+        depth, d, kind = _buf(depth, np.float32, (self.h, self.w), "the depth map", tensors="device")
+        res = _outputs({"count": ((self.h, self.w), np.uint8), "depth": ((self.h, self.w), np.float32)}, want, depth.device if kind == MEM_DEVICE else None)
         self._chk(self.L.tsar_geom_check(self._ctx, d, C.byref(p), _ptr(res.get("count"))[0], _ptr(res.get("depth"))[0], kind))
         return res
 
@@ -570,19 +522,11 @@ class Matcher:
         it.  Returns a dict with "depth" ([h, w] float32: Z where count >= min_views, else 0) and / or "count" ([h, w] uint8), as `want`
         names them: numpy arrays, or torch tensors on the context's device with device=True.  Nothing in the context changes."""
         p = GeomReprojectParams(float(depth_diff), int(min_views))
-        res = {}
+        target = None
         if device:
             import torch
-            dev = torch.device("cuda", self.device)
-            if "depth" in want:
-                res["depth"] = torch.empty((self.h, self.w), dtype=torch.float32, device=dev)
-            if "count" in want:
-                res["count"] = torch.empty((self.h, self.w), dtype=torch.uint8, device=dev)
-        else:
-            if "depth" in want:
-                res["depth"] = np.empty((self.h, self.w), np.float32)
-            if "count" in want:
-                res["count"] = np.empty((self.h, self.w), np.uint8)
+            target = torch.device("cuda", self.device)
+        res = _outputs({"depth": ((self.h, self.w), np.float32), "count": ((self.h, self.w), np.uint8)}, want, target)
         self._chk(self.L.tsar_geom_reproject(self._ctx, C.byref(p), _ptr(res.get("depth"))[0], _ptr(res.get("count"))[0], MEM_DEVICE if device else MEM_HOST))
         return res
 
@@ -590,13 +534,7 @@ class Matcher:
         """offer `depth` ([h, w] float32 in the reference camera, numpy or a torch device tensor; values outside [depth_min, depth_max] or
         not finite offer nothing) to the matcher (tsar_pm_merge_depths): the state is rescored, and each pixel takes the plane with its
         own normal through the offered depth where that scores strictly lower.  Returns the number of pixels that took it."""
-        on_device = _is_torch(depth) and depth.is_cuda
-        if not on_device:
-            depth = np.ascontiguousarray(depth.numpy() if _is_torch(depth) else depth, np.float32)
-        else:
-            assert str(depth.dtype) == "torch.float32"
-        assert tuple(depth.shape) == (self.h, self.w), "the depth map has shape %s, the views are %dx%d" % (tuple(depth.shape), self.w, self.h)
-        d, kind = _ptr(depth)
+        depth, d, kind = _buf(depth, np.float32, (self.h, self.w), "the depth map", tensors="device")
         taken = C.c_int64(0)
         self._chk(self.L.tsar_pm_merge_depths(self._ctx, d, kind, C.byref(taken)))
         return int(taken.value)
@@ -604,16 +542,13 @@ class Matcher:
     def get_result(self, want=("depth", "normal", "cost", "confid"), pinned=False, out=None):
         """pinned=True: the result arrays are page-locked (tsar_host_alloc), so the D2H copies run at PCIe rate.
         out: dict of caller-owned arrays to fill instead (e.g. page-locked ones allocated once and reused per view)."""
-        shapes = {"depth": (self.h, self.w), "normal": (self.h, self.w, 3), "cost": (self.h, self.w), "confid": (self.h, self.w)}
-        empty = pinned_empty if pinned else np.empty
-        res = {}
-        for k in ("depth", "normal", "cost", "confid"):
-            if out is not None and k in out:
-                a = out[k]
-                assert a.dtype == np.float32 and tuple(a.shape) == shapes[k] and a.flags["C_CONTIGUOUS"]
-                res[k] = a
-            elif out is None and k in want:
-                res[k] = empty(shapes[k], np.float32)
+        spec = {k: ((self.h, self.w, 3) if k == "normal" else (self.h, self.w), np.float32) for k in ("depth", "normal", "cost", "confid")}
+        if out is None:
+            res = _outputs(spec, want, empty=pinned_empty if pinned else np.empty)
+        else:
+            res = {k: out[k] for k in spec if k in out}
+            for k, a in res.items():
+                assert a.dtype == np.float32 and tuple(a.shape) == spec[k][0] and a.flags["C_CONTIGUOUS"]
         self._chk(self.L.tsar_get_result(self._ctx, _ptr(res.get("depth"))[0], _ptr(res.get("normal"))[0], _ptr(res.get("cost"))[0],
                                          _ptr(res.get("confid"))[0], MEM_HOST))
         return res
@@ -830,13 +765,6 @@ def run_multiscale(matcher: Matcher, levels: int, coarse_iters: int, fine_iters:
     return coarse
 
 
-def _check_cross_view(cross_view, cross_view_depth_diff):
-    if int(cross_view) != cross_view or not 0 <= cross_view <= MAX_VIEWS - 1:
-        raise ValueError("cross_view must be an integer in 0..63")
-    if cross_view and not (cross_view_depth_diff > 0 and np.isfinite(cross_view_depth_diff)):
-        raise ValueError("cross_view_depth_diff must be finite and > 0")
-
-
 def _cross_view_merge(matcher: Matcher, cross_view: int, cross_view_depth_diff: float) -> int:
     """the sources' maps rendered into the reference camera (kept where `cross_view` views agree) and offered to the matcher, on the
     device; the merge rescores first, so it stands in for rescore()"""
@@ -853,7 +781,14 @@ def _install_prior(matcher: Matcher, prior, prior_params):
 _BUILD_PRIOR_KEYS = {"cell": "cell", "max_levels": "max_levels", "reproj_error": "check", "depth_diff": "check", "min_consistent": "check"}
 
 
-def _check_prior_arguments(prior, prior_params, build_prior):
+def _check_geom_pass(counts, what, cross_view, cross_view_depth_diff, prior, prior_params, build_prior):
+    """the argument checks of both geometric passes; counts: the pass's own iteration (and level) counts, `what` names them"""
+    if any(c < 0 for c in counts):
+        raise ValueError(what + " must be >= 0")
+    if int(cross_view) != cross_view or not 0 <= cross_view <= MAX_VIEWS - 1:
+        raise ValueError("cross_view must be an integer in 0..63")
+    if cross_view and not (cross_view_depth_diff > 0 and np.isfinite(cross_view_depth_diff)):
+        raise ValueError("cross_view_depth_diff must be finite and > 0")
     if prior is not None and build_prior is not None:
         raise ValueError("prior and build_prior are mutually exclusive")
     if prior is None and build_prior is None and prior_params is not None:
@@ -879,6 +814,22 @@ def _build_prior(matcher: Matcher, own_depth, build_prior, prior_params):
     matcher.rescore()
 
 
+def _open_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, weight, clip, cross_view, cross_view_depth_diff, prior, prior_params,
+                    build_prior) -> bool:
+    """the opening of both geometric passes on the full-resolution matcher: the view's own planes, the sources' maps, the prior (given
+    or built), the cross-view merge.  Returns whether the planes are scored on the way out (_build_prior ends with a rescore, the merge
+    begins with one)."""
+    matcher.load_planes(own_depth, own_normal_world)
+    matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
+    if prior is not None:
+        _install_prior(matcher, prior, prior_params)
+    if build_prior is not None:
+        _build_prior(matcher, own_depth, build_prior, prior_params)
+    if cross_view:
+        _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
+    return bool(cross_view) or build_prior is not None
+
+
 def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, iters: int, weight: float = 0.2, clip: float = 3.0,
                   cross_view: int = 0, cross_view_depth_diff: float = 0.01, prior=None, prior_params=None, build_prior=None):
     """The geometric-consistency pass of one reference view: start from its own photometric result (depth [h, w], world normals
@@ -891,19 +842,9 @@ def run_geom_pass(matcher: Matcher, own_depth, own_normal_world, src_depths, ite
     build_prior = a dict (in place of prior): the prior is built from the view's own depth (_build_prior says how; the dict holds
     build_plane_prior's "cell" and "max_levels" and geom_check's "reproj_error", "depth_diff" and "min_consistent", each optional) and
     installed with prior_params."""
-    if iters < 0:
-        raise ValueError("iters must be >= 0")
-    _check_cross_view(cross_view, cross_view_depth_diff)
-    _check_prior_arguments(prior, prior_params, build_prior)
-    matcher.load_planes(own_depth, own_normal_world)
-    matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
-    if prior is not None:
-        _install_prior(matcher, prior, prior_params)
-    if build_prior is not None:
-        _build_prior(matcher, own_depth, build_prior, prior_params)
-    if cross_view:
-        _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
-    elif build_prior is None:              # (_build_prior ends with this rescore)
+    term = (weight, clip, cross_view, cross_view_depth_diff, prior, prior_params, build_prior)
+    _check_geom_pass((iters,), "iters", *term[2:])
+    if not _open_geom_pass(matcher, own_depth, own_normal_world, src_depths, *term):
         matcher.rescore()
     matcher.pm_iterate(iters)
     matcher.compute_disp()
@@ -922,27 +863,17 @@ def run_geom_pass_multiscale(matcher: Matcher, own_depth, own_normal_world, src_
     prior, prior_params: as in run_geom_pass, on the full-resolution matcher only (a prior is not carried to coarser levels: they score
     with their own cost); any prior the chain's contexts still hold is removed first, since tsar_pyramid_views refuses it.
     build_prior: as in run_geom_pass, on the full-resolution matcher only, right after its term is installed."""
-    if levels < 0 or coarse_iters < 0 or fine_iters < 0:
-        raise ValueError("levels and iteration counts must be >= 0")
-    _check_cross_view(cross_view, cross_view_depth_diff)
-    _check_prior_arguments(prior, prior_params, build_prior)
+    term = (weight, clip, cross_view, cross_view_depth_diff, prior, prior_params, build_prior)
+    _check_geom_pass((levels, coarse_iters, fine_iters), "levels and iteration counts", *term[2:])
     if levels == 0:
-        run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, weight=weight, clip=clip, cross_view=cross_view,
-                      cross_view_depth_diff=cross_view_depth_diff, prior=prior, prior_params=prior_params, build_prior=build_prior)
+        run_geom_pass(matcher, own_depth, own_normal_world, src_depths, fine_iters, *term)
         return list(coarse or [])
     def clear(m):
         m.clear_geom()
         if prior is not None or build_prior is not None:
             m.clear_plane_prior()
     coarse, chain = _pyramid_chain(matcher, levels, coarse, prepare=clear)
-    matcher.load_planes(own_depth, own_normal_world)
-    matcher.set_geom_depths(src_depths, weight=weight, clip=clip)
-    if prior is not None:
-        _install_prior(matcher, prior, prior_params)
-    if build_prior is not None:
-        _build_prior(matcher, own_depth, build_prior, prior_params)
-    if cross_view:
-        _cross_view_merge(matcher, cross_view, cross_view_depth_diff)
+    _open_geom_pass(matcher, own_depth, own_normal_world, src_depths, *term)
     for finer, coarser in zip(chain[:-1], chain[1:]):
         coarser.geom_pyramid_from(finer)
         coarser.pyramid_planes_from(finer)
@@ -968,30 +899,10 @@ def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = N
     if params is None:
         params = FusionParams()
         L.tsar_default_fusion_params(C.byref(params))
-    keep, kinds, devices = [], set(), set()
-
-    def ptrs(seq, shape):
-        arr = (C.c_void_p * n)()
-        for i, a in enumerate(seq):
-            if not _is_torch(a):
-                a = np.ascontiguousarray(a, np.float32)
-                keep.append(a)
-            else:
-                assert str(a.dtype) == "torch.float32"
-                if a.is_cuda:
-                    devices.add(a.device)
-            assert tuple(a.shape) == shape
-            p, kind = _ptr(a)
-            arr[i] = p
-            kinds.add(kind)
-        return arr
-    pd, pn, pg = ptrs(depths, (h, w)), ptrs(normals, (h, w, 3)), ptrs(grays, (h, w))
-    assert len(kinds) == 1, "all maps must live in the same memory space"
-    mem = kinds.pop()
-    cams = (Camera * n)()
-    K = np.asarray(K, np.float32).reshape(n, 9); R = np.asarray(R, np.float32).reshape(n, 9); t = np.asarray(t, np.float32).reshape(n, 3)
-    for i in range(n):
-        cams[i].K[:] = K[i].tolist(); cams[i].R[:] = R[i].tolist(); cams[i].t[:] = t[i].tolist()
+    maps = [[_buf(a, np.float32, shape, "%s map %d" % (name, i), tensors="any") for i, a in enumerate(seq)]
+            for name, seq, shape in (("depth", depths, (h, w)), ("normal", normals, (h, w, 3)), ("gray", grays, (h, w)))]
+    pd, pn, pg = (_ptr_array(bufs, n) for bufs in maps)
+    mem = _one_kind(sum(maps, []), "all maps")
     lists = [list(pairs[v]) for v in range(n)]
     off = np.zeros(n + 1, np.int32)
     off[1:] = np.cumsum([len(x) for x in lists])
@@ -1001,14 +912,12 @@ def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = N
     if mem == MEM_DEVICE:
         # device maps: the cloud is delivered on their device as well, never into a host array
         import torch
-        assert len(devices) == 1, "all maps must live on one device"
-        out = torch.empty((max(cap, 1), 9), dtype=torch.float32, device=devices.pop())
-        out_ptr = _ptr(out)[0]
+        out = torch.empty((max(cap, 1), 9), dtype=torch.float32, device=maps[0][0][0].device)
     else:
         out = np.empty((cap, 9), np.float32)
-        out_ptr = out.ctypes.data_as(C.c_void_p)
+    out_ptr = _ptr(out)[0]
     cnt = C.c_int64(0)
-    tail = (n, w, h, cams, pd, pn, pg, mem, off.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), C.byref(params),
+    tail = (n, w, h, _cameras(K, R, t, n), pd, pn, pg, mem, off.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), C.byref(params),
             out_ptr, cap, C.byref(cnt))
     rc = L.tsar_fuse_ctx(matcher._ctx, *tail) if matcher is not None else L.tsar_fuse(device, *tail)
     if rc != TSAR_OK:
@@ -1020,12 +929,23 @@ def fuse(depths, normals, grays, K, R, t, pairs, params: FusionParams | None = N
 
 def _cloud(a, name):
     """an [n, k >= 3] float32 cloud as the library takes it: a contiguous numpy array, or a contiguous torch device tensor"""
-    if _is_torch(a) and a.is_cuda:
-        assert str(a.dtype) == "torch.float32" and a.dim() == 2 and a.shape[1] >= 3 and a.is_contiguous(), name + " must be a contiguous [n, k >= 3] float32 tensor"
-        return a, True
-    a = np.ascontiguousarray(a.numpy() if _is_torch(a) else a, np.float32)
-    assert a.ndim == 2 and a.shape[1] >= 3, name + " must be [n, k >= 3]"
-    return a, False
+    a = _coerce(a, np.float32, None, name, tensors="device")
+    assert a.ndim == 2 and a.shape[1] >= 3 and (not _is_torch(a) or a.is_contiguous()), name + " must be a contiguous [n, k >= 3] array or tensor"
+    return a, _is_torch(a)
+
+
+@contextlib.contextmanager
+def _matcher_for(matcher, device, *inputs):
+    """the caller's Matcher; without one, a Matcher made for the block and closed after it, on the device of the first torch device
+    tensor among `inputs`, else on `device`"""
+    if matcher is not None:
+        yield matcher
+        return
+    m = Matcher(next((a.device.index for a in inputs if _is_torch(a) and a.is_cuda and a.device.index is not None), device))
+    try:
+        yield m
+    finally:
+        m.close()
 
 
 def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "index"), max_pairs=None, matcher=None, device=0):
@@ -1052,18 +972,9 @@ def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "ind
     tol = np.ascontiguousarray([] if tolerances is None else tolerances, np.float32).reshape(-1)
     within = np.zeros(len(tol), np.int64)
     nq = int(q.shape[0])
-    res = {}
-    for k, dt in (("dist2", "float32"), ("index", "int32")):
-        if k in want:
-            if q_dev:
-                import torch
-                res[k] = torch.empty((nq,), dtype=getattr(torch, dt), device=q.device)
-            else:
-                res[k] = np.empty(nq, dt)
+    res = _outputs({"dist2": ((nq,), np.float32), "index": ((nq,), np.int32)}, want, q.device if q_dev else None)
     n_valid, pairs = C.c_int64(0), C.c_int64(-1)
-    own = matcher is None
-    m = Matcher(q.device.index if q_dev and q.device.index is not None else device) if own else matcher
-    try:
+    with _matcher_for(matcher, device, q) as m:
         rc = L.tsar_cloud_distance_ctx(m._ctx, _ptr(q)[0] if nq else None, nq, int(q.shape[1]), _ptr(t)[0] if t.shape[0] else None, int(t.shape[0]), int(t.shape[1]),
                                        C.byref(p), len(tol), tol.ctypes.data_as(C.c_void_p), _ptr(res.get("dist2"))[0], _ptr(res.get("index"))[0],
                                        within.ctypes.data_as(C.c_void_p), C.byref(n_valid), C.byref(pairs), MEM_DEVICE if q_dev else MEM_HOST)
@@ -1071,9 +982,6 @@ def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "ind
             err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
             err.pairs = int(pairs.value) if pairs.value >= 0 else None      # filled when max_pairs refused the call
             raise err
-    finally:
-        if own:
-            m.close()
     res["within"] = within
     res["n_valid_query"] = int(n_valid.value)
     res["pairs"] = int(pairs.value)
@@ -1094,40 +1002,23 @@ def cloud_voxels(cloud, voxel, dist2=None, tolerances=None, want=("rank", "rep",
     n = int(c.shape[0])
     tol = np.ascontiguousarray([] if tolerances is None else tolerances, np.float32).reshape(-1)
     assert (dist2 is None) == (tolerances is None), "dist2 and tolerances go together"
-    d2 = None
-    if dist2 is not None:
-        if dev:
-            assert _is_torch(dist2) and dist2.is_cuda and dist2.device == c.device and str(dist2.dtype) == "torch.float32" and dist2.is_contiguous(), \
-                "dist2 must be a contiguous float32 tensor on the cloud's device"
-            d2 = dist2
-        else:
-            d2 = np.ascontiguousarray(dist2.cpu().numpy() if _is_torch(dist2) else dist2, np.float32)
-        assert tuple(d2.shape) == (n,), "dist2 must be [n]"
+    d2 = _coerce(dist2.cpu() if _is_torch(dist2) and not dev else dist2, np.float32, (n,), "dist2", tensors="device")
+    assert d2 is None or not dev or (_is_torch(d2) and d2.device == c.device and d2.is_contiguous()), "dist2 must be a contiguous tensor on the cloud's device"
     p = CloudVoxelsParams()
     L.tsar_default_cloud_voxels_params(C.byref(p))
     p.voxel = float(voxel)
-
-    def empty(shape):
-        if dev:
-            import torch
-            return torch.empty(shape, dtype=torch.int32, device=c.device)
-        return np.empty(shape, np.int32)
-    out = {k: empty((n,)) for k in ("rank", "rep", "count") if k in want}      # at most n voxels: the per-voxel arrays are trimmed below
+    spec = {k: ((n,), np.int32) for k in ("rank", "rep", "count")}             # at most n voxels: the per-voxel arrays are trimmed below
     if tolerances is not None:
-        out["within"] = empty((n, len(tol)))
+        spec["within"] = ((n, len(tol)), np.int32)
+    out = _outputs(spec, tuple(want) + ("within",), c.device if dev else None)
     n_voxels, n_valid = C.c_int64(0), C.c_int64(0)
-    own = matcher is None
-    m = Matcher(c.device.index if dev and c.device.index is not None else device) if own else matcher
-    try:
+    with _matcher_for(matcher, device, c) as m:
         rc = L.tsar_cloud_voxels_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), C.byref(p), _ptr(d2)[0], len(tol),
                                      tol.ctypes.data_as(C.c_void_p) if tolerances is not None else None, _ptr(out.get("rank"))[0], n, _ptr(out.get("rep"))[0],
                                      _ptr(out.get("count"))[0], _ptr(out.get("within"))[0] if len(tol) else None, C.byref(n_voxels), C.byref(n_valid),
                                      MEM_DEVICE if dev else MEM_HOST)
         if rc != TSAR_OK:
             raise TsarError(rc, L.tsar_last_error(m._ctx).decode())
-    finally:
-        if own:
-            m.close()
     nv = int(n_voxels.value)
     for k in ("rep", "count", "within"):
         if k in out:
@@ -1178,6 +1069,12 @@ def _voxel_share(within, count):
     return np.cumsum(within / count[:, None], axis=0)[-1] / np.float64(len(count))
 
 
+def _f1(a, c):
+    """the harmonic mean of two arrays of shares, in float64; 0 where both are 0"""
+    s = a + c
+    return np.where(s > 0, 2.0 * a * c / np.where(s > 0, s, 1.0), 0.0)
+
+
 def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, crop=None):
     """Accuracy and completeness of the cloud `recon` against the cloud `gt` at each of `tolerances`: the point-wise precision / recall /
     F-score.  Two cloud_distance calls with max_dist = max(tolerances):
@@ -1209,30 +1106,21 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
             raise ValueError("crop must be six finite numbers (x0, y0, z0, x1, y1, z1) with x0 <= x1, y0 <= y1, z0 <= z1")
         (recon, n_rc), (gt, n_gc) = _crop_cloud(recon, crop), _crop_cloud(gt, crop)
         cropped = {"n_recon_cropped": n_rc, "n_gt_cropped": n_gc}
-    own = matcher is None
-    if own:                                # one context for every call
-        matcher = Matcher(recon.device.index if _is_torch(recon) and recon.is_cuda and recon.device.index is not None else device)
     vox = None
-    try:
+    with _matcher_for(matcher, device, recon) as m:            # one context for every call
         want = () if voxel is None else ("dist2",)
-        a = cloud_distance(recon, gt, r, tol, want=want, matcher=matcher)
-        c = cloud_distance(gt, recon, r, tol, want=want, matcher=matcher)
+        a = cloud_distance(recon, gt, r, tol, want=want, matcher=m)
+        c = cloud_distance(gt, recon, r, tol, want=want, matcher=m)
         if voxel is not None:
-            va = cloud_voxels(recon, voxel, a["dist2"], tol, want=("count",), matcher=matcher)
-            vc = cloud_voxels(gt, voxel, c["dist2"], tol, want=("count",), matcher=matcher)
+            va = cloud_voxels(recon, voxel, a["dist2"], tol, want=("count",), matcher=m)
+            vc = cloud_voxels(gt, voxel, c["dist2"], tol, want=("count",), matcher=m)
             acc_v, com_v = _voxel_share(va["within"], va["count"]), _voxel_share(vc["within"], vc["count"])
-            sv = acc_v + com_v
-            vox = {"accuracy_voxel": acc_v, "completeness_voxel": com_v, "f1_voxel": np.where(sv > 0, 2.0 * acc_v * com_v / np.where(sv > 0, sv, 1.0), 0.0),
+            vox = {"accuracy_voxel": acc_v, "completeness_voxel": com_v, "f1_voxel": _f1(acc_v, com_v),
                    "n_recon_voxels": va["n_voxels"], "n_gt_voxels": vc["n_voxels"]}
-    finally:
-        if own:
-            matcher.close()
     na, nc = a["within"].astype(np.int64), c["within"].astype(np.int64)
     acc = na / np.float64(a["n_valid_query"]) if a["n_valid_query"] else np.zeros(tol.size, np.float64)
     com = nc / np.float64(c["n_valid_query"]) if c["n_valid_query"] else np.zeros(tol.size, np.float64)
-    s = acc + com
-    f1 = np.where(s > 0, 2.0 * acc * com / np.where(s > 0, s, 1.0), 0.0)
-    res = {"tolerances": tol.copy(), "accuracy": acc, "completeness": com, "f1": f1, "n_accurate": na, "n_complete": nc,
+    res = {"tolerances": tol.copy(), "accuracy": acc, "completeness": com, "f1": _f1(acc, com), "n_accurate": na, "n_complete": nc,
            "n_recon_valid": a["n_valid_query"], "n_gt_valid": c["n_valid_query"], "pairs_accuracy": a["pairs"], "pairs_completeness": c["pairs"]}
     if vox is not None:
         res.update(vox)
