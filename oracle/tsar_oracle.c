@@ -40,7 +40,10 @@
  *      uninitialised slot, gipuma.cu:505).
  *
  * The geometric-consistency term (geom_term, orc_set_geom, orc_pm_rescore) is not in the reference: it is restated from its
- * statement in include/tsar.h (tsar_set_geom_depths, tsar_pm_rescore), not from the kernels.
+ * statement in include/tsar.h (tsar_set_geom_depths, tsar_pm_rescore), not from the kernels.  The plane-prior term (prior_term,
+ * orc_set_plane_prior) is not in the reference either, and is restated the same way: from the text of include/tsar.h
+ * (tsar_set_plane_prior), one IEEE operation per operator of that text, not from the kernels.  It takes the prior as the context holds
+ * it (tsar_get_plane_prior), so the world-to-camera conversion of the normals stays orc_load_planes's.
  *
  * Build: see oracle/Makefile (gcc -O2 -ffp-contract=off -mfma -fopenmp -shared).
  */
@@ -120,6 +123,9 @@ typedef struct {
     float geom_weight, geom_clip;
     const float *geom_depth[ORC_MAX_VIEWS];          /* view v's depth map [h][w], borrowed; NULL = no term for v */
     float geom_F[ORC_MAX_VIEWS][12], geom_B[ORC_MAX_VIEWS][12];   /* row-major 3 x 4, as given (tsar_get_geom_matrices) */
+    /* plane-prior term (include/tsar.h, tsar_set_plane_prior): off unless prior != NULL */
+    const float *prior;                              /* [h][w][4] = (q_x, q_y, q_z, Dp) as the context holds it, borrowed */
+    float prior_wd, prior_wn, prior_dc, prior_nc;    /* weight_depth, weight_normal, depth_clip, normal_clip */
 } orc_state;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -328,6 +334,14 @@ static inline void view_vector(const orc_camera *cm, int x, int y, float *v) {
 float orc_getD(const orc_state *s, const float *n, int x, int y, float depth) { return getD(n, x, y, depth, &s->cam[0]); }
 float orc_depth_from_plane(const orc_state *s, const float *n4, int x, int y) { return depth_from_plane(&s->cam[0], n4, x, y); }
 void orc_view_vector(const orc_state *s, int x, int y, float *v) { view_vector(&s->cam[0], x, y, v); }
+/* depth_from_plane of planes[y][x] at (x, y), the whole image at once */
+void orc_depth_from_planes(const orc_state *s, const float *planes, float *depth) {
+    for (int y = 0; y < s->h; y++)
+        for (int x = 0; x < s->w; x++) {
+            size_t p = (size_t)y * s->w + x;
+            depth[p] = depth_from_plane(&s->cam[0], planes + 4 * p, x, y);
+        }
+}
 
 /* getHomography_cu gipuma.cu:207-224: H = K_to * ((R - t n^T / d) * K_ref^-1) */
 static inline void homography(const orc_camera *ref, const orc_camera *to, const float *n4, float *H) {
@@ -498,12 +512,30 @@ static float geom_term(const orc_state *s, int view, int x, int y, float D) {
 }
 float orc_geom_term(const orc_state *s, int view, int x, int y, float D) { return geom_term(s, view, x, y, D); }
 
+/* The plane-prior term t of a hypothesis n4 of depth D at (x, y), restated from the statement in include/tsar.h
+ * (tsar_set_plane_prior) the way geom_term is: plain float operations, each one IEEE operation (-ffp-contract=off, no fmaf: the same
+ * in every build of this file and in both arithmetic modes), the three quotients '/', the header's comparisons (NaN fails each one).
+ * 0 where the pixel has no prior (the held entry is all zero there: Dp > 0 fails). */
+static float prior_term(const orc_state *s, int x, int y, const float *n4, float D) {
+    const float *q = s->prior + 4 * ((size_t)y * s->w + x);
+    const float Dp = q[3];
+    if (!(Dp > 0.0f)) return 0.0f;
+    const float a = fabsf(D - Dp);
+    const float rel = a / Dp;
+    const float r_d = rel < s->prior_dc ? rel / s->prior_dc : 1.0f;
+    const float sn = 1.0f - ((n4[0] * q[0] + n4[1] * q[1]) + n4[2] * q[2]);
+    const float s0 = sn < 0.0f ? 0.0f : sn;
+    const float r_n = sn < s->prior_nc ? s0 / s->prior_nc : 1.0f;
+    return (s->prior_wd * r_d) + (s->prior_wn * r_n);
+}
+
 /* pmCostMultiview_cu gipuma.cu:455-518.  With a geometric term installed, view v's cost becomes c_v + lambda e_v after the validity
- * test (include/tsar.h); D is the hypothesis's depth at (x, y), once per hypothesis. */
+ * test (include/tsar.h); D is the hypothesis's depth at (x, y), once per hypothesis.  With a plane prior installed, a valid
+ * hypothesis's cost becomes c + t after the best-N division at pixels that have a prior; best view and ratio are not touched. */
 static float pm_cost_multiview(const orc_state *s, int x, int y, const float *n4, int *beview, float *ratio) {
     float cv[ORC_MAX_VIEWS], ov[ORC_MAX_VIEWS];
     int num = s->n_sel, valid = 0;
-    const float D = s->geom_on ? depth_from_plane(&s->cam[0], n4, x, y) : 0.0f;
+    const float D = (s->geom_on || s->prior) ? depth_from_plane(&s->cam[0], n4, x, y) : 0.0f;
     for (int i = 0; i < num; i++) {
         float c = pm_cost(s, s->sel[i], x, y, n4);
         if (c < ORC_MAXCOST) valid++; else c = ORC_MAXCOST;
@@ -522,6 +554,7 @@ static float pm_cost_multiview(const orc_state *s, int x, int y, const float *n4
         *beview = -1;
         for (int i = 0; i < num; i++)
             if (cv[0] == ov[i]) *beview = s->sel[i];
+        if (s->prior && s->prior[4 * ((size_t)y * s->w + x) + 3] > 0.0f) cost = cost + prior_term(s, x, y, n4, D);
     } else {
         cost = ORC_MAXCOST; *ratio = 0.0f; *beview = -1;
     }
@@ -1041,6 +1074,16 @@ void orc_clear_geom(orc_state *s) {
     memset(s->geom_depth, 0, sizeof s->geom_depth);
     memset(s->geom_F, 0, sizeof s->geom_F);
     memset(s->geom_B, 0, sizeof s->geom_B);
+}
+/* the plane-prior term: held = the [h][w][4] array the context holds (tsar_get_plane_prior: the normal in reference-camera
+ * coordinates and the depth, all zero where there is no prior), borrowed like the geometric maps; orc_clear_plane_prior removes it */
+void orc_set_plane_prior(orc_state *s, const float *held, float weight_depth, float weight_normal, float depth_clip, float normal_clip) {
+    s->prior = held;
+    s->prior_wd = weight_depth; s->prior_wn = weight_normal; s->prior_dc = depth_clip; s->prior_nc = normal_clip;
+}
+void orc_clear_plane_prior(orc_state *s) {
+    s->prior = NULL;
+    s->prior_wd = 0.0f; s->prior_wn = 0.0f; s->prior_dc = 0.0f; s->prior_nc = 0.0f;
 }
 float orc_rcp_gpu(const orc_state *s, float x) { return rcp_gpu(s, x); }
 void orc_set_subset(orc_state *s, int n, const int32_t *idx) {

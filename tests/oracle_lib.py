@@ -86,6 +86,8 @@ def _bind(L):
     L.orc_getD.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
     L.orc_depth_from_plane.restype = C.c_float
     L.orc_depth_from_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.orc_depth_from_planes.restype = None
+    L.orc_depth_from_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_min_disp.restype = C.c_float
     L.orc_max_disp.restype = C.c_float
     L.orc_min_disp.argtypes = [C.c_void_p]
@@ -139,6 +141,10 @@ def _bind(L):
     L.orc_set_geom_params.argtypes = [C.c_void_p, C.c_float, C.c_float]
     L.orc_clear_geom.restype = None
     L.orc_clear_geom.argtypes = [C.c_void_p]
+    L.orc_set_plane_prior.restype = None
+    L.orc_set_plane_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]
+    L.orc_clear_plane_prior.restype = None
+    L.orc_clear_plane_prior.argtypes = [C.c_void_p]
     L.orc_pm_rescore.restype = None
     L.orc_pm_rescore.argtypes = [C.c_void_p]
     L.orc_geom_term.restype = C.c_float
@@ -300,6 +306,14 @@ class Oracle:
         n4 = np.ascontiguousarray(n4, dtype=np.float32)
         return float(self.L.orc_depth_from_plane(self.s, _p(n4), x, y))
 
+    def depth_from_planes(self, planes):
+        """depth_from_plane of planes[y, x] at (x, y) for the whole image"""
+        planes = np.ascontiguousarray(planes, dtype=np.float32)
+        assert planes.shape == (self.h, self.w, 4)
+        out = np.empty((self.h, self.w), np.float32)
+        self.L.orc_depth_from_planes(self.s, _p(planes), _p(out))
+        return out
+
     def view_vector(self, x, y):
         v = np.empty(3, np.float32)
         self.L.orc_view_vector(self.s, C.c_int(x), C.c_int(y), _p(v))
@@ -349,6 +363,20 @@ class Oracle:
     def clear_geom(self):
         self.L.orc_clear_geom(self.s)
         self._geom_maps = []
+
+    def set_plane_prior(self, held, params):
+        """install the plane-prior term (include/tsar.h, tsar_set_plane_prior): held = the [h, w, 4] array the context holds
+        (Matcher.get_plane_prior(): the normal in reference-camera coordinates and the depth, all zero where there is no prior),
+        params = (weight_depth, weight_normal, depth_clip, normal_clip)"""
+        held = np.ascontiguousarray(held, np.float32)
+        assert held.shape == (self.h, self.w, 4)
+        wd, wn, dc, nc = (C.c_float(float(v)) for v in params)
+        self._prior = held                   # borrowed by the C side
+        self.L.orc_set_plane_prior(self.s, _p(held), wd, wn, dc, nc)
+
+    def clear_plane_prior(self):
+        self.L.orc_clear_plane_prior(self.s)
+        self._prior = None
 
     def rescore(self):
         """tsar_pm_rescore: keep the valid planes, redraw the others as pm_init does, score every pixel (sweep window)"""

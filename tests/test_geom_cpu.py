@@ -49,28 +49,12 @@ def geom_term(F, B, depth_v, x, y, D, weight, clip):
         return (F32(weight) * e).astype(F32)
 
 
-def expected_cost_planes(orc, matrices, maps, planes, n_best, weight, clip):
-    """what pm_cost_planes must return with `maps` installed: `orc`'s photometric cost per view (the oracle's pm_cost, which carries no
-    term), the numpy restatement of the term, the best-N of multiview_cost (pm_core.h) in numpy.  matrices[v] = (F, B) of view v."""
-    h, w = planes.shape[:2]
-    n_views = len(maps)
-    ys, xs = np.mgrid[0:h, 0:w]
-    D = np.empty((h, w), F32)
-    per_view = []
-    for y in range(h):
-        for x in range(w):
-            D[y, x] = orc.depth_from_plane(planes[y, x], x, y)
-    for v in range(1, n_views):
-        c = np.empty((h, w), F32)
-        for y in range(h):
-            for x in range(w):
-                c[y, x] = orc.pm_cost(v, x, y, planes[y, x])
-        c = np.minimum(c, MAXCOST)
-        valid = c < MAXCOST
-        F, B = matrices[v]
-        g = geom_term(F, B, maps[v], xs, ys, D, weight, clip) if maps[v] is not None else np.zeros((h, w), F32)
-        per_view.append((v, (c + g).astype(F32), valid))
-    # multiview_cost: last view attaining the minimum, the NB smallest sorted, nb = min(valid, n_best)
+def combine_view_costs(per_view, n_best, cost_comb=1):
+    """multiview_cost (pm_core.h) in numpy over per_view = [(view, cost with its term, valid), ...] in the order the views are
+    walked (the selection's): the last view attaining the minimum is the best view, the costs sorted, nb = min(valid, n_best) under
+    best-N (cost_comb 1) and the number of valid views under every other combination -- the sorted list then also holds the invalid
+    views at MAXCOST + lambda e, and the first nb entries are summed whatever they are."""
+    h, w = per_view[0][1].shape
     cmin = np.full((h, w), np.inf, F32)
     bv = np.full((h, w), -1, np.int32)
     nvalid = np.zeros((h, w), np.int32)
@@ -80,15 +64,45 @@ def expected_cost_planes(orc, matrices, maps, planes, n_best, weight, clip):
         cmin = np.minimum(cmin, c)
         nvalid += valid
     srt = np.sort(np.stack([c for _, c, _ in per_view]), axis=0)
-    nb = np.minimum(nvalid, n_best)
+    nb = np.minimum(nvalid, n_best) if cost_comb == 1 else nvalid
     cost = np.zeros((h, w), F32)
-    for k in range(min(n_best, srt.shape[0])):
+    for k in range(srt.shape[0]):
         cost = np.where(k < nb, (cost + srt[k]).astype(F32), cost)
-    cost = np.where(nb > 0, (cost / nb.astype(F32)).astype(F32), MAXCOST)
-    ratio = (srt[0] / srt[1]).astype(F32) if srt.shape[0] >= 2 else np.zeros((h, w), F32)
+    with np.errstate(all="ignore"):
+        cost = np.where(nb > 0, (cost / nb.astype(F32)).astype(F32), MAXCOST)
+        ratio = (srt[0] / srt[1]).astype(F32) if srt.shape[0] >= 2 else np.zeros((h, w), F32)
     ratio = np.where(nb > 0, ratio, F32(0))
     bv = np.where(nb > 0, bv, -1)
     return cost, bv, ratio
+
+
+def expected_cost_planes(orc, matrices, maps, planes, n_best, weight, clip, cost_comb=1, views=None, photometric=None):
+    """what pm_cost_planes must return with `maps` installed: `orc`'s photometric cost per view (the oracle's pm_cost, which carries no
+    term), the numpy restatement of the term, the combination of multiview_cost (pm_core.h) in numpy.  matrices[v] = (F, B) of view v.
+    views: the selected views in selection order (default: every source view).  photometric: {view: cost [h, w]} from elsewhere (the
+    device's own per-view score, say) in place of the oracle's pm_cost."""
+    h, w = planes.shape[:2]
+    n_views = len(maps)
+    ys, xs = np.mgrid[0:h, 0:w]
+    D = np.empty((h, w), F32)
+    per_view = []
+    for y in range(h):
+        for x in range(w):
+            D[y, x] = orc.depth_from_plane(planes[y, x], x, y)
+    for v in (range(1, n_views) if views is None else views):
+        if photometric is not None:
+            c = np.asarray(photometric[v], F32)
+        else:
+            c = np.empty((h, w), F32)
+            for y in range(h):
+                for x in range(w):
+                    c[y, x] = orc.pm_cost(v, x, y, planes[y, x])
+        c = np.minimum(c, MAXCOST)
+        valid = c < MAXCOST
+        F, B = matrices[v]
+        g = geom_term(F, B, maps[v], xs, ys, D, weight, clip) if maps[v] is not None else np.zeros((h, w), F32)
+        per_view.append((v, (c + g).astype(F32), valid))
+    return combine_view_costs(per_view, n_best, cost_comb)
 
 
 def relative_pose(K, R, t, v):
