@@ -43,6 +43,7 @@
  *   Fusion.exe (binary only; flags x/1.sh:20-30)         tsar_fuse
  *   (none: the reference ships no evaluation)            tsar_cloud_distance
  *   (none: the reference's fuser thins nothing)          tsar_cloud_voxels
+ *   (none: the reference renders no cloud)               tsar_cloud_render / tsar_depth_compare
  *
  * Conventions
  *   - every function returns an int status (TSAR_OK = 0, negative = error) and never exits the
@@ -642,6 +643,84 @@ int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int stride, con
                       int n_tol, const float* tol, int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out,
                       int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out, int mem);
 
+/* ---- a cloud rendered into a camera, and a depth map scored against such a map ------------------------------------------------------- */
+/* tsar_cloud_render: a point cloud (a scan, a fused cloud) rendered into one calibrated view as a depth map, occlusion by the cloud's own
+ * points handled: per pixel the depth of the front-most point that lands on it, how many points support that depth, and which point it is.
+ * Records are `stride` float32 each (>= 3), x y z first, so tsar_fuse's 9-float records go in as they are.  `mem` names where cloud,
+ * depth_out, count_out and index_out lie; cam, p and n_splats_out are host memory.
+ * Two buffers, because one is not enough: a pixel's depth comes only from points that land ON that pixel (a splat of constant depth over a
+ * footprint would pull every slanted surface forward), while the footprint of a point only OCCLUDES: it hides what lies clearly behind it
+ * on the neighbouring pixels, so that a thin cloud does not show the background through the holes of its foreground.
+ * The arithmetic, the same in both arithmetic modes: float32, every operation one IEEE-754 operation rounded to nearest, no fused
+ * multiply-add.
+ *   P (3 x 4), formed on the host in float64 from the float32 K, R, t and rounded once to float32 per element:
+ *     P[k][j] = (K[k][0] * R[0][j] + K[k][1] * R[1][j]) + K[k][2] * R[2][j], j = 0, 1, 2;   P[k][3] = (K[k][0] * t[0] + K[k][1] * t[1]) + K[k][2] * t[2]
+ *   candidate: a record whose x, y and z are all finite
+ *   p_k = ((P[k][0] * x + P[k][1] * y) + P[k][2] * z) + P[k][3], k = 0, 1, 2
+ *   x' = p_0 / p_2, y' = p_1 / p_2 (correctly rounded);  xi = floor(x' + 0.5), yi = floor(y' + 0.5) (the sum rounded first)
+ *   lands = candidate and p_2 > 0 and p_2 < inf and 0 <= xi <= w - 1 and 0 <= yi <= h - 1 (NaN fails every comparison): the point lands
+ *           on pixel (xi, yi) at depth p_2 (tsar_geom_reproject's chain from p_k on)
+ *   footprint half-width: fr = fl(K[0] * radius), one float32 product;  s = (int)min(floor(fr / p_2 + 0.5), max_px) in float32 (the
+ *           quotient correctly rounded, the sum rounded first); radius == 0 gives s = 0.  The footprint of a point that lands is the square
+ *           [xi - s, xi + s] x [yi - s, yi + s] clipped to the image.  A point whose centre is outside the image does not land and takes
+ *           no part at all: its footprint does not reach in from outside.
+ * and then for every pixel:
+ *   Zc, index = the minimal 64-bit code bits(p_2) << 32 | i over the points i that land on it: the front-most depth, and the smallest index
+ *           among the front-most (positive finite floats order like their bits)
+ *   Zo    = the minimum of p_2 over the points whose footprint covers the pixel (the centre pixel is covered: Zo <= Zc)
+ *   visible = something landed and Zc - Zo <= occlusion_diff * Zo
+ *   count = the number of points landing on the pixel with |p_2 - Zc| <= depth_diff * Zc (the winner counts itself)
+ *   kept  = visible and count >= min_points
+ *   count_out = min(count, 255) where something landed, else 0;  depth_out = Zc where kept, else 0;  index_out = index where kept, else -1
+ *   n_splats = the sum over the points that land of their clipped footprint's size (n_landing when radius == 0): the scatter's atomics
+ * Minima, integer sums and bit-defined comparisons: no output depends on the order of arrival, and every run gives the same bits.
+ * A call with n_splats > max_splats is refused before anything is written, with *n_splats_out still filled (max_pairs' rule of
+ * tsar_cloud_distance): a radius as large as the scene is 1089 atomics per point at max_px = 16.
+ * TSAR_ERR_INVALID, with the reason in tsar_last_error: cam or p NULL; cloud NULL with n > 0; all three outputs NULL; mem unknown; a stride
+ * below 3; n negative or above 2^31 - 1; w or h below 1, w + 2 or h + 2 not below 2^23 (the context's 24-bit addressing limit) or w * h
+ * above 2^31 - 1; radius negative or not finite, or fl(K[0] * radius) negative or not finite; max_px outside [1, 16]; occlusion_diff or
+ * depth_diff negative or not finite; min_points outside [1, 255]; max_splats negative; more than max_splats splats.
+ * tsar_cloud_render_ctx needs no views and no state, runs on the context's stream and changes nothing in the context; its temporaries (the
+ * two z-buffers and the counts) are pieces of the call's frame that never grow the context's scratch arena.  tsar_cloud_render is the
+ * context-free form.  Timed as "cloud_render_count", "cloud_render_scatter", "cloud_render_support" and "cloud_render_resolve". */
+typedef struct tsar_cloud_render_params {
+    float radius;             /* world units: the half-width of a point's occluder footprint; 0 = no footprint (a plain one-pixel z-buffer).  No default (0): the caller's scale */
+    int32_t max_px;           /* caps the footprint half-width in pixels; default 8, in [1, 16] */
+    float occlusion_diff;     /* relative, default 0.02: a pixel whose front-most landing lies further than this behind the occluder buffer is hidden */
+    float depth_diff;         /* relative, default 0.01: a landing supports the pixel's depth Zc when it is within depth_diff * Zc of it */
+    int32_t min_points;       /* default 1, in [1, 255]: depth_out is Zc only where at least this many landings support it */
+    int64_t max_splats;       /* a call that would issue more footprint atomics than this is refused; default 1 << 34 */
+} tsar_cloud_render_params;
+void tsar_default_cloud_render_params(tsar_cloud_render_params* p);
+int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h,
+                          const tsar_cloud_render_params* p, float* depth_out /* [h][w] or NULL */, uint8_t* count_out /* [h][w] or NULL */,
+                          int32_t* index_out /* [h][w] or NULL */, int64_t* n_splats_out /* host, may be NULL */, int mem);
+int tsar_cloud_render(int device, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h,
+                      const tsar_cloud_render_params* p, float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem);
+
+/* tsar_depth_compare: a depth map scored against a ground-truth map (tsar_cloud_render's, say) with the per-pixel bars: how many pixels
+ * lie within each relative tolerance, how many in front, how many behind.  depth [n], gt [n] float32, mask [n] uint8 (NULL: every pixel)
+ * and error_out [n] float32 (may be NULL) lie in `mem`; tol (n_tol relative tolerances, 1 <= n_tol <= 16) and the int64 outputs are host
+ * memory; each output may be NULL.  float32, one IEEE operation per operator, no fused multiply-add.  With D = depth[i], G = gt[i]:
+ *   ground-truth pixel: G > 0 and G < inf (NaN fails both) and mask[i] != 0
+ *   n_gt      = the number of ground-truth pixels
+ *   n_both    = the ground-truth pixels with D > 0 and D < inf
+ *   within[k] = the n_both pixels with |D - G| <= fl(tol[k] * G)
+ *   n_front   = the n_both pixels with D - G < -fl(tol[0] * G);  n_behind = those with D - G > fl(tol[0] * G)
+ *   error_out[i] = (D - G) / G (correctly rounded) on the n_both pixels, NaN elsewhere
+ * Only integer counts come back; a caller forms the ratios in float64: accuracy = within / n_both, completeness = within / n_gt, cover =
+ * n_both / n_gt.  Integer sums: the same in every run.
+ * TSAR_ERR_INVALID: depth, gt or tol NULL (depth and gt with n > 0); n negative or above 2^31 - 1; n_tol outside [1, 16]; a tolerance
+ * negative or not finite; mem unknown.  The _ctx form needs no views and no state and changes nothing in the context; timed as
+ * "depth_compare". */
+#define TSAR_DEPTH_COMPARE_MAX_TOL 16
+int tsar_depth_compare_ctx(tsar_ctx* ctx, const float* depth, const float* gt, const uint8_t* mask /* or NULL */, int64_t n, int n_tol,
+                           const float* tol /* host */, int64_t* n_gt_out, int64_t* n_both_out, int64_t* within_out /* host [n_tol] */,
+                           int64_t* n_front_out, int64_t* n_behind_out, float* error_out /* [n] or NULL */, int mem);
+int tsar_depth_compare(int device, const float* depth, const float* gt, const uint8_t* mask, int64_t n, int n_tol, const float* tol,
+                       int64_t* n_gt_out, int64_t* n_both_out, int64_t* within_out, int64_t* n_front_out, int64_t* n_behind_out,
+                       float* error_out, int mem);
+
 /* ---- page-locked host buffers --------------------------------------------------------------- */
 /* NULL on failure.  Replaces the reference's cudaMallocManaged host-visible planes (managed.h:7-15) on the host side of the
  * boundary: the caller's image / result buffers, allocated here, are DMA targets. */
@@ -656,6 +735,7 @@ void tsar_host_free(void* p);
 void* tsar_device_alloc(int device, size_t bytes);
 void tsar_device_free(int device, void* p);
 int tsar_device_write(int device, void* dst, const void* host_src, size_t bytes);     /* synchronous host -> device copy */
+int tsar_device_read(int device, void* host_dst, const void* src, size_t bytes);      /* synchronous device -> host copy */
 int tsar_peer_copy(int dst_device, void* dst, int src_device, const void* src, size_t bytes);
 
 /* ---- measurement ------------------------------------------------------------------------- */

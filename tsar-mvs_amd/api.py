@@ -79,6 +79,11 @@ class CloudVoxelsParams(C.Structure):
     _fields_ = [("voxel", C.c_float)]
 
 
+class CloudRenderParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("max_px", C.c_int32), ("occlusion_diff", C.c_float), ("depth_diff", C.c_float), ("min_points", C.c_int32),
+                ("max_splats", C.c_int64)]
+
+
 class KernelTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
@@ -93,6 +98,9 @@ _SET_VIEWS = (_I, [_P, _I, _I, _I, _p(_P), _I, _p(Camera)])
 _FUSE = (_I, [_I, _I, _I, _I, _p(Camera), _p(_P), _p(_P), _p(_P), _I, _P, _P, _p(FusionParams), _P, _L, _p(_L)])
 _CLOUD_DISTANCE = (_I, [_I, _P, _L, _I, _P, _L, _I, _p(CloudDistanceParams), _I, _P, _P, _P, _P, _p(_L), _p(_L), _I])
 _CLOUD_VOXELS = (_I, [_I, _P, _L, _I, _p(CloudVoxelsParams), _P, _I, _P, _P, _L, _P, _P, _P, _p(_L), _p(_L), _I])
+
+_CLOUD_RENDER = (_I, [_I, _P, _L, _I, _p(Camera), _I, _I, _p(CloudRenderParams), _P, _P, _P, _p(_L), _I])
+_DEPTH_COMPARE = (_I, [_I, _P, _P, _P, _L, _I, _P, _p(_L), _p(_L), _P, _p(_L), _p(_L), _P, _I])
 
 
 def _on_ctx(sig):
@@ -169,11 +177,17 @@ _ABI = {
     "tsar_default_cloud_voxels_params": (None, [_p(CloudVoxelsParams)]),
     "tsar_cloud_voxels_ctx": _on_ctx(_CLOUD_VOXELS),
     "tsar_cloud_voxels": _CLOUD_VOXELS,
+    "tsar_default_cloud_render_params": (None, [_p(CloudRenderParams)]),
+    "tsar_cloud_render_ctx": _on_ctx(_CLOUD_RENDER),
+    "tsar_cloud_render": _CLOUD_RENDER,
+    "tsar_depth_compare_ctx": _on_ctx(_DEPTH_COMPARE),
+    "tsar_depth_compare": _DEPTH_COMPARE,
     "tsar_host_alloc": (_P, [_Z]),
     "tsar_host_free": (None, [_P]),
     "tsar_device_alloc": (_P, [_I, _Z]),
     "tsar_device_free": (None, [_I, _P]),
     "tsar_device_write": (_I, [_I, _P, _P, _Z]),
+    "tsar_device_read": (_I, [_I, _P, _P, _Z]),
     "tsar_peer_copy": (_I, [_I, _P, _I, _P, _Z]),
     "tsar_enable_kernel_timing": (_I, [_P, _I]),
     "tsar_reset_kernel_timing": (_I, [_P]),
@@ -1127,6 +1141,117 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
     if cropped is not None:
         res.update(cropped)
     return res
+
+
+def cloud_render(cloud, K, R, t, w, h, radius=0.0, max_px=8, occlusion_diff=0.02, depth_diff=0.01, min_points=1, want=("depth", "count"), max_splats=None,
+                 matcher=None, device=0):
+    """`cloud` rendered into the view (K, R, t) of w x h pixels as a depth map, occlusion by the cloud's own points handled
+    (tsar_cloud_render_ctx; include/tsar.h states the arithmetic).  cloud: [n, k >= 3] float32, x y z first, a numpy array or a torch device
+    tensor (a fused cloud as api.fuse returns it goes in as it is).  radius (world units): the half-width of a point's occluder footprint, at
+    most max_px pixels; a pixel whose front-most landing lies more than occlusion_diff (relative) behind the nearest footprint over it is
+    hidden; 0 = a plain one-pixel z-buffer.  A pixel's depth comes only from points that land on it.  max_splats: the call is refused
+    (TsarError, TSAR_ERR_INVALID, with .n_splats) when the scatter would issue more atomics; None = the library's default.  matcher / device:
+    as cloud_distance.
+    Returns a dict: "depth" ([h, w] float32, 0 where nothing is kept), "count" ([h, w] uint8: the landings within depth_diff of the front-most,
+    saturated at 255), "index" ([h, w] int32: the front-most point, -1 where nothing is kept), as `want` names them (numpy arrays, or torch
+    tensors on the cloud's device), and the integer "n_splats"."""
+    L = load_library()
+    c, dev = _cloud(cloud, "cloud")
+    n, w, h = int(c.shape[0]), int(w), int(h)
+    assert w >= 1 and h >= 1 and len(want) > 0, "cloud_render needs a size of at least 1 x 1 and at least one output"
+    p = CloudRenderParams()
+    L.tsar_default_cloud_render_params(C.byref(p))
+    p.radius, p.max_px, p.occlusion_diff, p.depth_diff, p.min_points = float(radius), int(max_px), float(occlusion_diff), float(depth_diff), int(min_points)
+    if max_splats is not None:
+        p.max_splats = int(max_splats)
+    cam = _cameras(np.asarray(K, np.float32).reshape(1, 3, 3), np.asarray(R, np.float32).reshape(1, 3, 3), np.asarray(t, np.float32).reshape(1, 3), 1)
+    res = _outputs({"depth": ((h, w), np.float32), "count": ((h, w), np.uint8), "index": ((h, w), np.int32)}, want, c.device if dev else None)
+    n_splats = C.c_int64(-1)
+    with _matcher_for(matcher, device, c) as m:
+        rc = L.tsar_cloud_render_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), cam, w, h, C.byref(p), _ptr(res.get("depth"))[0], _ptr(res.get("count"))[0],
+                                     _ptr(res.get("index"))[0], C.byref(n_splats), MEM_DEVICE if dev else MEM_HOST)
+        if rc != TSAR_OK:
+            err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
+            err.n_splats = int(n_splats.value) if n_splats.value >= 0 else None     # filled when max_splats refused the call
+            raise err
+    res["n_splats"] = int(n_splats.value)
+    return res
+
+
+def _depth_ratios(rec):
+    """the float64 ratios of a record of depth_compare's counts, formed on the host (0 where a denominator is 0)"""
+    w = np.asarray(rec["within"], np.int64).astype(np.float64)
+    nb, ng = np.float64(rec["n_both"]), np.float64(rec["n_gt"])
+    rec["accuracy"] = w / nb if rec["n_both"] else np.zeros(len(w), np.float64)
+    rec["completeness"] = w / ng if rec["n_gt"] else np.zeros(len(w), np.float64)
+    rec["cover"] = float(nb / ng) if rec["n_gt"] else 0.0
+    return rec
+
+
+def depth_compare(depth, gt, tolerances, mask=None, want_error=False, matcher=None, device=0):
+    """The depth map `depth` scored against the ground-truth map `gt` with the per-pixel bars (tsar_depth_compare_ctx; include/tsar.h).  depth and
+    gt: float32 arrays of one shape, both numpy arrays or both torch device tensors; mask (uint8 / bool, same shape and memory; None = every
+    pixel) names the pixels that count; tolerances: 1 to 16 relative tolerances.  A ground-truth pixel has gt in (0, inf) and a set mask.
+    Returns a dict: "n_gt"; "n_both" (ground-truth pixels with a depth in (0, inf)); "within" (int64 array: per tolerance the n_both pixels with
+    |D - G| <= fl(tol * G)); "n_front" / "n_behind" (further than tolerances[0] in front of / behind the ground truth); the float64 ratios
+    "accuracy" = within / n_both, "completeness" = within / n_gt and "cover" = n_both / n_gt; "tolerances"; and with want_error "error"
+    ((D - G) / G on the n_both pixels, NaN elsewhere; like depth)."""
+    L = load_library()
+    d = _coerce(depth, np.float32, None, "depth", tensors="device")
+    g = _coerce(gt, np.float32, tuple(d.shape), "gt", tensors="device")
+    dev = _is_torch(d)
+    assert dev == _is_torch(g), "depth and gt must live in the same memory space"
+    if mask is not None and not _is_torch(mask):
+        mask = np.asarray(mask).astype(np.uint8)
+    elif mask is not None:
+        import torch
+        mask = mask.to(torch.uint8).contiguous()
+    mk = _coerce(mask, np.uint8, tuple(d.shape), "mask", tensors="device")
+    assert mk is None or _is_torch(mk) == dev, "mask must live where depth does"
+    assert not dev or (d.is_contiguous() and g.is_contiguous() and d.device == g.device and (mk is None or mk.device == d.device)), "tensors must be contiguous and on one device"
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    n = int(np.prod(d.shape))
+    within = np.zeros(len(tol), np.int64)
+    out = _outputs({"error": (tuple(d.shape), np.float32)}, ("error",) if want_error else (), d.device if dev else None)
+    cnt = [C.c_int64(0) for _ in range(4)]
+    with _matcher_for(matcher, device, d) as m:
+        rc = L.tsar_depth_compare_ctx(m._ctx, _ptr(d)[0] if n else None, _ptr(g)[0] if n else None, _ptr(mk)[0] if n else None, n, len(tol), tol.ctypes.data_as(C.c_void_p),
+                                      C.byref(cnt[0]), C.byref(cnt[1]), within.ctypes.data_as(C.c_void_p), C.byref(cnt[2]), C.byref(cnt[3]), _ptr(out.get("error"))[0],
+                                      MEM_DEVICE if dev else MEM_HOST)
+        if rc != TSAR_OK:
+            raise TsarError(rc, L.tsar_last_error(m._ctx).decode())
+    res = {"tolerances": tol.copy(), "n_gt": int(cnt[0].value), "n_both": int(cnt[1].value), "within": within, "n_front": int(cnt[2].value), "n_behind": int(cnt[3].value)}
+    res.update(out)
+    return _depth_ratios(res)
+
+
+def evaluate_depth_maps(depths, cloud, K, R, t, tolerances, radius, masks=None, matcher=None, device=0, **render_kw):
+    """Depth maps scored per pixel against the cloud `cloud` (a scan, a fused cloud as api.fuse returns it) rendered into their own cameras: per
+    view v one cloud_render of the cloud into (K[v], R[v], t[v]) at depths[v]'s size with the footprint `radius` (render_kw: max_px,
+    occlusion_diff, depth_diff, min_points, max_splats) and one depth_compare of depths[v] against it (masks[v] if given).  The project's own
+    per-pixel bars against a rendered cloud: not the evaluation program of a benchmark (no observation masks, no alignment).
+    Returns (views, total): per view depth_compare's dict plus "n_splats"; total adds the counts over the views first and forms the ratios
+    afterwards."""
+    views = []
+    c, dev = _cloud(cloud, "cloud")
+    with _matcher_for(matcher, device, c) as m:
+        for v, d in enumerate(depths):
+            h, w = int(d.shape[0]), int(d.shape[1])
+            r = cloud_render(c, K[v], R[v], t[v], w, h, radius, want=("depth",), matcher=m, **render_kw)
+            if dev != _is_torch(d):                  # the map goes where the cloud's render lies
+                if dev:
+                    import torch
+                    d = torch.from_numpy(np.ascontiguousarray(d, np.float32)).to(c.device)
+                else:
+                    d = d.cpu().numpy()
+            rec = depth_compare(d, r["depth"], tolerances, None if masks is None else masks[v], matcher=m)
+            rec["n_splats"] = r["n_splats"]
+            views.append(rec)
+    total = {"tolerances": np.ascontiguousarray(tolerances, np.float32).reshape(-1)}
+    for k in ("n_gt", "n_both", "n_front", "n_behind", "n_splats"):
+        total[k] = int(sum(rec[k] for rec in views))
+    total["within"] = np.sum([rec["within"] for rec in views], axis=0, dtype=np.int64) if views else np.zeros(len(total["tolerances"]), np.int64)
+    return views, _depth_ratios(total)
 
 
 def pinned_empty(shape, dtype=np.float32):

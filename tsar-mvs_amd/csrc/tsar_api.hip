@@ -229,6 +229,7 @@ static void read_knobs(tsar_ctx* ctx) {
     ctx->ransac_poll_limit = num("TSAR_RANSAC_POLL_LIMIT", 1 << 15);
     ctx->ransac_cooperative = on("TSAR_RANSAC_COOPERATIVE", true);
     ctx->ransac_force_fallback = on("TSAR_RANSAC_FORCE_FALLBACK", false);
+    ctx->render_skip = on("TSAR_RENDER_SKIP", true);
     ctx->trace_host = getenv("TSAR_TRACE_HOST") != nullptr;
 #ifdef TSAR_EXPERIMENTS
     ctx->lds_pad = (size_t)num("TSAR_LDS_PAD", 0);
@@ -1265,6 +1266,106 @@ extern "C" int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int 
     return rc;
 }
 
+// ---- a cloud rendered into a camera; a depth map scored against a map (cloud_render_kernels.hip) -----------------------------------------
+extern "C" void tsar_default_cloud_render_params(tsar_cloud_render_params* p) {
+    if (!p) return;
+    p->radius = 0.0f;                      // no default: the caller's scale (0 renders without a footprint)
+    p->max_px = 8;
+    p->occlusion_diff = 0.02f;
+    p->depth_diff = 0.01f;
+    p->min_points = 1;
+    p->max_splats = (int64_t)1 << 34;
+}
+
+// Like tsar_cloud_distance_ctx: no views, no state, nothing of the context written, and a frame that does not grow the arena.
+extern "C" int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p,
+                                     float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem) {
+    CHECK_CTX(ctx);
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: params is NULL");
+    if (!cam) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: cam is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: n must be in 0..2^31-1");
+    if (stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: the stride must be at least 3 floats (x y z first)");
+    if (n > 0 && !cloud) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: cloud is NULL");
+    if (!depth_out && !count_out && !index_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: depth_out, count_out and index_out are all NULL");
+    if (w < 1 || h < 1 || w + 2 >= (1 << 23) || h + 2 >= (1 << 23) || (int64_t)w * h > INT32_MAX)
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: w and h must be >= 1, with w + 2 and h + 2 < 2^23 (the 24-bit addressing limit) and w * h <= 2^31-1");
+    const float radius = p->radius;
+    const volatile float frv = cam->K[0] * radius;       // fl(K[0] * radius), one float32 product
+    const float fr = frv;
+    if (!(radius >= 0.0f && radius <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: radius must be finite and >= 0");
+    if (!(fr >= 0.0f && fr <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: K[0] * radius must be finite and >= 0 in float32");
+    if (p->max_px < 1 || p->max_px > 16) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: max_px must be in 1..16");
+    if (!(p->occlusion_diff >= 0.0f && p->occlusion_diff <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: occlusion_diff must be finite and >= 0");
+    if (!(p->depth_diff >= 0.0f && p->depth_diff <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: depth_diff must be finite and >= 0");
+    if (p->min_points < 1 || p->min_points > 255) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: min_points must be in 1..255");
+    if (p->max_splats < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: max_splats must be >= 0");
+    CrViewHost vh;
+    for (int k = 0; k < 3; k++) {                         // P = K [R | t]: float64 products and sums of the float32 elements, rounded once
+        const double k0 = cam->K[k * 3], k1 = cam->K[k * 3 + 1], k2 = cam->K[k * 3 + 2];
+        for (int j = 0; j < 3; j++) vh.P[k * 4 + j] = (float)((k0 * (double)cam->R[j] + k1 * (double)cam->R[3 + j]) + k2 * (double)cam->R[6 + j]);
+        vh.P[k * 4 + 3] = (float)((k0 * (double)cam->t[0] + k1 * (double)cam->t[1]) + k2 * (double)cam->t[2]);
+    }
+    vh.fr = radius > 0.0f ? fr : 0.0f;
+    vh.foot = radius > 0.0f;
+    vh.max_px = p->max_px;
+    vh.w = w;
+    vh.h = h;
+    CallFrame f(ctx, "tsar_cloud_render", nullptr, /*grow_arena=*/false);
+    const size_t np = (size_t)w * h;
+    const float* c = f.in(cloud, (size_t)n * stride, mem);
+    float* dd = f.out(depth_out, np, mem);
+    uint8_t* dc = f.out(count_out, np, mem);
+    int32_t* di = f.out(index_out, np, mem);
+    if (!f.ok()) return f.finish();
+    return run_cloud_render(f, c, n, stride, vh, p->occlusion_diff, p->depth_diff, p->min_points, p->max_splats, dd, dc, di, n_splats_out);
+}
+
+extern "C" int tsar_cloud_render(int device, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p,
+                                 float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem) {
+    tsar_ctx* ctx = nullptr;
+    const int rc0 = tsar_create(device, &ctx);
+    if (rc0 != TSAR_OK) return rc0;
+    const int rc = tsar_cloud_render_ctx(ctx, cloud, n, stride, cam, w, h, p, depth_out, count_out, index_out, n_splats_out, mem);
+    tsar_destroy(ctx);
+    return rc;
+}
+
+extern "C" int tsar_depth_compare_ctx(tsar_ctx* ctx, const float* depth, const float* gt, const uint8_t* mask, int64_t n, int n_tol, const float* tol, int64_t* n_gt_out,
+                                      int64_t* n_both_out, int64_t* within_out, int64_t* n_front_out, int64_t* n_behind_out, float* error_out, int mem) {
+    CHECK_CTX(ctx);
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: n must be in 0..2^31-1");
+    if (n > 0 && (!depth || !gt)) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: depth or gt is NULL");
+    if (n_tol < 1 || n_tol > TSAR_DEPTH_COMPARE_MAX_TOL || !tol) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: n_tol must be in 1..16, and tol not NULL");
+    for (int k = 0; k < n_tol; k++)
+        if (!(tol[k] >= 0.0f && tol[k] <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: every tolerance must be finite and >= 0");
+    CallFrame f(ctx, "tsar_depth_compare", nullptr, /*grow_arena=*/false);
+    const float* d = f.in(depth, (size_t)n, mem);
+    const float* g = f.in(gt, (size_t)n, mem);
+    const uint8_t* m = f.in(mask, (size_t)n, mem);
+    float* e = f.out(error_out, (size_t)n, mem);
+    if (!f.ok()) return f.finish();
+    unsigned long long counters[4 + TSAR_DEPTH_COMPARE_MAX_TOL] = {0};
+    TRY(run_depth_compare(f, d, g, m, n, n_tol, tol, e, counters));
+    if (n_gt_out) *n_gt_out = (int64_t)counters[0];
+    if (n_both_out) *n_both_out = (int64_t)counters[1];
+    if (n_front_out) *n_front_out = (int64_t)counters[2];
+    if (n_behind_out) *n_behind_out = (int64_t)counters[3];
+    for (int k = 0; k < n_tol && within_out; k++) within_out[k] = (int64_t)counters[4 + k];
+    return TSAR_OK;
+}
+
+extern "C" int tsar_depth_compare(int device, const float* depth, const float* gt, const uint8_t* mask, int64_t n, int n_tol, const float* tol, int64_t* n_gt_out,
+                                  int64_t* n_both_out, int64_t* within_out, int64_t* n_front_out, int64_t* n_behind_out, float* error_out, int mem) {
+    tsar_ctx* ctx = nullptr;
+    const int rc0 = tsar_create(device, &ctx);
+    if (rc0 != TSAR_OK) return rc0;
+    const int rc = tsar_depth_compare_ctx(ctx, depth, gt, mask, n, n_tol, tol, n_gt_out, n_both_out, within_out, n_front_out, n_behind_out, error_out, mem);
+    tsar_destroy(ctx);
+    return rc;
+}
+
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
     CHECK_CTX(ctx);
     NEED_STATE(ctx);
@@ -1403,6 +1504,11 @@ extern "C" void tsar_device_free(int device, void* p) {
 extern "C" int tsar_device_write(int device, void* dst, const void* host_src, size_t bytes) {
     if (!dst || !host_src) return TSAR_ERR_INVALID;
     if (hipSetDevice(device) != hipSuccess || hipMemcpy(dst, host_src, bytes, hipMemcpyHostToDevice) != hipSuccess) return TSAR_ERR_HIP;
+    return TSAR_OK;
+}
+extern "C" int tsar_device_read(int device, void* host_dst, const void* src, size_t bytes) {
+    if (!host_dst || !src) return TSAR_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess || hipMemcpy(host_dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return TSAR_ERR_HIP;
     return TSAR_OK;
 }
 extern "C" int tsar_peer_copy(int dst_device, void* dst, int src_device, const void* src, size_t bytes) {

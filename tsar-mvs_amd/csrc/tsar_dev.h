@@ -198,6 +198,7 @@ struct tsar_ctx {
     bool ransac_cooperative = true;       // TSAR_RANSAC_COOPERATIVE=0: plain launch of the multi-workgroup stage 2
     bool ransac_force_fallback = false;   // TSAR_RANSAC_FORCE_FALLBACK=1: pre-set the give-up flag (tests of that path)
     bool trace_host = false;     // TSAR_TRACE_HOST=1: host-side steps of the refinement operators on stderr
+    bool render_skip = true;     // TSAR_RENDER_SKIP=0: tsar_cloud_render's footprint loop issues every minimum, without the plain load that lets a lane skip one
 #ifdef TSAR_EXPERIMENTS
     size_t lds_pad = 0;          // TSAR_LDS_PAD=n: unused LDS per sweep workgroup (occupancy experiments)
 #endif
@@ -463,6 +464,12 @@ int run_cloud_distance(CallFrame& f, const float* query, long long n_query, int 
 int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, double voxel, const float* dist2, int n_tol, const float* tol2, int32_t* rank_out,
                      long long cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
                      int mem);                                                                  // cloud_voxel_kernels.hip (cloud, dist2: device; outputs in `mem`; finishes the frame)
+struct CrViewHost { float P[12]; float fr; int max_px, w, h; bool foot; };                       // tsar_cloud_render's view: P, fl(K[0] * radius), radius > 0
+int run_cloud_render(CallFrame& f, const float* cloud, long long n, int stride, const CrViewHost& vh, float occlusion_diff, float depth_diff, int min_points,
+                     long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,
+                     int64_t* n_splats_out);                                                     // cloud_render_kernels.hip (device pointers; finishes the frame)
+int run_depth_compare(CallFrame& f, const float* depth, const float* gt, const uint8_t* mask, long long n, int n_tol, const float* tol, float* error_out,
+                      unsigned long long* counters_out);                                         // cloud_render_kernels.hip (counters: n_gt, n_both, n_front, n_behind, within[16])
 int launch_compute_disp(tsar_ctx* ctx);
 int launch_compute_disp_final(tsar_ctx* ctx, const float4* resize4, const float* text);
 int launch_depth_to_plane(tsar_ctx* ctx);
