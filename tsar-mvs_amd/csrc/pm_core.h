@@ -233,7 +233,9 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
     static_assert(!PRUNE || !GEOM, "the bound speaks of the photometric cost alone");
     constexpr bool PAIR = (V & TSAR_V_PAIR) != 0;
     static_assert(!PAIR || (!PRUNE && !GEOM), "the paired gathers exist for the plain fast box-11 kernels");
-    constexpr int VT = V & ~(TSAR_V_GEOM | TSAR_V_REDRAW | TSAR_V_PRUNE | TSAR_V_PAIR);
+    constexpr bool RING = (V & TSAR_V_RING) != 0;
+    constexpr int VT = V & ~(TSAR_V_GEOM | TSAR_V_REDRAW | TSAR_V_PRUNE | TSAR_V_PAIR | TSAR_V_RING);
+    static_assert(!RING || (VT == (250 | TSAR_V_BUF | TSAR_V_MIX) && !GEOM && !PAIR && !STRICT && QUAD && HR == 5), "the ring exists for the fast difference-texture box-11 kernels");
     float best[NB];
 #pragma unroll
     for (int k = 0; k < NB; k++) best[k] = __builtin_inff();
@@ -257,13 +259,13 @@ DEVFN float multiview_cost(const DevScene* __restrict__ sc, const typename TileO
             ViewPrune vp;
             vp.on = prune; vp.skipped = false;
             vp.cost_now = cmin < cost_now ? TSAR_MAXCOST : cost_now;          // (a lane that will accept needs exact values)
-            c = view_cost_r5<false, true, true, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK, 0, true>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4, &vp);
+            c = view_cost_r5<false, true, true, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK, 0, true, false, RING>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4, &vp);
             if (vp.skipped) *skipped += 1;
         } else if constexpr (QUAD && HR == 5 && PAIR && VT == 250) {
             static_assert(!STRICT, "the paired gathers exist for the fast row-wise loop");
             c = view_cost_r5<false, true, true, false, false, BLK, 0, false, true>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
         } else if constexpr (QUAD && HR == 5 && r5_production_variant(VT))
-            c = view_cost_r5<STRICT, (VT & 128) != 0 && !STRICT, (VT & 8) != 0, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
+            c = view_cost_r5<STRICT, (VT & 128) != 0 && !STRICT, (VT & 8) != 0, (VT & TSAR_V_BUF) != 0, (VT & TSAR_V_MIX) != 0, BLK, 0, false, false, RING>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);
 #ifdef TSAR_EXPERIMENTS
         else if constexpr (QUAD && HR == 5 && PAIR && VT == (250 | 4194304))
             c = view_cost_r5<false, true, true, false, false, BLK, 3, false, true>(sc, sc->view[vi], tile, tw, own, wts, pr, x, y, n4);

@@ -67,7 +67,10 @@ static int launch_sweep_nh(tsar_ctx* ctx, int colour, const PlaneBuf& a, const P
         // ... and where the choice is the plain global-load kernel <2, 5, false, true, 250, B> (the first sweep of a run: random planes,
         // every lane on its own cache line), the paired-gather kernel of pm_pair.hip (TSAR_PAIR bit 1)
         const bool pair = NB == 2 && !strict && v == 250 && !buf && !prune && (ctx->pair & 2) && !scene_has_terms(ctx->hscene);
-#define SWEEP_R5_FAST250(B) (prune ? SWEEP_R5_PRUNE(B) : pair ? launch_pm_sweep_pair(ctx, B, colour, a, b, c, sid, dp, dr) : SWEEP_R5_FAST250_ALL(B))
+        // ... and where it is a difference-texture kernel of the best-two-views form without terms, plain or checking, the ring kernel
+        // of pm_ring.hip, from sweep TSAR_RING of a run on (the same counter as TSAR_BUFFER_FROM)
+        const bool ring = NB == 2 && mix && ctx->ring > 0 && ctx->sweeps_done >= ctx->ring && !scene_has_terms(ctx->hscene);
+#define SWEEP_R5_FAST250(B) (ring ? launch_pm_sweep_ring(ctx, B, prune, colour, a, b, c, sid, dp, dr) : prune ? SWEEP_R5_PRUNE(B) : pair ? launch_pm_sweep_pair(ctx, B, colour, a, b, c, sid, dp, dr) : SWEEP_R5_FAST250_ALL(B))
         if constexpr (NB == 2) {
             // small images: 128-thread workgroups (see SWEEP_SMALL_IMAGE_TILES); TSAR_BLOCK=128|256 forces a shape (A/B runs)
             const int tiles256 = ((ctx->hscene.w + PM_RW - 1) / PM_RW) * ((ctx->hscene.h + 15) / 16);

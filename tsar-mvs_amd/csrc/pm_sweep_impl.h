@@ -491,7 +491,7 @@ __global__ __launch_bounds__(BLK) void pm_sweep_kernel(const DevScene* __restric
 
 // the tap loops of 8-bit imagery — box 11's own and the general-window one — have a packed form (CMP) beside the rolled one
 template <int HR, bool QUAD, int V>
-constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~(TSAR_V_GEOM | TSAR_V_PRUNE))) || (V & TSAR_V_LUT) != 0); }
+constexpr bool sweep_has_packed_form() { return QUAD && ((HR == 5 && r5_production_variant(V & ~(TSAR_V_GEOM | TSAR_V_PRUNE | TSAR_V_RING))) || (V & TSAR_V_LUT) != 0); }
 
 template <int NB, int HR, bool STRICT, bool QUAD, int V = 0, int BLK = PM_BLOCK>
 static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
@@ -523,6 +523,7 @@ static int launch_sweep_t(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, co
         ScopedKernelTimer tm_packed(ctx, packed ? "pm_sweep_packed" : nullptr);      // (the packed launches a second time under their own name)
         ScopedKernelTimer tm_prune(ctx, (V & TSAR_V_PRUNE) ? "pm_sweep_prune" : nullptr);   // (and the pruning kernels, checking or not)
         ScopedKernelTimer tm_pair(ctx, (V & TSAR_V_PAIR) ? "pm_sweep_pair" : nullptr);      // (and the paired-gather kernels)
+        ScopedKernelTimer tm_ring(ctx, (V & TSAR_V_RING) ? "pm_sweep_ring" : nullptr);      // (and the ring kernels)
         hipLaunchKernelGGL(kern, dim3(g.n_tiles), dim3(BLK), g.lds, ctx->stream, ctx->dscene, colour, same_in.c, same_in.n4, other.c,
                            other.n4, same_out.c, same_out.n4, ctx->ratio, ctx->beview, stream_id, do_prop, do_refine, g.tiles_x, g.n_tiles,
                            ctx->cost_consistent ? 1 : 0, strip_width(ctx->strip_w, g.tiles_x), ctx->final_text, memo);

@@ -54,9 +54,18 @@
 // reaches blend_quad unchanged and in the same order: the same bits, with ~38 % fewer L1 look-ups where every lane is on its own
 // line (init, the first sweep of a view).
 // DIAG 3 (experiments build only, WRONG RESULTS): PAIR with the uncovered lanes' gathers left out: the ceiling of the paired loop.
-template <bool STRICT, bool ROW, bool D16, bool BUF, bool MIX, int BLK, int DIAG = 0, bool PRUNE = false, bool PAIR = false>
+// RING (variant bit TSAR_V_RING; the MIX form only, with or without PRUNE): the unrolled clamp-free walk as a ring of six taps.  The
+// three-phase line issues six gathers and waits at once for the oldest; the ring issues line 0's six, then per tap t = 0..29 waits
+// for tap t alone (vmcnt(5): gathers return in order), blends and accumulates it, computes the position of tap t + 6 and issues its
+// gather into the slot tap t has just left; taps 30..35 drain with the counts 5..0.  Five or six gathers are in flight from the
+// first tap of a view to its thirtieth.  The same calls with the same operands in the same order per tap, and the taps enter the three
+// sums in the same order: the same bits.  A line's base is dead once its sixth position exists, so the next line's takes its
+// registers; a line's nine LDS loads are issued at the line's first blend (their registers hold the previous line's until then).
+// The ring drains at the end of a view: the next view's homography is not known earlier.  Every other loop is as it was.
+template <bool STRICT, bool ROW, bool D16, bool BUF, bool MIX, int BLK, int DIAG = 0, bool PRUNE = false, bool PAIR = false, bool RING = false>
 DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, const unsigned short* tile, int tw, int own, const float* wts,
                          const PixelRef& pr, int x, int y, const float4& n4, ViewPrune* vp = nullptr) {
+    static_assert(!RING || (MIX && ROW && D16 && DIAG == 0 && !PAIR), "the ring is a form of the unrolled difference-texture walk");
     static_assert(!(STRICT && ROW), "the row-wise walk changes the summation order: fast mode only");
     static_assert(!PRUNE || (ROW && D16 && !STRICT && DIAG == 0), "the partial-window bound is written for the fast row-wise loop");
     static_assert(!MIX || (BUF && !STRICT), "the half-float difference texture serves the fast arithmetic's blend through buffer loads");
@@ -284,8 +293,65 @@ DEVFN float view_cost_r5(const DevScene* __restrict__ sc, const DevView& vw, con
     } else if (MIX && !(PRUNE && vp->on)) {      // (a checked hypothesis walks the rolled loop below: the checks sit between its trips)
         // the converged launches' hot path: the six lines unrolled (-6 VALU and the loop's scalar bookkeeping per line; +0.65 %
         // Mpix/s, profiles/r04/ab_unrolled_lines)
+        if constexpr (RING) {
+            constexpr int U = BLK / 64;
+            const float uhi = (float)(w - 1), vhi = (float)(h - 1);
+            const uint32_t wa = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)wts;
+            const uint32_t a0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned short*)(tile + own - 5 * tw - 5);
+            float bx, by, bz, ax[6], ay[6], rcol[6];
+            f32x2 wcol[3];
+            uint64_t q2[6];
+            __builtin_amdgcn_s_setprio(2);               // constant: the ring has no phases (none: +1 ms per view, 1 / 2 / 3 alike: profiles/ring)
+            tap_line_base<false, true>(H, (float)(y - 5), bx, by, bz);
 #pragma unroll
-        for (int i = -5; i <= 5; i += 2) line6(i, std::false_type(), std::bool_constant<MIX>());
+            for (int jj = 0; jj < 6; jj++) {                    // prologue: line 0's positions and gathers
+                float X, Y, Z;
+                int lin;
+                tap_homogeneous<false, true>(H, (float)(x + 2 * jj - 5), bx, by, bz, X, Y, Z);
+                tap_position<false, false>(X, Y, Z, uhi, vhi, qp, ax[jj], ay[jj], lin);
+                q2[jj] = buffer_gather<true>(lin, rsrc);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < 36; t++) {
+                const int line = t / 6, jj = t % 6;
+                if (jj == 0) {
+                    // the line's weights and reference texels (line6's loads, unrolled form); the unused operand keeps them behind the
+                    // previous line's last tap, whose registers they take, and inside the view loop
+                    const float dep = line == 0 ? bz : sum_ref_src;
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+                        asm("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(wcol[k]) : "v"(wa), "n"(2 * U * 6 * k + U * line), "n"(2 * U * 6 * k + U * 6 + U * line), "v"(dep));
+#pragma unroll
+                    for (int k = 0; k < 6; k++)
+                        asm("ds_read_u16_d16_hi %0, %1 offset:%2" : "=v"(rcol[k]) : "v"(a0), "n"(k * 4 + line * 2 * (PM_RW + 10) * 2), "v"(dep));
+                }
+                // tap t is the oldest gather in flight: five younger ones behind it until tap 30, then 35 - t.  The input is the
+                // youngest gather issued (each wait stays behind it), the accumulator keeps the wait behind the previous tap
+                if (t == 0) asm("s_waitcnt vmcnt(5)" : "+v"(q2[0]) : "v"(q2[5]));
+                else if (t < 35) asm("s_waitcnt vmcnt(%2)" : "+v"(q2[jj]), "+v"(sum_src_src) : "n"(t < 30 ? 5 : 35 - t), "v"(q2[t < 30 ? (jj + 5) % 6 : 5]));
+                else asm("s_waitcnt vmcnt(0)" : "+v"(q2[5]), "+v"(sum_src_src));
+                float s = blend_dquad(q2[jj], ax[jj], ay[jj]);
+                if (jj == 0)
+                    asm("s_waitcnt lgkmcnt(0)" : "+v"(rcol[0]), "+v"(rcol[1]), "+v"(rcol[2]), "+v"(rcol[3]), "+v"(rcol[4]), "+v"(rcol[5]),
+                        "+v"(wcol[0]), "+v"(wcol[1]), "+v"(wcol[2]), "+v"(s));
+                const TapSums ts = tap_accumulate<false>(TapSums{sum_src, sum_src_src, sum_ref_src}, wcol[jj >> 1][jj & 1], rcol[jj], s);
+                sum_src = ts.src; sum_src_src = ts.src_src; sum_ref_src = ts.ref_src;
+                if (t < 30) {                                   // tap t + 6 into the slot tap t has left
+                    if (jj == 0) tap_line_base<false, true>(H, (float)(y + 2 * (line + 1) - 5), bx, by, bz);
+                    float X, Y, Z;
+                    int lin;
+                    tap_homogeneous<false, true>(H, (float)(x + 2 * jj - 5), bx, by, bz, X, Y, Z);
+                    tap_position<false, false>(X, Y, Z, uhi, vhi, qp, ax[jj], ay[jj], lin);
+                    q2[jj] = buffer_gather<true>(lin, rsrc);
+                }
+                __builtin_amdgcn_sched_barrier(0);              // one tap at a time: the gathers stay one per tap
+            }
+            __builtin_amdgcn_s_setprio(0);
+        } else {
+#pragma unroll
+            for (int i = -5; i <= 5; i += 2) line6(i, std::false_type(), std::bool_constant<MIX>());
+        }
     } else {
 #pragma unroll 1
         for (int i = -5; i <= 5; i += 2) { line6(i, std::false_type(), std::false_type()); if (pruned((i + 5) >> 1)) return TSAR_MAXCOST; }

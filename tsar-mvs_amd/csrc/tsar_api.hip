@@ -222,6 +222,7 @@ static void read_knobs(tsar_ctx* ctx) {
     ctx->prune_steps = std::min(std::max(num("TSAR_PRUNE_STEPS", 2), 0), 8);      // (the census keeps eight steps' counters)
     ctx->prune_from = num("TSAR_PRUNE_FROM", 1);
     ctx->pair = num("TSAR_PAIR", 3);
+    ctx->ring = num("TSAR_RING", ctx->ring);
     ctx->lut_mode = num("TSAR_LUT", 1);
     ctx->ransac_wgs = num("TSAR_RANSAC_WGS", 8);
     ctx->ransac_chain = num("TSAR_RANSAC_CHAIN", 8);

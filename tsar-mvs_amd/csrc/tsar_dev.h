@@ -93,6 +93,7 @@ static inline bool scene_has_terms(const DevScene& s) { return s.geom_on != 0 ||
 #define TSAR_V_GEOM 16777216      // bit 24: multiview_cost adds lambda e to each view's cost (pm_core.h geom_term) and the plane-prior term to the result (add_prior_term)
 #define TSAR_V_PRUNE 67108864     // bit 26, with 250 and its BUF / MIX forms, sweep only: wide refinement steps leave a view the partial-window bound proves rejected (pm_tap_r5.h PRUNE)
 #define TSAR_V_PAIR 134217728     // bit 27, with 250 alone (pm_pair.hip): one 16-byte gather per pair of row taps (pm_tap_r5.h PAIR)
+#define TSAR_V_RING 268435456     // bit 28, with 250 | TSAR_V_BUF | TSAR_V_MIX and its TSAR_V_PRUNE form, sweep only (pm_ring.hip): the unrolled clamp-free walk keeps six gathers in flight across a view's lines (pm_tap_r5.h RING)
 #define TSAR_V_REDRAW 33554432    // bit 25, with INIT: pm_full_kernel keeps the given plane where it is a valid hypothesis (tsar_pm_rescore)
 
 // State planes of one ping-pong buffer (linestate.h:12-13).
@@ -169,6 +170,11 @@ struct tsar_ctx {
     // Paired gathers in the random-plane launches (pm_pair.hip, pm_tap_r5.h PAIR): TSAR_PAIR=0 neither, 1 the initialisation, 2 the
     // first sweep of a run (the plain global-load launches), 3 both
     int pair = 3;
+    // The ring form of the difference-texture launches' unrolled walk (pm_ring.hip, pm_tap_r5.h RING): TSAR_RING=0 never, n >= 1 from
+    // sweep n of a run on (1: every difference-texture launch).  Measured per launch (profiles/ring): sweep 1, whose planes have seen one
+    // sweep and are still unrelated between neighbouring lanes, loses 5 ms to the ring (a row's six gathers no longer reach L1 together),
+    // sweep 2 0.35 ms; every later one gains 0.3 - 1 ms.
+    int ring = 3;
     uint32_t* prune_counts = nullptr; // tsar_selftest_prune_census: device counters while a census runs, else null
     // coarse-to-fine mode (tsar_pyramid_views / tsar_upsample_planes)
     std::vector<tsar_camera> cams;    // the cameras tsar_set_views was given (before cam_scale), from which a coarser level derives its own
@@ -417,6 +423,8 @@ int launch_pm_init(tsar_ctx* ctx);
 int launch_pm_init_pair(tsar_ctx* ctx);    // pm_pair.hip: the plain fast box-11 configuration with paired gathers
 int launch_pm_sweep_pair(tsar_ctx* ctx, int block, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
                          uint32_t stream_id, int do_prop, int do_refine);   // pm_pair.hip
+int launch_pm_sweep_ring(tsar_ctx* ctx, int block, bool prune, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
+                         uint32_t stream_id, int do_prop, int do_refine);   // pm_ring.hip
 bool probe_d16_hi_zeroes(tsar_ctx* ctx);   // pm_sweep.hip
 int launch_pm_sweep(tsar_ctx* ctx, int colour, const PlaneBuf& same_in, const PlaneBuf& other, const PlaneBuf& same_out,
                     uint32_t stream_id, int do_prop, int do_refine);
