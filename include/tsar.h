@@ -43,6 +43,7 @@
  *   Fusion.exe (binary only; flags x/1.sh:20-30)         tsar_fuse
  *   (none: the reference ships no evaluation)            tsar_cloud_distance
  *   (none: the reference's fuser thins nothing)          tsar_cloud_voxels
+ *   (none: the reference's fuser cleans nothing)         tsar_cloud_neighbors
  *   (none: the reference renders no cloud)               tsar_cloud_render / tsar_depth_compare
  *
  * Conventions
@@ -642,6 +643,48 @@ int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stri
 int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2,
                       int n_tol, const float* tol, int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out,
                       int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out, int mem);
+
+/* ---- neighbourhood statistics of a cloud (removing stray points from a fused cloud before it is thinned or scored) ----------------- */
+/* Per point of one cloud: how many other points lie within a radius R, and the k smallest squared distances among those.  Records are
+ * `stride` float32 each (>= 3), x y z first.  `mem` names where cloud, count_out and knn_dist2_out lie; n_valid_out and pairs_out are host
+ * memory.  The arithmetic, the same in both arithmetic modes: float32, every operation one IEEE-754 operation rounded to nearest, no
+ * fused multiply-add.
+ *   candidate: a record whose x, y and z are all finite (tsar_cloud_distance's rule)
+ *   for candidates i and j:  dx = xi - xj, dy = yi - yj, dz = zi - zj;  d2(i, j) = (dx * dx + dy * dy) + dz * dz (tsar_cloud_distance's)
+ *   R2 = fl(R * R), one float32 product
+ *   count[i] = the number of candidates j != i with d2(i, j) <= R2.  The point itself is excluded by its index, not by its distance: a
+ *     duplicate of the point counts, with d2 = +0.  count[i] = -1 for a record that is no candidate
+ *   knn_dist2[i][0 .. k) = the k smallest values, ascending, of the multiset { d2(i, j) : j != i, j a candidate, d2(i, j) <= R2 }, padded
+ *     with +inf where the multiset has fewer than k values; all +inf for a record that is no candidate.  A multiset of values: ties
+ *     need no index rule
+ *   n_valid = the number of candidates
+ *   pairs = the number of (i, j) the call looked at: the sum over the candidates i of the candidates in the 27 cells around i's, the
+ *     point itself included
+ * Integer counts and order statistics of bit-defined values: no output depends on an order of arrival, and every run gives the same
+ * bits.  How the pairs are found changes none of them: tsar_cloud_distance's grid over the candidates (origin = their per-axis minimum,
+ * cell edge (double)R * (1 + 2^-10), the float64 cell function), and the argument written there carries over: two points with d2 <= R2
+ * lie in cells that differ by at most 1 per axis, so the 27 cells hold every pair that counts.
+ * n == 0 or no candidate: success, every count -1, n_valid 0, pairs 0.
+ * TSAR_ERR_INVALID, with the reason in tsar_last_error: p NULL; mem unknown; a stride below 3; n negative or above 2^31 - 1; radius not
+ * finite, or fl(R * R) not finite or not > 0; k outside 0 .. TSAR_CLOUD_KNN_MAX; knn_dist2_out given with k == 0; max_pairs negative; a
+ * grid of 2^20 cells or more on an axis (radius is too small for the cloud's extent); more than max_pairs pairs — then *pairs_out is
+ * still filled and nothing else is written.
+ * tsar_cloud_neighbors_ctx needs no views and no state, runs on the context's stream and changes nothing in the context; its temporaries
+ * (24 bytes per point, 16 per candidate and the sort's scratch) are pieces of the call's frame that never grow the context's scratch arena.  tsar_cloud_neighbors is
+ * the context-free form, like tsar_cloud_voxels.  Timed as "cloud_bounds", "cloud_keys", "cloud_sort", "cloud_gather", "cloud_pairs" and
+ * "cloud_neighbors" (the search, and the pass that marks the records that are no candidates). */
+#define TSAR_CLOUD_KNN_MAX 32
+typedef struct tsar_cloud_neighbors_params {
+    float radius;         /* R: finite, fl(R * R) finite and > 0.  No default (0): the caller's scale */
+    int32_t k;            /* 0 .. TSAR_CLOUD_KNN_MAX: how many nearest neighbours' distances to return; 0 = counts only */
+    int64_t max_pairs;    /* as tsar_cloud_distance: a call that would look at more pairs is refused; default 1 << 40 */
+} tsar_cloud_neighbors_params;
+void tsar_default_cloud_neighbors_params(tsar_cloud_neighbors_params* p);
+int tsar_cloud_neighbors_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_neighbors_params* p,
+                             int32_t* count_out /* [n] or NULL */, float* knn_dist2_out /* [n][k] or NULL */,
+                             int64_t* n_valid_out, int64_t* pairs_out /* host, may be NULL */, int mem);
+int tsar_cloud_neighbors(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_neighbors_params* p, int32_t* count_out,
+                         float* knn_dist2_out, int64_t* n_valid_out, int64_t* pairs_out, int mem);
 
 /* ---- a cloud rendered into a camera, and a depth map scored against such a map ------------------------------------------------------- */
 /* tsar_cloud_render: a point cloud (a scan, a fused cloud) rendered into one calibrated view as a depth map, occlusion by the cloud's own

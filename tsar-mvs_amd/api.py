@@ -79,6 +79,10 @@ class CloudVoxelsParams(C.Structure):
     _fields_ = [("voxel", C.c_float)]
 
 
+class CloudNeighborsParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("k", C.c_int32), ("max_pairs", C.c_int64)]
+
+
 class CloudRenderParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("max_px", C.c_int32), ("occlusion_diff", C.c_float), ("depth_diff", C.c_float), ("min_points", C.c_int32),
                 ("max_splats", C.c_int64)]
@@ -98,6 +102,7 @@ _SET_VIEWS = (_I, [_P, _I, _I, _I, _p(_P), _I, _p(Camera)])
 _FUSE = (_I, [_I, _I, _I, _I, _p(Camera), _p(_P), _p(_P), _p(_P), _I, _P, _P, _p(FusionParams), _P, _L, _p(_L)])
 _CLOUD_DISTANCE = (_I, [_I, _P, _L, _I, _P, _L, _I, _p(CloudDistanceParams), _I, _P, _P, _P, _P, _p(_L), _p(_L), _I])
 _CLOUD_VOXELS = (_I, [_I, _P, _L, _I, _p(CloudVoxelsParams), _P, _I, _P, _P, _L, _P, _P, _P, _p(_L), _p(_L), _I])
+_CLOUD_NEIGHBORS = (_I, [_I, _P, _L, _I, _p(CloudNeighborsParams), _P, _P, _p(_L), _p(_L), _I])
 
 _CLOUD_RENDER = (_I, [_I, _P, _L, _I, _p(Camera), _I, _I, _p(CloudRenderParams), _P, _P, _P, _p(_L), _I])
 _DEPTH_COMPARE = (_I, [_I, _P, _P, _P, _L, _I, _P, _p(_L), _p(_L), _P, _p(_L), _p(_L), _P, _I])
@@ -177,6 +182,9 @@ _ABI = {
     "tsar_default_cloud_voxels_params": (None, [_p(CloudVoxelsParams)]),
     "tsar_cloud_voxels_ctx": _on_ctx(_CLOUD_VOXELS),
     "tsar_cloud_voxels": _CLOUD_VOXELS,
+    "tsar_default_cloud_neighbors_params": (None, [_p(CloudNeighborsParams)]),
+    "tsar_cloud_neighbors_ctx": _on_ctx(_CLOUD_NEIGHBORS),
+    "tsar_cloud_neighbors": _CLOUD_NEIGHBORS,
     "tsar_default_cloud_render_params": (None, [_p(CloudRenderParams)]),
     "tsar_cloud_render_ctx": _on_ctx(_CLOUD_RENDER),
     "tsar_cloud_render": _CLOUD_RENDER,
@@ -1052,6 +1060,114 @@ def voxel_downsample(cloud, voxel, matcher=None, device=0):
     return c[np.sort(rep)].copy()
 
 
+def cloud_neighbors(cloud, radius, k=0, want=("count", "knn_dist2"), max_pairs=None, matcher=None, device=0):
+    """Per point of `cloud` the number of its other points within `radius`, and the k smallest squared float32 distances among those
+    (tsar_cloud_neighbors_ctx; include/tsar.h states the arithmetic).  cloud: [n, c >= 3] float32, x y z first, a numpy array or a torch
+    device tensor; records with a non-finite coordinate take no part.  The point itself is left out by its index, so a duplicate of it
+    counts, at distance 0.  k: 0 .. 32; 0 = counts only ("knn_dist2" is then not returned).  max_pairs: the call is refused (TsarError,
+    TSAR_ERR_INVALID, with .pairs) when it would look at more pairs; None = the library's default.  matcher / device: as cloud_distance.
+    Returns a dict: "count" ([n] int32, -1 for a non-candidate) and / or "knn_dist2" ([n, k] float32, ascending, +inf where fewer than k
+    points lie within radius), as `want` names them (numpy arrays, or torch tensors on the cloud's device); the integers "n_valid"
+    (records with finite coordinates) and "pairs" (pairs looked at)."""
+    L = load_library()
+    c, dev = _cloud(cloud, "cloud")
+    n, k = int(c.shape[0]), int(k)
+    p = CloudNeighborsParams()
+    L.tsar_default_cloud_neighbors_params(C.byref(p))
+    p.radius, p.k = float(radius), k
+    if max_pairs is not None:
+        p.max_pairs = int(max_pairs)
+    spec = {"count": ((n,), np.int32)}
+    if k > 0:
+        spec["knn_dist2"] = ((n, k), np.float32)
+    res = _outputs(spec, want, c.device if dev else None)
+    n_valid, pairs = C.c_int64(0), C.c_int64(-1)
+    with _matcher_for(matcher, device, c) as m:
+        rc = L.tsar_cloud_neighbors_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), C.byref(p), _ptr(res.get("count"))[0], _ptr(res.get("knn_dist2"))[0],
+                                        C.byref(n_valid), C.byref(pairs), MEM_DEVICE if dev else MEM_HOST)
+        if rc != TSAR_OK:
+            err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
+            err.pairs = int(pairs.value) if pairs.value >= 0 else None      # filled when max_pairs refused the call
+            raise err
+    res["n_valid"] = int(n_valid.value)
+    res["pairs"] = int(pairs.value)
+    return res
+
+
+def _outlier_settings(radius, min_neighbors, k, ratio):
+    """the settings of remove_outliers as (float, int or None, int or None, float); ValueError on what the tools refuse as well"""
+    radius, ratio = float(radius), float(ratio)
+    if min_neighbors is None and k is None:
+        raise ValueError("outlier removal needs min_neighbors, k or both")
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be a finite number > 0")
+    if min_neighbors is not None and int(min_neighbors) < 1:
+        raise ValueError("min_neighbors must be at least 1")
+    if k is not None and not 1 <= int(k) <= 32:
+        raise ValueError("k must be in 1..32")
+    if not (np.isfinite(ratio) and ratio > 0):
+        raise ValueError("ratio must be a finite number > 0")
+    return radius, None if min_neighbors is None else int(min_neighbors), None if k is None else int(k), ratio
+
+
+def _outlier_mask(c, dev, radius, min_neighbors, k, ratio, matcher, device):
+    """the keep mask of remove_outliers over the rows of the cloud c (_cloud's), a bool numpy array or tensor like c"""
+    res = cloud_neighbors(c, radius, k or 0, want=("count",) + (("knn_dist2",) if k else ()), matcher=matcher, device=device)
+    keep = res["count"] >= (0 if min_neighbors is None else min_neighbors)              # count is -1 for a non-candidate
+    if k:
+        s = res["knn_dist2"][:, k - 1]
+        if dev:
+            import torch
+            finite = s[torch.isfinite(s)]
+            m = int(finite.numel())
+            med = float(torch.kthvalue(finite, (m - 1) // 2 + 1).values.item()) if m else None
+        else:
+            finite = s[np.isfinite(s)]
+            m = int(finite.size)
+            med = np.partition(finite, (m - 1) // 2)[(m - 1) // 2] if m else None
+        if m == 0:
+            keep = keep & False
+        else:
+            T = np.float32(np.float32(np.float32(ratio) * np.float32(ratio)) * np.float32(med))      # two float32 products
+            keep = keep & (s <= float(T))                                                              # (a float32 value: exact as a Python float)
+    return keep
+
+
+def remove_outliers(cloud, radius, min_neighbors=None, k=None, ratio=2.0, return_mask=False, matcher=None, device=0):
+    """`cloud` without its stray points: the rows that are candidates (finite x y z) and pass every rule given, whole records (normals,
+    colours), in the cloud's own order; an array or tensor like `cloud`.  One cloud_neighbors call at `radius`.
+      radius rule (min_neighbors=N): at least N other points lie within radius of the point.
+      k-th-neighbour rule (k=K, ratio=Q): s = the squared distance to the point's K-th nearest neighbour within radius (+inf if it has
+        fewer); med = the lower median of the finite s (element (m - 1) // 2 of the m finite values in ascending order); the point is kept
+        iff s <= fl(fl(Q * Q) * med), two float32 products: its K-th neighbour lies within Q times the cloud's median K-th-neighbour
+        distance.  Without a finite s nothing passes.
+    At least one of min_neighbors and k must be given.  The k-th-neighbour rule is the scale-free form of statistical outlier removal: an
+    order statistic and two products, the same bits wherever it is computed.  It is NOT PCL's StatisticalOutlierRemoval, whose threshold is
+    the mean plus a multiple of the standard deviation of the mean neighbour distances: float sums that depend on their order.
+    return_mask=True returns (rows, the boolean keep mask over the cloud's rows)."""
+    radius, min_neighbors, k, ratio = _outlier_settings(radius, min_neighbors, k, ratio)
+    c, dev = _cloud(cloud, "cloud")
+    keep = _outlier_mask(c, dev, radius, min_neighbors, k, ratio, matcher, device)
+    rows = c[keep].clone() if dev else c[keep].copy()
+    return (rows, keep) if return_mask else rows
+
+
+def _clean_cloud(cloud, clean, matcher):
+    """-> (a copy of `cloud` with x y z of every record remove_outliers(**clean) removes replaced by NaN, the number of candidate records so
+    removed, the settings as a dict)"""
+    radius, min_neighbors, k, ratio = _outlier_settings(clean.get("radius"), clean.get("min_neighbors"), clean.get("k"), clean.get("ratio", 2.0))
+    c, dev = _cloud(cloud, "cloud")
+    keep = _outlier_mask(c, dev, radius, min_neighbors, k, ratio, matcher, 0)
+    out = c.clone() if dev else c.copy()
+    out[~keep, :3] = float("nan")
+    if dev:
+        import torch
+        n_removed = int((torch.isfinite(c[:, :3]).all(dim=1) & ~keep).sum().item())
+    else:
+        n_removed = int(np.count_nonzero(np.isfinite(c[:, :3]).all(axis=1) & ~keep))
+    return out, n_removed, {"radius": radius, "min_neighbors": min_neighbors, "k": k, "ratio": ratio}
+
+
 def _crop_cloud(cloud, crop):
     """-> (a copy of `cloud` with x y z of every record outside the closed box replaced by NaN, the number of candidate records so removed)"""
     c, dev = _cloud(cloud, "cloud")
@@ -1089,7 +1205,7 @@ def _f1(a, c):
     return np.where(s > 0, 2.0 * a * c / np.where(s > 0, s, 1.0), 0.0)
 
 
-def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, crop=None):
+def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, crop=None, clean=None):
     """Accuracy and completeness of the cloud `recon` against the cloud `gt` at each of `tolerances`: the point-wise precision / recall /
     F-score.  Two cloud_distance calls with max_dist = max(tolerances):
       accuracy[k]     = the share of recon's candidate points (finite coordinates) with a gt point within tolerances[k];
@@ -1101,6 +1217,8 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
     (Each share is one float64 division of two integer counts; the shares are added in ascending voxel order, one after another.)
     crop=(x0, y0, z0, x1, y1, z1) first makes every record of either cloud outside the closed box a non-candidate (on a copy: its
     coordinates become NaN), before anything else is computed.
+    clean=dict(radius=, min_neighbors=, k=, ratio=) first removes recon's stray points by remove_outliers' rules (on a copy: the removed
+    records' coordinates become NaN), before crop and before any scoring; gt is left as it is.
     This is NOT the evaluation program of a benchmark.  With voxel and crop it averages over voxels and crops to a box in the manner of
     the benchmarks, but ETH3D's program defines its voxels and its observed volume from the scanner's positions, DTU's applies observation
     masks, and both align the clouds first: nothing is registered here, there are no occlusion or observation masks, and the clouds are
@@ -1108,11 +1226,18 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
     Returns {"tolerances", "accuracy", "completeness", "f1"} as float64 numpy arrays (ratios formed on the host from the integer
     counts; 0 where a denominator is 0), {"n_accurate", "n_complete"} as int64 arrays, and the integers "n_recon_valid", "n_gt_valid",
     "pairs_accuracy", "pairs_completeness"; with voxel also "accuracy_voxel", "completeness_voxel", "f1_voxel" (float64 arrays),
-    "n_recon_voxels" and "n_gt_voxels"; with crop also "n_recon_cropped" and "n_gt_cropped" (the candidate records outside the box)."""
+    "n_recon_voxels" and "n_gt_voxels"; with crop also "n_recon_cropped" and "n_gt_cropped" (the candidate records outside the box); with clean also "clean" (the settings)
+    and "n_recon_cleaned" (the candidate records of recon removed)."""
     tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
     if tol.size == 0:
         raise ValueError("evaluate_cloud needs at least one tolerance")
     r = float(tol.max())
+    if clean is not None:
+        with _matcher_for(matcher, device, recon) as m:        # one context for the cleaning and the scoring
+            recon, n_cleaned, settings = _clean_cloud(recon, dict(clean), m)
+            res = evaluate_cloud(recon, gt, tol, matcher=m, voxel=voxel, crop=crop)
+        res.update({"clean": settings, "n_recon_cleaned": n_cleaned})
+        return res
     cropped = None
     if crop is not None:
         crop = tuple(float(v) for v in crop)

@@ -1,6 +1,8 @@
-// cloud_grid.h — what the operators on point clouds share (cloud_distance_kernels.hip, cloud_voxel_kernels.hip): the candidate rule, the
-// order-preserving float codes, the float64 cell function of include/tsar.h, the bounds pass over a cloud and the radix sort of
-// (key, index) pairs.  Kernels here are `static`: each translation unit that includes this file carries its own copy.
+// cloud_grid.h — what the operators on point clouds share (cloud_distance_kernels.hip, cloud_voxel_kernels.hip,
+// cloud_neighbor_kernels.hip): the candidate rule, the order-preserving float codes, the float64 cell function of include/tsar.h, the
+// bounds pass over a cloud, the radix sort of (key, index) pairs and, for the two searches, the grid of edge R (1 + 2^-10), its 16-byte
+// records and the walk over a query's nine key ranges.  Kernels here are `static`: each translation unit that includes this file carries
+// its own copy.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -45,6 +47,42 @@ static __global__ __launch_bounds__(CD_BLOCK) void cd_bounds_kernel(const float*
 
 static inline unsigned cd_blocks(long long n) { return (unsigned)((n + CD_BLOCK - 1) / CD_BLOCK); }
 static inline unsigned cd_bounds_blocks(long long n) { return cd_blocks(n) < 2048u ? cd_blocks(n) : 2048u; }
+
+#define CD_T_NONE (1ull << 60)            // key of a target that is no candidate: above every cell key (3 x 20 bits)
+#define CD_Q_NONE (1ull << 63)            // key of a query that is no candidate: above every query key (3 x 21 bits)
+#define CD_MAX_EXTENT (1 << 20)           // cells per axis: refused from here on
+
+struct CdGrid {
+    double ox, oy, oz;                    // per-axis minimum of the candidate targets
+    double e;                             // cell edge (double)R * (1 + 2^-10)
+    int ex, ey, ez;                       // cells per axis: the targets' cells are 0 .. ex - 1
+};
+struct __align__(16) CdRec { float x, y, z; uint32_t j; };
+
+__device__ __forceinline__ int cd_clampi(double c, int lo, int hi) { return c < (double)lo ? lo : (c > (double)hi ? hi : (int)c); }
+
+// [b, e) = the sorted keys in [klo, khi]: a binary search for the start, then a gallop for the end (a range is short next to n)
+__device__ __forceinline__ void cd_range(const unsigned long long* __restrict__ keys, uint32_t n, unsigned long long klo, unsigned long long khi, uint32_t& b, uint32_t& e) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (keys[mid] < klo) lo = mid + 1; else hi = mid; }
+    b = lo;
+    uint32_t l = lo, h = lo, step = 1;
+    while (h < n && keys[h] <= khi) { l = h + 1; h = (n - h > step) ? h + step : n; step <<= 1; }
+    while (l < h) { const uint32_t mid = l + ((h - l) >> 1); if (keys[mid] <= khi) l = mid + 1; else h = mid; }
+    e = l;
+}
+
+// the query's r-th range, r = 3 (dz + 1) + (dy + 1): false when that row of cells lies outside the grid
+__device__ __forceinline__ bool cd_query_range(unsigned long long qkey, int r, const CdGrid& g, const unsigned long long* __restrict__ tkeys, uint32_t n_cand,
+                                               uint32_t& b, uint32_t& e) {
+    const int cx = (int)(qkey & 0x1fffffu) - 2, cy = (int)((qkey >> 21) & 0x1fffffu) - 2, cz = (int)((qkey >> 42) & 0x1fffffu) - 2;
+    const int ty = cy + (r % 3) - 1, tz = cz + (r / 3) - 1;
+    const int xlo = cx - 1 < 0 ? 0 : cx - 1, xhi = cx + 1 > g.ex - 1 ? g.ex - 1 : cx + 1;
+    if (ty < 0 || ty >= g.ey || tz < 0 || tz >= g.ez || xlo > xhi) return false;
+    const unsigned long long row = ((unsigned long long)tz << 40) | ((unsigned long long)ty << 20);
+    cd_range(tkeys, n_cand, row | (unsigned)xlo, row | (unsigned)xhi, b, e);
+    return true;
+}
 
 // keys_in / vals_in sorted into keys_out / vals_out (bits [0, end_bit)); the sort's scratch is a piece of the frame
 template <typename F>

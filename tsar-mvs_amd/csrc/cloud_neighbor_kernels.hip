@@ -1,0 +1,209 @@
+// cloud_neighbor_kernels.hip — neighbourhood statistics of one point cloud (include/tsar.h tsar_cloud_neighbors): per point the number of
+// other points within a radius R and the k smallest squared distances among them.  The result is the brute-force definition written
+// there (a count and an order statistic of float32 d2 over every other candidate); the uniform grid only decides which pairs are looked
+// at, and every pair with d2 <= fl(R * R) lies in the 27 cells around the point's (include/tsar.h says why), so no bit of the result
+// depends on it, nor on the order in which a point's neighbours arrive.
+//
+// Per call:  bounds of the candidates (cloud_grid.h) -> 60-bit z-major cell keys, radix-sorted with the indices
+//            -> the candidates copied into key order as 16-byte records (x, y, z, index)
+//            -> the pair count: per sorted record the sizes of its 9 key ranges (the record itself is in one of them)
+//            -> the search kernel: lane t takes sorted record t as its query, so that a wave's lanes walk the same cells and one sort
+//               serves queries and targets; a count, and a sorted list of the KCAP smallest d2 kept in registers.
+// The list is indexed by compile-time constants only (a template over KCAP, every loop over it unrolled): insertion is a chain of
+// integer min / max on the bit patterns (d2 >= +0 and never NaN, so the bits order like the values), run only when some lane of the wave
+// holds a value below its list's last entry.  No atomics on the per-point outputs, no LDS, no scratch.
+#include "cloud_grid.h"
+
+#define CN_INF_BITS 0x7f800000u
+
+__global__ __launch_bounds__(CD_BLOCK) void cn_keys_kernel(const float* __restrict__ pts, long long n, int stride, CdGrid g, unsigned long long* __restrict__ keys,
+                                                           uint32_t* __restrict__ vals) {
+    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float* p = pts + (size_t)i * stride;
+    const float x = p[0], y = p[1], z = p[2];
+    unsigned long long key = CD_T_NONE;
+    if (cd_candidate(x, y, z)) {
+        // (the origin is the minimum and the extent comes from the maximum through the same monotone function: the clamps never bind)
+        const unsigned long long cx = (unsigned)cd_clampi(cd_cell(x, g.ox, g.e), 0, g.ex - 1), cy = (unsigned)cd_clampi(cd_cell(y, g.oy, g.e), 0, g.ey - 1),
+                                 cz = (unsigned)cd_clampi(cd_cell(z, g.oz, g.e), 0, g.ez - 1);
+        key = (cz << 40) | (cy << 20) | cx;
+    }
+    keys[i] = key;
+    vals[i] = (uint32_t)i;
+}
+
+__global__ __launch_bounds__(CD_BLOCK) void cn_gather_kernel(const float* __restrict__ pts, int stride, const uint32_t* __restrict__ vals, uint32_t n_cand,
+                                                             CdRec* __restrict__ rec) {
+    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
+    if (t >= n_cand) return;
+    const uint32_t j = vals[t];
+    const float* p = pts + (size_t)j * stride;
+    CdRec r;
+    r.x = p[0]; r.y = p[1]; r.z = p[2]; r.j = j;
+    rec[t] = r;
+}
+
+// a sorted record's cell key (3 x 20 bits) as the query key cd_query_range reads (3 x 21 bits, each coordinate + 2)
+__device__ __forceinline__ unsigned long long cn_query_key(unsigned long long key) {
+    return (((key >> 40) + 2ull) << 42) | ((((key >> 20) & 0xfffffull) + 2ull) << 21) | ((key & 0xfffffull) + 2ull);
+}
+
+// *pairs += the number of candidates in the 27 cells around every candidate, itself included: what the search kernel looks at
+__global__ __launch_bounds__(CD_BLOCK) void cn_pairs_kernel(const unsigned long long* __restrict__ keys, uint32_t n_cand, CdGrid g, unsigned long long* __restrict__ pairs) {
+    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
+    unsigned long long cnt = 0;
+    if (t < n_cand) {
+        const unsigned long long qkey = cn_query_key(keys[t]);
+        for (int r = 0; r < 9; r++) {
+            uint32_t b, e;
+            if (cd_query_range(qkey, r, g, keys, n_cand, b, e)) cnt += e - b;
+        }
+    }
+    cnt = cd_wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(pairs, cnt);
+}
+
+// One lane per candidate, in key order.  KCAP = 0: the count only.  k <= KCAP values of the list are written.
+template <int KCAP>
+__global__ __launch_bounds__(CD_BLOCK) void cn_search_kernel(const unsigned long long* __restrict__ keys, const CdRec* __restrict__ rec, uint32_t n_cand, CdGrid g, float r2,
+                                                             int k, int32_t* __restrict__ count_out, float* __restrict__ knn_out) {
+    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
+    if (t >= n_cand) return;
+    const CdRec q = rec[t];
+    const unsigned long long qkey = cn_query_key(keys[t]);
+    uint32_t a[KCAP > 0 ? KCAP : 1];
+#pragma unroll
+    for (int s = 0; s < KCAP; s++) a[s] = CN_INF_BITS;
+    int32_t cnt = 0;
+    for (int r = 0; r < 9; r++) {
+        uint32_t b, e;
+        if (!cd_query_range(qkey, r, g, keys, n_cand, b, e)) continue;
+#pragma unroll 4
+        for (uint32_t u = b; u < e; u++) {       // (unrolled like cd_query_kernel: four record loads in flight per lane)
+            const CdRec c = rec[u];
+            const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
+            const float d2 = (dx * dx + dy * dy) + dz * dz;                  // no fused operation: the library is built with -ffp-contract=off
+            const bool in = d2 <= r2 && c.j != q.j;                          // the point itself is excluded by index, not by distance
+            cnt += in ? 1 : 0;
+            if constexpr (KCAP > 0) {
+                uint32_t x = in ? __float_as_uint(d2) : CN_INF_BITS;
+                if (__ballot(x < a[KCAP - 1])) {                             // wave-uniform among the lanes still in the loop
+#pragma unroll
+                    for (int s = 0; s < KCAP; s++) {
+                        const uint32_t lo = a[s] < x ? a[s] : x;
+                        x = a[s] < x ? x : a[s];
+                        a[s] = lo;
+                    }
+                }
+            }
+        }
+    }
+    if (count_out) count_out[q.j] = cnt;
+    if constexpr (KCAP > 0) {
+        float* o = knn_out + (size_t)q.j * k;
+#pragma unroll
+        for (int s = 0; s < KCAP; s++)
+            if (s < k) o[s] = __uint_as_float(a[s]);
+    }
+}
+
+// the records that are no candidates: count -1, every distance +inf (the search kernel writes the candidates' rows)
+__global__ __launch_bounds__(CD_BLOCK) void cn_fill_kernel(const float* __restrict__ pts, long long n, int stride, int k, int32_t* __restrict__ count_out,
+                                                           float* __restrict__ knn_out) {
+    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float* p = pts + (size_t)i * stride;
+    if (cd_candidate(p[0], p[1], p[2])) return;
+    if (count_out) count_out[i] = -1;
+    if (knn_out)
+        for (int s = 0; s < k; s++) knn_out[(size_t)i * k + s] = INFINITY;
+}
+
+template <int KCAP>
+static void cn_launch_search(hipStream_t st, const unsigned long long* keys, const CdRec* rec, uint32_t n_cand, const CdGrid& g, float r2, int k, int32_t* count_out,
+                             float* knn_out) {
+    hipLaunchKernelGGL(cn_search_kernel<KCAP>, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, keys, rec, n_cand, g, r2, k, count_out, knn_out);
+}
+
+// cloud and the two per-point outputs are device pointers (the frame's views of the caller's buffers); n_valid_out and pairs_out are the
+// caller's host memory.  The arguments have been checked (tsar_api.hip): 0 <= n < 2^31, 0 <= k <= TSAR_CLOUD_KNN_MAX, knn_out only with k > 0.
+int run_cloud_neighbors(CallFrame& f, const float* cloud, long long n, int stride, float r2, double edge, int k, long long max_pairs, int32_t* count_out, float* knn_out,
+                        int64_t* n_valid_out, int64_t* pairs_out) {
+    tsar_ctx* ctx = f.ctx;
+    hipStream_t st = ctx->stream;
+    struct Head { uint32_t bounds[6]; uint32_t pad[2]; unsigned long long n_cand, pairs; } head;
+    for (int a = 0; a < 3; a++) { head.bounds[a] = 0xffffffffu; head.bounds[3 + a] = 0u; }
+    head.pad[0] = head.pad[1] = 0;
+    head.n_cand = head.pairs = 0;
+    Head* dh = f.tmp<Head>(1);
+    if (!f.ok()) return f.finish();
+    f.copy(dh, &head, sizeof(Head), hipMemcpyHostToDevice);
+    if (n > 0 && f.ok()) {
+        ScopedKernelTimer tm(ctx, "cloud_bounds");
+        hipLaunchKernelGGL(cd_bounds_kernel, dim3(cd_bounds_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, dh->bounds, &dh->n_cand);
+    }
+    f.launched();
+    f.copy(&head, dh, sizeof(Head), hipMemcpyDeviceToHost);
+    if (!f.sync()) return f.finish();
+    const long long n_cand = (long long)head.n_cand;
+    CdGrid g = {};
+    unsigned long long *k0 = nullptr, *k1 = nullptr;
+    uint32_t *v0 = nullptr, *v1 = nullptr;
+    CdRec* rec = nullptr;
+    if (n_cand > 0) {
+        g.ox = (double)cd_decode(head.bounds[0]); g.oy = (double)cd_decode(head.bounds[1]); g.oz = (double)cd_decode(head.bounds[2]);
+        g.e = edge;
+        const double ext[3] = {cd_cell_host(cd_decode(head.bounds[3]), g.ox, edge) + 1.0, cd_cell_host(cd_decode(head.bounds[4]), g.oy, edge) + 1.0,
+                               cd_cell_host(cd_decode(head.bounds[5]), g.oz, edge) + 1.0};
+        for (int a = 0; a < 3; a++)
+            if (!(ext[a] >= 1.0 && ext[a] < (double)CD_MAX_EXTENT))
+                return f.fail(TSAR_ERR_INVALID, "tsar_cloud_neighbors: the cloud spans 2^20 cells or more of edge radius on an axis: radius is too small for this cloud's extent");
+        g.ex = (int)ext[0]; g.ey = (int)ext[1]; g.ez = (int)ext[2];
+        k0 = f.tmp<unsigned long long>((size_t)n); k1 = f.tmp<unsigned long long>((size_t)n);
+        v0 = f.tmp<uint32_t>((size_t)n); v1 = f.tmp<uint32_t>((size_t)n);
+        rec = f.tmp<CdRec>((size_t)n_cand);
+        if (!f.ok()) return f.finish();
+        {
+            ScopedKernelTimer tm(ctx, "cloud_keys");
+            hipLaunchKernelGGL(cn_keys_kernel, dim3(cd_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, g, k0, v0);
+        }
+        f.launched();
+        if (!cd_sort(f, "cloud_sort", k0, k1, v0, v1, n, 61)) return f.finish();
+        {
+            ScopedKernelTimer tm(ctx, "cloud_gather");
+            hipLaunchKernelGGL(cn_gather_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, cloud, stride, v1, (uint32_t)n_cand, rec);
+        }
+        f.launched();
+        {
+            ScopedKernelTimer tm(ctx, "cloud_pairs");
+            hipLaunchKernelGGL(cn_pairs_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, k1, (uint32_t)n_cand, g, &dh->pairs);
+        }
+        f.launched();
+        f.copy(&head, dh, sizeof(Head), hipMemcpyDeviceToHost);
+        if (!f.sync()) return f.finish();
+    }
+    if (pairs_out) *pairs_out = (int64_t)head.pairs;
+    if (head.pairs > (unsigned long long)max_pairs) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "tsar_cloud_neighbors: the call would look at %llu pairs, more than max_pairs = %lld: lower radius or raise max_pairs", head.pairs, max_pairs);
+        return f.fail(TSAR_ERR_INVALID, msg);
+    }
+    if (f.ok() && n > 0 && n_cand < n && (count_out || knn_out)) {
+        ScopedKernelTimer tm(ctx, "cloud_neighbors");
+        hipLaunchKernelGGL(cn_fill_kernel, dim3(cd_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, k, count_out, knn_out);
+    }
+    f.launched();
+    if (f.ok() && n_cand > 0 && (count_out || knn_out)) {
+        ScopedKernelTimer tm(ctx, "cloud_neighbors");
+        const int kk = knn_out ? k : 0;          // the smallest list that holds k
+        if (kk == 0) cn_launch_search<0>(st, k1, rec, (uint32_t)n_cand, g, r2, 0, count_out, nullptr);
+        else if (kk <= 4) cn_launch_search<4>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        else if (kk <= 8) cn_launch_search<8>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        else if (kk <= 16) cn_launch_search<16>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        else cn_launch_search<32>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+    }
+    f.launched();
+    if (n_valid_out) *n_valid_out = (int64_t)n_cand;
+    return f.finish();
+}

@@ -1267,6 +1267,50 @@ extern "C" int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int 
     return rc;
 }
 
+// ---- neighbourhood statistics of a cloud (cloud_neighbor_kernels.hip) -------------------------------------------------------------------
+extern "C" void tsar_default_cloud_neighbors_params(tsar_cloud_neighbors_params* p) {
+    if (!p) return;
+    p->radius = 0.0f;                      // no default: the caller's scale
+    p->k = 0;
+    p->max_pairs = (int64_t)1 << 40;
+}
+
+// Like tsar_cloud_distance_ctx: no views, no state, nothing of the context written, and a frame that does not grow the arena.
+extern "C" int tsar_cloud_neighbors_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_neighbors_params* p, int32_t* count_out,
+                                        float* knn_dist2_out, int64_t* n_valid_out, int64_t* pairs_out, int mem) {
+    CHECK_CTX(ctx);
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: params is NULL");
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
+    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: n must be in 0..2^31-1");
+    if (stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: the stride must be at least 3 floats (x y z first)");
+    if (n > 0 && !cloud) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: cloud is NULL");
+    const float R = p->radius;
+    const volatile float r2v = R * R;      // fl(R * R), one float32 product
+    const float r2 = r2v;
+    if (!(fabsf(R) <= FLT_MAX) || !(r2 > 0.0f && r2 <= FLT_MAX) || !(R > 0.0f))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: radius must be finite and > 0, with radius * radius finite and > 0 in float32");
+    if (p->k < 0 || p->k > TSAR_CLOUD_KNN_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: k must be in 0..TSAR_CLOUD_KNN_MAX (32)");
+    if (p->k == 0 && knn_dist2_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: knn_dist2_out needs k > 0");
+    if (p->max_pairs < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: max_pairs must be >= 0");
+    CallFrame f(ctx, "tsar_cloud_neighbors", nullptr, /*grow_arena=*/false);
+    const float* c = f.in(cloud, (size_t)n * stride, mem);
+    int32_t* cnt = f.out(count_out, (size_t)n, mem);
+    float* knn = f.out(knn_dist2_out, (size_t)n * (size_t)p->k, mem);
+    if (!f.ok()) return f.finish();
+    return run_cloud_neighbors(f, c, n, stride, r2, (double)R * (1.0 + 1.0 / 1024.0), p->k, p->max_pairs, cnt, knn, n_valid_out, pairs_out);
+}
+
+// Context-free form (the fuser's cleaning step): a context of its own for the duration of the call.
+extern "C" int tsar_cloud_neighbors(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_neighbors_params* p, int32_t* count_out, float* knn_dist2_out,
+                                    int64_t* n_valid_out, int64_t* pairs_out, int mem) {
+    tsar_ctx* ctx = nullptr;
+    const int rc0 = tsar_create(device, &ctx);
+    if (rc0 != TSAR_OK) return rc0;
+    const int rc = tsar_cloud_neighbors_ctx(ctx, cloud, n, stride, p, count_out, knn_dist2_out, n_valid_out, pairs_out, mem);
+    tsar_destroy(ctx);
+    return rc;
+}
+
 // ---- a cloud rendered into a camera; a depth map scored against a map (cloud_render_kernels.hip) -----------------------------------------
 extern "C" void tsar_default_cloud_render_params(tsar_cloud_render_params* p) {
     if (!p) return;

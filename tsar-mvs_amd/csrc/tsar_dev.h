@@ -472,6 +472,8 @@ int run_cloud_distance(CallFrame& f, const float* query, long long n_query, int 
 int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, double voxel, const float* dist2, int n_tol, const float* tol2, int32_t* rank_out,
                      long long cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
                      int mem);                                                                  // cloud_voxel_kernels.hip (cloud, dist2: device; outputs in `mem`; finishes the frame)
+int run_cloud_neighbors(CallFrame& f, const float* cloud, long long n, int stride, float r2, double edge, int k, long long max_pairs, int32_t* count_out,
+                        float* knn_out, int64_t* n_valid_out, int64_t* pairs_out);              // cloud_neighbor_kernels.hip (device pointers; finishes the frame)
 struct CrViewHost { float P[12]; float fr; int max_px, w, h; bool foot; };                       // tsar_cloud_render's view: P, fl(K[0] * radius), radius > 0
 int run_cloud_render(CallFrame& f, const float* cloud, long long n, int stride, const CrViewHost& vh, float occlusion_diff, float depth_diff, int min_points,
                      long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,

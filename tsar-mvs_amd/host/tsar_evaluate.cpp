@@ -1,5 +1,6 @@
 // tsar_evaluate — accuracy and completeness of a reconstructed cloud against a ground-truth cloud, on the GPU:
 //   tsar_evaluate RECON.ply GT.ply --tolerances=0.01,0.02,0.05 [--max_pairs=N] [--device=D] [--json=FILE] [--voxel=V] [--crop=x0,y0,z0,x1,y1,z1]
+//                 [--clean_radius=R [--clean_min_neighbors=N] [--clean_knn=K [--clean_ratio=Q]]]
 // accuracy(tau) = the share of RECON's points with a GT point within tau; completeness(tau) = the share of GT's points with a RECON point
 // within tau; f1 = their harmonic mean: the point-wise precision / recall / F-score.  Not ETH3D's or DTU's evaluation program: nothing is
 // masked or aligned, and without the two switches below nothing is down-sampled or cropped.  Two tsar_cloud_distance_ctx calls with max_dist = the largest tolerance (include/tsar.h);
@@ -7,12 +8,15 @@
 // --voxel=V adds the voxel-averaged figures (a grid of edge V over each cloud, tsar_cloud_voxels_ctx: per occupied voxel the share of its
 // points within tau, averaged over the voxels in ascending voxel order, one float64 term after another), --crop= first makes every point
 // outside the closed box a non-candidate.  In the manner of the benchmarks, still not their programs: no alignment, no observation masks.
+// --clean_radius=R with --clean_min_neighbors=N and / or --clean_knn=K first removes RECON's stray points (host/tsar_outliers.h: the rules of
+// api.remove_outliers, one tsar_cloud_neighbors_ctx call), before the crop and before any scoring; GT is left as it is.
 #include <math.h>
 #include <stdlib.h>
 
 #include <chrono>
 
 #include "tsar_io.h"
+#include "tsar_outliers.h"
 
 // The entries that only --voxel calls are referred to weakly: the tool still links against, and runs with, a library that lacks them, and
 // refuses the switch there.
@@ -48,10 +52,11 @@ static std::string json_list(const std::vector<T>& v, Fmt fmt) {
 int main(int argc, char** argv) {
     (void)write_cloud_ply;                         // (tsar_io.h's writer, unused here)
     const char* usage = "usage: tsar_evaluate RECON.ply GT.ply --tolerances=T1[,T2...] [--max_pairs=N] [--device=D] [--json=FILE] [--voxel=V]\n"
-                        "                     [--crop=x0,y0,z0,x1,y1,z1]\n"
+                        "                     [--crop=x0,y0,z0,x1,y1,z1] [--clean_radius=R [--clean_min_neighbors=N] [--clean_knn=K [--clean_ratio=Q]]]\n"
                         "       point-wise accuracy / completeness / F-score of RECON against GT at each tolerance; --voxel=V adds the figures averaged\n"
                         "       over the occupied voxels of edge V, --crop= drops the points outside the closed box first (not ETH3D's or DTU's\n"
-                        "       program: no masks, no alignment)\n";
+                        "       program: no masks, no alignment); --clean_radius=R first removes RECON's points with fewer than N others within R and / or\n"
+                        "       whose K-th neighbour within R lies beyond Q (2) times the median K-th-neighbour distance\n";
     if (argc >= 2 && (!strcmp(argv[1], "-h") || !strcmp(argv[1], "--help"))) { printf("%s", usage); return 0; }
     std::vector<std::string> paths;
     std::vector<float> tol;
@@ -62,10 +67,12 @@ int main(int argc, char** argv) {
     bool have_voxel = false, have_crop = false;
     float voxel = 0.0f;
     float crop[6] = {0, 0, 0, 0, 0, 0};
+    OutlierSettings clean("--clean_");
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&](const char* opt) -> const char* { const size_t n = strlen(opt); return a.compare(0, n, opt) == 0 ? argv[i] + n : nullptr; };
         const char* v;
+        std::string why;
         if ((v = value("--tolerances="))) {
             have_tol = true;
             const char* s = v;
@@ -105,6 +112,14 @@ int main(int argc, char** argv) {
             for (int a = 0; a < 3; a++)
                 if (!(crop[a] <= crop[3 + a])) return refuse(msg);
             have_crop = true;
+        } else if ((v = value("--clean_radius="))) {
+            if (!(why = clean.parse('r', v)).empty()) return refuse(why);
+        } else if ((v = value("--clean_min_neighbors="))) {
+            if (!(why = clean.parse('n', v)).empty()) return refuse(why);
+        } else if ((v = value("--clean_knn="))) {
+            if (!(why = clean.parse('k', v)).empty()) return refuse(why);
+        } else if ((v = value("--clean_ratio="))) {
+            if (!(why = clean.parse('q', v)).empty()) return refuse(why);
         } else if ((v = value("--json="))) {
             json_path = v;
         } else if (a.compare(0, 2, "--") == 0) {
@@ -116,12 +131,30 @@ int main(int argc, char** argv) {
     if (paths.size() != 2) { fprintf(stderr, "%s", usage); return 1; }
     if (!have_tol || tol.empty()) return refuse("--tolerances=T1[,T2...] is required");
     if (have_voxel && (!tsar_cloud_voxels_ctx || !tsar_default_cloud_voxels_params)) return refuse("--voxel: this libtsar_hip.so has no tsar_cloud_voxels");
+    { const std::string why = clean.check(); if (!why.empty()) return refuse(why); }
     std::vector<float> cloud[2];
     int64_t n[2] = {0, 0};
     for (int k = 0; k < 2; k++) {
         std::string why;
         if (!read_cloud_ply(paths[k], cloud[k], n[k], why)) return refuse(why);
         if (n[k] > INT32_MAX) return refuse(paths[k] + ": more than 2^31 - 1 points");
+    }
+    tsar_ctx* ctx = nullptr;
+    if (tsar_create(device, &ctx) != TSAR_OK) return refuse("tsar_create failed (is a HIP device visible?)");
+    int64_t cleaned = 0;
+    if (clean.on()) {                               // RECON's stray points become non-candidates, before the crop and the scoring
+        std::vector<uint8_t> keep;
+        if (!outlier_keep_mask(ctx, cloud[0].data(), n[0], 3, clean, keep)) {
+            fprintf(stderr, "%s\n", tsar_last_error(ctx));
+            tsar_destroy(ctx);
+            return 1;
+        }
+        for (int64_t i = 0; i < n[0]; i++) {
+            float* p = cloud[0].data() + 3 * i;
+            if (keep[(size_t)i] || !(fabsf(p[0]) <= FLT_MAX && fabsf(p[1]) <= FLT_MAX && fabsf(p[2]) <= FLT_MAX)) continue;
+            p[0] = p[1] = p[2] = NAN;
+            cleaned++;
+        }
     }
     int64_t cropped[2] = {0, 0};
     for (int k = 0; k < 2 && have_crop; k++)        // a point outside the closed box becomes a non-candidate
@@ -136,8 +169,6 @@ int main(int argc, char** argv) {
     tsar_default_cloud_distance_params(&prm);
     for (const float t : tol) prm.max_dist = t > prm.max_dist ? t : prm.max_dist;
     if (max_pairs >= 0) prm.max_pairs = max_pairs;
-    tsar_ctx* ctx = nullptr;
-    if (tsar_create(device, &ctx) != TSAR_OK) return refuse("tsar_create failed (is a HIP device visible?)");
     // direction 0: RECON against GT (accuracy); direction 1: GT against RECON (completeness)
     std::vector<int64_t> within[2] = {std::vector<int64_t>(tol.size(), 0), std::vector<int64_t>(tol.size(), 0)};
     int64_t valid[2] = {0, 0}, pairs[2] = {0, 0};
@@ -205,6 +236,7 @@ int main(int argc, char** argv) {
                 json_list(vshare[0], f17) + ", \"completeness_voxel\": " + json_list(vshare[1], f17) + ", \"f1_voxel\": " + json_list(vf1, f17);
     if (have_crop)
         more += ", \"crop\": " + json_list(std::vector<float>(crop, crop + 6), f9) + ", \"n_recon_cropped\": " + i64(cropped[0]) + ", \"n_gt_cropped\": " + i64(cropped[1]);
+    if (clean.on()) more += ", \"clean\": " + clean.json() + ", \"n_recon_cleaned\": " + i64(cleaned);
     const std::string rec = "{\"recon\": " + json_string(paths[0]) + ", \"gt\": " + json_string(paths[1]) + ", " + head + "\"tolerances\": " + json_list(tol, f9) +
                             ", \"n_accurate\": " + json_list(within[0], i64) + ", \"n_complete\": " + json_list(within[1], i64) + ", \"accuracy\": " + json_list(acc, f17) +
                             ", \"completeness\": " + json_list(com, f17) + ", \"f1\": " + json_list(f1, f17) + ", " + tail + more + "}";

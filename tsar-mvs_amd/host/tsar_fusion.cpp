@@ -6,6 +6,9 @@
 // the GPU (tsar_fuse) and writes <dir>/APD/APD_TSAR.ply (binary little-endian: x y z nx ny nz red green blue).
 // --voxel=V thins the fused cloud before it is written: a grid of edge V over it (tsar_cloud_voxels), and per occupied voxel the record of
 // the point nearest the voxel's centre, whole, in the cloud's own order.
+// --outlier_radius=R with --outlier_min_neighbors=N and / or --outlier_knn=K [--outlier_ratio=Q] removes the fused cloud's stray points
+// first (host/tsar_outliers.h: the rules of api.remove_outliers, one tsar_cloud_neighbors_ctx call): before --voxel thins and before the
+// cloud is written.
 #include <math.h>
 #include <stdlib.h>
 
@@ -15,6 +18,7 @@
 
 #include "tsar_io.h"
 #include "tsar_jpeg.h"
+#include "tsar_outliers.h"
 
 // The entries that only --voxel calls are referred to weakly: the tool still links against, and runs with, a library that lacks them, and
 // refuses the switch there.
@@ -28,8 +32,11 @@ int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stri
 int main(int argc, char** argv) {
     if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
         printf("usage: tsar_fusion <mslp_dir> [--num_consistent= N] [--reproj_error= PX] [--depth_diff= REL] [--angle= DEG] [--used_list= 0|1] [--gpu=K] [--geom] [--voxel=V]\n"
+               "                  [--outlier_radius=R [--outlier_min_neighbors=N] [--outlier_knn=K [--outlier_ratio=Q]]]\n"
                "       --geom: fuse APD/%%08d/TSAR_geom_disp.dmb + TSAR_geom_normals.dmb instead of TSAR_disp.dmb + TSAR_normals.dmb\n"
-               "       --voxel=V: write one point per occupied voxel of edge V (the one nearest the voxel's centre, its whole record)\n");
+               "       --voxel=V: write one point per occupied voxel of edge V (the one nearest the voxel's centre, its whole record)\n"
+               "       --outlier_radius=R: first drop the points with fewer than N others within R and / or whose K-th neighbour within R lies\n"
+               "                           beyond Q (2) times the median K-th-neighbour distance\n");
         return argc < 2 ? 1 : 0;
     }
     std::string dir = argv[1];
@@ -38,7 +45,9 @@ int main(int argc, char** argv) {
     tsar_default_fusion_params(&prm);
     int gpu = 0;
     float voxel = 0.0f;         // --voxel=V: thin the fused cloud (0: off)
+    OutlierSettings outlier("--outlier_");
     bool geom = false;          // --geom: the geometric-consistency pass's maps (tsar_gipuma --all --geom_consistency)
+    std::string why;            // the one-line refusal of an --outlier_ switch
     for (int i = 2; i < argc; i++) {
         const char* a = argv[i];
         auto value = [&](const char* opt) -> const char* {      // "--opt=VALUE" or "--opt= VALUE"
@@ -62,8 +71,14 @@ int main(int argc, char** argv) {
             voxel = (float)t;
             if (!tsar_cloud_voxels_ctx || !tsar_default_cloud_voxels_params) { fprintf(stderr, "--voxel: this libtsar_hip.so has no tsar_cloud_voxels\n"); return 1; }
         }
+        else if ((v = value("--outlier_radius="))) { if (!(why = outlier.parse('r', v)).empty()) break; }
+        else if ((v = value("--outlier_min_neighbors="))) { if (!(why = outlier.parse('n', v)).empty()) break; }
+        else if ((v = value("--outlier_knn="))) { if (!(why = outlier.parse('k', v)).empty()) break; }
+        else if ((v = value("--outlier_ratio="))) { if (!(why = outlier.parse('q', v)).empty()) break; }
         else printf("Command-line parameter warning: unknown option %s\n", a);
     }
+    if (why.empty()) why = outlier.check();
+    if (!why.empty()) { fprintf(stderr, "%s\n", why.c_str()); return 1; }
     printf("num_consistent: %d\nreproj_error: %g\ndepth_diff: %g\nangle: %g\nused_list: %d\n", prm.num_consistent, prm.reproj_error, prm.depth_diff, prm.angle_deg, prm.used_list);
     const std::string depth_file = geom ? "TSAR_geom_disp.dmb" : "TSAR_disp.dmb", normal_file = geom ? "TSAR_geom_normals.dmb" : "TSAR_normals.dmb";
     std::map<int, std::vector<int>> pairs;
@@ -127,6 +142,24 @@ int main(int argc, char** argv) {
     const int rc = tsar_fuse(gpu, n, w, h, cams.data(), pd.data(), pn.data(), pg.data(), TSAR_MEM_HOST, off.data(), idx.data(), &prm, pts.get(), cap, &cnt);
     if (rc != TSAR_OK) { fprintf(stderr, "tsar_fuse failed: %d\n", rc); return 1; }
     if (cnt > cap) cnt = cap;
+    if (outlier.on()) {
+        if (cnt > INT32_MAX) { fprintf(stderr, "--outlier_radius: more than 2^31 - 1 fused points\n"); return 1; }
+        std::vector<uint8_t> keep;
+        tsar_ctx* ctx = nullptr;
+        if (tsar_create(gpu, &ctx) != TSAR_OK) { fprintf(stderr, "tsar_create failed\n"); return 1; }
+        const bool ok = outlier_keep_mask(ctx, pts.get(), cnt, 9, outlier, keep);
+        if (!ok) fprintf(stderr, "%s\n", tsar_last_error(ctx));
+        tsar_destroy(ctx);
+        if (!ok) return 1;
+        int64_t kept = 0;                                     // the kept records in the cloud's own order, moved towards the front in place
+        for (int64_t i = 0; i < cnt; i++) {
+            if (!keep[(size_t)i]) continue;
+            if (kept != i) memmove(pts.get() + 9 * (size_t)kept, pts.get() + 9 * (size_t)i, 9 * sizeof(float));
+            kept++;
+        }
+        printf("--outlier_radius=%g: %lld points -> %lld points\n", (double)outlier.radius, (long long)cnt, (long long)kept);
+        cnt = kept;
+    }
     if (voxel > 0.0f) {
         if (cnt > INT32_MAX) { fprintf(stderr, "--voxel: more than 2^31 - 1 fused points\n"); return 1; }
         tsar_cloud_voxels_params vp;
