@@ -154,6 +154,33 @@ def test_a_flat_cloud_a_line_and_one_far_point(ctxs):
     assert ref["count"][-1] == 0 and np.isposinf(ref["knn_dist2"][-1]).all() and 5000 / (0.01 * (1 + 2.0 ** -10)) < (1 << 20)
 
 
+# ---- the three grid operators in turn on one context ----------------------------------------------------------------------------------------
+def test_voxels_distance_neighbors_and_voxels_again_on_one_context(ctxs):
+    """The operators share the measuring of a cloud and the sorted index of its cells (cloud_grid.hip), and on one context the same arena:
+    nothing of one call may reach the next.  257 points, rows 100..102 a NaN, a +inf and a -inf beside the finite row 103, the last point far
+    off (the grid is mostly empty cells): every call counts the same 254 candidates, every array is the restatement's bit for bit, and the
+    voxel result after the two searches is the one before them."""
+    rng = np.random.default_rng(11)
+    cloud = rng.random((257, 3), dtype=F)
+    cloud[100, 1], cloud[101, 0], cloud[102, 2] = np.nan, np.inf, -np.inf
+    cloud[256] = 300                                                      # 2000 cells of edge R, 3000 voxels away on every axis
+    R, V, m = 0.15, 0.1, ctxs["fast"]
+    dref, nref, vref = cloud_distance_ref(cloud, cloud, R), cloud_neighbors_ref(cloud, R, 4), cloud_voxels_ref(cloud, V)
+    assert dref["n_valid_query"] == nref["n_valid"] == vref["n_valid"] == 254 and vref["n_voxels"] > 100 and vref["rank"][103] >= 0
+    for on_device in (False, True):
+        c = torch.from_numpy(cloud).cuda() if on_device else cloud
+        v1 = api.cloud_voxels(c, V, matcher=m)
+        d = api.cloud_distance(c, c, R, matcher=m)
+        nb = api.cloud_neighbors(c, R, 4, matcher=m)
+        v2 = api.cloud_voxels(c, V, matcher=m)
+        assert v1["n_valid"] == d["n_valid_query"] == nb["n_valid"] == v2["n_valid"] == 254, on_device
+        assert v1["n_voxels"] == v2["n_voxels"] == vref["n_voxels"] and nb["pairs"] == nref["pairs"], on_device
+        for k in ("rank", "rep", "count"):
+            assert np.array_equal(host(v1[k]), vref[k]) and np.array_equal(host(v2[k]), host(v1[k])), (k, on_device)
+        assert np.array_equal(bits(d["dist2"]), bits(dref["dist2"])) and np.array_equal(host(d["index"]), dref["index"]), on_device
+        assert np.array_equal(host(nb["count"]), nref["count"]) and np.array_equal(bits(nb["knn_dist2"]), bits(nref["knn_dist2"])), on_device
+
+
 # ---- order and repeatability ----------------------------------------------------------------------------------------------------------------
 def test_a_shuffled_cloud_gives_the_same_outputs_permuted_and_two_runs_the_same_bits(ctxs):
     rng = np.random.default_rng(6)

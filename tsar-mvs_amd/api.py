@@ -970,6 +970,13 @@ def _matcher_for(matcher, device, *inputs):
         m.close()
 
 
+def _error_with_pairs(rc, L, m, pairs):
+    """the TsarError of a refused cloud_distance / cloud_neighbors call; .pairs is filled when max_pairs refused it, else None"""
+    err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
+    err.pairs = int(pairs.value) if pairs.value >= 0 else None
+    return err
+
+
 def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "index"), max_pairs=None, matcher=None, device=0):
     """For every point of `query` the squared float32 distance to its nearest point of `target` within max_dist, and that point's index
     (tsar_cloud_distance_ctx; include/tsar.h states the arithmetic).  query, target: [n, k >= 3] float32, x y z first, both numpy arrays
@@ -1001,9 +1008,7 @@ def cloud_distance(query, target, max_dist, tolerances=None, want=("dist2", "ind
                                        C.byref(p), len(tol), tol.ctypes.data_as(C.c_void_p), _ptr(res.get("dist2"))[0], _ptr(res.get("index"))[0],
                                        within.ctypes.data_as(C.c_void_p), C.byref(n_valid), C.byref(pairs), MEM_DEVICE if q_dev else MEM_HOST)
         if rc != TSAR_OK:
-            err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
-            err.pairs = int(pairs.value) if pairs.value >= 0 else None      # filled when max_pairs refused the call
-            raise err
+            raise _error_with_pairs(rc, L, m, pairs)
     res["within"] = within
     res["n_valid_query"] = int(n_valid.value)
     res["pairs"] = int(pairs.value)
@@ -1086,9 +1091,7 @@ def cloud_neighbors(cloud, radius, k=0, want=("count", "knn_dist2"), max_pairs=N
         rc = L.tsar_cloud_neighbors_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), C.byref(p), _ptr(res.get("count"))[0], _ptr(res.get("knn_dist2"))[0],
                                         C.byref(n_valid), C.byref(pairs), MEM_DEVICE if dev else MEM_HOST)
         if rc != TSAR_OK:
-            err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
-            err.pairs = int(pairs.value) if pairs.value >= 0 else None      # filled when max_pairs refused the call
-            raise err
+            raise _error_with_pairs(rc, L, m, pairs)
     res["n_valid"] = int(n_valid.value)
     res["pairs"] = int(pairs.value)
     return res

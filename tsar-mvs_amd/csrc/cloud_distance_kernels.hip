@@ -5,31 +5,14 @@
 //
 // Per call:  bounds of the candidate targets (integer atomics on order-preserving float codes: a minimum, exact in any order)
 //            -> 60-bit z-major cell keys of the targets, radix-sorted with their indices (stable: equal keys keep index order)
-//            -> the targets copied into key order as 16-byte records (x, y, z, index)
+//            -> the targets copied into key order as 16-byte records (x, y, z, index)        [these three: cloud_grid.hip]
 //            -> 63-bit cell keys of the queries, radix-sorted, so that a wave's lanes walk the same cells
 //            -> the pair count: per query the sizes of its 9 key ranges (cells x-1 .. x+1 of one (y, z) are one contiguous range)
 //            -> the query kernel: one lane per query in key order, a running minimum of the 64-bit (d2 bits, index) code.
 // No floating-point atomics and no order of arrival anywhere: the outputs are the same bits in every run.
-// (The candidate rule, the float codes, the cell function, the bounds pass, the sort, the grid and the walk over a query's key ranges live in
-// cloud_grid.h, shared with cloud_voxel_kernels.hip and cloud_neighbor_kernels.hip.)
+// (The candidate rule, the float codes, the cell function, the grid and the walk over a query's key ranges are inlined from cloud_grid.h;
+// the bounds pass, the sort and the targets' index are cloud_grid.hip's, shared with cloud_voxel_kernels.hip and cloud_neighbor_kernels.hip.)
 #include "cloud_grid.h"
-
-__global__ __launch_bounds__(CD_BLOCK) void cd_target_keys_kernel(const float* __restrict__ pts, long long n, int stride, CdGrid g,
-                                                                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
-    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const float* p = pts + (size_t)i * stride;
-    const float x = p[0], y = p[1], z = p[2];
-    unsigned long long key = CD_T_NONE;
-    if (cd_candidate(x, y, z)) {
-        // (the origin is the minimum and the extent comes from the maximum through the same monotone function: the clamps never bind)
-        const unsigned long long cx = (unsigned)cd_clampi(cd_cell(x, g.ox, g.e), 0, g.ex - 1), cy = (unsigned)cd_clampi(cd_cell(y, g.oy, g.e), 0, g.ey - 1),
-                                 cz = (unsigned)cd_clampi(cd_cell(z, g.oz, g.e), 0, g.ez - 1);
-        key = (cz << 40) | (cy << 20) | cx;
-    }
-    keys[i] = key;
-    vals[i] = (uint32_t)i;
-}
 
 // a query's cell may lie outside the targets' grid: kept exactly from -2 (no cell of the grid is its neighbour) to extent + 1, plus 2
 __global__ __launch_bounds__(CD_BLOCK) void cd_query_keys_kernel(const float* __restrict__ pts, long long n, int stride, CdGrid g,
@@ -52,17 +35,6 @@ __global__ __launch_bounds__(CD_BLOCK) void cd_query_keys_kernel(const float* __
     }
     const unsigned long long m = __ballot(cand);
     if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(n_valid, (unsigned long long)__popcll(m));
-}
-
-__global__ __launch_bounds__(CD_BLOCK) void cd_gather_kernel(const float* __restrict__ pts, int stride, const uint32_t* __restrict__ vals, uint32_t n_cand,
-                                                             CdRec* __restrict__ rec) {
-    const uint32_t k = blockIdx.x * CD_BLOCK + threadIdx.x;
-    if (k >= n_cand) return;
-    const uint32_t j = vals[k];
-    const float* p = pts + (size_t)j * stride;
-    CdRec r;
-    r.x = p[0]; r.y = p[1]; r.z = p[2]; r.j = j;
-    rec[k] = r;
 }
 
 // *pairs += the number of targets in the 27 cells around every candidate query: what the query kernel would evaluate
@@ -145,94 +117,68 @@ int run_cloud_distance(CallFrame& f, const float* query, long long n_query, int 
                        int64_t* n_valid_out, int64_t* pairs_out) {
     tsar_ctx* ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    // counters: [0..5] the bounds' codes, then (8-byte aligned) the candidate targets, the candidate queries, the pairs, within[n_tol]
-    struct Head { uint32_t bounds[6]; uint32_t pad[2]; unsigned long long n_cand, n_valid, pairs; } head;
-    for (int a = 0; a < 3; a++) { head.bounds[a] = 0xffffffffu; head.bounds[3 + a] = 0u; }
-    head.pad[0] = head.pad[1] = 0;
-    head.n_cand = head.n_valid = head.pairs = 0;
-    char* d_head = f.tmp<char>(sizeof(Head) + 8 * (size_t)(n_tol > 0 ? n_tol : 1));
+    // counters (cloud_grid.h): own[0] the candidate queries, own[1] the pairs; within[n_tol] follows them
+    char* d_head = f.tmp<char>(sizeof(CdCounters) + 8 * (size_t)(n_tol > 0 ? n_tol : 1));
     float* d_tol2 = f.tmp<float>(n_tol > 0 ? n_tol : 1);
     if (!f.ok()) return f.finish();
-    Head* dh = (Head*)d_head;
-    unsigned long long* d_within = (unsigned long long*)(d_head + sizeof(Head));
-    f.copy(d_head, &head, sizeof(Head), hipMemcpyHostToDevice);
+    CdCounters* dc = (CdCounters*)d_head;
+    unsigned long long *d_n_valid = &dc->own[0], *d_pairs = &dc->own[1], *d_within = (unsigned long long*)(d_head + sizeof(CdCounters));
+    unsigned long long own[2] = {0, 0};              // the host's copy of dc->own
     f.zero(d_within, 8 * (size_t)(n_tol > 0 ? n_tol : 1));
     if (n_tol > 0) f.copy(d_tol2, tol2, 4 * (size_t)n_tol, hipMemcpyHostToDevice);
-    if (n_target > 0 && f.ok()) {
-        ScopedKernelTimer tm(ctx, "cloud_bounds");
-        const unsigned blocks = cd_blocks(n_target) < 2048u ? cd_blocks(n_target) : 2048u;
-        hipLaunchKernelGGL(cd_bounds_kernel, dim3(blocks), dim3(CD_BLOCK), 0, st, target, n_target, target_stride, dh->bounds, &dh->n_cand);
-    }
-    f.launched();
-    f.copy(&head, d_head, sizeof(Head), hipMemcpyDeviceToHost);
-    if (!f.sync()) return f.finish();
-    const long long n_cand = (long long)head.n_cand;
+    CdBounds bounds;
+    if (!cd_measure(f, target, n_target, target_stride, dc, bounds)) return f.finish();
+    const long long n_cand = bounds.n_cand;
     std::vector<unsigned long long> h_within(n_tol > 0 ? n_tol : 1, 0ull);
     if (n_cand == 0 || n_query == 0) {               // nothing to search: +inf and -1 throughout
         if (n_query > 0) {
             ScopedKernelTimer tm(ctx, "cloud_distance");
-            hipLaunchKernelGGL(cd_fill_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, n_query, query_stride, dist2_out, index_out, &dh->n_valid);
+            hipLaunchKernelGGL(cd_fill_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, n_query, query_stride, dist2_out, index_out, d_n_valid);
         }
         f.launched();
-        f.copy(&head, d_head, sizeof(Head), hipMemcpyDeviceToHost);
+        f.copy(own, dc->own, sizeof own, hipMemcpyDeviceToHost);
         if (!f.sync()) return f.finish();
         if (pairs_out) *pairs_out = 0;
-        if (n_valid_out) *n_valid_out = (int64_t)head.n_valid;
+        if (n_valid_out) *n_valid_out = (int64_t)own[0];
         for (int t = 0; t < n_tol && within_out; t++) within_out[t] = 0;
         return f.finish();
     }
     CdGrid g;
-    g.ox = (double)cd_decode(head.bounds[0]); g.oy = (double)cd_decode(head.bounds[1]); g.oz = (double)cd_decode(head.bounds[2]);
-    g.e = edge;
-    const double ext[3] = {cd_cell_host(cd_decode(head.bounds[3]), g.ox, edge) + 1.0, cd_cell_host(cd_decode(head.bounds[4]), g.oy, edge) + 1.0,
-                           cd_cell_host(cd_decode(head.bounds[5]), g.oz, edge) + 1.0};
-    for (int a = 0; a < 3; a++)
-        if (!(ext[a] >= 1.0 && ext[a] < (double)CD_MAX_EXTENT))
-            return f.fail(TSAR_ERR_INVALID, "tsar_cloud_distance: the targets span 2^20 cells or more of edge max_dist on an axis: max_dist is too small for this cloud's extent");
-    g.ex = (int)ext[0]; g.ey = (int)ext[1]; g.ez = (int)ext[2];
+    if (!cd_grid(f, bounds, edge, CD_MAX_EXTENT,
+                 "tsar_cloud_distance: the targets span 2^20 cells or more of edge max_dist on an axis: max_dist is too small for this cloud's extent", g))
+        return f.finish();
 
-    unsigned long long *tk0 = f.tmp<unsigned long long>((size_t)n_target), *tk1 = f.tmp<unsigned long long>((size_t)n_target);
-    uint32_t *tv0 = f.tmp<uint32_t>((size_t)n_target), *tv1 = f.tmp<uint32_t>((size_t)n_target);
-    CdRec* rec = f.tmp<CdRec>((size_t)n_cand);
     unsigned long long *qk0 = f.tmp<unsigned long long>((size_t)n_query), *qk1 = f.tmp<unsigned long long>((size_t)n_query);
     uint32_t *qv0 = f.tmp<uint32_t>((size_t)n_query), *qv1 = f.tmp<uint32_t>((size_t)n_query);
-    if (!f.ok()) return f.finish();
-    {
-        ScopedKernelTimer tm(ctx, "cloud_keys");
-        hipLaunchKernelGGL(cd_target_keys_kernel, dim3(cd_blocks(n_target)), dim3(CD_BLOCK), 0, st, target, n_target, target_stride, g, tk0, tv0);
-        hipLaunchKernelGGL(cd_query_keys_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, n_query, query_stride, g, qk0, qv0, &dh->n_valid);
-    }
-    f.launched();
-    if (!cd_sort(f, "cloud_sort", tk0, tk1, tv0, tv1, n_target, 61)) return f.finish();
+    CdIndex tx;                                       // the targets', with the query keys launched in its cloud_keys group
+    if (!cd_index(f, target, n_target, target_stride, n_cand, g, tx, [&] {
+            hipLaunchKernelGGL(cd_query_keys_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, n_query, query_stride, g, qk0, qv0, d_n_valid);
+        }))
+        return f.finish();
     if (!cd_sort(f, "cloud_sort", qk0, qk1, qv0, qv1, n_query, 64)) return f.finish();
     {
-        ScopedKernelTimer tm(ctx, "cloud_gather");
-        hipLaunchKernelGGL(cd_gather_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, target, target_stride, tv1, (uint32_t)n_cand, rec);
-    }
-    f.launched();
-    {
         ScopedKernelTimer tm(ctx, "cloud_pairs");
-        hipLaunchKernelGGL(cd_pairs_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, qk1, n_query, g, tk1, (uint32_t)n_cand, &dh->pairs);
+        hipLaunchKernelGGL(cd_pairs_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, qk1, n_query, g, tx.keys, (uint32_t)n_cand, d_pairs);
     }
     f.launched();
-    f.copy(&head, d_head, sizeof(Head), hipMemcpyDeviceToHost);
+    f.copy(own, dc->own, sizeof own, hipMemcpyDeviceToHost);
     if (!f.sync()) return f.finish();
-    if (pairs_out) *pairs_out = (int64_t)head.pairs;
-    if (head.pairs > (unsigned long long)max_pairs) {
+    if (pairs_out) *pairs_out = (int64_t)own[1];
+    if (own[1] > (unsigned long long)max_pairs) {
         char msg[256];
         snprintf(msg, sizeof msg, "tsar_cloud_distance: the call would evaluate %llu pairs, more than max_pairs = %lld: lower max_dist or raise max_pairs",
-                 head.pairs, max_pairs);
+                 own[1], max_pairs);
         return f.fail(TSAR_ERR_INVALID, msg);
     }
     {
         ScopedKernelTimer tm(ctx, "cloud_distance");
-        hipLaunchKernelGGL(cd_query_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, query_stride, qk1, qv1, n_query, g, tk1, rec, (uint32_t)n_cand, r2,
+        hipLaunchKernelGGL(cd_query_kernel, dim3(cd_blocks(n_query)), dim3(CD_BLOCK), 0, st, query, query_stride, qk1, qv1, n_query, g, tx.keys, tx.rec, (uint32_t)n_cand, r2,
                            n_tol, d_tol2, dist2_out, index_out, d_within);
     }
     f.launched();
     if (n_tol > 0) f.copy(h_within.data(), d_within, 8 * (size_t)n_tol, hipMemcpyDeviceToHost);
     if (!f.sync()) return f.finish();
-    if (n_valid_out) *n_valid_out = (int64_t)head.n_valid;
+    if (n_valid_out) *n_valid_out = (int64_t)own[0];
     for (int t = 0; t < n_tol && within_out; t++) within_out[t] = (int64_t)h_within[t];
     return f.finish();
 }

@@ -1,12 +1,14 @@
 // cloud_grid.h — what the operators on point clouds share (cloud_distance_kernels.hip, cloud_voxel_kernels.hip,
-// cloud_neighbor_kernels.hip): the candidate rule, the order-preserving float codes, the float64 cell function of include/tsar.h, the
-// bounds pass over a cloud, the radix sort of (key, index) pairs and, for the two searches, the grid of edge R (1 + 2^-10), its 16-byte
-// records and the walk over a query's nine key ranges.  Kernels here are `static`: each translation unit that includes this file carries
-// its own copy.
+// cloud_neighbor_kernels.hip).  Inlined into their kernels from here: the candidate rule, the order-preserving float codes, the float64
+// cell function of include/tsar.h, the wave reductions and, for the two searches, the grid of edge R (1 + 2^-10), its 16-byte records and
+// the walk over a query's nine key ranges.  Compiled once, in cloud_grid.hip, and declared here: the bounds pass over a cloud
+// (cd_measure), the grid over those bounds (cd_grid), the radix sort of (key, index) pairs (cd_sort) and the sorted index of a cloud's
+// cells with its records (cd_index).
 #pragma once
 #include <float.h>
 #include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
+
+#include <functional>
 
 #include "tsar_dev.h"
 
@@ -15,38 +17,14 @@
 __device__ __forceinline__ bool cd_candidate(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }   // NaN fails
 // unsigned codes in the order of the floats they stand for (-0.0 below +0.0: the same double either way)
 __device__ __forceinline__ uint32_t cd_code(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-static inline float cd_decode(uint32_t c) { const uint32_t u = (c & 0x80000000u) ? (c & 0x7fffffffu) : ~c; float f; memcpy(&f, &u, 4); return f; }
 // the cell coordinate of include/tsar.h, as a double: floor(((double)p - (double)o) / e), the quotient correctly rounded
 __device__ __forceinline__ double cd_cell(float p, double o, double e) { return floor(((double)p - o) / e); }
-static inline double cd_cell_host(float p, double o, double e) { return floor(((double)p - o) / e); }
 
 __device__ __forceinline__ uint32_t cd_wave_min(uint32_t v) { for (int s = 32; s > 0; s >>= 1) { const uint32_t o = __shfl_xor(v, s, 64); v = o < v ? o : v; } return v; }
 __device__ __forceinline__ uint32_t cd_wave_max(uint32_t v) { for (int s = 32; s > 0; s >>= 1) { const uint32_t o = __shfl_xor(v, s, 64); v = o > v ? o : v; } return v; }
 __device__ __forceinline__ unsigned long long cd_wave_sum(unsigned long long v) { for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64); return v; }
 
-// bounds[0..2] = codes of the per-axis minima, bounds[3..5] = of the maxima, *count = the candidates
-static __global__ __launch_bounds__(CD_BLOCK) void cd_bounds_kernel(const float* __restrict__ pts, long long n, int stride, uint32_t* __restrict__ bounds,
-                                                                    unsigned long long* __restrict__ count) {
-    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    unsigned long long cnt = 0;
-    for (long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * CD_BLOCK) {
-        const float* p = pts + (size_t)i * stride;
-        const float x = p[0], y = p[1], z = p[2];
-        if (!cd_candidate(x, y, z)) continue;
-        const uint32_t c[3] = {cd_code(x), cd_code(y), cd_code(z)};
-        for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
-        cnt++;
-    }
-    for (int a = 0; a < 3; a++) { lo[a] = cd_wave_min(lo[a]); hi[a] = cd_wave_max(hi[a]); }
-    cnt = cd_wave_sum(cnt);
-    if ((threadIdx.x & 63) == 0 && cnt) {
-        for (int a = 0; a < 3; a++) { atomicMin(&bounds[a], lo[a]); atomicMax(&bounds[3 + a], hi[a]); }
-        atomicAdd(count, cnt);
-    }
-}
-
 static inline unsigned cd_blocks(long long n) { return (unsigned)((n + CD_BLOCK - 1) / CD_BLOCK); }
-static inline unsigned cd_bounds_blocks(long long n) { return cd_blocks(n) < 2048u ? cd_blocks(n) : 2048u; }
 
 #define CD_T_NONE (1ull << 60)            // key of a target that is no candidate: above every cell key (3 x 20 bits)
 #define CD_Q_NONE (1ull << 63)            // key of a query that is no candidate: above every query key (3 x 21 bits)
@@ -84,13 +62,26 @@ __device__ __forceinline__ bool cd_query_range(unsigned long long qkey, int r, c
     return true;
 }
 
+// ---- cloud_grid.hip's host steps: every one works on the call's frame and leaves a failure in it (false: the caller returns f.finish()) ----
+
+// The counters of one call, a piece of the frame: what the bounds pass fills, and two slots that are the operator's own (the searches
+// count their candidate queries and their pairs there), so that one upload zeroes them all.
+struct CdCounters {
+    uint32_t bounds[6];                   // codes of the per-axis minima [0..2] and maxima [3..5] of the candidates
+    uint32_t pad[2];
+    unsigned long long n_cand;
+    unsigned long long own[2];
+};
+struct CdBounds { float lo[3], hi[3]; long long n_cand; };   // lo / hi mean nothing when n_cand is 0
+
+// *dc initialised, the bounds pass over the cloud (timer cloud_bounds), the result read back: the stream is idle on return
+bool cd_measure(CallFrame& f, const float* pts, long long n, int stride, CdCounters* dc, CdBounds& b);
+// the grid of edge `edge` whose origin is b.lo; the frame fails with `refusal` when an axis has `limit` cells or more
+bool cd_grid(CallFrame& f, const CdBounds& b, double edge, int limit, const char* refusal, CdGrid& g);
 // keys_in / vals_in sorted into keys_out / vals_out (bits [0, end_bit)); the sort's scratch is a piece of the frame
-template <typename F>
-static bool cd_sort(F& f, const char* name, unsigned long long* keys_in, unsigned long long* keys_out, uint32_t* vals_in, uint32_t* vals_out, long long n, int end_bit) {
-    size_t bytes = 0;
-    if (!f.ok() || !f.hip(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, end_bit, f.ctx->stream), "rocprim::radix_sort_pairs sizing")) return false;
-    void* tmp = f.template tmp<char>(bytes);
-    if (!f.ok()) return false;
-    ScopedKernelTimer tm(f.ctx, name);
-    return f.hip(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, end_bit, f.ctx->stream), "rocprim::radix_sort_pairs");
-}
+bool cd_sort(CallFrame& f, const char* name, unsigned long long* keys_in, unsigned long long* keys_out, uint32_t* vals_in, uint32_t* vals_out, long long n, int end_bit);
+// The cloud's 60-bit z-major cell keys (timer cloud_keys), sorted with the indices (cloud_sort; stable: equal keys keep index order;
+// the non-candidates last) and the candidates copied into key order as records (cloud_gather).  also_keys, if any, launches the
+// caller's own key kernel in the cloud_keys group.
+struct CdIndex { unsigned long long* keys; uint32_t* vals; CdRec* rec; };   // n sorted keys, n sorted indices, n_cand records
+bool cd_index(CallFrame& f, const float* pts, long long n, int stride, long long n_cand, const CdGrid& g, CdIndex& ix, const std::function<void()>& also_keys = nullptr);

@@ -4,8 +4,8 @@
 // at, and every pair with d2 <= fl(R * R) lies in the 27 cells around the point's (include/tsar.h says why), so no bit of the result
 // depends on it, nor on the order in which a point's neighbours arrive.
 //
-// Per call:  bounds of the candidates (cloud_grid.h) -> 60-bit z-major cell keys, radix-sorted with the indices
-//            -> the candidates copied into key order as 16-byte records (x, y, z, index)
+// Per call:  bounds of the candidates -> 60-bit z-major cell keys, radix-sorted with the indices
+//            -> the candidates copied into key order as 16-byte records (x, y, z, index)     [so far: cloud_grid.hip, shared with the other two]
 //            -> the pair count: per sorted record the sizes of its 9 key ranges (the record itself is in one of them)
 //            -> the search kernel: lane t takes sorted record t as its query, so that a wave's lanes walk the same cells and one sort
 //               serves queries and targets; a count, and a sorted list of the KCAP smallest d2 kept in registers.
@@ -15,34 +15,6 @@
 #include "cloud_grid.h"
 
 #define CN_INF_BITS 0x7f800000u
-
-__global__ __launch_bounds__(CD_BLOCK) void cn_keys_kernel(const float* __restrict__ pts, long long n, int stride, CdGrid g, unsigned long long* __restrict__ keys,
-                                                           uint32_t* __restrict__ vals) {
-    const long long i = (long long)blockIdx.x * CD_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const float* p = pts + (size_t)i * stride;
-    const float x = p[0], y = p[1], z = p[2];
-    unsigned long long key = CD_T_NONE;
-    if (cd_candidate(x, y, z)) {
-        // (the origin is the minimum and the extent comes from the maximum through the same monotone function: the clamps never bind)
-        const unsigned long long cx = (unsigned)cd_clampi(cd_cell(x, g.ox, g.e), 0, g.ex - 1), cy = (unsigned)cd_clampi(cd_cell(y, g.oy, g.e), 0, g.ey - 1),
-                                 cz = (unsigned)cd_clampi(cd_cell(z, g.oz, g.e), 0, g.ez - 1);
-        key = (cz << 40) | (cy << 20) | cx;
-    }
-    keys[i] = key;
-    vals[i] = (uint32_t)i;
-}
-
-__global__ __launch_bounds__(CD_BLOCK) void cn_gather_kernel(const float* __restrict__ pts, int stride, const uint32_t* __restrict__ vals, uint32_t n_cand,
-                                                             CdRec* __restrict__ rec) {
-    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
-    if (t >= n_cand) return;
-    const uint32_t j = vals[t];
-    const float* p = pts + (size_t)j * stride;
-    CdRec r;
-    r.x = p[0]; r.y = p[1]; r.z = p[2]; r.j = j;
-    rec[t] = r;
-}
 
 // a sorted record's cell key (3 x 20 bits) as the query key cd_query_range reads (3 x 21 bits, each coordinate + 2)
 __device__ __forceinline__ unsigned long long cn_query_key(unsigned long long key) {
@@ -132,61 +104,31 @@ int run_cloud_neighbors(CallFrame& f, const float* cloud, long long n, int strid
                         int64_t* n_valid_out, int64_t* pairs_out) {
     tsar_ctx* ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    struct Head { uint32_t bounds[6]; uint32_t pad[2]; unsigned long long n_cand, pairs; } head;
-    for (int a = 0; a < 3; a++) { head.bounds[a] = 0xffffffffu; head.bounds[3 + a] = 0u; }
-    head.pad[0] = head.pad[1] = 0;
-    head.n_cand = head.pairs = 0;
-    Head* dh = f.tmp<Head>(1);
+    CdCounters* dc = f.tmp<CdCounters>(1);           // (cloud_grid.h) own[0]: the pairs
     if (!f.ok()) return f.finish();
-    f.copy(dh, &head, sizeof(Head), hipMemcpyHostToDevice);
-    if (n > 0 && f.ok()) {
-        ScopedKernelTimer tm(ctx, "cloud_bounds");
-        hipLaunchKernelGGL(cd_bounds_kernel, dim3(cd_bounds_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, dh->bounds, &dh->n_cand);
-    }
-    f.launched();
-    f.copy(&head, dh, sizeof(Head), hipMemcpyDeviceToHost);
-    if (!f.sync()) return f.finish();
-    const long long n_cand = (long long)head.n_cand;
+    CdBounds bounds;
+    if (!cd_measure(f, cloud, n, stride, dc, bounds)) return f.finish();
+    const long long n_cand = bounds.n_cand;
+    unsigned long long pairs = 0;
     CdGrid g = {};
-    unsigned long long *k0 = nullptr, *k1 = nullptr;
-    uint32_t *v0 = nullptr, *v1 = nullptr;
-    CdRec* rec = nullptr;
+    CdIndex ix = {};
     if (n_cand > 0) {
-        g.ox = (double)cd_decode(head.bounds[0]); g.oy = (double)cd_decode(head.bounds[1]); g.oz = (double)cd_decode(head.bounds[2]);
-        g.e = edge;
-        const double ext[3] = {cd_cell_host(cd_decode(head.bounds[3]), g.ox, edge) + 1.0, cd_cell_host(cd_decode(head.bounds[4]), g.oy, edge) + 1.0,
-                               cd_cell_host(cd_decode(head.bounds[5]), g.oz, edge) + 1.0};
-        for (int a = 0; a < 3; a++)
-            if (!(ext[a] >= 1.0 && ext[a] < (double)CD_MAX_EXTENT))
-                return f.fail(TSAR_ERR_INVALID, "tsar_cloud_neighbors: the cloud spans 2^20 cells or more of edge radius on an axis: radius is too small for this cloud's extent");
-        g.ex = (int)ext[0]; g.ey = (int)ext[1]; g.ez = (int)ext[2];
-        k0 = f.tmp<unsigned long long>((size_t)n); k1 = f.tmp<unsigned long long>((size_t)n);
-        v0 = f.tmp<uint32_t>((size_t)n); v1 = f.tmp<uint32_t>((size_t)n);
-        rec = f.tmp<CdRec>((size_t)n_cand);
-        if (!f.ok()) return f.finish();
-        {
-            ScopedKernelTimer tm(ctx, "cloud_keys");
-            hipLaunchKernelGGL(cn_keys_kernel, dim3(cd_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, g, k0, v0);
-        }
-        f.launched();
-        if (!cd_sort(f, "cloud_sort", k0, k1, v0, v1, n, 61)) return f.finish();
-        {
-            ScopedKernelTimer tm(ctx, "cloud_gather");
-            hipLaunchKernelGGL(cn_gather_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, cloud, stride, v1, (uint32_t)n_cand, rec);
-        }
-        f.launched();
+        if (!cd_grid(f, bounds, edge, CD_MAX_EXTENT,
+                     "tsar_cloud_neighbors: the cloud spans 2^20 cells or more of edge radius on an axis: radius is too small for this cloud's extent", g))
+            return f.finish();
+        if (!cd_index(f, cloud, n, stride, n_cand, g, ix)) return f.finish();
         {
             ScopedKernelTimer tm(ctx, "cloud_pairs");
-            hipLaunchKernelGGL(cn_pairs_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, k1, (uint32_t)n_cand, g, &dh->pairs);
+            hipLaunchKernelGGL(cn_pairs_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, ix.keys, (uint32_t)n_cand, g, &dc->own[0]);
         }
         f.launched();
-        f.copy(&head, dh, sizeof(Head), hipMemcpyDeviceToHost);
+        f.copy(&pairs, &dc->own[0], sizeof pairs, hipMemcpyDeviceToHost);
         if (!f.sync()) return f.finish();
     }
-    if (pairs_out) *pairs_out = (int64_t)head.pairs;
-    if (head.pairs > (unsigned long long)max_pairs) {
+    if (pairs_out) *pairs_out = (int64_t)pairs;
+    if (pairs > (unsigned long long)max_pairs) {
         char msg[256];
-        snprintf(msg, sizeof msg, "tsar_cloud_neighbors: the call would look at %llu pairs, more than max_pairs = %lld: lower radius or raise max_pairs", head.pairs, max_pairs);
+        snprintf(msg, sizeof msg, "tsar_cloud_neighbors: the call would look at %llu pairs, more than max_pairs = %lld: lower radius or raise max_pairs", pairs, max_pairs);
         return f.fail(TSAR_ERR_INVALID, msg);
     }
     if (f.ok() && n > 0 && n_cand < n && (count_out || knn_out)) {
@@ -197,11 +139,11 @@ int run_cloud_neighbors(CallFrame& f, const float* cloud, long long n, int strid
     if (f.ok() && n_cand > 0 && (count_out || knn_out)) {
         ScopedKernelTimer tm(ctx, "cloud_neighbors");
         const int kk = knn_out ? k : 0;          // the smallest list that holds k
-        if (kk == 0) cn_launch_search<0>(st, k1, rec, (uint32_t)n_cand, g, r2, 0, count_out, nullptr);
-        else if (kk <= 4) cn_launch_search<4>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
-        else if (kk <= 8) cn_launch_search<8>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
-        else if (kk <= 16) cn_launch_search<16>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
-        else cn_launch_search<32>(st, k1, rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        if (kk == 0) cn_launch_search<0>(st, ix.keys, ix.rec, (uint32_t)n_cand, g, r2, 0, count_out, nullptr);
+        else if (kk <= 4) cn_launch_search<4>(st, ix.keys, ix.rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        else if (kk <= 8) cn_launch_search<8>(st, ix.keys, ix.rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        else if (kk <= 16) cn_launch_search<16>(st, ix.keys, ix.rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
+        else cn_launch_search<32>(st, ix.keys, ix.rec, (uint32_t)n_cand, g, r2, k, count_out, knn_out);
     }
     f.launched();
     if (n_valid_out) *n_valid_out = (int64_t)n_cand;

@@ -3,9 +3,9 @@
 // number of its voxel.  Every output is an integer count or a minimum of a bit-defined 64-bit code, so the result is the same bits in
 // every run and equals the numpy restatement (tests/cloud_voxels_ref.py).
 //
-// Per call:  bounds of the candidates (cloud_grid.h: the origin is their per-axis minimum)
+// Per call:  bounds of the candidates (cloud_grid.hip: the origin is their per-axis minimum; the extents come from there too)
 //            -> a cell key per point, z-major (z, y, x packed with as many bits per axis as the extents need, which orders the keys like
-//               z << 42 | y << 21 | x), non-candidates above all; radix-sorted with the indices (stable: a voxel's points keep index order)
+//               z << 42 | y << 21 | x), non-candidates above all; radix-sorted with the indices (cloud_grid.hip's sort; stable: a voxel's points keep index order)
 //            -> head flags over the sorted keys and an inclusive scan: the voxel number of every sorted position
 //            -> the reduce kernel, one lane per sorted point: its code (d2f bits, index) and its tolerance flags, reduced over the wave's
 //               runs of one voxel by the head mask; the first lane of each (wave, run) issues one 64-bit atomicMin and one 32-bit
@@ -132,22 +132,12 @@ int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, 
                      long long cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out, int mem) {
     tsar_ctx* ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    struct Head { uint32_t bounds[6]; uint32_t n_voxels; uint32_t pad; unsigned long long n_cand; } head;
-    for (int a = 0; a < 3; a++) { head.bounds[a] = 0xffffffffu; head.bounds[3 + a] = 0u; }
-    head.n_voxels = head.pad = 0;
-    head.n_cand = 0;
-    Head* dh = f.tmp<Head>(1);
+    CdCounters* dc = f.tmp<CdCounters>(1);           // (cloud_grid.h; this operator has no counter of its own on the device)
     int32_t* d_rank = f.out(rank_out, (size_t)n, mem);
     if (!f.ok()) return f.finish();
-    f.copy(dh, &head, sizeof(Head), hipMemcpyHostToDevice);
-    if (n > 0 && f.ok()) {
-        ScopedKernelTimer tm(ctx, "cloud_bounds");
-        hipLaunchKernelGGL(cd_bounds_kernel, dim3(cd_bounds_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, dh->bounds, &dh->n_cand);
-    }
-    f.launched();
-    f.copy(&head, dh, sizeof(Head), hipMemcpyDeviceToHost);
-    if (!f.sync()) return f.finish();
-    const long long n_cand = (long long)head.n_cand;
+    CdBounds bounds;
+    if (!cd_measure(f, cloud, n, stride, dc, bounds)) return f.finish();
+    const long long n_cand = bounds.n_cand;
     if (n_cand == 0) {                               // no voxel: every rank is -1
         if (n > 0 && d_rank) {
             ScopedKernelTimer tm(ctx, "voxel_reduce");
@@ -158,15 +148,13 @@ int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, 
         if (n_valid_out) *n_valid_out = 0;
         return f.finish();
     }
+    CdGrid cg;
+    if (!cd_grid(f, bounds, voxel, CV_MAX_EXTENT, "tsar_cloud_voxels: the cloud spans 2^21 cells or more of edge voxel on an axis: voxel is too small for this cloud's extent", cg))
+        return f.finish();
     CvGrid g;
-    g.ox = (double)cd_decode(head.bounds[0]); g.oy = (double)cd_decode(head.bounds[1]); g.oz = (double)cd_decode(head.bounds[2]);
+    g.ox = cg.ox; g.oy = cg.oy; g.oz = cg.oz;
     g.v = voxel;
-    const double ext[3] = {cd_cell_host(cd_decode(head.bounds[3]), g.ox, voxel) + 1.0, cd_cell_host(cd_decode(head.bounds[4]), g.oy, voxel) + 1.0,
-                           cd_cell_host(cd_decode(head.bounds[5]), g.oz, voxel) + 1.0};
-    for (int a = 0; a < 3; a++)
-        if (!(ext[a] >= 1.0 && ext[a] < (double)CV_MAX_EXTENT))
-            return f.fail(TSAR_ERR_INVALID, "tsar_cloud_voxels: the cloud spans 2^21 cells or more of edge voxel on an axis: voxel is too small for this cloud's extent");
-    g.ex = (int)ext[0]; g.ey = (int)ext[1]; g.ez = (int)ext[2];
+    g.ex = cg.ex; g.ey = cg.ey; g.ez = cg.ez;
     g.bx = cv_bits(g.ex); g.by = cv_bits(g.ey);
     const int key_bits = g.bx + g.by + cv_bits(g.ez);        // at most 63
     g.none = 1ull << key_bits;
@@ -195,9 +183,10 @@ int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, 
         ScopedKernelTimer tm(ctx, "voxel_scan");
         if (!f.hip(rocprim::inclusive_scan(tmp, bytes, d_head, d_incl, (size_t)n_cand, rocprim::plus<uint32_t>(), st), "rocprim::inclusive_scan")) return f.finish();
     }
-    f.copy(&head.n_voxels, d_incl + (n_cand - 1), sizeof(uint32_t), hipMemcpyDeviceToHost);
+    uint32_t last_voxel = 0;                                 // the last candidate's inclusive scan: the number of voxels
+    f.copy(&last_voxel, d_incl + (n_cand - 1), sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (!f.sync()) return f.finish();
-    const long long n_voxels = (long long)head.n_voxels;
+    const long long n_voxels = (long long)last_voxel;
     const long long n_write = n_voxels < cap ? n_voxels : cap;
     const bool per_voxel = n_write > 0 && (rep_out || count_out || within_out);
     const bool want_best = per_voxel && rep_out, want_start = per_voxel && count_out, want_within = per_voxel && within_out;

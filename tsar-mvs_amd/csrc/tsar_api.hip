@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 
 #include "tsar_dev.h"
 
@@ -1166,6 +1167,52 @@ extern "C" int tsar_pm_merge_depths(tsar_ctx* ctx, const float* depth, int mem, 
     return TSAR_OK;
 }
 
+// ---- what the entries on point clouds share ---------------------------------------------------------------------------------------------
+// The checks every one of them makes on its memory space and its clouds, in this order: mem, every n, every stride, every pointer.  The
+// wording of an entry with one cloud is the default; tsar_cloud_distance, with two, passes its own.
+struct CloudArg { const void* pts; int64_t n; int stride; };
+static int check_clouds(tsar_ctx* ctx, const char* entry, int mem, std::initializer_list<CloudArg> clouds, const char* n_names = "n", const char* stride_names = "the stride",
+                        const char* pts_names = "cloud") {
+    std::string msg;
+    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) msg = "mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE";
+    for (const CloudArg& c : clouds)
+        if (msg.empty() && (c.n < 0 || c.n > INT32_MAX)) msg = std::string(n_names) + " must be in 0..2^31-1";
+    for (const CloudArg& c : clouds)
+        if (msg.empty() && c.stride < 3) msg = std::string(stride_names) + " must be at least 3 floats (x y z first)";
+    for (const CloudArg& c : clouds)
+        if (msg.empty() && c.n > 0 && !c.pts) msg = std::string(pts_names) + " is NULL";
+    return msg.empty() ? TSAR_OK : fail(ctx, TSAR_ERR_INVALID, (std::string(entry) + ": " + msg).c_str());
+}
+
+// *r2 = fl(R * R), one float32 product; false unless R and the product are finite and > 0
+static bool cloud_radius2(float R, float* r2) {
+    const volatile float r2v = R * R;
+    *r2 = r2v;
+    return fabsf(R) <= FLT_MAX && *r2 > 0.0f && *r2 <= FLT_MAX && R > 0.0f;
+}
+
+// tol2[k] = fl(tol[k] * tol[k]), one float32 product each; a tolerance outside (0, bound] refuses the call with `refusal`
+static int square_tolerances(tsar_ctx* ctx, int n_tol, const float* tol, float bound, const char* refusal, std::vector<float>& tol2) {
+    tol2.resize((size_t)n_tol);
+    for (int k = 0; k < n_tol; k++) {
+        if (!(tol[k] > 0.0f && tol[k] <= bound)) return fail(ctx, TSAR_ERR_INVALID, refusal);
+        const volatile float t2 = tol[k] * tol[k];
+        tol2[k] = t2;
+    }
+    return TSAR_OK;
+}
+
+// The context-free form of an entry: a context of its own for the duration of the call.
+template <typename Call>
+static int with_own_ctx(int device, Call call) {
+    tsar_ctx* ctx = nullptr;
+    const int rc0 = tsar_create(device, &ctx);
+    if (rc0 != TSAR_OK) return rc0;
+    const int rc = call(ctx);
+    tsar_destroy(ctx);
+    return rc;
+}
+
 // ---- cloud-to-cloud distances (cloud_distance_kernels.hip) ----------------------------------------------------------------------------
 extern "C" void tsar_default_cloud_distance_params(tsar_cloud_distance_params* p) {
     if (!p) return;
@@ -1180,24 +1227,16 @@ extern "C" int tsar_cloud_distance_ctx(tsar_ctx* ctx, const float* query, int64_
                                        int64_t* within_out, int64_t* n_valid_query_out, int64_t* pairs_out, int mem) {
     CHECK_CTX(ctx);
     if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: params is NULL");
-    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    if (n_query < 0 || n_target < 0 || n_query > INT32_MAX || n_target > INT32_MAX)
-        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: n_query and n_target must be in 0..2^31-1");
-    if (query_stride < 3 || target_stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: a stride must be at least 3 floats (x y z first)");
-    if ((n_query > 0 && !query) || (n_target > 0 && !target)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: query or target is NULL");
+    TRY(check_clouds(ctx, "tsar_cloud_distance", mem, {{query, n_query, query_stride}, {target, n_target, target_stride}}, "n_query and n_target", "a stride",
+                     "query or target"));
     const float R = p->max_dist;
-    const volatile float r2v = R * R;      // fl(R * R), one float32 product
-    const float r2 = r2v;
-    if (!(fabsf(R) <= FLT_MAX) || !(r2 > 0.0f && r2 <= FLT_MAX) || !(R > 0.0f))
+    float r2;
+    if (!cloud_radius2(R, &r2))
         return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: max_dist must be finite and > 0, with max_dist * max_dist finite and > 0 in float32");
     if (p->max_pairs < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: max_pairs must be >= 0");
     if (n_tol < 0 || (n_tol > 0 && !tol)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: n_tol < 0, or tol is NULL");
-    std::vector<float> tol2((size_t)n_tol);
-    for (int k = 0; k < n_tol; k++) {
-        if (!(tol[k] > 0.0f && tol[k] <= R)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_distance: every tolerance must be finite, > 0 and <= max_dist");
-        const volatile float t2 = tol[k] * tol[k];
-        tol2[k] = t2;
-    }
+    std::vector<float> tol2;
+    TRY(square_tolerances(ctx, n_tol, tol, R, "tsar_cloud_distance: every tolerance must be finite, > 0 and <= max_dist", tol2));
     CallFrame f(ctx, "tsar_cloud_distance", nullptr, /*grow_arena=*/false);
     const float* q = f.in(query, (size_t)n_query * query_stride, mem);
     const float* t = (target == query && n_target == n_query && target_stride == query_stride) ? q : f.in(target, (size_t)n_target * target_stride, mem);
@@ -1208,17 +1247,14 @@ extern "C" int tsar_cloud_distance_ctx(tsar_ctx* ctx, const float* query, int64_
                               within_out, n_valid_query_out, pairs_out);
 }
 
-// Context-free form (the evaluation tool's two calls per pair of clouds): a context of its own for the duration of the call.
+// Context-free form (the evaluation tool's two calls per pair of clouds).
 extern "C" int tsar_cloud_distance(int device, const float* query, int64_t n_query, int query_stride, const float* target, int64_t n_target, int target_stride,
                                    const tsar_cloud_distance_params* p, int n_tol, const float* tol, float* dist2_out, int32_t* index_out, int64_t* within_out,
                                    int64_t* n_valid_query_out, int64_t* pairs_out, int mem) {
-    tsar_ctx* ctx = nullptr;
-    const int rc0 = tsar_create(device, &ctx);
-    if (rc0 != TSAR_OK) return rc0;
-    const int rc = tsar_cloud_distance_ctx(ctx, query, n_query, query_stride, target, n_target, target_stride, p, n_tol, tol, dist2_out, index_out, within_out,
-                                           n_valid_query_out, pairs_out, mem);
-    tsar_destroy(ctx);
-    return rc;
+    return with_own_ctx(device, [&](tsar_ctx* ctx) {
+        return tsar_cloud_distance_ctx(ctx, query, n_query, query_stride, target, n_target, target_stride, p, n_tol, tol, dist2_out, index_out, within_out, n_valid_query_out,
+                                       pairs_out, mem);
+    });
 }
 
 // ---- a voxel grid over a cloud (cloud_voxel_kernels.hip) -------------------------------------------------------------------------------
@@ -1233,21 +1269,14 @@ extern "C" int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t 
                                      int64_t* n_valid_out, int mem) {
     CHECK_CTX(ctx);
     if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: params is NULL");
-    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: n must be in 0..2^31-1");
-    if (stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: the stride must be at least 3 floats (x y z first)");
-    if (n > 0 && !cloud) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: cloud is NULL");
+    TRY(check_clouds(ctx, "tsar_cloud_voxels", mem, {{cloud, n, stride}}));
     const float V = p->voxel;
     if (!(fabsf(V) <= FLT_MAX) || !(V > 0.0f)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: voxel must be finite and > 0");
     if (cap < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: cap must be >= 0");
     if (n_tol < 0 || (n_tol > 0 && (!tol || (!dist2 && n > 0)))) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: n_tol < 0, or tolerances without tol or without dist2");
     if (n_tol == 0 && within_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: within_out needs tolerances (n_tol is 0)");
-    std::vector<float> tol2((size_t)n_tol);
-    for (int k = 0; k < n_tol; k++) {
-        if (!(tol[k] > 0.0f && tol[k] <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_voxels: every tolerance must be finite and > 0");
-        const volatile float t2 = tol[k] * tol[k];      // fl(tol * tol), one float32 product
-        tol2[k] = t2;
-    }
+    std::vector<float> tol2;
+    TRY(square_tolerances(ctx, n_tol, tol, FLT_MAX, "tsar_cloud_voxels: every tolerance must be finite and > 0", tol2));
     CallFrame f(ctx, "tsar_cloud_voxels", nullptr, /*grow_arena=*/false);
     const float* c = f.in(cloud, (size_t)n * stride, mem);
     const float* d2 = n_tol > 0 ? f.in(dist2, (size_t)n, mem) : nullptr;
@@ -1255,16 +1284,13 @@ extern "C" int tsar_cloud_voxels_ctx(tsar_ctx* ctx, const float* cloud, int64_t 
     return run_cloud_voxels(f, c, n, stride, (double)V, d2, n_tol, tol2.data(), rank_out, cap, rep_out, count_out, within_out, n_voxels_out, n_valid_out, mem);
 }
 
-// Context-free form (the fuser's thinning step): a context of its own for the duration of the call.
+// Context-free form (the fuser's thinning step).
 extern "C" int tsar_cloud_voxels(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_voxels_params* p, const float* dist2, int n_tol, const float* tol,
                                  int32_t* rank_out, int64_t cap, int32_t* rep_out, int32_t* count_out, int32_t* within_out, int64_t* n_voxels_out, int64_t* n_valid_out,
                                  int mem) {
-    tsar_ctx* ctx = nullptr;
-    const int rc0 = tsar_create(device, &ctx);
-    if (rc0 != TSAR_OK) return rc0;
-    const int rc = tsar_cloud_voxels_ctx(ctx, cloud, n, stride, p, dist2, n_tol, tol, rank_out, cap, rep_out, count_out, within_out, n_voxels_out, n_valid_out, mem);
-    tsar_destroy(ctx);
-    return rc;
+    return with_own_ctx(device, [&](tsar_ctx* ctx) {
+        return tsar_cloud_voxels_ctx(ctx, cloud, n, stride, p, dist2, n_tol, tol, rank_out, cap, rep_out, count_out, within_out, n_voxels_out, n_valid_out, mem);
+    });
 }
 
 // ---- neighbourhood statistics of a cloud (cloud_neighbor_kernels.hip) -------------------------------------------------------------------
@@ -1280,14 +1306,10 @@ extern "C" int tsar_cloud_neighbors_ctx(tsar_ctx* ctx, const float* cloud, int64
                                         float* knn_dist2_out, int64_t* n_valid_out, int64_t* pairs_out, int mem) {
     CHECK_CTX(ctx);
     if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: params is NULL");
-    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: n must be in 0..2^31-1");
-    if (stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: the stride must be at least 3 floats (x y z first)");
-    if (n > 0 && !cloud) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: cloud is NULL");
+    TRY(check_clouds(ctx, "tsar_cloud_neighbors", mem, {{cloud, n, stride}}));
     const float R = p->radius;
-    const volatile float r2v = R * R;      // fl(R * R), one float32 product
-    const float r2 = r2v;
-    if (!(fabsf(R) <= FLT_MAX) || !(r2 > 0.0f && r2 <= FLT_MAX) || !(R > 0.0f))
+    float r2;
+    if (!cloud_radius2(R, &r2))
         return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: radius must be finite and > 0, with radius * radius finite and > 0 in float32");
     if (p->k < 0 || p->k > TSAR_CLOUD_KNN_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: k must be in 0..TSAR_CLOUD_KNN_MAX (32)");
     if (p->k == 0 && knn_dist2_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_neighbors: knn_dist2_out needs k > 0");
@@ -1300,15 +1322,10 @@ extern "C" int tsar_cloud_neighbors_ctx(tsar_ctx* ctx, const float* cloud, int64
     return run_cloud_neighbors(f, c, n, stride, r2, (double)R * (1.0 + 1.0 / 1024.0), p->k, p->max_pairs, cnt, knn, n_valid_out, pairs_out);
 }
 
-// Context-free form (the fuser's cleaning step): a context of its own for the duration of the call.
+// Context-free form (the fuser's cleaning step).
 extern "C" int tsar_cloud_neighbors(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_neighbors_params* p, int32_t* count_out, float* knn_dist2_out,
                                     int64_t* n_valid_out, int64_t* pairs_out, int mem) {
-    tsar_ctx* ctx = nullptr;
-    const int rc0 = tsar_create(device, &ctx);
-    if (rc0 != TSAR_OK) return rc0;
-    const int rc = tsar_cloud_neighbors_ctx(ctx, cloud, n, stride, p, count_out, knn_dist2_out, n_valid_out, pairs_out, mem);
-    tsar_destroy(ctx);
-    return rc;
+    return with_own_ctx(device, [&](tsar_ctx* ctx) { return tsar_cloud_neighbors_ctx(ctx, cloud, n, stride, p, count_out, knn_dist2_out, n_valid_out, pairs_out, mem); });
 }
 
 // ---- a cloud rendered into a camera; a depth map scored against a map (cloud_render_kernels.hip) -----------------------------------------
@@ -1328,10 +1345,7 @@ extern "C" int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t 
     CHECK_CTX(ctx);
     if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: params is NULL");
     if (!cam) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: cam is NULL");
-    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: n must be in 0..2^31-1");
-    if (stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: the stride must be at least 3 floats (x y z first)");
-    if (n > 0 && !cloud) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: cloud is NULL");
+    TRY(check_clouds(ctx, "tsar_cloud_render", mem, {{cloud, n, stride}}));
     if (!depth_out && !count_out && !index_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: depth_out, count_out and index_out are all NULL");
     if (w < 1 || h < 1 || w + 2 >= (1 << 23) || h + 2 >= (1 << 23) || (int64_t)w * h > INT32_MAX)
         return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: w and h must be >= 1, with w + 2 and h + 2 < 2^23 (the 24-bit addressing limit) and w * h <= 2^31-1");
@@ -1368,20 +1382,13 @@ extern "C" int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t 
 
 extern "C" int tsar_cloud_render(int device, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p,
                                  float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem) {
-    tsar_ctx* ctx = nullptr;
-    const int rc0 = tsar_create(device, &ctx);
-    if (rc0 != TSAR_OK) return rc0;
-    const int rc = tsar_cloud_render_ctx(ctx, cloud, n, stride, cam, w, h, p, depth_out, count_out, index_out, n_splats_out, mem);
-    tsar_destroy(ctx);
-    return rc;
+    return with_own_ctx(device, [&](tsar_ctx* ctx) { return tsar_cloud_render_ctx(ctx, cloud, n, stride, cam, w, h, p, depth_out, count_out, index_out, n_splats_out, mem); });
 }
 
 extern "C" int tsar_depth_compare_ctx(tsar_ctx* ctx, const float* depth, const float* gt, const uint8_t* mask, int64_t n, int n_tol, const float* tol, int64_t* n_gt_out,
                                       int64_t* n_both_out, int64_t* within_out, int64_t* n_front_out, int64_t* n_behind_out, float* error_out, int mem) {
     CHECK_CTX(ctx);
-    if (mem != TSAR_MEM_HOST && mem != TSAR_MEM_DEVICE) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: mem must be TSAR_MEM_HOST or TSAR_MEM_DEVICE");
-    if (n < 0 || n > INT32_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: n must be in 0..2^31-1");
-    if (n > 0 && (!depth || !gt)) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: depth or gt is NULL");
+    TRY(check_clouds(ctx, "tsar_depth_compare", mem, {{depth, n, 3}, {gt, n, 3}}, "n", "", "depth or gt"));      // (maps: no stride to check)
     if (n_tol < 1 || n_tol > TSAR_DEPTH_COMPARE_MAX_TOL || !tol) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: n_tol must be in 1..16, and tol not NULL");
     for (int k = 0; k < n_tol; k++)
         if (!(tol[k] >= 0.0f && tol[k] <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_depth_compare: every tolerance must be finite and >= 0");
@@ -1403,12 +1410,9 @@ extern "C" int tsar_depth_compare_ctx(tsar_ctx* ctx, const float* depth, const f
 
 extern "C" int tsar_depth_compare(int device, const float* depth, const float* gt, const uint8_t* mask, int64_t n, int n_tol, const float* tol, int64_t* n_gt_out,
                                   int64_t* n_both_out, int64_t* within_out, int64_t* n_front_out, int64_t* n_behind_out, float* error_out, int mem) {
-    tsar_ctx* ctx = nullptr;
-    const int rc0 = tsar_create(device, &ctx);
-    if (rc0 != TSAR_OK) return rc0;
-    const int rc = tsar_depth_compare_ctx(ctx, depth, gt, mask, n, n_tol, tol, n_gt_out, n_both_out, within_out, n_front_out, n_behind_out, error_out, mem);
-    tsar_destroy(ctx);
-    return rc;
+    return with_own_ctx(device, [&](tsar_ctx* ctx) {
+        return tsar_depth_compare_ctx(ctx, depth, gt, mask, n, n_tol, tol, n_gt_out, n_both_out, within_out, n_front_out, n_behind_out, error_out, mem);
+    });
 }
 
 extern "C" int tsar_depth_to_plane(tsar_ctx* ctx) {
