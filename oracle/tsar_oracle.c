@@ -304,6 +304,17 @@ void orc_derive_cameras(orc_state *s, int n_views, const float *K, const float *
 
 /* ------------------------------------------------------------------------------------------ */
 /* geometry helpers                                                                            */
+/* -v through the sign bit.  Written as `-fmaf(a, b, c)` the compiler may emit ONE fused negate-multiply-subtract, (-a b) - c, which
+ * differs from -(a b + c) in the sign of an exact zero (a b = +0, c = -0: -(+0) = -0, but (-0) - (-0) = +0).  A plane offset of
+ * exactly +-0 (a plane through a point at depth 0: the weighted median filter at a tap whose lines->depth is infinite) then gives
+ * a depth of -+0 and a disparity of -+inf, and inf - inf against inf + inf decides a pixel's reliability. */
+static inline float neg_exact(float v) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    u ^= 0x80000000u;
+    memcpy(&v, &u, 4);
+    return v;
+}
 /* getD_cu gipuma.cu:71-86 */
 static inline float getD(const float *n, int x, int y, float depth, const orc_camera *cm) {
     float pt[3], X[3];
@@ -311,7 +322,7 @@ static inline float getD(const float *n, int x, int y, float depth, const orc_ca
     pt[1] = depth * (float)y - cm->P34[1];
     pt[2] = depth - cm->P34[2];
     mat3vec(cm->Minv, pt, X);
-    return -dot3f(n, X);
+    return neg_exact(dot3f(n, X));
 }
 /* getDepthFromPlane3_cu / getDisparity_cu gipuma.cu:436-453 */
 static inline float depth_from_plane(const orc_camera *cm, const float *n4, int x, int y) {
