@@ -9,7 +9,15 @@ tap by ~1e-4 pixel and a cost by ~1e-5, three hundred times less than the margin
 
     python tools/prune_bound_census.py [--width 768 --height 512 --views 10 --waves 600 --iters 1,2,4,8]
 
-prints one JSON line per (state, step).  tests/test_prune_bound_cpu.py imports the functions below."""
+prints one JSON line per (state, step).
+
+    python tools/prune_bound_census.py --adversarial [--windows 20000]
+
+holds the same restatement to synthetic windows chosen to sit at the rounding allowances (bright, low-variance, binary, nearly
+weightless and uniform references; sources whose first lines say nothing of the rest, noisy copies, inverted halves, unrelated ones)
+and prints one JSON line per (class, mode): eligible windows, windows proven at cost_now = 0.02, false proofs with cost_now just
+above the window's own cost, the largest |fp32 - float64| cost.  tests/test_prune_bound_cpu.py and
+tests/test_prune_bound_adversarial_cpu.py import the functions below."""
 import argparse
 import json
 import os
@@ -30,17 +38,17 @@ def fma(a, b, c):
     return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f32)
 
 
-def reference_window(img, xs, ys):
-    """weights and reference texels of the box-11 window of pixels (xs, ys), [N, row, tap along x], and the hoisted PixelRef terms
-    (hoist_reference: summed column by column)"""
-    h, w = img.shape
-    yy = np.clip(ys[:, None, None] + OFFS[None, :, None], 0, h - 1)
-    xx = np.clip(xs[:, None, None] + OFFS[None, None, :], 0, w - 1)
-    r = img[yy, xx].astype(f32)
-    cen = img[ys, xs].astype(f32)[:, None, None]
+def window_weights(r, cen):
+    """the kernel's tap weights exp(-sd / 50 - |r - centre| / 18) of box-11 windows r [N, row, tap along x] with centre texels cen [N]"""
     sd = np.sqrt((OFFS[None, :, None] ** 2 + OFFS[None, None, :] ** 2).astype(f32))
-    wt = np.exp(-sd / f32(50.0) - np.abs(r - cen) / f32(18.0)).astype(f32)
-    s_r = np.zeros(len(xs), f32); s_rr = np.zeros(len(xs), f32); s_w = np.zeros(len(xs), f32)
+    return np.exp(-sd / f32(50.0) - np.abs(r - cen[:, None, None]) / f32(18.0)).astype(f32)
+
+
+def hoisted_terms(wt, r):
+    """the hoisted PixelRef terms of windows with weights wt and reference texels r (hoist_reference: summed column by column):
+    inv_wsum, mean_ref, var_ref"""
+    n = wt.shape[0]
+    s_r = np.zeros(n, f32); s_rr = np.zeros(n, f32); s_w = np.zeros(n, f32)
     for i in range(6):            # column
         for j in range(6):        # row
             wr = wt[:, j, i] * r[:, j, i]
@@ -50,6 +58,24 @@ def reference_window(img, xs, ys):
     inv_wsum = f32(1.0) / s_w
     mean = s_r * inv_wsum
     var_ref = s_rr * inv_wsum - mean * mean
+    return inv_wsum, mean, var_ref
+
+
+def reference_window_mean(img, xs, ys):
+    """weights and reference texels of the box-11 window of pixels (xs, ys), [N, row, tap along x], and the hoisted PixelRef terms
+    inv_wsum, mean_ref, var_ref"""
+    h, w = img.shape
+    yy = np.clip(ys[:, None, None] + OFFS[None, :, None], 0, h - 1)
+    xx = np.clip(xs[:, None, None] + OFFS[None, None, :], 0, w - 1)
+    r = img[yy, xx].astype(f32)
+    wt = window_weights(r, img[ys, xs].astype(f32))
+    inv_wsum, mean, var_ref = hoisted_terms(wt, r)
+    return wt, r, inv_wsum, mean, var_ref
+
+
+def reference_window(img, xs, ys):
+    """reference_window_mean without the mean: wt, r, inv_wsum, var_ref"""
+    wt, r, inv_wsum, _, var_ref = reference_window_mean(img, xs, ys)
     return wt, r, inv_wsum, var_ref
 
 
@@ -116,6 +142,120 @@ def proven_after_lines(wt, r, s, inv_wsum, var_ref, cost_now):
             rhs = (fma(tt, tt, -SLACK) * (one - E_FULL * (one / vr))) * (one - E_FULL * (one / vs))
             out.append((cost_now < one) & (vr >= f32(2.0) * E_FULL) & (vs >= f32(2.0) * E_FULL) & (lhs <= rhs))
     return np.stack(out, axis=1)
+
+
+MAXCOST = f32(2.0)
+
+
+def full_window_cost(wt, r, s, inv_wsum, mean_ref, var_ref):
+    """the fast arithmetic's cost of the whole window: tap_accumulate<false> over rows of six, then ncc_cost's tail with the correctly
+    rounded root (sqrt_rsq_exact is one); MAXCOST below the variance thresholds"""
+    n = wt.shape[0]
+    src, src_src, ref_src = np.zeros(n, f32), np.zeros(n, f32), np.zeros(n, f32)
+    for line in range(6):
+        for j in range(6):
+            ws = wt[:, line, j] * s[:, line, j]
+            src = src + ws
+            src_src = fma(ws, s[:, line, j], src_src)
+            ref_src = fma(ws, r[:, line, j], ref_src)
+    src, src_src, ref_src = src * inv_wsum, src_src * inv_wsum, ref_src * inv_wsum
+    var_src = src_src - src * src
+    covar = ref_src - mean_ref * src
+    with np.errstate(all="ignore"):
+        vrs = np.sqrt(var_ref * var_src).astype(f32)
+        cost = np.maximum(f32(0.0), np.minimum(MAXCOST, f32(1.0) - covar / vrs)).astype(f32)
+    return np.where((var_ref < f32(1e-5)) | (var_src < f32(1e-5)), MAXCOST, cost).astype(f32)
+
+
+def float64_window_cost(wt, r, s):
+    """1 - weighted NCC of the same weights, texels and samples in float64 throughout (centred sums); NaN without variance"""
+    w_, r_, s_ = (np.asarray(a, np.float64).reshape(len(wt), -1) for a in (wt, r, s))
+    W = w_.sum(axis=1, keepdims=True)
+    dr, ds = r_ - (w_ * r_).sum(axis=1, keepdims=True) / W, s_ - (w_ * s_).sum(axis=1, keepdims=True) / W
+    with np.errstate(all="ignore"):
+        return 1.0 - (w_ * dr * ds).sum(axis=1) / np.sqrt((w_ * dr * dr).sum(axis=1) * (w_ * ds * ds).sum(axis=1))
+
+
+# ---- adversarial windows: synthetic box-11 windows near the rounding allowances, where natural texture never goes -------------------
+REF_CLASSES = ("bright", "lowvar", "binary", "lonely", "uniform")
+SRC_MODES = ("tail", "noisy", "anti", "random")
+COST_NOW_STEPS = (None, 3e-5, 1e-4, 1e-3, 1e-2)        # cost_now = nextafter(c) and c + each of these
+
+
+def adversarial_reference(rng, n, cls):
+    """n reference windows of class cls: texels [n, row, tap along x] and the centre texel [n] (not one of the 36 taps), 8-bit values.
+    bright: 246..255 (the largest sums, the smallest variances beside them).  lowvar: a base value plus 0..5, var_ref on both sides
+    of the variance gate (var_ref - E_FULL >= 2 E_FULL).  binary: 0 or 255 (the largest variance; half the weights ~1e-6).  lonely: 0..39 under a centre of 255, every weight
+    ~1e-6.  uniform: 0..255."""
+    shape = (n, 7, 6)                                                           # the 36 taps and, in [:, 6, 0], the centre
+    if cls == "bright":
+        t = rng.integers(246, 256, shape)
+    elif cls == "lowvar":
+        t = rng.integers(0, 250, (n, 1, 1)) + rng.integers(0, 6, shape)
+    elif cls == "binary":
+        t = 255 * rng.integers(0, 2, shape)
+    elif cls == "lonely":
+        t = rng.integers(0, 40, shape)
+        t[:, 6, 0] = 255
+    elif cls == "uniform":
+        t = rng.integers(0, 256, shape)
+    else:
+        raise ValueError(cls)
+    return t[:, :6].astype(f32), t[:, 6, 0].astype(f32)
+
+
+def adversarial_source(rng, n, mode, r, cls):
+    """source samples [n, row, tap along x] for the reference windows r of class cls.  tail: the first 2 to 4 lines are an unrelated
+    window of the class, the rest equals the reference (the partial window says nothing of the whole; the bound is tightest here).
+    noisy: the reference plus Gaussian noise of sigma 0.2 to 3, kept in 0..255 (costs of 1e-4 .. 1e-1, fractional samples).  anti:
+    the first three lines are 255 - r.  random: an unrelated window of the class."""
+    other = adversarial_reference(rng, n, cls)[0]
+    if mode == "tail":
+        lines = rng.integers(2, 5, n)
+        return np.where(np.arange(6)[None, :, None] < lines[:, None, None], other, r).astype(f32)
+    if mode == "noisy":
+        sigma = rng.uniform(0.2, 3.0, (n, 1, 1))
+        return np.clip(r + sigma * rng.standard_normal(r.shape), 0.0, 255.0).astype(f32)
+    if mode == "anti":
+        return np.where(np.arange(6)[None, :, None] < 3, f32(255.0) - r, r).astype(f32)
+    if mode == "random":
+        return other
+    raise ValueError(mode)
+
+
+def cost_now_values(cost):
+    """the five costs a lane is tried with: the next float above the window's cost, and the cost plus 3e-5 .. 1e-2"""
+    return [np.nextafter(cost, f32(np.inf)) if d is None else (cost + f32(d)).astype(f32) for d in COST_NOW_STEPS]
+
+
+def adversarial_census(cls, mode, n, rng, inv_wsum_scale=1.0):
+    """n windows of (cls, mode): the fast arithmetic's cost of each whole window, and prune_proven's verdicts with cost_now just above
+    it.  A proven verdict of an eligible window (var_ref >= 1e-5, cost < 1) is a false proof: the kernel would leave a view that
+    scores below the lane's cost.  inv_wsum_scale mis-scales the check's inv_wsum alone (a mutation for the tests)."""
+    r, cen = adversarial_reference(rng, n, cls)
+    wt = window_weights(r, cen)
+    inv_wsum, mean_ref, var_ref = hoisted_terms(wt, r)
+    s = adversarial_source(rng, n, mode, r, cls)
+    cost = full_window_cost(wt, r, s, inv_wsum, mean_ref, var_ref)
+    eligible = (var_ref >= f32(1e-5)) & (cost < f32(1.0))
+    check_inv = (inv_wsum * f32(inv_wsum_scale)).astype(f32)
+    verdicts = np.stack([proven_after_lines(wt, r, s, check_inv, var_ref, cn) for cn in cost_now_values(cost)], axis=1)   # [n, 5, checks]
+    power = proven_after_lines(wt, r, s, check_inv, var_ref, np.full(n, 0.02, f32))
+    with np.errstate(all="ignore"):
+        err = np.abs(cost.astype(np.float64) - float64_window_cost(wt, r, s))
+    err = err[eligible & (cost > 0) & np.isfinite(err)]                         # (a cost clamped at 0 says nothing of the rounding)
+    return {"n": n, "eligible": eligible, "verdicts": verdicts, "false": verdicts & eligible[:, None, None], "power": power,
+            "cost": cost, "var_ref": var_ref, "max_err": float(err.max()) if err.size else 0.0}
+
+
+def adversarial_main(n):
+    for cls in REF_CLASSES:
+        for mode in SRC_MODES:
+            c = adversarial_census(cls, mode, n, np.random.default_rng(1))
+            print(json.dumps({"class": cls, "mode": mode, "windows": n, "eligible": int(c["eligible"].sum()),
+                              "proven_at_0.02": int(c["power"].any(axis=1).sum()), "falsely_proven": int(c["false"].sum()),
+                              "verdicts": int(c["verdicts"].size), "max_abs_fp32_minus_float64": float("%.3g" % c["max_err"]),
+                              "var_ref_p1": round(float(np.percentile(c["var_ref"], 1)), 2)}), flush=True)
 
 
 def draw_hypotheses(orc, sc, xs, ys, step, rng):
@@ -185,7 +325,11 @@ def main():
     ap.add_argument("--width", type=int, default=768); ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--views", type=int, default=10); ap.add_argument("--waves", type=int, default=600)
     ap.add_argument("--iters", default="1,2,4,8"); ap.add_argument("--steps", default="0,1,2")
+    ap.add_argument("--adversarial", action="store_true", help="the synthetic window classes instead of a scene: one line per (class, mode)")
+    ap.add_argument("--windows", type=int, default=20000, help="windows per (class, mode) with --adversarial")
     args = ap.parse_args()
+    if args.adversarial:
+        return adversarial_main(args.windows)
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     import oracle_lib as ol
     from tsar_mvs_amd import synth
