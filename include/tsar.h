@@ -44,6 +44,7 @@
  *   (none: the reference ships no evaluation)            tsar_cloud_distance
  *   (none: the reference's fuser thins nothing)          tsar_cloud_voxels
  *   (none: the reference's fuser cleans nothing)         tsar_cloud_neighbors
+ *   (none: the reference estimates no cloud normals)     tsar_cloud_normals / tsar_cloud_normal_compare
  *   (none: the reference renders no cloud)               tsar_cloud_render / tsar_depth_compare
  *
  * Conventions
@@ -685,6 +686,84 @@ int tsar_cloud_neighbors_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int s
                              int64_t* n_valid_out, int64_t* pairs_out /* host, may be NULL */, int mem);
 int tsar_cloud_neighbors(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_neighbors_params* p, int32_t* count_out,
                          float* knn_dist2_out, int64_t* n_valid_out, int64_t* pairs_out, int mem);
+
+/* ---- normals of a cloud (a scan has none: this gives a reconstruction's normals something to be judged against) -------------------- */
+/* tsar_cloud_normals: per point of one cloud the indices of its k nearest neighbours within a radius R, and the PCA normal and surface
+ * variation of that neighbourhood.  Records are `stride` float32 each (>= 3), x y z first.  `mem` names where cloud and the five per-point
+ * outputs lie; n_valid_out, n_normals_out and pairs_out are host memory.  Every output may be NULL.  The arithmetic, the same in both
+ * arithmetic modes: every operation one IEEE-754 operation rounded to nearest, no fused multiply-add; float64 `/` and sqrt correctly
+ * rounded.
+ * Neighbours (float32):
+ *   candidate, d2(i, j) and R2 = fl(R * R): those of tsar_cloud_neighbors
+ *   point i's neighbour list = the candidates j != i with d2(i, j) <= R2, ordered by the 64-bit code bits(d2) << 32 | j (the smallest d2
+ *     first, then the smallest index), cut at k.  m = its length.  The point itself is excluded by its index: a duplicate counts
+ *   knn_index[i][s] = the s-th j for s < m, -1 from m on;  n_used[i] = m.  A record that is no candidate: n_used -1, every index -1
+ * Moments (float64, relative to the point, in list order s = 0 .. m - 1):
+ *   u = (double)p_j - (double)p_i per axis;  S_a += u_a;  Q_ab += u_a * u_b (one product, one sum), both from 0
+ *   M = (double)(m + 1): the point itself is part of its neighbourhood, with u = 0
+ *   mu_a = S_a / M;  C_ab = Q_ab / M - mu_a * mu_b;  cov = C_xx C_xy C_xz C_yy C_yz C_zz
+ * Eigenvectors (float64): cyclic Jacobi on a = C, V = I, exactly 6 sweeps; a sweep is the rotations (p, q, r) = (0, 1, 2), (0, 2, 1),
+ * (1, 2, 0); a rotation is skipped iff a_pq == 0, otherwise
+ *   theta = (a_qq - a_pp) / (2 * a_pq);  t = (theta < 0 ? -1 : 1) / (|theta| + sqrt(theta * theta + 1));  c = 1 / sqrt(t * t + 1);  s = t * c
+ *   h = t * a_pq;  a_pp = a_pp - h;  a_qq = a_qq + h;  a_pq = 0
+ *   (a_rp, a_rq) <- (c * a_rp - s * a_rq, s * a_rp + c * a_rq);  for each row k of V: (v_kp, v_kq) <- (c * v_kp - s * v_kq, s * v_kp + c * v_kq)
+ *   lambda0 = the smallest diagonal entry of a, the lowest index on ties;  v = that column of V
+ * Orientation: first the canonical sign: if the component of v with the largest magnitude (the lowest index on ties) is < 0, v = -v.
+ *   orient 1: w = (double)viewpoint - (double)p_i;  d = (v_x * w_x + v_y * w_y) + v_z * w_z;  v = -v iff d < 0
+ *   orient 2: the same with w = the record's floats 3 .. 5 widened (its own normal); a NaN d leaves the canonical sign
+ *   normal = (float)v per component, not renormalised
+ * Curvature (surface variation): sum = (a_00 + a_11) + a_22;  curvature = (float)((lambda0 > 0 ? lambda0 : 0) / sum) if sum > 0, else 0
+ * No normal: a record that is no candidate, or a point with m < min_neighbors: normal 0 0 0, curvature -1, cov 0 (knn_index and n_used are
+ * still the list's).  n_normals = the number of points that have a normal; n_valid = the number of candidates; pairs as tsar_cloud_neighbors.
+ * An order statistic of bit-defined codes, sums in list order and a fixed number of rotations: no output depends on an order of arrival,
+ * and every run gives the same bits.  The pairs are found as in tsar_cloud_neighbors (the grid, the 27 cells).
+ * TSAR_ERR_INVALID, with the reason in tsar_last_error: tsar_cloud_neighbors' refusals (p NULL; mem unknown; a stride below 3; n negative or
+ * above 2^31 - 1; radius; max_pairs negative; 2^20 cells or more on an axis; more than max_pairs pairs, with *pairs_out still filled and
+ * nothing else written); k outside 3 .. TSAR_CLOUD_KNN_MAX; min_neighbors outside 2 .. k; orient outside 0 .. 2; orient 2 with a stride
+ * below 6; orient 1 with a viewpoint that is not finite.
+ * tsar_cloud_normals_ctx needs no views and no state, runs on the context's stream and changes nothing in the context; its temporaries are
+ * pieces of the call's frame that never grow the context's scratch arena.  tsar_cloud_normals is the context-free form.  Timed as
+ * "cloud_bounds", "cloud_keys", "cloud_sort", "cloud_gather", "cloud_pairs" and "cloud_normals" (search, moments and Jacobi in one kernel,
+ * and the pass that marks the records that are no candidates).
+ * This is the plain PCA normal over the k nearest neighbours within R: no orientation is propagated across the cloud, nothing is meshed. */
+typedef struct tsar_cloud_normals_params {
+    float radius;          /* R: finite, fl(R * R) finite and > 0.  No default (0): the caller's scale */
+    int32_t k;             /* 3 .. TSAR_CLOUD_KNN_MAX: the neighbours used at most; default 16 */
+    int32_t min_neighbors; /* 2 .. k: a point with fewer neighbours within R gets no normal; default 5 */
+    int32_t orient;        /* 0 the canonical sign (default), 1 towards viewpoint, 2 along the record's own normal (floats 3 .. 5; stride >= 6) */
+    float viewpoint[3];    /* read with orient 1 */
+    int64_t max_pairs;     /* as tsar_cloud_neighbors; default 1 << 40 */
+} tsar_cloud_normals_params;
+void tsar_default_cloud_normals_params(tsar_cloud_normals_params* p);
+int tsar_cloud_normals_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_normals_params* p,
+                           int32_t* knn_index_out /* [n][k] or NULL */, int32_t* n_used_out /* [n] or NULL */, float* normal_out /* [n][3] or NULL */,
+                           float* curvature_out /* [n] or NULL */, double* cov_out /* [n][6] or NULL */, int64_t* n_valid_out,
+                           int64_t* n_normals_out, int64_t* pairs_out /* host, may be NULL */, int mem);
+int tsar_cloud_normals(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_normals_params* p, int32_t* knn_index_out,
+                       int32_t* n_used_out, float* normal_out, float* curvature_out, double* cov_out, int64_t* n_valid_out,
+                       int64_t* n_normals_out, int64_t* pairs_out, int mem);
+
+/* tsar_cloud_normal_compare: the agreement of the normals of cloud a with those of cloud b, as integer counts.  normal_a: n rows of stride_a
+ * float32 (>= 3), the normal first; normal_b: n_b rows of stride_b; index [n] int32: per row of a the row of b it is compared with, or -1
+ * (tsar_cloud_distance's index_out); dist2 [n] float32 or NULL, with max_dist.  These and cos_out lie in `mem`; min_cos (n_tol thresholds,
+ * 0 .. 16, each in [-1, 1]) and the int64 outputs are host memory.  Row i is compared iff
+ *   0 <= index[i] < n_b;  dist2 is NULL or dist2[i] <= fl(max_dist * max_dist) (one float32 product; NaN fails);  all six components finite;
+ *   aa = (a_x * a_x + a_y * a_y) + a_z * a_z > 0 and bb likewise, in float64 on the widened floats
+ * and then c = ((a_x * b_x + a_y * b_y) + a_z * b_z) / sqrt(aa * bb) in float64, c = |c| unless is_signed.
+ *   cos_out[i] = (float)c, NaN for a row that is not compared;  within[k] = the compared rows with c >= min_cos[k];  n_compared
+ * No angle is formed: a caller turns degrees into min_cos with one host cos.  Integer sums: the same in every run.
+ * TSAR_ERR_INVALID: mem unknown; n or n_b negative or above 2^31 - 1; a stride below 3; normal_a or index NULL with n > 0, normal_b NULL with
+ * n_b > 0; n_tol outside 0 .. 16, or min_cos NULL with n_tol > 0; a threshold outside [-1, 1]; with dist2, max_dist not finite or
+ * fl(max_dist * max_dist) not finite or not > 0.  The _ctx form needs no views and no state and changes nothing in the context; timed as
+ * "cloud_normal_compare". */
+#define TSAR_NORMAL_COMPARE_MAX_TOL 16
+int tsar_cloud_normal_compare_ctx(tsar_ctx* ctx, const float* normal_a, int stride_a, int64_t n, const float* normal_b, int stride_b, int64_t n_b,
+                                  const int32_t* index, const float* dist2 /* [n] or NULL */, float max_dist, int n_tol,
+                                  const double* min_cos /* host */, int is_signed, float* cos_out /* [n] or NULL */,
+                                  int64_t* within_out /* host [n_tol] or NULL */, int64_t* n_compared_out /* host, may be NULL */, int mem);
+int tsar_cloud_normal_compare(int device, const float* normal_a, int stride_a, int64_t n, const float* normal_b, int stride_b, int64_t n_b,
+                              const int32_t* index, const float* dist2, float max_dist, int n_tol, const double* min_cos, int is_signed,
+                              float* cos_out, int64_t* within_out, int64_t* n_compared_out, int mem);
 
 /* ---- a cloud rendered into a camera, and a depth map scored against such a map ------------------------------------------------------- */
 /* tsar_cloud_render: a point cloud (a scan, a fused cloud) rendered into one calibrated view as a depth map, occlusion by the cloud's own

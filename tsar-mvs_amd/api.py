@@ -83,6 +83,10 @@ class CloudNeighborsParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("k", C.c_int32), ("max_pairs", C.c_int64)]
 
 
+class CloudNormalsParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("k", C.c_int32), ("min_neighbors", C.c_int32), ("orient", C.c_int32), ("viewpoint", C.c_float * 3), ("max_pairs", C.c_int64)]
+
+
 class CloudRenderParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("max_px", C.c_int32), ("occlusion_diff", C.c_float), ("depth_diff", C.c_float), ("min_points", C.c_int32),
                 ("max_splats", C.c_int64)]
@@ -103,6 +107,8 @@ _FUSE = (_I, [_I, _I, _I, _I, _p(Camera), _p(_P), _p(_P), _p(_P), _I, _P, _P, _p
 _CLOUD_DISTANCE = (_I, [_I, _P, _L, _I, _P, _L, _I, _p(CloudDistanceParams), _I, _P, _P, _P, _P, _p(_L), _p(_L), _I])
 _CLOUD_VOXELS = (_I, [_I, _P, _L, _I, _p(CloudVoxelsParams), _P, _I, _P, _P, _L, _P, _P, _P, _p(_L), _p(_L), _I])
 _CLOUD_NEIGHBORS = (_I, [_I, _P, _L, _I, _p(CloudNeighborsParams), _P, _P, _p(_L), _p(_L), _I])
+_CLOUD_NORMALS = (_I, [_I, _P, _L, _I, _p(CloudNormalsParams), _P, _P, _P, _P, _P, _p(_L), _p(_L), _p(_L), _I])
+_CLOUD_NORMAL_COMPARE = (_I, [_I, _P, _I, _L, _P, _I, _L, _P, _P, _F, _I, _P, _I, _P, _P, _p(_L), _I])
 
 _CLOUD_RENDER = (_I, [_I, _P, _L, _I, _p(Camera), _I, _I, _p(CloudRenderParams), _P, _P, _P, _p(_L), _I])
 _DEPTH_COMPARE = (_I, [_I, _P, _P, _P, _L, _I, _P, _p(_L), _p(_L), _P, _p(_L), _p(_L), _P, _I])
@@ -185,6 +191,11 @@ _ABI = {
     "tsar_default_cloud_neighbors_params": (None, [_p(CloudNeighborsParams)]),
     "tsar_cloud_neighbors_ctx": _on_ctx(_CLOUD_NEIGHBORS),
     "tsar_cloud_neighbors": _CLOUD_NEIGHBORS,
+    "tsar_default_cloud_normals_params": (None, [_p(CloudNormalsParams)]),
+    "tsar_cloud_normals_ctx": _on_ctx(_CLOUD_NORMALS),
+    "tsar_cloud_normals": _CLOUD_NORMALS,
+    "tsar_cloud_normal_compare_ctx": _on_ctx(_CLOUD_NORMAL_COMPARE),
+    "tsar_cloud_normal_compare": _CLOUD_NORMAL_COMPARE,
     "tsar_default_cloud_render_params": (None, [_p(CloudRenderParams)]),
     "tsar_cloud_render_ctx": _on_ctx(_CLOUD_RENDER),
     "tsar_cloud_render": _CLOUD_RENDER,
@@ -1097,6 +1108,91 @@ def cloud_neighbors(cloud, radius, k=0, want=("count", "knn_dist2"), max_pairs=N
     return res
 
 
+_ORIENT = {None: 0, "viewpoint": 1, "record": 2}
+
+
+def cloud_normals(cloud, radius, k=16, min_neighbors=5, orient=None, viewpoint=None, want=("normal", "curvature"), max_pairs=None, matcher=None, device=0):
+    """Per point of `cloud` its k nearest neighbours within `radius` and the PCA normal and surface variation of that neighbourhood
+    (tsar_cloud_normals_ctx; include/tsar.h states the arithmetic).  cloud: [n, c >= 3] float32, x y z first, a numpy array or a torch
+    device tensor (a fused cloud as api.fuse returns it goes in as it is); records with a non-finite coordinate take no part.  k: 3 .. 32;
+    a point with fewer than min_neighbors (2 .. k) neighbours within radius gets no normal.  orient: None = the canonical sign (the
+    component of largest magnitude is positive), "viewpoint" = towards `viewpoint` (three finite numbers), "record" = along the record's
+    own normal, floats 3 .. 5 (c >= 6).  max_pairs, matcher / device: as cloud_neighbors.
+    This is the plain PCA normal: no orientation is propagated across the cloud and nothing is meshed.
+    Returns a dict: "normal" ([n, 3] float32, 0 0 0 without a normal), "curvature" ([n] float32, -1 without), "knn_index" ([n, k] int32,
+    nearest first, -1 padded), "n_used" ([n] int32: the neighbours used, -1 for a non-candidate), "cov" ([n, 6] float64: xx xy xz yy yz zz),
+    as `want` names them (numpy arrays, or torch tensors on the cloud's device); the integers "n_valid", "n_normals" and "pairs"."""
+    L = load_library()
+    c, dev = _cloud(cloud, "cloud")
+    n, k = int(c.shape[0]), int(k)
+    assert orient in _ORIENT, "orient must be None, \"viewpoint\" or \"record\""
+    assert (orient == "viewpoint") == (viewpoint is not None), "viewpoint goes with orient=\"viewpoint\""
+    p = CloudNormalsParams()
+    L.tsar_default_cloud_normals_params(C.byref(p))
+    p.radius, p.k, p.min_neighbors, p.orient = float(radius), k, int(min_neighbors), _ORIENT[orient]
+    if viewpoint is not None:
+        p.viewpoint[:] = [float(v) for v in np.asarray(viewpoint, np.float32).reshape(3)]
+    if max_pairs is not None:
+        p.max_pairs = int(max_pairs)
+    spec = {"knn_index": ((n, max(k, 0)), np.int32), "n_used": ((n,), np.int32), "normal": ((n, 3), np.float32), "curvature": ((n,), np.float32),
+            "cov": ((n, 6), np.float64)}
+    res = _outputs(spec, want, c.device if dev else None)
+    n_valid, n_normals, pairs = C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+    with _matcher_for(matcher, device, c) as m:
+        rc = L.tsar_cloud_normals_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), C.byref(p), *(_ptr(res.get(key))[0] for key in spec), C.byref(n_valid),
+                                      C.byref(n_normals), C.byref(pairs), MEM_DEVICE if dev else MEM_HOST)
+        if rc != TSAR_OK:
+            raise _error_with_pairs(rc, L, m, pairs)
+    res["n_valid"] = int(n_valid.value)
+    res["n_normals"] = int(n_normals.value)
+    res["pairs"] = int(pairs.value)
+    return res
+
+
+def min_cos_of(tolerances_deg):
+    """the thresholds tsar_cloud_normal_compare takes for angles in degrees: one float64 cos each"""
+    return np.cos(np.deg2rad(np.ascontiguousarray(tolerances_deg, np.float64).reshape(-1)))
+
+
+def normal_compare(normal_a, normal_b, index, tolerances_deg, dist2=None, max_dist=None, signed=False, want_cos=False, matcher=None, device=0):
+    """The normals of cloud a scored against those of cloud b (tsar_cloud_normal_compare_ctx; include/tsar.h).  normal_a: [n, c >= 3] float32,
+    the normal in the first three columns; normal_b: [n_b, c >= 3]; index: [n] int32, per row of a the row of b to compare with or -1
+    (cloud_distance's "index"); dist2 ([n] float32) with max_dist: only rows with dist2 <= fl(max_dist * max_dist) are compared.  All numpy
+    arrays or all torch tensors on one device.  tolerances_deg: up to 16 angles in degrees, each turned into a threshold with one float64 cos.
+    A row is compared iff its index names a row of b, its dist2 passes, and both normals are finite and not zero; signed=False compares
+    lines (|cos|), signed=True directions.
+    Returns a dict: "n_compared"; "within" (int64 array: per tolerance the compared rows whose angle is within it); "tolerances_deg"; "min_cos";
+    "accuracy" (float64: within / n_compared, 0 where nothing is compared); with want_cos "cos" ([n] float32, NaN where not compared)."""
+    L = load_library()
+    a, dev = _cloud(normal_a, "normal_a")
+    b, b_dev = _cloud(normal_b, "normal_b")
+    n = int(a.shape[0])
+    assert dev == b_dev and (not dev or a.device == b.device), "normal_a and normal_b must live in the same memory space"
+    assert (dist2 is None) == (max_dist is None), "dist2 and max_dist go together"
+    side = lambda x: x.cpu() if _is_torch(x) and not dev else x
+    idx = _coerce(side(index), np.int32, (n,), "index", tensors="device")
+    d2 = _coerce(side(dist2), np.float32, (n,), "dist2", tensors="device")
+    for x, name in ((idx, "index"), (d2, "dist2")):
+        assert x is None or not dev or (_is_torch(x) and x.device == a.device and x.is_contiguous()), name + " must be a contiguous tensor on the normals' device"
+    deg = np.ascontiguousarray(tolerances_deg, np.float64).reshape(-1)
+    mc = min_cos_of(deg)
+    within = np.zeros(len(mc), np.int64)
+    out = _outputs({"cos": ((n,), np.float32)}, ("cos",) if want_cos else (), a.device if dev else None)
+    n_cmp = C.c_int64(0)
+    with _matcher_for(matcher, device, a) as m:
+        rc = L.tsar_cloud_normal_compare_ctx(m._ctx, _ptr(a)[0] if n else None, int(a.shape[1]), n, _ptr(b)[0] if b.shape[0] else None, int(b.shape[1]), int(b.shape[0]),
+                                             _ptr(idx)[0] if n else None, _ptr(d2)[0] if n else None, 0.0 if max_dist is None else float(max_dist), len(mc),
+                                             mc.ctypes.data_as(C.c_void_p), 1 if signed else 0, _ptr(out.get("cos"))[0], within.ctypes.data_as(C.c_void_p), C.byref(n_cmp),
+                                             MEM_DEVICE if dev else MEM_HOST)
+        if rc != TSAR_OK:
+            raise TsarError(rc, L.tsar_last_error(m._ctx).decode())
+    nc = int(n_cmp.value)
+    res = {"n_compared": nc, "within": within, "tolerances_deg": deg, "min_cos": mc,
+           "accuracy": within / np.float64(nc) if nc else np.zeros(len(mc), np.float64)}
+    res.update(out)
+    return res
+
+
 def _outlier_settings(radius, min_neighbors, k, ratio):
     """the settings of remove_outliers as (float, int or None, int or None, float); ValueError on what the tools refuse as well"""
     radius, ratio = float(radius), float(ratio)
@@ -1208,7 +1304,7 @@ def _f1(a, c):
     return np.where(s > 0, 2.0 * a * c / np.where(s > 0, s, 1.0), 0.0)
 
 
-def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, crop=None, clean=None):
+def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, crop=None, clean=None, normals=None):
     """Accuracy and completeness of the cloud `recon` against the cloud `gt` at each of `tolerances`: the point-wise precision / recall /
     F-score.  Two cloud_distance calls with max_dist = max(tolerances):
       accuracy[k]     = the share of recon's candidate points (finite coordinates) with a gt point within tolerances[k];
@@ -1222,6 +1318,10 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
     coordinates become NaN), before anything else is computed.
     clean=dict(radius=, min_neighbors=, k=, ratio=) first removes recon's stray points by remove_outliers' rules (on a copy: the removed
     records' coordinates become NaN), before crop and before any scoring; gt is left as it is.
+    normals=dict(radius=, k=16, min_neighbors=5, tolerances_deg=(10, 30), signed=False) also scores recon's normals (columns 3 .. 5 of its
+    records) against normals estimated from gt's points (cloud_normals with the canonical sign, after crop): one normal_compare of every
+    recon point with the gt point nearest to it within max(tolerances).  The plain PCA normal over the k nearest neighbours within radius:
+    no orientation is propagated and nothing is meshed; with signed=False (the default) lines are compared, not directions.
     This is NOT the evaluation program of a benchmark.  With voxel and crop it averages over voxels and crops to a box in the manner of
     the benchmarks, but ETH3D's program defines its voxels and its observed volume from the scanner's positions, DTU's applies observation
     masks, and both align the clouds first: nothing is registered here, there are no occlusion or observation masks, and the clouds are
@@ -1230,7 +1330,8 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
     counts; 0 where a denominator is 0), {"n_accurate", "n_complete"} as int64 arrays, and the integers "n_recon_valid", "n_gt_valid",
     "pairs_accuracy", "pairs_completeness"; with voxel also "accuracy_voxel", "completeness_voxel", "f1_voxel" (float64 arrays),
     "n_recon_voxels" and "n_gt_voxels"; with crop also "n_recon_cropped" and "n_gt_cropped" (the candidate records outside the box); with clean also "clean" (the settings)
-    and "n_recon_cleaned" (the candidate records of recon removed)."""
+    and "n_recon_cleaned" (the candidate records of recon removed); with normals also "normals" (the settings), "normal_tolerances_deg",
+    "n_gt_normals", "n_normal_compared", "n_normal_within" (int64 array) and "normal_accuracy" (float64 array: within / compared)."""
     tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
     if tol.size == 0:
         raise ValueError("evaluate_cloud needs at least one tolerance")
@@ -1238,7 +1339,7 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
     if clean is not None:
         with _matcher_for(matcher, device, recon) as m:        # one context for the cleaning and the scoring
             recon, n_cleaned, settings = _clean_cloud(recon, dict(clean), m)
-            res = evaluate_cloud(recon, gt, tol, matcher=m, voxel=voxel, crop=crop)
+            res = evaluate_cloud(recon, gt, tol, matcher=m, voxel=voxel, crop=crop, normals=normals)
         res.update({"clean": settings, "n_recon_cleaned": n_cleaned})
         return res
     cropped = None
@@ -1248,11 +1349,26 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
             raise ValueError("crop must be six finite numbers (x0, y0, z0, x1, y1, z1) with x0 <= x1, y0 <= y1, z0 <= z1")
         (recon, n_rc), (gt, n_gc) = _crop_cloud(recon, crop), _crop_cloud(gt, crop)
         cropped = {"n_recon_cropped": n_rc, "n_gt_cropped": n_gc}
-    vox = None
+    vox = nrm = None
+    if normals is not None:
+        normals = dict(normals)
+        settings = {"k": int(normals.pop("k", 16)), "radius": float(normals.pop("radius")), "min_neighbors": int(normals.pop("min_neighbors", 5)),
+                    "signed": bool(normals.pop("signed", False))}
+        deg = np.ascontiguousarray(normals.pop("tolerances_deg", (10.0, 30.0)), np.float64).reshape(-1)
+        if normals:
+            raise ValueError("normals: unknown settings %s" % sorted(normals))
+        if recon.shape[1] < 6:
+            raise ValueError("normals needs recon's normals in columns 3..5 of its records")
     with _matcher_for(matcher, device, recon) as m:            # one context for every call
         want = () if voxel is None else ("dist2",)
-        a = cloud_distance(recon, gt, r, tol, want=want, matcher=m)
+        a = cloud_distance(recon, gt, r, tol, want=want if normals is None else ("dist2", "index"), matcher=m)
         c = cloud_distance(gt, recon, r, tol, want=want, matcher=m)
+        if normals is not None:
+            g = cloud_normals(gt, settings["radius"], settings["k"], settings["min_neighbors"], want=("normal",), matcher=m)
+            rn = recon[:, 3:6].contiguous() if _is_torch(recon) else np.ascontiguousarray(recon[:, 3:6], np.float32)
+            s = normal_compare(rn, g["normal"], a["index"], deg, dist2=a["dist2"], max_dist=r, signed=settings["signed"], matcher=m)
+            nrm = {"normals": settings, "normal_tolerances_deg": deg, "n_gt_normals": g["n_normals"], "n_normal_compared": s["n_compared"],
+                   "n_normal_within": s["within"], "normal_accuracy": s["accuracy"]}
         if voxel is not None:
             va = cloud_voxels(recon, voxel, a["dist2"], tol, want=("count",), matcher=m)
             vc = cloud_voxels(gt, voxel, c["dist2"], tol, want=("count",), matcher=m)
@@ -1268,6 +1384,8 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
         res.update(vox)
     if cropped is not None:
         res.update(cropped)
+    if nrm is not None:
+        res.update(nrm)
     return res
 
 

@@ -1328,6 +1328,90 @@ extern "C" int tsar_cloud_neighbors(int device, const float* cloud, int64_t n, i
     return with_own_ctx(device, [&](tsar_ctx* ctx) { return tsar_cloud_neighbors_ctx(ctx, cloud, n, stride, p, count_out, knn_dist2_out, n_valid_out, pairs_out, mem); });
 }
 
+// ---- normals of a cloud; two sets of normals compared (cloud_normal_kernels.hip) -----------------------------------------------------------
+extern "C" void tsar_default_cloud_normals_params(tsar_cloud_normals_params* p) {
+    if (!p) return;
+    p->radius = 0.0f;                      // no default: the caller's scale
+    p->k = 16;
+    p->min_neighbors = 5;
+    p->orient = 0;
+    p->viewpoint[0] = p->viewpoint[1] = p->viewpoint[2] = 0.0f;
+    p->max_pairs = (int64_t)1 << 40;
+}
+
+// Like tsar_cloud_distance_ctx: no views, no state, nothing of the context written, and a frame that does not grow the arena.
+extern "C" int tsar_cloud_normals_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_cloud_normals_params* p, int32_t* knn_index_out,
+                                      int32_t* n_used_out, float* normal_out, float* curvature_out, double* cov_out, int64_t* n_valid_out, int64_t* n_normals_out,
+                                      int64_t* pairs_out, int mem) {
+    CHECK_CTX(ctx);
+    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: params is NULL");
+    TRY(check_clouds(ctx, "tsar_cloud_normals", mem, {{cloud, n, stride}}));
+    const float R = p->radius;
+    float r2;
+    if (!cloud_radius2(R, &r2))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: radius must be finite and > 0, with radius * radius finite and > 0 in float32");
+    if (p->k < 3 || p->k > TSAR_CLOUD_KNN_MAX) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: k must be in 3..TSAR_CLOUD_KNN_MAX (32)");
+    if (p->min_neighbors < 2 || p->min_neighbors > p->k) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: min_neighbors must be in 2..k");
+    if (p->orient < 0 || p->orient > 2) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: orient must be 0 (canonical), 1 (viewpoint) or 2 (the record's normal)");
+    if (p->orient == 2 && stride < 6) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: orient 2 reads the record's floats 3..5: the stride must be at least 6");
+    if (p->orient == 1 && !(fabsf(p->viewpoint[0]) <= FLT_MAX && fabsf(p->viewpoint[1]) <= FLT_MAX && fabsf(p->viewpoint[2]) <= FLT_MAX))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: orient 1 needs a finite viewpoint");
+    if (p->max_pairs < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normals: max_pairs must be >= 0");
+    CallFrame f(ctx, "tsar_cloud_normals", nullptr, /*grow_arena=*/false);
+    const float* c = f.in(cloud, (size_t)n * stride, mem);
+    int32_t* knn = f.out(knn_index_out, (size_t)n * (size_t)p->k, mem);
+    int32_t* used = f.out(n_used_out, (size_t)n, mem);
+    float* nrm = f.out(normal_out, (size_t)n * 3, mem);
+    float* curv = f.out(curvature_out, (size_t)n, mem);
+    double* cov = f.out(cov_out, (size_t)n * 6, mem);
+    if (!f.ok()) return f.finish();
+    return run_cloud_normals(f, c, n, stride, r2, (double)R * (1.0 + 1.0 / 1024.0), *p, knn, used, nrm, curv, cov, n_valid_out, n_normals_out, pairs_out);
+}
+
+// Context-free form (the evaluation tool's normals of the ground truth).
+extern "C" int tsar_cloud_normals(int device, const float* cloud, int64_t n, int stride, const tsar_cloud_normals_params* p, int32_t* knn_index_out, int32_t* n_used_out,
+                                  float* normal_out, float* curvature_out, double* cov_out, int64_t* n_valid_out, int64_t* n_normals_out, int64_t* pairs_out, int mem) {
+    return with_own_ctx(device, [&](tsar_ctx* ctx) {
+        return tsar_cloud_normals_ctx(ctx, cloud, n, stride, p, knn_index_out, n_used_out, normal_out, curvature_out, cov_out, n_valid_out, n_normals_out, pairs_out, mem);
+    });
+}
+
+extern "C" int tsar_cloud_normal_compare_ctx(tsar_ctx* ctx, const float* normal_a, int stride_a, int64_t n, const float* normal_b, int stride_b, int64_t n_b,
+                                             const int32_t* index, const float* dist2, float max_dist, int n_tol, const double* min_cos, int is_signed, float* cos_out,
+                                             int64_t* within_out, int64_t* n_compared_out, int mem) {
+    CHECK_CTX(ctx);
+    TRY(check_clouds(ctx, "tsar_cloud_normal_compare", mem, {{normal_a, n, stride_a}, {normal_b, n_b, stride_b}}, "n and n_b", "a stride", "normal_a or normal_b"));
+    if (n > 0 && !index) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normal_compare: index is NULL");
+    if (n_tol < 0 || n_tol > TSAR_NORMAL_COMPARE_MAX_TOL || (n_tol > 0 && !min_cos))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normal_compare: n_tol must be in 0..16, and min_cos not NULL with n_tol > 0");
+    for (int k = 0; k < n_tol; k++)
+        if (!(min_cos[k] >= -1.0 && min_cos[k] <= 1.0)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normal_compare: every threshold must be in [-1, 1]");
+    float md2 = 0.0f;
+    if (dist2 && !cloud_radius2(max_dist, &md2))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_normal_compare: with dist2, max_dist must be finite and > 0, with max_dist * max_dist finite and > 0 in float32");
+    CallFrame f(ctx, "tsar_cloud_normal_compare", nullptr, /*grow_arena=*/false);
+    const float* a = f.in(normal_a, (size_t)n * stride_a, mem);
+    const float* b = (normal_b == normal_a && n_b == n && stride_b == stride_a) ? a : f.in(normal_b, (size_t)n_b * stride_b, mem);
+    const int32_t* idx = f.in(index, (size_t)n, mem);
+    const float* d2 = f.in(dist2, (size_t)n, mem);
+    float* co = f.out(cos_out, (size_t)n, mem);
+    if (!f.ok()) return f.finish();
+    unsigned long long counters[1 + TSAR_NORMAL_COMPARE_MAX_TOL] = {0};
+    TRY(run_cloud_normal_compare(f, a, stride_a, n, b, stride_b, n_b, idx, d2, md2, n_tol, min_cos, is_signed, co, counters));
+    if (n_compared_out) *n_compared_out = (int64_t)counters[0];
+    for (int k = 0; k < n_tol && within_out; k++) within_out[k] = (int64_t)counters[1 + k];
+    return TSAR_OK;
+}
+
+extern "C" int tsar_cloud_normal_compare(int device, const float* normal_a, int stride_a, int64_t n, const float* normal_b, int stride_b, int64_t n_b, const int32_t* index,
+                                         const float* dist2, float max_dist, int n_tol, const double* min_cos, int is_signed, float* cos_out, int64_t* within_out,
+                                         int64_t* n_compared_out, int mem) {
+    return with_own_ctx(device, [&](tsar_ctx* ctx) {
+        return tsar_cloud_normal_compare_ctx(ctx, normal_a, stride_a, n, normal_b, stride_b, n_b, index, dist2, max_dist, n_tol, min_cos, is_signed, cos_out, within_out,
+                                             n_compared_out, mem);
+    });
+}
+
 // ---- a cloud rendered into a camera; a depth map scored against a map (cloud_render_kernels.hip) -----------------------------------------
 extern "C" void tsar_default_cloud_render_params(tsar_cloud_render_params* p) {
     if (!p) return;

@@ -474,6 +474,12 @@ int run_cloud_voxels(CallFrame& f, const float* cloud, long long n, int stride, 
                      int mem);                                                                  // cloud_voxel_kernels.hip (cloud, dist2: device; outputs in `mem`; finishes the frame)
 int run_cloud_neighbors(CallFrame& f, const float* cloud, long long n, int stride, float r2, double edge, int k, long long max_pairs, int32_t* count_out,
                         float* knn_out, int64_t* n_valid_out, int64_t* pairs_out);              // cloud_neighbor_kernels.hip (device pointers; finishes the frame)
+int run_cloud_normals(CallFrame& f, const float* cloud, long long n, int stride, float r2, double edge, const tsar_cloud_normals_params& p, int32_t* knn_index_out,
+                      int32_t* n_used_out, float* normal_out, float* curvature_out, double* cov_out, int64_t* n_valid_out, int64_t* n_normals_out,
+                      int64_t* pairs_out);                                                          // cloud_normal_kernels.hip (device pointers; finishes the frame)
+int run_cloud_normal_compare(CallFrame& f, const float* normal_a, int stride_a, long long n, const float* normal_b, int stride_b, long long n_b, const int32_t* index,
+                             const float* dist2, float md2, int n_tol, const double* min_cos, int is_signed, float* cos_out,
+                             unsigned long long* counters_out);                                   // cloud_normal_kernels.hip (counters: n_compared, within[16])
 struct CrViewHost { float P[12]; float fr; int max_px, w, h; bool foot; };                       // tsar_cloud_render's view: P, fl(K[0] * radius), radius > 0
 int run_cloud_render(CallFrame& f, const float* cloud, long long n, int stride, const CrViewHost& vh, float occlusion_diff, float depth_diff, int min_points,
                      long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,

@@ -465,6 +465,107 @@ static inline bool read_cloud_ply(const std::string& path, std::vector<float>& x
     return true;
 }
 
+// As read_cloud_ply, for a cloud that carries normals: x y z nx ny nz of the vertex element as n records of 6 floats (each of the six float
+// or double, a double rounded once to float32).  So it reads APD_TSAR.ply and TSAR_model.ply.  A file without one of nx, ny, nz is refused
+// with a one-line reason, like everything read_cloud_ply refuses.
+static inline bool read_cloud_ply_normals(const std::string& path, std::vector<float>& rec6, int64_t& n, std::string& why) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) { why = "cannot open " + path; return false; }
+    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+    auto bad = [&](const std::string& m) { why = path + ": " + m; return false; };
+    char line[1024];
+    auto next_line = [&]() -> bool {
+        if (!fgets(line, sizeof line, f)) return false;
+        size_t len = strlen(line);
+        while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = '\0';
+        return true;
+    };
+    if (!next_line() || strcmp(line, "ply") != 0) return bad("not a PLY file");
+    struct Prop { std::string name; int size; int kind; };   // kind 0 integer (skipped), 1 float, 2 double
+    std::vector<Prop> props;
+    std::string format;
+    long long count = -1;
+    bool in_vertex = false, seen_vertex = false, ended = false;
+    while (next_line()) {
+        char a[64] = "", b[64] = "", c[64] = "", d[64] = "";
+        const int nw = sscanf(line, "%63s %63s %63s %63s", a, b, c, d);
+        if (nw < 1 || !strcmp(a, "comment") || !strcmp(a, "obj_info")) continue;
+        if (!strcmp(a, "end_header")) { ended = true; break; }
+        if (!strcmp(a, "format")) format = b;
+        else if (!strcmp(a, "element")) {
+            if (nw != 3) return bad("malformed element line");
+            in_vertex = !strcmp(b, "vertex");
+            if (in_vertex) {
+                char* end = nullptr;
+                count = strtoll(c, &end, 10);
+                if (*end != '\0' || count < 0) return bad("malformed vertex count");
+                seen_vertex = true;
+            } else if (!seen_vertex) return bad("an element comes before the vertices");
+        } else if (!strcmp(a, "property") && in_vertex) {
+            if (!strcmp(b, "list")) return bad("a list property inside the vertex element");
+            if (nw != 3) return bad("malformed property line");
+            static const struct { const char* name; int size; int kind; } types[] = {
+                {"char", 1, 0}, {"int8", 1, 0}, {"uchar", 1, 0}, {"uint8", 1, 0}, {"short", 2, 0}, {"int16", 2, 0}, {"ushort", 2, 0}, {"uint16", 2, 0},
+                {"int", 4, 0}, {"int32", 4, 0}, {"uint", 4, 0}, {"uint32", 4, 0}, {"float", 4, 1}, {"float32", 4, 1}, {"double", 8, 2}, {"float64", 8, 2}};
+            int found = -1;
+            for (int k = 0; k < 16; k++)
+                if (!strcmp(b, types[k].name)) found = k;
+            if (found < 0) return bad(std::string("unknown property type ") + b);
+            props.push_back({c, types[found].size, types[found].kind});
+        }
+    }
+    if (!ended) return bad("the header does not end");
+    const bool ascii = format == "ascii";
+    if (!ascii && format != "binary_little_endian") return bad("format " + format + " is not supported (ascii and binary_little_endian are)");
+    if (count < 0) return bad("no vertex element");
+    static const char* const names[6] = {"x", "y", "z", "nx", "ny", "nz"};
+    int col[6] = {-1, -1, -1, -1, -1, -1}, off[6] = {0, 0, 0, 0, 0, 0}, rec_bytes = 0;
+    for (size_t k = 0; k < props.size(); k++) {
+        for (int c = 0; c < 6; c++)
+            if (props[k].name == names[c]) {
+                if (col[c] >= 0) return bad("property " + props[k].name + " appears twice");
+                if (props[k].kind == 0) return bad("property " + props[k].name + " is neither float nor double");
+                col[c] = (int)k; off[c] = rec_bytes;
+            }
+        rec_bytes += props[k].size;
+    }
+    for (int c = 0; c < 6; c++)
+        if (col[c] < 0) return bad(std::string("the vertex element has no property ") + names[c]);
+    char msg[96];
+    snprintf(msg, sizeof msg, "the file holds fewer than %lld vertices", count);
+    const long body_at = ftell(f);
+    if (fseek(f, 0, SEEK_END) != 0) return bad("cannot seek");
+    const long long body_bytes = (long long)ftell(f) - body_at;
+    if (fseek(f, body_at, SEEK_SET) != 0) return bad("cannot seek");
+    const long long least = ascii ? 2 * (long long)props.size() - 1 : (long long)rec_bytes;
+    if (count > 0 && (least <= 0 || count > body_bytes / least + 1)) return bad(msg);
+    n = count;
+    rec6.resize((size_t)count * 6);
+    if (ascii) {
+        for (long long i = 0; i < count; i++)
+            for (size_t k = 0; k < props.size(); k++) {
+                double v;
+                if (fscanf(f, "%lf", &v) != 1) return bad(msg);
+                for (int c = 0; c < 6; c++)
+                    if (col[c] == (int)k) rec6[(size_t)i * 6 + c] = (float)v;
+            }
+        return true;
+    }
+    const long long chunk = 1 << 16;
+    std::vector<unsigned char> buf((size_t)chunk * rec_bytes);
+    for (long long i0 = 0; i0 < count; i0 += chunk) {
+        const long long m = count - i0 < chunk ? count - i0 : chunk;
+        if (fread(buf.data(), (size_t)rec_bytes, (size_t)m, f) != (size_t)m) return bad(msg);
+        for (long long i = 0; i < m; i++)
+            for (int c = 0; c < 6; c++) {
+                const unsigned char* s = buf.data() + (size_t)i * rec_bytes + off[c];
+                if (props[col[c]].kind == 1) { float v; memcpy(&v, s, 4); rec6[(size_t)(i0 + i) * 6 + c] = v; }
+                else { double v; memcpy(&v, s, 8); rec6[(size_t)(i0 + i) * 6 + c] = (float)v; }
+            }
+    }
+    return true;
+}
+
 // fused cloud, binary little-endian: x y z nx ny nz red green blue per point (records of 9 floats from tsar_fuse)
 static bool write_cloud_ply(const std::string& path, const float* pts, int64_t n) {
     FILE* f = fopen(path.c_str(), "wb");

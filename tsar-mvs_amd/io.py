@@ -212,23 +212,39 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def write_ply(path: str, xyz, binary: bool = True) -> None:
+def write_ply(path: str, xyz, binary: bool = True, normals=None) -> None:
     """x y z of an [n, k >= 3] cloud as a PLY of float vertices (binary little-endian, or ASCII with nine significant digits:
-    enough to read every float32 back exactly)"""
+    enough to read every float32 back exactly); with normals ([n, 3]) also nx ny nz"""
     a = np.ascontiguousarray(np.asarray(xyz, np.float32)[:, :3], "<f4")
+    more = ""
+    if normals is not None:
+        nrm = np.asarray(normals, np.float32)
+        assert nrm.shape == a.shape, "normals must be [n, 3] like the points"
+        a = np.ascontiguousarray(np.concatenate([a, nrm], axis=1), "<f4")
+        more = "property float nx\nproperty float ny\nproperty float nz\n"
     with open(path, "wb") as f:
-        f.write(("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\nend_header\n"
-                 % ("binary_little_endian" if binary else "ascii", a.shape[0])).encode())
+        f.write(("ply\nformat %s 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%send_header\n"
+                 % ("binary_little_endian" if binary else "ascii", a.shape[0], more)).encode())
         if binary:
             f.write(a.tobytes())
         else:
-            f.write("".join("%.9g %.9g %.9g\n" % tuple(r) for r in a.tolist()).encode())
+            f.write("".join(" ".join("%.9g" % v for v in r) + "\n" for r in a.tolist()).encode())
 
 
 def read_ply(path: str) -> np.ndarray:
     """[n, 3] float32: the x, y, z of a PLY's vertex element (`ascii 1.0` or `binary_little_endian 1.0`; any scalar properties in any
     order; float or double coordinates, a double rounded once to float32; elements after the vertices are ignored).  What
     host/tsar_io.h read_cloud_ply reads, with its refusals as ValueError."""
+    return _read_ply_columns(path, ("x", "y", "z"))
+
+
+def read_ply_normals(path: str) -> np.ndarray:
+    """[n, 6] float32: x y z nx ny nz of a PLY's vertex element, read like read_ply; a file without nx, ny or nz is refused (ValueError).
+    What host/tsar_io.h read_cloud_ply_normals reads."""
+    return _read_ply_columns(path, ("x", "y", "z", "nx", "ny", "nz"))
+
+
+def _read_ply_columns(path: str, want) -> np.ndarray:
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -263,7 +279,7 @@ def read_ply(path: str) -> np.ndarray:
         if n is None or n < 0:
             raise ValueError(f"{path}: no vertex element")
         names = [p[0] for p in props]
-        for c in "xyz":
+        for c in want:
             if names.count(c) != 1:
                 raise ValueError(f"{path}: the vertex element has no property {c}")
             if dict(props)[c] not in ("f4", "f8"):
@@ -273,13 +289,13 @@ def read_ply(path: str) -> np.ndarray:
             if len(tok) < n * len(props):
                 raise ValueError(f"{path}: the file holds fewer than {n} vertices")
             rows = np.array(tok[: n * len(props)], dtype=object).reshape(n, len(props))
-            return np.stack([np.array(rows[:, names.index(c)], dtype=np.float64) for c in "xyz"], axis=1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+            return np.stack([np.array(rows[:, names.index(c)], dtype=np.float64) for c in want], axis=1).astype(np.float32) if n else np.zeros((0, len(want)), np.float32)
         dt = np.dtype([(nm, "<" + ty) for nm, ty in props])
         body = f.read(n * dt.itemsize)
         if len(body) != n * dt.itemsize:
             raise ValueError(f"{path}: the file holds fewer than {n} vertices")
         rec = np.frombuffer(body, dt)
-        return np.stack([rec[c].astype(np.float32) for c in "xyz"], axis=1) if n else np.zeros((0, 3), np.float32)
+        return np.stack([rec[c].astype(np.float32) for c in want], axis=1) if n else np.zeros((0, len(want)), np.float32)
 
 
 # ---- a whole synthetic scene on disk, laid out like data/TRAIN/<scene>/ ---------------------------------
