@@ -9,8 +9,16 @@
  * functions over arrays) and tests/golden/make_slic_ref_golden.py records its outputs in tests/golden/slic_ref.npz.
  * tests/test_slic_reference_golden.py holds every function below to them: rgb2xyz, the linear branch of rgb2CIELab,
  * init_cluster_centers_shared (both branches), compute_slic_distance, find_center_association_shared,
- * finalize_reduction_result_shared and supress_local_lable BIT FOR BIT / label for label.  NOT reachable by a host compiler and
- * therefore still unpinned: Update_Cluster_Center_device (GPU.cu:260-357, restated in block_partial below) and CUDA's own pow().
+ * finalize_reduction_result_shared and supress_local_lable BIT FOR BIT / label for label.  NOT reachable by a host compiler:
+ * Update_Cluster_Center_device (GPU.cu:260-357, restated in block_partial below) and CUDA's own pow().
+ * The update stage is held by a PLAIN STATEMENT of what it sums instead (tests/slic_cases.py plain_update: per superpixel, a mask over
+ * the 3S x 3S window of the pixels the block grid visits — xo / 16 < bpl and (yo / 16) bpl + xo / 16 < nblk — with no block loop and no
+ * tree; tests/test_slic_edges_cpu.py for update_centers below, tests/test_gpu_slic_edges.py for the kernel): BIT FOR BIT in RGB space,
+ * where every sum is an integer below 2^24 and float32 summation is exact in any order, and within the derived bound
+ * g_k sum|v| / n, k = nblk + 9 roundings, in CIELAB, XYZ and at S = 256 — at every size class of the window (bpl clamped at S = 4, 5;
+ * right columns never visited at 235 of the 253 sizes, the superpixel's own cell cut at S = 9, 10; a ragged last block row at 103
+ * sizes; exact at S = 4, 5 and the multiples of 16).  What pins which pixels a centre sums is therefore no longer this file's own
+ * restatement; the ORDER of the float additions (the tree) is still only restated, and bounded.  Still not held: CUDA's own pow().
  *
  * pow(x, 1.0f / 3.0f) of rgb2CIELab (shared.h:41-46): a libm call whose result depends on the libm (CUDA's libdevice powf on the
  * reference's GPU, glibc's powf in the host build of the reference).  Here it is orc_pow_third: the CORRECTLY ROUNDED fp32 value of
