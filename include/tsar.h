@@ -46,6 +46,7 @@
  *   (none: the reference's fuser cleans nothing)         tsar_cloud_neighbors
  *   (none: the reference estimates no cloud normals)     tsar_cloud_normals / tsar_cloud_normal_compare
  *   (none: the reference renders no cloud)               tsar_cloud_render / tsar_depth_compare
+ *   (none: nor one with oriented occluders)              tsar_cloud_render_oriented
  *
  * Conventions
  *   - every function returns an int status (TSAR_OK = 0, negative = error) and never exits the
@@ -819,6 +820,50 @@ int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stri
                           int32_t* index_out /* [h][w] or NULL */, int64_t* n_splats_out /* host, may be NULL */, int mem);
 int tsar_cloud_render(int device, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h,
                       const tsar_cloud_render_params* p, float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem);
+
+/* tsar_cloud_render_oriented: tsar_cloud_render with a normal-oriented occluder.  The square footprint at the constant depth p_2 stands in
+ * front of a slanted surface's own neighbouring pixels: from a slope of about 2 on, a surface hides itself.  Here a point occludes as its
+ * tangent disc of world radius `radius`: the depth of its plane along each pixel's ray, only where that ray meets the disc, cut to the
+ * square that s allows.  It is still a square-clipped disc per point: nothing is meshed, and a point whose centre is outside the image
+ * still takes no part.
+ * Everything is tsar_cloud_render's (P, candidate, lands, s, the clipped square, n_splats, Zc and index, visible, count, kept and the three
+ * outputs) except the value a point writes into the occluder buffer.  float32, every operation one IEEE-754 operation, no fused
+ * multiply-add, unless stated.  The normal of point i is normals[i * normal_stride + 0..2], or with normals NULL the record's floats 3..5.
+ *   on the host, in float64 from float32 elements, each element of A, M and C rounded once to float32:
+ *     A = K R: A[k][j] = (K[k][0] * R[0][j] + K[k][1] * R[1][j]) + K[k][2] * R[2][j]  (P's first three columns); the cofactors below are
+ *         float64 operations on the rounded A
+ *     M = A^-1 by cofactors: c[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1] with i1 = (i + 1) mod 3, i2 = (i + 2) mod 3 and j1, j2
+ *         likewise;  det = (A[0][0] * c[0][0] + A[0][1] * c[0][1]) + A[0][2] * c[0][2];  M[j][i] = c[i][j] / det
+ *     C[j] = -((R[0][j] * t[0] + R[1][j] * t[1]) + R[2][j] * t[2])  (the camera centre);   r2 = fl(radius * radius), one float32 product
+ *   per point that lands, with its position X and normal n:
+ *     oriented = n_0, n_1 and n_2 are all finite and not all zero
+ *     a_k = X_k - C_k;   num = (n_0 * a_0 + n_1 * a_1) + n_2 * a_2;   g_j = (M[0][j] * n_0 + M[1][j] * n_1) + M[2][j] * n_2
+ *   the centre pixel (xi, yi): covered, with the value p_2, always (so Zo <= Zc still holds)
+ *   every other pixel (u, v) of the clipped square, u and v as float32:
+ *     den = g_0 * u + (g_1 * v + g_2);   z = num / den (correctly rounded);   d_k = M[k][0] * u + (M[k][1] * v + M[k][2])
+ *     e_k = z * d_k - a_k;   q = (e_0 * e_0 + e_1 * e_1) + e_2 * e_2
+ *     an oriented point covers the pixel iff z > 0 and z < inf and q <= r2 (NaN fails every comparison), with the value z
+ *     a point that is not oriented covers the whole clipped square with the value p_2: tsar_cloud_render's rule
+ *   Zo = the float whose bits are the minimum of bits(value) over the points that cover the pixel (values are positive and finite)
+ *   occluder_out = Zo where something covers the pixel, else 0
+ *   n_covered = the number of (point, pixel) pairs that cover, centres included: an integer sum, the same whatever TSAR_RENDER_SKIP says;
+ *           n_splats (the pixels examined) is tsar_cloud_render's, and max_splats bounds it in the same way, before anything is written
+ * The result does not depend on the sign of n (num and den change sign together).  radius == 0 is allowed: s = 0, only centres cover, and
+ * the result is the one-pixel render.  Minima and integer sums: every run gives the same bits.
+ * `mem` names where cloud, normals and the four planes lie; cam, p, n_splats_out and n_covered_out (filled when the call succeeds; both may
+ * be NULL) are host memory.
+ * TSAR_ERR_INVALID: tsar_cloud_render's refusals, with all FOUR planes NULL in place of three; normals NULL with a stride below 6; normals
+ * given with normal_stride below 3; det == 0, or an element of M or C that is not finite.
+ * The _ctx form needs no views and no state and changes nothing in the context, like tsar_cloud_render_ctx.  Timed as "cloud_splat_count",
+ * "cloud_splat_scatter", "cloud_splat_support" and "cloud_splat_resolve". */
+int tsar_cloud_render_oriented_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride,
+                                   const float* normals /* [n][normal_stride], the normal first; NULL: the record's floats 3..5 */, int normal_stride,
+                                   const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p, float* depth_out /* [h][w] or NULL */,
+                                   uint8_t* count_out /* [h][w] or NULL */, int32_t* index_out /* [h][w] or NULL */, float* occluder_out /* [h][w] or NULL */,
+                                   int64_t* n_splats_out /* host, may be NULL */, int64_t* n_covered_out /* host, may be NULL */, int mem);
+int tsar_cloud_render_oriented(int device, const float* cloud, int64_t n, int stride, const float* normals, int normal_stride, const tsar_camera* cam,
+                               int w, int h, const tsar_cloud_render_params* p, float* depth_out, uint8_t* count_out, int32_t* index_out,
+                               float* occluder_out, int64_t* n_splats_out, int64_t* n_covered_out, int mem);
 
 /* tsar_depth_compare: a depth map scored against a ground-truth map (tsar_cloud_render's, say) with the per-pixel bars: how many pixels
  * lie within each relative tolerance, how many in front, how many behind.  depth [n], gt [n] float32, mask [n] uint8 (NULL: every pixel)

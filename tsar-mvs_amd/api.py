@@ -111,6 +111,7 @@ _CLOUD_NORMALS = (_I, [_I, _P, _L, _I, _p(CloudNormalsParams), _P, _P, _P, _P, _
 _CLOUD_NORMAL_COMPARE = (_I, [_I, _P, _I, _L, _P, _I, _L, _P, _P, _F, _I, _P, _I, _P, _P, _p(_L), _I])
 
 _CLOUD_RENDER = (_I, [_I, _P, _L, _I, _p(Camera), _I, _I, _p(CloudRenderParams), _P, _P, _P, _p(_L), _I])
+_CLOUD_RENDER_ORIENTED = (_I, [_I, _P, _L, _I, _P, _I, _p(Camera), _I, _I, _p(CloudRenderParams), _P, _P, _P, _P, _p(_L), _p(_L), _I])
 _DEPTH_COMPARE = (_I, [_I, _P, _P, _P, _L, _I, _P, _p(_L), _p(_L), _P, _p(_L), _p(_L), _P, _I])
 
 
@@ -199,6 +200,8 @@ _ABI = {
     "tsar_default_cloud_render_params": (None, [_p(CloudRenderParams)]),
     "tsar_cloud_render_ctx": _on_ctx(_CLOUD_RENDER),
     "tsar_cloud_render": _CLOUD_RENDER,
+    "tsar_cloud_render_oriented_ctx": _on_ctx(_CLOUD_RENDER_ORIENTED),
+    "tsar_cloud_render_oriented": _CLOUD_RENDER_ORIENTED,
     "tsar_depth_compare_ctx": _on_ctx(_DEPTH_COMPARE),
     "tsar_depth_compare": _DEPTH_COMPARE,
     "tsar_host_alloc": (_P, [_Z]),
@@ -1390,7 +1393,7 @@ def evaluate_cloud(recon, gt, tolerances, matcher=None, device=0, voxel=None, cr
 
 
 def cloud_render(cloud, K, R, t, w, h, radius=0.0, max_px=8, occlusion_diff=0.02, depth_diff=0.01, min_points=1, want=("depth", "count"), max_splats=None,
-                 matcher=None, device=0):
+                 matcher=None, device=0, normals=None):
     """`cloud` rendered into the view (K, R, t) of w x h pixels as a depth map, occlusion by the cloud's own points handled
     (tsar_cloud_render_ctx; include/tsar.h states the arithmetic).  cloud: [n, k >= 3] float32, x y z first, a numpy array or a torch device
     tensor (a fused cloud as api.fuse returns it goes in as it is).  radius (world units): the half-width of a point's occluder footprint, at
@@ -1400,27 +1403,50 @@ def cloud_render(cloud, K, R, t, w, h, radius=0.0, max_px=8, occlusion_diff=0.02
     as cloud_distance.
     Returns a dict: "depth" ([h, w] float32, 0 where nothing is kept), "count" ([h, w] uint8: the landings within depth_diff of the front-most,
     saturated at 255), "index" ([h, w] int32: the front-most point, -1 where nothing is kept), as `want` names them (numpy arrays, or torch
-    tensors on the cloud's device), and the integer "n_splats"."""
+    tensors on the cloud's device), and the integer "n_splats".
+    normals: None = the square occluder above.  "record" (the records' floats 3..5, k >= 6) or an [n, 3] float32 array or device tensor,
+    living where the cloud does: the normal-oriented occluder (tsar_cloud_render_oriented_ctx): a point occludes as its tangent disc of radius
+    `radius`, cut to the square; a point with a zero or non-finite normal keeps the square.  `want` may then name "occluder" ([h, w] float32:
+    the occluder buffer, 0 where nothing covers), and the result has "n_covered", the covering (point, pixel) pairs."""
     L = load_library()
     c, dev = _cloud(cloud, "cloud")
     n, w, h = int(c.shape[0]), int(w), int(h)
     assert w >= 1 and h >= 1 and len(want) > 0, "cloud_render needs a size of at least 1 x 1 and at least one output"
+    assert normals is not None or "occluder" not in want, "the occluder plane comes with normals"
     p = CloudRenderParams()
     L.tsar_default_cloud_render_params(C.byref(p))
     p.radius, p.max_px, p.occlusion_diff, p.depth_diff, p.min_points = float(radius), int(max_px), float(occlusion_diff), float(depth_diff), int(min_points)
     if max_splats is not None:
         p.max_splats = int(max_splats)
     cam = _cameras(np.asarray(K, np.float32).reshape(1, 3, 3), np.asarray(R, np.float32).reshape(1, 3, 3), np.asarray(t, np.float32).reshape(1, 3), 1)
-    res = _outputs({"depth": ((h, w), np.float32), "count": ((h, w), np.uint8), "index": ((h, w), np.int32)}, want, c.device if dev else None)
-    n_splats = C.c_int64(-1)
+    spec = {"depth": ((h, w), np.float32), "count": ((h, w), np.uint8), "index": ((h, w), np.int32)}
+    if normals is not None:
+        spec["occluder"] = ((h, w), np.float32)
+    res = _outputs(spec, want, c.device if dev else None)
+    n_splats, n_covered = C.c_int64(-1), C.c_int64(-1)
+    planes = [_ptr(res.get(key))[0] for key in spec]
+    nrm = None
+    if normals is not None and not isinstance(normals, str):
+        nrm, nrm_dev = _cloud(normals, "normals")
+        assert int(nrm.shape[0]) == n and nrm_dev == dev and (not dev or nrm.device == c.device), "normals must be [n, k >= 3] and live where the cloud does"
+    else:
+        assert normals in (None, "record"), "normals must be None, \"record\" or an [n, 3] array"
+    no_points = (C.c_float * 3)()                     # (n == 0: a normals pointer that is not NULL, which would mean "record"; nothing reads it)
     with _matcher_for(matcher, device, c) as m:
-        rc = L.tsar_cloud_render_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), cam, w, h, C.byref(p), _ptr(res.get("depth"))[0], _ptr(res.get("count"))[0],
-                                     _ptr(res.get("index"))[0], C.byref(n_splats), MEM_DEVICE if dev else MEM_HOST)
+        if normals is None:
+            rc = L.tsar_cloud_render_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), cam, w, h, C.byref(p), *planes, C.byref(n_splats),
+                                         MEM_DEVICE if dev else MEM_HOST)
+        else:
+            rc = L.tsar_cloud_render_oriented_ctx(m._ctx, _ptr(c)[0] if n else None, n, int(c.shape[1]), None if nrm is None else _ptr(nrm)[0] if n else C.cast(no_points, C.c_void_p),
+                                                  int(nrm.shape[1]) if nrm is not None else 0, cam, w, h, C.byref(p), *planes, C.byref(n_splats), C.byref(n_covered),
+                                                  MEM_DEVICE if dev else MEM_HOST)
         if rc != TSAR_OK:
             err = TsarError(rc, L.tsar_last_error(m._ctx).decode())
             err.n_splats = int(n_splats.value) if n_splats.value >= 0 else None     # filled when max_splats refused the call
             raise err
     res["n_splats"] = int(n_splats.value)
+    if normals is not None:
+        res["n_covered"] = int(n_covered.value)
     return res
 
 
@@ -1471,19 +1497,20 @@ def depth_compare(depth, gt, tolerances, mask=None, want_error=False, matcher=No
     return _depth_ratios(res)
 
 
-def evaluate_depth_maps(depths, cloud, K, R, t, tolerances, radius, masks=None, matcher=None, device=0, **render_kw):
+def evaluate_depth_maps(depths, cloud, K, R, t, tolerances, radius, masks=None, matcher=None, device=0, normals=None, **render_kw):
     """Depth maps scored per pixel against the cloud `cloud` (a scan, a fused cloud as api.fuse returns it) rendered into their own cameras: per
     view v one cloud_render of the cloud into (K[v], R[v], t[v]) at depths[v]'s size with the footprint `radius` (render_kw: max_px,
     occlusion_diff, depth_diff, min_points, max_splats) and one depth_compare of depths[v] against it (masks[v] if given).  The project's own
-    per-pixel bars against a rendered cloud: not the evaluation program of a benchmark (no observation masks, no alignment).
-    Returns (views, total): per view depth_compare's dict plus "n_splats"; total adds the counts over the views first and forms the ratios
-    afterwards."""
+    per-pixel bars against a rendered cloud: not the evaluation program of a benchmark (no observation masks, no alignment).  normals:
+    cloud_render's (None, "record" or an [n, 3] array): the renders use the normal-oriented occluder.
+    Returns (views, total): per view depth_compare's dict plus "n_splats" (and "n_covered" with normals); total adds the counts over the views
+    first and forms the ratios afterwards."""
     views = []
     c, dev = _cloud(cloud, "cloud")
     with _matcher_for(matcher, device, c) as m:
         for v, d in enumerate(depths):
             h, w = int(d.shape[0]), int(d.shape[1])
-            r = cloud_render(c, K[v], R[v], t[v], w, h, radius, want=("depth",), matcher=m, **render_kw)
+            r = cloud_render(c, K[v], R[v], t[v], w, h, radius, want=("depth",), matcher=m, normals=normals, **render_kw)
             if dev != _is_torch(d):                  # the map goes where the cloud's render lies
                 if dev:
                     import torch
@@ -1492,9 +1519,11 @@ def evaluate_depth_maps(depths, cloud, K, R, t, tolerances, radius, masks=None, 
                     d = d.cpu().numpy()
             rec = depth_compare(d, r["depth"], tolerances, None if masks is None else masks[v], matcher=m)
             rec["n_splats"] = r["n_splats"]
+            if normals is not None:
+                rec["n_covered"] = r["n_covered"]
             views.append(rec)
     total = {"tolerances": np.ascontiguousarray(tolerances, np.float32).reshape(-1)}
-    for k in ("n_gt", "n_both", "n_front", "n_behind", "n_splats"):
+    for k in ("n_gt", "n_both", "n_front", "n_behind", "n_splats") + (("n_covered",) if normals is not None else ()):
         total[k] = int(sum(rec[k] for rec in views))
     total["within"] = np.sum([rec["within"] for rec in views], axis=0, dtype=np.int64) if views else np.zeros(len(total["tolerances"]), np.int64)
     return views, _depth_ratios(total)

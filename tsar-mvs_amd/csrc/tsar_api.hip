@@ -1423,37 +1423,47 @@ extern "C" void tsar_default_cloud_render_params(tsar_cloud_render_params* p) {
     p->max_splats = (int64_t)1 << 34;
 }
 
+// The checks and the view that tsar_cloud_render and tsar_cloud_render_oriented share, in the order the header lists the refusals; `entry`
+// names the caller in the message, no_outputs is its "every output is NULL" refusal (null: the caller has an output).
+static int cloud_render_view(tsar_ctx* ctx, const char* entry, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h,
+                             const tsar_cloud_render_params* p, const char* no_outputs, int mem, CrViewHost* vh) {
+    const auto refuse = [&](const char* why) { return fail(ctx, TSAR_ERR_INVALID, (std::string(entry) + ": " + why).c_str()); };
+    if (!p) return refuse("params is NULL");
+    if (!cam) return refuse("cam is NULL");
+    TRY(check_clouds(ctx, entry, mem, {{cloud, n, stride}}));
+    if (no_outputs) return refuse(no_outputs);
+    if (w < 1 || h < 1 || w + 2 >= (1 << 23) || h + 2 >= (1 << 23) || (int64_t)w * h > INT32_MAX)
+        return refuse("w and h must be >= 1, with w + 2 and h + 2 < 2^23 (the 24-bit addressing limit) and w * h <= 2^31-1");
+    const float radius = p->radius;
+    const volatile float frv = cam->K[0] * radius;       // fl(K[0] * radius), one float32 product
+    const float fr = frv;
+    if (!(radius >= 0.0f && radius <= FLT_MAX)) return refuse("radius must be finite and >= 0");
+    if (!(fr >= 0.0f && fr <= FLT_MAX)) return refuse("K[0] * radius must be finite and >= 0 in float32");
+    if (p->max_px < 1 || p->max_px > 16) return refuse("max_px must be in 1..16");
+    if (!(p->occlusion_diff >= 0.0f && p->occlusion_diff <= FLT_MAX)) return refuse("occlusion_diff must be finite and >= 0");
+    if (!(p->depth_diff >= 0.0f && p->depth_diff <= FLT_MAX)) return refuse("depth_diff must be finite and >= 0");
+    if (p->min_points < 1 || p->min_points > 255) return refuse("min_points must be in 1..255");
+    if (p->max_splats < 0) return refuse("max_splats must be >= 0");
+    for (int k = 0; k < 3; k++) {                         // P = K [R | t]: float64 products and sums of the float32 elements, rounded once
+        const double k0 = cam->K[k * 3], k1 = cam->K[k * 3 + 1], k2 = cam->K[k * 3 + 2];
+        for (int j = 0; j < 3; j++) vh->P[k * 4 + j] = (float)((k0 * (double)cam->R[j] + k1 * (double)cam->R[3 + j]) + k2 * (double)cam->R[6 + j]);
+        vh->P[k * 4 + 3] = (float)((k0 * (double)cam->t[0] + k1 * (double)cam->t[1]) + k2 * (double)cam->t[2]);
+    }
+    vh->fr = radius > 0.0f ? fr : 0.0f;
+    vh->foot = radius > 0.0f;
+    vh->max_px = p->max_px;
+    vh->w = w;
+    vh->h = h;
+    return TSAR_OK;
+}
+
 // Like tsar_cloud_distance_ctx: no views, no state, nothing of the context written, and a frame that does not grow the arena.
 extern "C" int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p,
                                      float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem) {
     CHECK_CTX(ctx);
-    if (!p) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: params is NULL");
-    if (!cam) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: cam is NULL");
-    TRY(check_clouds(ctx, "tsar_cloud_render", mem, {{cloud, n, stride}}));
-    if (!depth_out && !count_out && !index_out) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: depth_out, count_out and index_out are all NULL");
-    if (w < 1 || h < 1 || w + 2 >= (1 << 23) || h + 2 >= (1 << 23) || (int64_t)w * h > INT32_MAX)
-        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: w and h must be >= 1, with w + 2 and h + 2 < 2^23 (the 24-bit addressing limit) and w * h <= 2^31-1");
-    const float radius = p->radius;
-    const volatile float frv = cam->K[0] * radius;       // fl(K[0] * radius), one float32 product
-    const float fr = frv;
-    if (!(radius >= 0.0f && radius <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: radius must be finite and >= 0");
-    if (!(fr >= 0.0f && fr <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: K[0] * radius must be finite and >= 0 in float32");
-    if (p->max_px < 1 || p->max_px > 16) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: max_px must be in 1..16");
-    if (!(p->occlusion_diff >= 0.0f && p->occlusion_diff <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: occlusion_diff must be finite and >= 0");
-    if (!(p->depth_diff >= 0.0f && p->depth_diff <= FLT_MAX)) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: depth_diff must be finite and >= 0");
-    if (p->min_points < 1 || p->min_points > 255) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: min_points must be in 1..255");
-    if (p->max_splats < 0) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render: max_splats must be >= 0");
     CrViewHost vh;
-    for (int k = 0; k < 3; k++) {                         // P = K [R | t]: float64 products and sums of the float32 elements, rounded once
-        const double k0 = cam->K[k * 3], k1 = cam->K[k * 3 + 1], k2 = cam->K[k * 3 + 2];
-        for (int j = 0; j < 3; j++) vh.P[k * 4 + j] = (float)((k0 * (double)cam->R[j] + k1 * (double)cam->R[3 + j]) + k2 * (double)cam->R[6 + j]);
-        vh.P[k * 4 + 3] = (float)((k0 * (double)cam->t[0] + k1 * (double)cam->t[1]) + k2 * (double)cam->t[2]);
-    }
-    vh.fr = radius > 0.0f ? fr : 0.0f;
-    vh.foot = radius > 0.0f;
-    vh.max_px = p->max_px;
-    vh.w = w;
-    vh.h = h;
+    TRY(cloud_render_view(ctx, "tsar_cloud_render", cloud, n, stride, cam, w, h, p,
+                          !depth_out && !count_out && !index_out ? "depth_out, count_out and index_out are all NULL" : nullptr, mem, &vh));
     CallFrame f(ctx, "tsar_cloud_render", nullptr, /*grow_arena=*/false);
     const size_t np = (size_t)w * h;
     const float* c = f.in(cloud, (size_t)n * stride, mem);
@@ -1467,6 +1477,73 @@ extern "C" int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t 
 extern "C" int tsar_cloud_render(int device, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p,
                                  float* depth_out, uint8_t* count_out, int32_t* index_out, int64_t* n_splats_out, int mem) {
     return with_own_ctx(device, [&](tsar_ctx* ctx) { return tsar_cloud_render_ctx(ctx, cloud, n, stride, cam, w, h, p, depth_out, count_out, index_out, n_splats_out, mem); });
+}
+
+// The oriented occluder's host side (include/tsar.h): A = K R, M = A^-1 by cofactors and C = -R^T t in float64 from the float32 elements, each
+// result rounded once.  false: A is singular, or an element of M or C is not finite.
+static bool cloud_splat_view(const tsar_camera* cam, float radius, CsViewHost* sh) {
+    double A[3][3], c[3][3];
+    for (int k = 0; k < 3; k++)
+        for (int j = 0; j < 3; j++)
+            A[k][j] = (double)(float)(((double)cam->K[k * 3] * (double)cam->R[j] + (double)cam->K[k * 3 + 1] * (double)cam->R[3 + j]) +
+                                      (double)cam->K[k * 3 + 2] * (double)cam->R[6 + j]);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            c[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+        }
+    const double det = (A[0][0] * c[0][0] + A[0][1] * c[0][1]) + A[0][2] * c[0][2];
+    if (det == 0.0) return false;
+    bool finite = true;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            sh->M[j * 3 + i] = (float)(c[i][j] / det);
+            finite = finite && fabsf(sh->M[j * 3 + i]) <= FLT_MAX;
+        }
+    for (int j = 0; j < 3; j++) {
+        sh->C[j] = (float)-(((double)cam->R[j] * (double)cam->t[0] + (double)cam->R[3 + j] * (double)cam->t[1]) + (double)cam->R[6 + j] * (double)cam->t[2]);
+        finite = finite && fabsf(sh->C[j]) <= FLT_MAX;
+    }
+    const volatile float r2v = radius * radius;          // fl(radius * radius), one float32 product
+    sh->r2 = r2v;
+    return finite;
+}
+
+// tsar_cloud_render_ctx with the normal-oriented occluder (cloud_splat_kernels.hip); the same frame rules.
+extern "C" int tsar_cloud_render_oriented_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const float* normals, int normal_stride, const tsar_camera* cam,
+                                              int w, int h, const tsar_cloud_render_params* p, float* depth_out, uint8_t* count_out, int32_t* index_out,
+                                              float* occluder_out, int64_t* n_splats_out, int64_t* n_covered_out, int mem) {
+    CHECK_CTX(ctx);
+    CrViewHost vh;
+    TRY(cloud_render_view(ctx, "tsar_cloud_render_oriented", cloud, n, stride, cam, w, h, p,
+                          !depth_out && !count_out && !index_out && !occluder_out ? "depth_out, count_out, index_out and occluder_out are all NULL" : nullptr, mem, &vh));
+    if (!normals && stride < 6)
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render_oriented: normals is NULL, so the normal is the record's floats 3..5: the stride must be at least 6");
+    if (normals && normal_stride < 3) return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render_oriented: normal_stride must be at least 3 floats (the normal first)");
+    CsViewHost sh;
+    if (!cloud_splat_view(cam, p->radius, &sh))
+        return fail(ctx, TSAR_ERR_INVALID, "tsar_cloud_render_oriented: K R is singular, or its inverse or the camera centre is not finite in float32");
+    CallFrame f(ctx, "tsar_cloud_render_oriented", nullptr, /*grow_arena=*/false);
+    const size_t np = (size_t)w * h;
+    const float* c = f.in(cloud, (size_t)n * stride, mem);
+    const float* nr = normals && n > 0 ? f.in(normals, (size_t)n * normal_stride, mem) : nullptr;
+    float* dd = f.out(depth_out, np, mem);
+    uint8_t* dc = f.out(count_out, np, mem);
+    int32_t* di = f.out(index_out, np, mem);
+    float* dz = f.out(occluder_out, np, mem);
+    if (!f.ok()) return f.finish();
+    // (n == 0: no lane reads a normal, and c may be null)
+    return run_cloud_splat(f, c, n > 0 ? (normals ? nr : c + 3) : nullptr, n, stride, normals ? normal_stride : stride, vh, sh, p->occlusion_diff, p->depth_diff, p->min_points,
+                           p->max_splats, dd, dc, di, dz, n_splats_out, n_covered_out);
+}
+
+extern "C" int tsar_cloud_render_oriented(int device, const float* cloud, int64_t n, int stride, const float* normals, int normal_stride, const tsar_camera* cam, int w, int h,
+                                          const tsar_cloud_render_params* p, float* depth_out, uint8_t* count_out, int32_t* index_out, float* occluder_out,
+                                          int64_t* n_splats_out, int64_t* n_covered_out, int mem) {
+    return with_own_ctx(device, [&](tsar_ctx* ctx) {
+        return tsar_cloud_render_oriented_ctx(ctx, cloud, n, stride, normals, normal_stride, cam, w, h, p, depth_out, count_out, index_out, occluder_out, n_splats_out,
+                                              n_covered_out, mem);
+    });
 }
 
 extern "C" int tsar_depth_compare_ctx(tsar_ctx* ctx, const float* depth, const float* gt, const uint8_t* mask, int64_t n, int n_tol, const float* tol, int64_t* n_gt_out,

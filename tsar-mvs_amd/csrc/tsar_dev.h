@@ -204,7 +204,7 @@ struct tsar_ctx {
     bool ransac_cooperative = true;       // TSAR_RANSAC_COOPERATIVE=0: plain launch of the multi-workgroup stage 2
     bool ransac_force_fallback = false;   // TSAR_RANSAC_FORCE_FALLBACK=1: pre-set the give-up flag (tests of that path)
     bool trace_host = false;     // TSAR_TRACE_HOST=1: host-side steps of the refinement operators on stderr
-    bool render_skip = true;     // TSAR_RENDER_SKIP=0: tsar_cloud_render's footprint loop issues every minimum, without the plain load that lets a lane skip one
+    bool render_skip = true;     // TSAR_RENDER_SKIP=0: tsar_cloud_render[_oriented]'s footprint loop issues every minimum, without the plain load that lets a lane skip one
 #ifdef TSAR_EXPERIMENTS
     size_t lds_pad = 0;          // TSAR_LDS_PAD=n: unused LDS per sweep workgroup (occupancy experiments)
 #endif
@@ -484,6 +484,10 @@ struct CrViewHost { float P[12]; float fr; int max_px, w, h; bool foot; };      
 int run_cloud_render(CallFrame& f, const float* cloud, long long n, int stride, const CrViewHost& vh, float occlusion_diff, float depth_diff, int min_points,
                      long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,
                      int64_t* n_splats_out);                                                     // cloud_render_kernels.hip (device pointers; finishes the frame)
+struct CsViewHost { float M[9]; float C[3]; float r2; };                                          // tsar_cloud_render_oriented's: (K R)^-1, -R^T t, fl(radius * radius)
+int run_cloud_splat(CallFrame& f, const float* cloud, const float* normals, long long n, int stride, int normal_stride, const CrViewHost& vh, const CsViewHost& sh,
+                    float occlusion_diff, float depth_diff, int min_points, long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,
+                    float* occluder_out, int64_t* n_splats_out, int64_t* n_covered_out);          // cloud_splat_kernels.hip (device pointers; finishes the frame)
 int run_depth_compare(CallFrame& f, const float* depth, const float* gt, const uint8_t* mask, long long n, int n_tol, const float* tol, float* error_out,
                       unsigned long long* counters_out);                                         // cloud_render_kernels.hip (counters: n_gt, n_both, n_front, n_behind, within[16])
 int launch_compute_disp(tsar_ctx* ctx);
