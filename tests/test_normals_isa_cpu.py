@@ -31,4 +31,4 @@ def test_normal_kernels_use_no_scratch_and_the_longest_list_fits_128_vgprs(tmp_p
             others.add(re.search(r"(nr_[a-z_]+_kernel)", name).group(1))
     assert sorted(caps) == [8, 16, 32], caps                 # one list length per template instance
     assert caps[32] <= 128, f"the 32-entry instance takes {caps[32]} VGPRs (four waves per SIMD need <= 128)"
-    assert others == {"nr_pairs_kernel", "nr_fill_kernel", "nr_compare_kernel"}, others
+    assert others == {"nr_fill_kernel", "nr_compare_kernel"}, others      # (the pair count is cloud_grid.hip's: tests/test_neighbors_isa_cpu.py)

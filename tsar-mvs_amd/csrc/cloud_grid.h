@@ -1,9 +1,10 @@
 // cloud_grid.h — what the operators on point clouds share (cloud_distance_kernels.hip, cloud_voxel_kernels.hip,
-// cloud_neighbor_kernels.hip).  Inlined into their kernels from here: the candidate rule, the order-preserving float codes, the float64
-// cell function of include/tsar.h, the wave reductions and, for the two searches, the grid of edge R (1 + 2^-10), its 16-byte records and
-// the walk over a query's nine key ranges.  Compiled once, in cloud_grid.hip, and declared here: the bounds pass over a cloud
-// (cd_measure), the grid over those bounds (cd_grid), the radix sort of (key, index) pairs (cd_sort) and the sorted index of a cloud's
-// cells with its records (cd_index).
+// cloud_neighbor_kernels.hip, cloud_normal_kernels.hip).  Inlined into their kernels from here: the candidate rule, the order-preserving
+// float codes, the float64 cell function of include/tsar.h, the wave reductions and, for the three searches, the grid of edge
+// R (1 + 2^-10), its 16-byte records, the walk over a query's nine key ranges and the query key of a sorted record.  Compiled once, in
+// cloud_grid.hip, and declared here: the bounds pass over a cloud (cd_measure), the grid over those bounds (cd_grid), the radix sort of
+// (key, index) pairs (cd_sort), the sorted index of a cloud's cells with its records (cd_index) and, for the two searches of a cloud among
+// its own points, everything up to the max_pairs refusal (cd_self_search).
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -62,6 +63,11 @@ __device__ __forceinline__ bool cd_query_range(unsigned long long qkey, int r, c
     return true;
 }
 
+// a sorted record's cell key (3 x 20 bits) as the query key cd_query_range reads (3 x 21 bits, each coordinate + 2)
+__device__ __forceinline__ unsigned long long cd_self_query_key(unsigned long long key) {
+    return (((key >> 40) + 2ull) << 42) | ((((key >> 20) & 0xfffffull) + 2ull) << 21) | ((key & 0xfffffull) + 2ull);
+}
+
 // ---- cloud_grid.hip's host steps: every one works on the call's frame and leaves a failure in it (false: the caller returns f.finish()) ----
 
 // The counters of one call, a piece of the frame: what the bounds pass fills, and two slots that are the operator's own (the searches
@@ -85,3 +91,10 @@ bool cd_sort(CallFrame& f, const char* name, unsigned long long* keys_in, unsign
 // caller's own key kernel in the cloud_keys group.
 struct CdIndex { unsigned long long* keys; uint32_t* vals; CdRec* rec; };   // n sorted keys, n sorted indices, n_cand records
 bool cd_index(CallFrame& f, const float* pts, long long n, int stride, long long n_cand, const CdGrid& g, CdIndex& ix, const std::function<void()>& also_keys = nullptr);
+// What a search of a cloud among its own points begins with (tsar_cloud_neighbors, tsar_cloud_normals; the frame names the entry in the
+// two refusals): the call's counters, cd_measure, cd_grid with cells of `edge` (refused from CD_MAX_EXTENT cells on an axis), cd_index,
+// the pair count (timer cloud_pairs: per sorted record the sizes of its nine key ranges, into own[0]) read back and given to *pairs_out,
+// and the max_pairs refusal.  Without a candidate there is no grid and no index, and no pair.  own[1] is the caller's; the stream is idle
+// on return.
+struct CdSelf { CdCounters* dc; long long n_cand; CdGrid g; CdIndex ix; };
+bool cd_self_search(CallFrame& f, const float* pts, long long n, int stride, double edge, long long max_pairs, int64_t* pairs_out, CdSelf& s);

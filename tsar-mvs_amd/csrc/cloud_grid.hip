@@ -1,6 +1,7 @@
 // cloud_grid.hip — the steps every grid operator on a point cloud begins with (cloud_grid.h declares them): the bounds of the candidates,
-// the grid over those bounds, the radix sort of (key, index) pairs, and the sorted index of a cloud's cells with its 16-byte records.
-// rocPRIM's radix sort is instantiated here and nowhere else in the library.
+// the grid over those bounds, the radix sort of (key, index) pairs, the sorted index of a cloud's cells with its 16-byte records, and the
+// pair count and refusals of a search of a cloud among its own points.  rocPRIM's radix sort is instantiated here and nowhere else in
+// the library.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "cloud_grid.h"
@@ -52,6 +53,22 @@ __global__ __launch_bounds__(CD_BLOCK) void cd_gather_kernel(const float* __rest
     CdRec r;
     r.x = p[0]; r.y = p[1]; r.z = p[2]; r.j = j;
     rec[k] = r;
+}
+
+// *pairs += the number of candidates in the 27 cells around every candidate, itself included: what a search of the cloud among its own
+// points looks at (cd_pairs_kernel of cloud_distance_kernels.hip counts for queries from another cloud)
+__global__ __launch_bounds__(CD_BLOCK) void cd_self_pairs_kernel(const unsigned long long* __restrict__ keys, uint32_t n_cand, CdGrid g, unsigned long long* __restrict__ pairs) {
+    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
+    unsigned long long cnt = 0;
+    if (t < n_cand) {
+        const unsigned long long qkey = cd_self_query_key(keys[t]);
+        for (int r = 0; r < 9; r++) {
+            uint32_t b, e;
+            if (cd_query_range(qkey, r, g, keys, n_cand, b, e)) cnt += e - b;
+        }
+    }
+    cnt = cd_wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(pairs, cnt);
 }
 
 static inline float cd_decode(uint32_t c) { const uint32_t u = (c & 0x80000000u) ? (c & 0x7fffffffu) : ~c; float f; memcpy(&f, &u, 4); return f; }
@@ -115,4 +132,34 @@ bool cd_index(CallFrame& f, const float* pts, long long n, int stride, long long
         hipLaunchKernelGGL(cd_gather_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, pts, stride, ix.vals, (uint32_t)n_cand, ix.rec);
     }
     return f.launched();
+}
+
+bool cd_self_search(CallFrame& f, const float* pts, long long n, int stride, double edge, long long max_pairs, int64_t* pairs_out, CdSelf& s) {
+    s = {};
+    s.dc = f.tmp<CdCounters>(1);
+    if (!f.ok()) return false;
+    CdBounds bounds;
+    if (!cd_measure(f, pts, n, stride, s.dc, bounds)) return false;
+    s.n_cand = bounds.n_cand;
+    unsigned long long pairs = 0;
+    if (s.n_cand > 0) {
+        const std::string refusal = std::string(f.entry) + ": the cloud spans 2^20 cells or more of edge radius on an axis: radius is too small for this cloud's extent";
+        if (!cd_grid(f, bounds, edge, CD_MAX_EXTENT, refusal.c_str(), s.g)) return false;
+        if (!cd_index(f, pts, n, stride, s.n_cand, s.g, s.ix)) return false;
+        {
+            ScopedKernelTimer tm(f.ctx, "cloud_pairs");
+            hipLaunchKernelGGL(cd_self_pairs_kernel, dim3(cd_blocks(s.n_cand)), dim3(CD_BLOCK), 0, f.ctx->stream, s.ix.keys, (uint32_t)s.n_cand, s.g, &s.dc->own[0]);
+        }
+        f.launched();
+        f.copy(&pairs, &s.dc->own[0], sizeof pairs, hipMemcpyDeviceToHost);
+        if (!f.sync()) return false;
+    }
+    if (pairs_out) *pairs_out = (int64_t)pairs;
+    if (pairs > (unsigned long long)max_pairs) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: the call would look at %llu pairs, more than max_pairs = %lld: lower radius or raise max_pairs", f.entry, pairs, max_pairs);
+        f.fail(TSAR_ERR_INVALID, msg);
+        return false;
+    }
+    return true;
 }

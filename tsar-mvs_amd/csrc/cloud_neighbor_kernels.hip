@@ -5,8 +5,9 @@
 // depends on it, nor on the order in which a point's neighbours arrive.
 //
 // Per call:  bounds of the candidates -> 60-bit z-major cell keys, radix-sorted with the indices
-//            -> the candidates copied into key order as 16-byte records (x, y, z, index)     [so far: cloud_grid.hip, shared with the other two]
-//            -> the pair count: per sorted record the sizes of its 9 key ranges (the record itself is in one of them)
+//            -> the candidates copied into key order as 16-byte records (x, y, z, index)
+//            -> the pair count: per sorted record the sizes of its 9 key ranges (the record itself is in one of them), and the
+//               max_pairs refusal                               [so far: cd_self_search of cloud_grid.hip, shared with cloud_normal_kernels.hip]
 //            -> the search kernel: lane t takes sorted record t as its query, so that a wave's lanes walk the same cells and one sort
 //               serves queries and targets; a count, and a sorted list of the KCAP smallest d2 kept in registers.
 // The list is indexed by compile-time constants only (a template over KCAP, every loop over it unrolled): insertion is a chain of
@@ -16,26 +17,6 @@
 
 #define CN_INF_BITS 0x7f800000u
 
-// a sorted record's cell key (3 x 20 bits) as the query key cd_query_range reads (3 x 21 bits, each coordinate + 2)
-__device__ __forceinline__ unsigned long long cn_query_key(unsigned long long key) {
-    return (((key >> 40) + 2ull) << 42) | ((((key >> 20) & 0xfffffull) + 2ull) << 21) | ((key & 0xfffffull) + 2ull);
-}
-
-// *pairs += the number of candidates in the 27 cells around every candidate, itself included: what the search kernel looks at
-__global__ __launch_bounds__(CD_BLOCK) void cn_pairs_kernel(const unsigned long long* __restrict__ keys, uint32_t n_cand, CdGrid g, unsigned long long* __restrict__ pairs) {
-    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
-    unsigned long long cnt = 0;
-    if (t < n_cand) {
-        const unsigned long long qkey = cn_query_key(keys[t]);
-        for (int r = 0; r < 9; r++) {
-            uint32_t b, e;
-            if (cd_query_range(qkey, r, g, keys, n_cand, b, e)) cnt += e - b;
-        }
-    }
-    cnt = cd_wave_sum(cnt);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(pairs, cnt);
-}
-
 // One lane per candidate, in key order.  KCAP = 0: the count only.  k <= KCAP values of the list are written.
 template <int KCAP>
 __global__ __launch_bounds__(CD_BLOCK) void cn_search_kernel(const unsigned long long* __restrict__ keys, const CdRec* __restrict__ rec, uint32_t n_cand, CdGrid g, float r2,
@@ -43,7 +24,7 @@ __global__ __launch_bounds__(CD_BLOCK) void cn_search_kernel(const unsigned long
     const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
     if (t >= n_cand) return;
     const CdRec q = rec[t];
-    const unsigned long long qkey = cn_query_key(keys[t]);
+    const unsigned long long qkey = cd_self_query_key(keys[t]);
     uint32_t a[KCAP > 0 ? KCAP : 1];
 #pragma unroll
     for (int s = 0; s < KCAP; s++) a[s] = CN_INF_BITS;
@@ -104,33 +85,11 @@ int run_cloud_neighbors(CallFrame& f, const float* cloud, long long n, int strid
                         int64_t* n_valid_out, int64_t* pairs_out) {
     tsar_ctx* ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    CdCounters* dc = f.tmp<CdCounters>(1);           // (cloud_grid.h) own[0]: the pairs
-    if (!f.ok()) return f.finish();
-    CdBounds bounds;
-    if (!cd_measure(f, cloud, n, stride, dc, bounds)) return f.finish();
-    const long long n_cand = bounds.n_cand;
-    unsigned long long pairs = 0;
-    CdGrid g = {};
-    CdIndex ix = {};
-    if (n_cand > 0) {
-        if (!cd_grid(f, bounds, edge, CD_MAX_EXTENT,
-                     "tsar_cloud_neighbors: the cloud spans 2^20 cells or more of edge radius on an axis: radius is too small for this cloud's extent", g))
-            return f.finish();
-        if (!cd_index(f, cloud, n, stride, n_cand, g, ix)) return f.finish();
-        {
-            ScopedKernelTimer tm(ctx, "cloud_pairs");
-            hipLaunchKernelGGL(cn_pairs_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, ix.keys, (uint32_t)n_cand, g, &dc->own[0]);
-        }
-        f.launched();
-        f.copy(&pairs, &dc->own[0], sizeof pairs, hipMemcpyDeviceToHost);
-        if (!f.sync()) return f.finish();
-    }
-    if (pairs_out) *pairs_out = (int64_t)pairs;
-    if (pairs > (unsigned long long)max_pairs) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "tsar_cloud_neighbors: the call would look at %llu pairs, more than max_pairs = %lld: lower radius or raise max_pairs", pairs, max_pairs);
-        return f.fail(TSAR_ERR_INVALID, msg);
-    }
+    CdSelf s;
+    if (!cd_self_search(f, cloud, n, stride, edge, max_pairs, pairs_out, s)) return f.finish();
+    const long long n_cand = s.n_cand;
+    const CdGrid& g = s.g;
+    const CdIndex& ix = s.ix;
     if (f.ok() && n > 0 && n_cand < n && (count_out || knn_out)) {
         ScopedKernelTimer tm(ctx, "cloud_neighbors");
         hipLaunchKernelGGL(cn_fill_kernel, dim3(cd_blocks(n)), dim3(CD_BLOCK), 0, st, cloud, n, stride, k, count_out, knn_out);

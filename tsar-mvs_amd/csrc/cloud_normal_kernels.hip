@@ -4,13 +4,14 @@
 // the 64-bit codes bits(d2) << 32 | j, the moments are float64 sums in list order, the eigenvectors a fixed number of Jacobi sweeps, so
 // no bit depends on the grid or on the order in which a point's neighbours arrive.  tests/cloud_normals_ref.py restates both in numpy.
 //
-// Per call:  the shared grid (cloud_grid.hip: bounds, keys, sort, records in key order) and the pair count, as cloud_neighbor_kernels.hip
+// Per call:  cd_self_search of cloud_grid.hip (bounds, keys, sort, records in key order, the pair count, the refusals), as cloud_neighbor_kernels.hip
 //            -> nr_normals_kernel: lane t takes sorted record t as its query; the KCAP smallest codes kept sorted in registers (a
 //               template over KCAP, every loop over the list unrolled, insertion only when some lane of the wave holds a code below its
 //               list's last entry); then the moments, by re-loading the listed points from the cloud; then six Jacobi sweeps.
 // No LDS, no scratch; one atomic per wave for the count of normals.  The library is built with -ffp-contract=off: no product and sum
 // below is fused, and float64 `/` and `sqrt` are correctly rounded on the device (plane_prior_build_kernels.hip relies on the same).
 #include "cloud_grid.h"
+#include "tsar_device_math.h"             // block_add_counters
 
 #define NR_NONE 0xffffffffffffffffull     // above every code: d2 <= R2 is finite, so bits(d2) < 0x7f800000
 
@@ -26,26 +27,6 @@ struct NrArgs {
     double* cov;                          // [n][6]
     unsigned long long* n_normals;
 };
-
-// a sorted record's cell key (3 x 20 bits) as the query key cd_query_range reads (3 x 21 bits, each coordinate + 2)
-__device__ __forceinline__ unsigned long long nr_query_key(unsigned long long key) {
-    return (((key >> 40) + 2ull) << 42) | ((((key >> 20) & 0xfffffull) + 2ull) << 21) | ((key & 0xfffffull) + 2ull);
-}
-
-// *pairs += the number of candidates in the 27 cells around every candidate, itself included: what the search looks at
-__global__ __launch_bounds__(CD_BLOCK) void nr_pairs_kernel(const unsigned long long* __restrict__ keys, uint32_t n_cand, CdGrid g, unsigned long long* __restrict__ pairs) {
-    const uint32_t t = blockIdx.x * CD_BLOCK + threadIdx.x;
-    unsigned long long cnt = 0;
-    if (t < n_cand) {
-        const unsigned long long qkey = nr_query_key(keys[t]);
-        for (int r = 0; r < 9; r++) {
-            uint32_t b, e;
-            if (cd_query_range(qkey, r, g, keys, n_cand, b, e)) cnt += e - b;
-        }
-    }
-    cnt = cd_wave_sum(cnt);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(pairs, cnt);
-}
 
 // One Jacobi rotation in the (p, q) plane of the symmetric a, r the third index; skipped iff a_pq == 0 (include/tsar.h)
 __device__ __forceinline__ void nr_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q, double& v1p, double& v1q, double& v2p,
@@ -86,7 +67,7 @@ __global__ __launch_bounds__(CD_BLOCK) void nr_normals_kernel(const unsigned lon
     bool has = false;
     if (t < n_cand) {
         const CdRec q = rec[t];
-        const unsigned long long qkey = nr_query_key(keys[t]);
+        const unsigned long long qkey = cd_self_query_key(keys[t]);
         unsigned long long a[KCAP];
 #pragma unroll
         for (int s = 0; s < KCAP; s++) a[s] = NR_NONE;
@@ -234,34 +215,13 @@ int run_cloud_normals(CallFrame& f, const float* cloud, long long n, int stride,
                       int32_t* n_used_out, float* normal_out, float* curvature_out, double* cov_out, int64_t* n_valid_out, int64_t* n_normals_out, int64_t* pairs_out) {
     tsar_ctx* ctx = f.ctx;
     hipStream_t st = ctx->stream;
-    CdCounters* dc = f.tmp<CdCounters>(1);           // (cloud_grid.h) own[0]: the pairs, own[1]: the points with a normal
-    if (!f.ok()) return f.finish();
-    CdBounds bounds;
-    if (!cd_measure(f, cloud, n, stride, dc, bounds)) return f.finish();
-    const long long n_cand = bounds.n_cand;
-    unsigned long long pairs = 0, n_normals = 0;
-    CdGrid g = {};
-    CdIndex ix = {};
-    if (n_cand > 0) {
-        if (!cd_grid(f, bounds, edge, CD_MAX_EXTENT,
-                     "tsar_cloud_normals: the cloud spans 2^20 cells or more of edge radius on an axis: radius is too small for this cloud's extent", g))
-            return f.finish();
-        if (!cd_index(f, cloud, n, stride, n_cand, g, ix)) return f.finish();
-        {
-            ScopedKernelTimer tm(ctx, "cloud_pairs");
-            hipLaunchKernelGGL(nr_pairs_kernel, dim3(cd_blocks(n_cand)), dim3(CD_BLOCK), 0, st, ix.keys, (uint32_t)n_cand, g, &dc->own[0]);
-        }
-        f.launched();
-        f.copy(&pairs, &dc->own[0], sizeof pairs, hipMemcpyDeviceToHost);
-        if (!f.sync()) return f.finish();
-    }
-    if (pairs_out) *pairs_out = (int64_t)pairs;
-    if (pairs > (unsigned long long)p.max_pairs) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "tsar_cloud_normals: the call would look at %llu pairs, more than max_pairs = %lld: lower radius or raise max_pairs", pairs,
-                 (long long)p.max_pairs);
-        return f.fail(TSAR_ERR_INVALID, msg);
-    }
+    CdSelf s;                                        // (cloud_grid.h) own[1] of its counters: the points with a normal
+    if (!cd_self_search(f, cloud, n, stride, edge, p.max_pairs, pairs_out, s)) return f.finish();
+    const long long n_cand = s.n_cand;
+    const CdGrid& g = s.g;
+    const CdIndex& ix = s.ix;
+    CdCounters* dc = s.dc;
+    unsigned long long n_normals = 0;
     NrArgs A = {cloud, stride, p.k, p.min_neighbors, p.orient, r2, p.viewpoint[0], p.viewpoint[1], p.viewpoint[2], knn_index_out, n_used_out, normal_out, curvature_out,
                 cov_out, &dc->own[1]};
     const bool any_out = knn_index_out || n_used_out || normal_out || curvature_out || cov_out;
@@ -287,14 +247,13 @@ int run_cloud_normals(CallFrame& f, const float* cloud, long long n, int stride,
 
 // ---- tsar_cloud_normal_compare --------------------------------------------------------------------------------------------------------------
 // counters: 0 n_compared, 1 + k within[k].  Per lane in registers (the loop over the thresholds is unrolled over the fixed maximum, so
-// nothing is indexed at run time), one wave-level reduction, then one atomic per block and counter (depth_compare_kernel's scheme).
+// nothing is indexed at run time), then block_add_counters (LDS: the partials of the block's waves), as depth_compare_kernel.
 #define NC_COUNTERS (1 + TSAR_NORMAL_COMPARE_MAX_TOL)
 struct NcTol { double c[TSAR_NORMAL_COMPARE_MAX_TOL]; int n; };
 
 __global__ __launch_bounds__(CD_BLOCK) void nr_compare_kernel(const float* __restrict__ na, int stride_a, long long n, const float* __restrict__ nb, int stride_b, long long n_b,
                                                               const int32_t* __restrict__ index, const float* __restrict__ dist2, float md2, NcTol tol, int is_signed,
                                                               float* __restrict__ cos_out, unsigned long long* __restrict__ counters) {
-    __shared__ uint32_t part[CD_BLOCK / 64][NC_COUNTERS];
     uint32_t cnt[NC_COUNTERS];
 #pragma unroll
     for (int k = 0; k < NC_COUNTERS; k++) cnt[k] = 0;
@@ -317,19 +276,7 @@ __global__ __launch_bounds__(CD_BLOCK) void nr_compare_kernel(const float* __res
         for (int k = 0; k < TSAR_NORMAL_COMPARE_MAX_TOL; k++) cnt[1 + k] += k < tol.n && cmp && c >= tol.c[k];
         if (cos_out) cos_out[i] = cmp ? (float)c : __builtin_nanf("");
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NC_COUNTERS; k++) {
-        uint32_t s = cnt[k];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NC_COUNTERS) {
-        unsigned long long s = 0;
-        for (int wv = 0; wv < CD_BLOCK / 64; wv++) s += part[wv][threadIdx.x];
-        if (s) __hip_atomic_fetch_add(counters + threadIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    block_add_counters<NC_COUNTERS, CD_BLOCK>(cnt, counters);
 }
 
 // the arrays are device pointers; min_cos (n_tol thresholds) and counters_out ([NC_COUNTERS]) are host memory.  dist2 == NULL: md2 is not read

@@ -1471,7 +1471,7 @@ extern "C" int tsar_cloud_render_ctx(tsar_ctx* ctx, const float* cloud, int64_t 
     uint8_t* dc = f.out(count_out, np, mem);
     int32_t* di = f.out(index_out, np, mem);
     if (!f.ok()) return f.finish();
-    return run_cloud_render(f, c, n, stride, vh, p->occlusion_diff, p->depth_diff, p->min_points, p->max_splats, dd, dc, di, n_splats_out);
+    return run_cloud_render(f, c, nullptr, n, stride, 0, vh, nullptr, p->occlusion_diff, p->depth_diff, p->min_points, p->max_splats, dd, dc, di, nullptr, n_splats_out, nullptr);
 }
 
 extern "C" int tsar_cloud_render(int device, const float* cloud, int64_t n, int stride, const tsar_camera* cam, int w, int h, const tsar_cloud_render_params* p,
@@ -1509,7 +1509,7 @@ static bool cloud_splat_view(const tsar_camera* cam, float radius, CsViewHost* s
     return finite;
 }
 
-// tsar_cloud_render_ctx with the normal-oriented occluder (cloud_splat_kernels.hip); the same frame rules.
+// tsar_cloud_render_ctx with the normal-oriented occluder (the same driver of cloud_render_kernels.hip); the same frame rules.
 extern "C" int tsar_cloud_render_oriented_ctx(tsar_ctx* ctx, const float* cloud, int64_t n, int stride, const float* normals, int normal_stride, const tsar_camera* cam,
                                               int w, int h, const tsar_cloud_render_params* p, float* depth_out, uint8_t* count_out, int32_t* index_out,
                                               float* occluder_out, int64_t* n_splats_out, int64_t* n_covered_out, int mem) {
@@ -1533,8 +1533,8 @@ extern "C" int tsar_cloud_render_oriented_ctx(tsar_ctx* ctx, const float* cloud,
     float* dz = f.out(occluder_out, np, mem);
     if (!f.ok()) return f.finish();
     // (n == 0: no lane reads a normal, and c may be null)
-    return run_cloud_splat(f, c, n > 0 ? (normals ? nr : c + 3) : nullptr, n, stride, normals ? normal_stride : stride, vh, sh, p->occlusion_diff, p->depth_diff, p->min_points,
-                           p->max_splats, dd, dc, di, dz, n_splats_out, n_covered_out);
+    return run_cloud_render(f, c, n > 0 ? (normals ? nr : c + 3) : nullptr, n, stride, normals ? normal_stride : stride, vh, &sh, p->occlusion_diff, p->depth_diff, p->min_points,
+                            p->max_splats, dd, dc, di, dz, n_splats_out, n_covered_out);
 }
 
 extern "C" int tsar_cloud_render_oriented(int device, const float* cloud, int64_t n, int stride, const float* normals, int normal_stride, const tsar_camera* cam, int w, int h,

@@ -481,13 +481,10 @@ int run_cloud_normal_compare(CallFrame& f, const float* normal_a, int stride_a, 
                              const float* dist2, float md2, int n_tol, const double* min_cos, int is_signed, float* cos_out,
                              unsigned long long* counters_out);                                   // cloud_normal_kernels.hip (counters: n_compared, within[16])
 struct CrViewHost { float P[12]; float fr; int max_px, w, h; bool foot; };                       // tsar_cloud_render's view: P, fl(K[0] * radius), radius > 0
-int run_cloud_render(CallFrame& f, const float* cloud, long long n, int stride, const CrViewHost& vh, float occlusion_diff, float depth_diff, int min_points,
-                     long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,
-                     int64_t* n_splats_out);                                                     // cloud_render_kernels.hip (device pointers; finishes the frame)
 struct CsViewHost { float M[9]; float C[3]; float r2; };                                          // tsar_cloud_render_oriented's: (K R)^-1, -R^T t, fl(radius * radius)
-int run_cloud_splat(CallFrame& f, const float* cloud, const float* normals, long long n, int stride, int normal_stride, const CrViewHost& vh, const CsViewHost& sh,
-                    float occlusion_diff, float depth_diff, int min_points, long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,
-                    float* occluder_out, int64_t* n_splats_out, int64_t* n_covered_out);          // cloud_splat_kernels.hip (device pointers; finishes the frame)
+int run_cloud_render(CallFrame& f, const float* cloud, const float* normals, long long n, int stride, int normal_stride, const CrViewHost& vh, const CsViewHost* sh,
+                     float occlusion_diff, float depth_diff, int min_points, long long max_splats, float* depth_out, uint8_t* count_out, int32_t* index_out,
+                     float* occluder_out, int64_t* n_splats_out, int64_t* n_covered_out);         // cloud_render_kernels.hip (device pointers; sh null: the square occluder; finishes the frame)
 int run_depth_compare(CallFrame& f, const float* depth, const float* gt, const uint8_t* mask, long long n, int n_tol, const float* tol, float* error_out,
                       unsigned long long* counters_out);                                         // cloud_render_kernels.hip (counters: n_gt, n_both, n_front, n_behind, within[16])
 int launch_compute_disp(tsar_ctx* ctx);

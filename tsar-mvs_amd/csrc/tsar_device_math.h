@@ -1,4 +1,5 @@
-// tsar_device_math.h — per-hypothesis geometry and RNG for the gfx950 kernels.
+// tsar_device_math.h — per-hypothesis geometry and RNG for the gfx950 kernels; at the end, the block-level counter reduction of the
+// two compare kernels.
 // Compiled with -ffp-contract=off: a fused multiply-add exists only where __builtin_fmaf is
 // written, every other operation is a single IEEE-754 fp32 operation (hipcc keeps '/' and sqrtf
 // correctly rounded without fast-math).  That makes all per-hypothesis quantities (planes, depths,
@@ -224,4 +225,25 @@ DEVFN void plane_homography_fast(const DevRef& rf, const DevView& vw, const floa
     for (int r = 0; r < 3; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++) H[r * 3 + c] = fma_(-vw.b[r], m[c], vw.A[r * 3 + c]);
+}
+
+// The NC counters every lane of a block of BLOCK lanes holds, added to counters[0 .. NC): one wave-level reduction per counter, the
+// waves' partials in LDS, then one relaxed agent-scope add per block and counter (none where the block's sum is 0).  Every lane of the
+// block calls it, once, at the kernel's end (depth_compare_kernel, nr_compare_kernel).
+template <int NC, int BLOCK>
+DEVFN void block_add_counters(const uint32_t (&c)[NC], unsigned long long* __restrict__ counters) {
+    __shared__ uint32_t part[BLOCK / 64][NC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+        uint32_t s = c[k];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) part[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NC) {
+        unsigned long long s = 0;
+        for (int wv = 0; wv < BLOCK / 64; wv++) s += part[wv][threadIdx.x];
+        if (s) __hip_atomic_fetch_add(counters + threadIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
